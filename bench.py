@@ -9,7 +9,13 @@ Contract (one JSON line on rank 0):
           cumsumcorr kernels, IF samples already resident in the HBM ring.  Frequencies are held over a
           launch (OPEN LOOP: the correlator's throughput); the NCO chain is the reference's, bit for bit.
   value   tap-correlations per second, whole job (all ranks), of that open-loop pass; x_realtime =
-          signal-ms processed per wall-ms for the whole 32-SV set.
+          signal-ms processed per wall-ms for the whole 32-SV set; ms_per_step = wall ms of one timed step.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line.  `--dump-outputs DIR` then also writes
+what the last timed step computed (dump_outputs()).  Everything below runs only with `--full`:
+  also    "kernels_ms_per_launch": HIP events around every kernel of two more steps; "integrity": the timed
+          launches' ring and NCO-table checks, channel 0 of one more launch against the CPU oracle; "gpu_clocks".
+  also    "host_fed", "host_fed_sharded": the IF stream from host memory.
   also    "closed_loop": the same 32 channels with cumsumcorr + pll + dll on the device
           (gnsscorr_trk_run_loop), x real time with a filter update every period (before nav bit sync,
           ref src/sdrmain.c:272-276) and every 10 periods (after, :277-302).
@@ -71,7 +77,9 @@ def make_signal(gc, synth, nms, seed):
     cache = f"/tmp/gnsscorr_if_{nms}ms_{seed}.npy"
     if os.path.exists(cache):
         try:
-            return np.load(cache), synth.default_sats(list(range(1, 33)), seed=seed)
+            data = np.load(cache)
+            if data.shape == (nms * NSAMP, 2) and data.dtype == np.int8:
+                return data, synth.default_sats(list(range(1, 33)), seed=seed)
         except Exception:
             pass
     codes = {p: gc.gencode(p, gc.CTYPE_L1CA) for p in range(1, 33)}
@@ -79,11 +87,37 @@ def make_signal(gc, synth, nms, seed):
     t0 = time.time()
     data = synth.make_if(codes, nms * NSAMP, f_sf=F_SF, f_if=0.0, dtype=2, sats=sats, seed=seed)
     log(f"synthetic IF: {nms} ms generated in {time.time() - t0:.1f} s")
-    try:
-        np.save(cache, data)
+    try:                                            # (whole or not at all: another run may be reading it)
+        tmp = f"{cache}.{os.getpid()}.tmp"
+        with open(tmp, "wb") as f:
+            np.save(f, data)
+        os.replace(tmp, cache)
     except Exception:
         pass
     return data, sats
+
+
+def dump_outputs(out_dir, eng, cap_bytes=64 << 20, seed=0):
+    """What the last timed step computed, as a caller of the tracking path receives it, in float64: the E/P/L sums of
+    its last launch (trk_II, trk_QQ: channel x period x tap, gnsscorr_trk_fetch), the samples of every period
+    (trk_nsamp: channel x period) and the channels' NCO state after it (state_<field>: one value per channel).  Over
+    cap_bytes the periods are a fixed, seeded sample, listed in trk_periods."""
+    II, QQ, ns = eng.trk_fetch()
+    st = eng.trk_get_state()
+    nch, ne, nt = II.shape
+    periods = np.arange(ne)
+    per_period = nch * (2 * nt + 1) * 8
+    if ne * per_period > cap_bytes - (1 << 20):
+        keep = (cap_bytes - (1 << 20)) // per_period
+        periods = np.sort(np.random.default_rng(seed).choice(ne, size=keep, replace=False))
+    arrays = {"trk_II": II[:, periods], "trk_QQ": QQ[:, periods], "trk_nsamp": ns[:, periods],
+              "trk_periods": periods}
+    for k in ("carrfreq", "codefreq", "remcode", "remcarr", "buffloc"):
+        arrays["state_" + k] = np.array([s[k] for s in st])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
 
 
 def channel_set(gc, rank):
@@ -197,7 +231,14 @@ def main():
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-acq", action="store_true", help="skip the acquisition leg")
     ap.add_argument("--seed", type=int, default=20240601)
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beside the headline: per-kernel times and rooflines, integrity and oracle checks, "
+                         "host-fed, closed-loop, acquisition and CPU baseline legs, GPU clocks")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import gnsscorr_loader
@@ -279,9 +320,9 @@ def main():
         step(i)
     se.wait()
     barrier()
-    # HIP events around the correlator launches only (roofline.launch_ms); the other kernels of the step are
-    # timed in a short pass after the timed region
-    eng.timing(0 if os.environ.get("BENCH_NOTIMING") else 2)
+    # (--full) HIP events around the correlator launches only (roofline.launch_ms); the other kernels of the step
+    # are timed in a short pass after the timed region
+    eng.timing(0 if os.environ.get("BENCH_NOTIMING") or not args.full else 2)
     eng.timing_reset()
     log(f"tracking leg: {args.steps} steps x {args.inner} launches x {E} periods")
     t0 = time.perf_counter()
@@ -313,6 +354,37 @@ def main():
                     v = pp[chx, w] / nl
                     log("  channel %d (carrfreq %.1f): loop %.0f  slow path %.0f (%.1f periods)  waiting for rows %.0f  waiting for n %.0f" % (
                         chx, states0[chx]["carrfreq"], v[0], v[1], v[4], v[2], v[3]))
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(args.dump_outputs, eng)
+        log(f"outputs of the last timed step: {', '.join(names)} in {args.dump_outputs}")
+    dt_max = dt
+    if dist is not None:
+        t = torch.tensor([dt], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt_max = float(t.item())
+
+    units = NCH * E * args.inner * args.steps * world     # channel-epochs, whole job
+    value = units * ntap / dt_max
+    x_rt = (E * args.inner * args.steps / dt_max) / 1000.0    # epochs/s of the SV set / 1000 (per rank set)
+    out = {
+        "metric": METRIC, "value": value, "unit": "correlations/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": dt_max / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "int8 samples x int8 carrier LUT -> int32 accumulators (exact); NCOs: the reference's fp64 running sums, bit for bit",
+        "data": "synthetic", "x_realtime": x_rt,
+        "config": {"workload": "BASELINE configs[2]: 32-SV GPS L1CA tracking, 5-tap E/P/L correlators "
+                               "(CORRN=2, CORRD=3), 1 ms coherent, 16.368 Msps int8 IQ, per GPU",
+                   "channels_per_gpu": NCH, "epochs_per_launch": E, "launches_per_step": args.inner,
+                   "epochs_per_step": E * args.inner, "taps": ntap, "loop": "open (frequencies held per launch); see closed_loop (--full)",
+                   "if_broadcast": "RCCL broadcast of each step's IF chunk" if world > 1 else "none (1 GPU)"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        eng.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     k_ms, k_n = eng.timing_read("trk_corr")
     # per-kernel times of the whole step: two more steps, every kernel bracketed by events (not part of `value`)
     eng.timing_reset()
@@ -350,15 +422,6 @@ def main():
             b += o.currnsamp
         assert bad == 0, f"bench: {bad} of {ncheck} periods of channel 0 differ from the oracle"
         integrity["oracle_check"] = f"channel 0, {ncheck} periods of the launch after the timed region: II/QQ/currnsamp bit for bit"
-    dt_max = dt
-    if dist is not None:
-        t = torch.tensor([dt], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt_max = float(t.item())
-
-    units = NCH * E * args.inner * args.steps * world     # channel-epochs, whole job
-    value = units * ntap / dt_max
-    x_rt = (E * args.inner * args.steps / dt_max) / 1000.0    # epochs/s of the SV set / 1000 (per rank set)
     bytes_unit = 32840                                    # algorithmic bytes per channel-epoch (int8 IQ, 5 taps)
     k_avg_ms = k_ms / max(k_n, 1)
     ach = NCH * E * bytes_unit / (k_avg_ms * 1e-3) / 1e9 if k_n else 0.0
@@ -366,16 +429,8 @@ def main():
     roof = dict(kernel="trk_corr", bound="hbm", achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s",
                 frac=ach / HBM_PEAK_GBS, traffic=t_bytes, traffic_source=t_src, launch_ms=k_avg_ms, launches=k_n,
                 algorithmic_bytes_per_launch=NCH * E * bytes_unit)
-    out = {
-        "metric": METRIC, "value": value, "unit": "correlations/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": dt_max / args.steps * 1e3, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "int8 samples x int8 carrier LUT -> int32 accumulators (exact); NCOs: the reference's fp64 running sums, bit for bit",
-        "data": "synthetic", "x_realtime": x_rt, "gpu_clocks": gpu_clocks() if rank == 0 else None,
-        "config": {"workload": "BASELINE configs[2]: 32-SV GPS L1CA tracking, 5-tap E/P/L correlators "
-                               "(CORRN=2, CORRD=3), 1 ms coherent, 16.368 Msps int8 IQ, per GPU",
-                   "channels_per_gpu": NCH, "epochs_per_launch": E, "launches_per_step": args.inner,
-                   "epochs_per_step": E * args.inner, "taps": ntap, "loop": "open (frequencies held per launch); see closed_loop",
-                   "if_broadcast": "RCCL broadcast of each step's IF chunk" if world > 1 else "none (1 GPU)"},
+    out.update({
+        "gpu_clocks": gpu_clocks() if rank == 0 else None,
         "roofline": roof,
         "integrity": integrity,
         "kernels_ms_per_launch": {"trk_spec": (lambda a: a[0] / max(a[1], 1))(eng.timing_read("trk_spec")),
@@ -383,7 +438,7 @@ def main():
                                   "trk_expand": (lambda a: a[0] / max(a[1], 1))(eng.timing_read("trk_expand")),
                                   "trk_edges": (lambda a: a[0] / max(a[1], 1))(eng.timing_read("trk_edges")),
                                   "trk_corr": k_ms / max(k_n, 1), "trk_finish": s_ms / max(s_n, 1)},
-    }
+    })
 
     # the same accounting over everything that produces the E/P/L sums of a launch on the main stream (the roofline
     # line above is the dominant kernel alone; trk_edges and trk_expand prepare its look-ups and tables)

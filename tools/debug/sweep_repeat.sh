@@ -1,7 +1,7 @@
 #!/bin/bash
 # debug: repeat the sweep's child runs (tools/debug/plan_sweep.py) and report every configuration whose digest differs
 # between repetitions -- a result that is not a function of its inputs.
-cd /root/repo
+cd "$(dirname "$0")/../.."
 export SWEEP_SEED=${SWEEP_SEED:-31337} SWEEP_NCFG=${SWEEP_NCFG:-160} SWEEP_NEPOCH=${SWEEP_NEPOCH:-500}
 i=0
 for mode in default default default default verify verify replica replica; do

@@ -1,10 +1,11 @@
 #!/bin/bash
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 200 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_LDS_BANK_CONFLICT --kernel-trace --output-format csv -d gpurun_out/pmc_acq1 -- python3 bench.py --steps 1 --warmup 1 --acq-steps 2 --no-cpu > /dev/null 2> gpurun_out/pmc_acq1.err
-timeout -k 10 200 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_WR --kernel-trace --output-format csv -d gpurun_out/pmc_acq2 -- python3 bench.py --steps 1 --warmup 1 --acq-steps 2 --no-cpu > /dev/null 2> gpurun_out/pmc_acq2.err
+cd "$(dirname "$0")/.." && export TMPDIR=/tmp
+OUT=${OUT:-prof_out}; export OUT; mkdir -p "$OUT"
+timeout -k 10 200 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_LDS_BANK_CONFLICT --kernel-trace --output-format csv -d "$OUT/pmc_acq1" -- python3 bench.py --full --steps 1 --warmup 1 --acq-steps 2 --no-cpu > /dev/null 2> "$OUT/pmc_acq1.err"
+timeout -k 10 200 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_WR --kernel-trace --output-format csv -d "$OUT/pmc_acq2" -- python3 bench.py --full --steps 1 --warmup 1 --acq-steps 2 --no-cpu > /dev/null 2> "$OUT/pmc_acq2.err"
 python3 - <<'PY'
-import csv,glob,collections,re
-for d in ("gpurun_out/pmc_acq1","gpurun_out/pmc_acq2"):
+import csv,glob,collections,re,os
+for d in (os.environ["OUT"]+"/pmc_acq1",os.environ["OUT"]+"/pmc_acq2"):
     for f in glob.glob(d+"/*/*counter_collection.csv"):
         agg=collections.defaultdict(lambda: collections.defaultdict(list))
         for r in csv.DictReader(open(f)):
