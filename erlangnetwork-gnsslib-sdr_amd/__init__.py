@@ -255,6 +255,7 @@ def lib():
     L.gnsscorr_timing_enable.argtypes = [C.c_void_p, C.c_int]
     L.gnsscorr_timing_reset.argtypes = [C.c_void_p]
     L.gnsscorr_timing_read.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
+    L.gnsscorr_debug_poison.argtypes = [C.c_void_p, C.c_int]      # (tests; not part of include/gnsscorr.h)
     # reference-named symbols (bound when present; tests/test_abi.py checks that all are)
     def _sig(name, restype, argtypes):
         try:
@@ -397,6 +398,11 @@ class Engine:
 
     def sync(self):
         _check(self._L.gnsscorr_sync(self.h))
+
+    def debug_poison(self, byte):
+        """(tests) Fill every device buffer the context allocates from now on with `byte` (0..255) before its
+        first use, instead of whatever the memory held; -1: off (the default)."""
+        _check(self._L.gnsscorr_debug_poison(self.h, byte))
 
     # -- ring
     def ring_create(self, ftype, dtype, ringlen, devptr=None):

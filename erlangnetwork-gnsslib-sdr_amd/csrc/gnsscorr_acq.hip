@@ -854,11 +854,11 @@ static int acq_tables(gnsscorr_ctx *ctx)
     if (!ctx->acq) ctx->acq = new GcAcqWork();
     GcAcqWork *w = ctx->acq;
     if (w->tw16k) return GNSSCORR_OK;
-    GC_HIP(hipMalloc((void **)&w->tw16k, sizeof(float2) * GC_LH));
-    GC_HIP(hipMalloc((void **)&w->tw32k, sizeof(float2) * GC_LH));
-    GC_HIP(hipMalloc((void **)&w->tw32p, sizeof(float2) * GC_LH));
-    GC_HIP(hipMalloc((void **)&w->tw64p1, sizeof(float2) * GC_LH));
-    GC_HIP(hipMalloc((void **)&w->tw64p3, sizeof(float2) * GC_LH));
+    GC_ALLOC(ctx, &w->tw16k, sizeof(float2) * GC_LH);
+    GC_ALLOC(ctx, &w->tw32k, sizeof(float2) * GC_LH);
+    GC_ALLOC(ctx, &w->tw32p, sizeof(float2) * GC_LH);
+    GC_ALLOC(ctx, &w->tw64p1, sizeof(float2) * GC_LH);
+    GC_ALLOC(ctx, &w->tw64p3, sizeof(float2) * GC_LH);
     hipLaunchKernelGGL(tw_init_kernel, dim3(GC_LH / 256), dim3(256), 0, ctx->stream, w->tw16k, w->tw32k, w->tw32p);
     hipLaunchKernelGGL(tw64_init_kernel, dim3(GC_LH / 256), dim3(256), 0, ctx->stream, w->tw64p1, w->tw64p3);
     GC_HIP(hipGetLastError());
@@ -898,18 +898,18 @@ static int acq_prepare(gnsscorr_ctx *ctx)
         if (c.intg > w->maxintg) w->maxintg = c.intg;
     }
     w->X_elems = (size_t)w->ngrid * w->maxintg * w->maxfreq * w->L;
-    GC_HIP(hipMalloc((void **)&w->X, sizeof(float2) * w->X_elems));
-    GC_HIP(hipMalloc((void **)&w->C, sizeof(float2) * (size_t)nch * w->L));
-    GC_HIP(hipMalloc((void **)&w->rows, sizeof(GcAcqRow) * (size_t)nch * w->maxintg * w->maxfreq));
-    GC_HIP(hipMalloc((void **)&w->arrive, sizeof(int) * ((size_t)nch * w->maxintg + nch)));
-    GC_HIP(hipMalloc((void **)&w->iters, sizeof(int) * nch));
-    GC_HIP(hipMalloc((void **)&w->res, sizeof(gnsscorr_acqres_t) * nch));
-    GC_HIP(hipMalloc((void **)&w->d_grid_chan, sizeof(int) * w->ngrid));
-    GC_HIP(hipMalloc((void **)&w->d_grid_wrpos, sizeof(uint64_t) * w->ngrid));
+    GC_ALLOC(ctx, &w->X, sizeof(float2) * w->X_elems);
+    GC_ALLOC(ctx, &w->C, sizeof(float2) * (size_t)nch * w->L);
+    GC_ALLOC(ctx, &w->rows, sizeof(GcAcqRow) * (size_t)nch * w->maxintg * w->maxfreq);
+    GC_ALLOC(ctx, &w->arrive, sizeof(int) * ((size_t)nch * w->maxintg + nch));
+    GC_ALLOC(ctx, &w->iters, sizeof(int) * nch);
+    GC_ALLOC(ctx, &w->res, sizeof(gnsscorr_acqres_t) * nch);
+    GC_ALLOC(ctx, &w->d_grid_chan, sizeof(int) * w->ngrid);
+    GC_ALLOC(ctx, &w->d_grid_wrpos, sizeof(uint64_t) * w->ngrid);
     GC_HIP(hipMemcpyAsync(w->d_grid_chan, w->grid_chan.data(), sizeof(int) * w->ngrid, hipMemcpyHostToDevice,
                           ctx->stream));
-    GC_HIP(hipMalloc((void **)&w->car, sizeof(GcAcqCar) * (size_t)w->ngrid * w->maxfreq));
-    GC_HIP(hipMalloc((void **)&w->car_overflow, sizeof(int)));
+    GC_ALLOC(ctx, &w->car, sizeof(GcAcqCar) * (size_t)w->ngrid * w->maxfreq);
+    GC_ALLOC(ctx, &w->car_overflow, sizeof(int));
     GC_HIP(hipMemsetAsync(w->car_overflow, 0, sizeof(int), ctx->stream));
     hipLaunchKernelGGL(acq_nco_kernel, dim3((w->ngrid * w->maxfreq + 63) / 64), dim3(64), 0, ctx->stream, ctx->dchan,
                        w->d_grid_chan, ctx->dfreqs, w->car, w->ngrid, w->maxfreq, w->car_overflow);
@@ -1051,7 +1051,7 @@ extern "C" int gnsscorr_acq_power(gnsscorr_ctx *ctx, int ch, double *power)
     const size_t elems = (size_t)c.nfreq * c.nsamp;
     if (elems > w->P_elems) {
         hipFree(w->P); w->P = nullptr; w->P_elems = 0;
-        GC_HIP(hipMalloc((void **)&w->P, sizeof(double) * elems));
+        GC_ALLOC(ctx, &w->P, sizeof(double) * elems);
         w->P_elems = elems;
     }
     // iteration count of the last run is still in w->iters[ch]; rows of this channel are rewritten

@@ -198,20 +198,28 @@ extern "C" int gnsscorr_ring_create(gnsscorr_ctx *ctx, int ftype, int dtype, uin
     if (devmem && ((uintptr_t)devmem & 15))
         return gc_fail(GNSSCORR_EINVAL, "ring_create: device buffer must be 16-byte aligned");
     GC_HIP(hipSetDevice(ctx->device));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    if (r->owned && r->mem) hipFree(r->mem);
-    r->mem = nullptr;
-    r->owned = false;
-    if (devmem) {
-        r->mem = (int8_t *)devmem;
-    } else {
-        GC_HIP(hipMalloc((void **)&r->mem, (size_t)dtype * ringlen));
-        GC_HIP(hipMemsetAsync(r->mem, 0, (size_t)dtype * ringlen, ctx->stream));
-        r->owned = true;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mtx);
+        // transfers into the old ring (ingest stream) and kernels reading it (compute stream) are over before it goes
+        if (ctx->stream_in) GC_HIP(hipStreamSynchronize(ctx->stream_in));
+        GC_HIP(hipStreamSynchronize(ctx->stream));
+        if (r->owned && r->mem) hipFree(r->mem);
+        r->mem = nullptr;
+        r->owned = false;
+        if (devmem) {
+            r->mem = (int8_t *)devmem;
+        } else {
+            GC_HIP(hipMalloc((void **)&r->mem, (size_t)dtype * ringlen));
+            // the zero fill is over before the first push: pushes run on the ingest stream, which nothing orders
+            // behind the compute stream
+            GC_HIP(hipMemsetAsync(r->mem, 0, (size_t)dtype * ringlen, ctx->stream));
+            GC_HIP(hipStreamSynchronize(ctx->stream));
+            r->owned = true;
+        }
+        r->dtype = dtype;
+        r->ringlen = ringlen;
+        r->wrpos = 0;
     }
-    r->dtype = dtype;
-    r->ringlen = ringlen;
-    r->wrpos = 0;
     retarget_rings(ctx);
     return GNSSCORR_OK;
 }
@@ -525,16 +533,16 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
         if (g.smax > ctx->smax_max) ctx->smax_max = g.smax;
         if (d.nsamp + 100 > ctx->max_n) ctx->max_n = d.nsamp + 100;   // ref src/sdrtrk.c:23
     }
-    GC_HIP(hipMalloc((void **)&ctx->dchan, sizeof(GcChan) * nch));
-    GC_HIP(hipMalloc((void **)&ctx->dcodes, codes.size()));
-    GC_HIP(hipMalloc((void **)&ctx->dfreqs, sizeof(double) * freqs.size()));
+    GC_ALLOC(ctx, &ctx->dchan, sizeof(GcChan) * nch);
+    GC_ALLOC(ctx, &ctx->dcodes, codes.size());
+    GC_ALLOC(ctx, &ctx->dfreqs, sizeof(double) * freqs.size());
     for (int i = 0; i < 2; i++) {
-        GC_HIP(hipMalloc((void **)&ctx->dstate2[i], sizeof(GcTrkState) * nch));
+        GC_ALLOC(ctx, &ctx->dstate2[i], sizeof(GcTrkState) * nch);
         GC_HIP(hipMemsetAsync(ctx->dstate2[i], 0, sizeof(GcTrkState) * nch, ctx->stream));
     }
-    GC_HIP(hipMalloc((void **)&ctx->dloop, sizeof(gnsscorr_loop_t) * nch));
+    GC_ALLOC(ctx, &ctx->dloop, sizeof(gnsscorr_loop_t) * nch);
     GC_HIP(hipMemsetAsync(ctx->dloop, 0, sizeof(gnsscorr_loop_t) * nch, ctx->stream));
-    GC_HIP(hipMalloc((void **)&ctx->dloopdone, sizeof(int) * nch + sizeof(uint64_t) * nch + 8));
+    GC_ALLOC(ctx, &ctx->dloopdone, sizeof(int) * nch + sizeof(uint64_t) * nch + 8);
     GC_HIP(hipMemsetAsync(ctx->dloopdone, 0, sizeof(int) * nch + sizeof(uint64_t) * nch + 8, ctx->stream));
     GC_HIP(hipMemcpyAsync(ctx->dcodes, codes.data(), codes.size(), hipMemcpyHostToDevice, ctx->stream));
     GC_HIP(hipMemcpyAsync(ctx->dfreqs, freqs.data(), sizeof(double) * freqs.size(), hipMemcpyHostToDevice,
@@ -600,15 +608,15 @@ static int ensure_trk_buffers(gnsscorr_ctx *ctx, int nepoch)
         ctx->ahead_valid = false;
     }
     free_trk_buffers(ctx);
-    for (int i = 0; i < 2; i++) GC_HIP(hipMalloc((void **)&ctx->dplan2[i], sizeof(GcTrkPlan) * units));
-    for (int i = 0; i < 2; i++) GC_HIP(hipMalloc((void **)&ctx->dspec2[i], sizeof(int) * gc_trk_spec_ints(units)));
-    GC_HIP(hipMalloc((void **)&ctx->detab, sizeof(unsigned short) * units * GC_EDGTAB));
+    for (int i = 0; i < 2; i++) GC_ALLOC(ctx, &ctx->dplan2[i], sizeof(GcTrkPlan) * units);
+    for (int i = 0; i < 2; i++) GC_ALLOC(ctx, &ctx->dspec2[i], sizeof(int) * gc_trk_spec_ints(units));
+    GC_ALLOC(ctx, &ctx->detab, sizeof(unsigned short) * units * GC_EDGTAB);
     ctx->spec_ahead_valid = false;
-    GC_HIP(hipMalloc((void **)&ctx->dcorrI, sizeof(double) * units * ctx->ntap));
-    GC_HIP(hipMalloc((void **)&ctx->dcorrQ, sizeof(double) * units * ctx->ntap));
-    GC_HIP(hipMalloc((void **)&ctx->dsumI, sizeof(double) * ctx->nch * ctx->ntap));
-    GC_HIP(hipMalloc((void **)&ctx->dsumQ, sizeof(double) * ctx->nch * ctx->ntap));
-    GC_HIP(hipMalloc((void **)&ctx->dfinish, sizeof(unsigned long long) * ctx->nch * GC_FINISH_SCRATCH));
+    GC_ALLOC(ctx, &ctx->dcorrI, sizeof(double) * units * ctx->ntap);
+    GC_ALLOC(ctx, &ctx->dcorrQ, sizeof(double) * units * ctx->ntap);
+    GC_ALLOC(ctx, &ctx->dsumI, sizeof(double) * ctx->nch * ctx->ntap);
+    GC_ALLOC(ctx, &ctx->dsumQ, sizeof(double) * ctx->nch * ctx->ntap);
+    GC_ALLOC(ctx, &ctx->dfinish, sizeof(unsigned long long) * ctx->nch * GC_FINISH_SCRATCH);
     GC_HIP(hipMemsetAsync(ctx->dfinish, 0, sizeof(unsigned long long) * ctx->nch * GC_FINISH_SCRATCH, ctx->stream));
     ctx->nseg = 1;
     for (int i = 0; i < ctx->nch; i++) {
@@ -616,18 +624,41 @@ static int ensure_trk_buffers(gnsscorr_ctx *ctx, int nepoch)
         if (s > ctx->nseg) ctx->nseg = s;
     }
     for (int i = 0; i < 2; i++)
-        GC_HIP(hipMalloc((void **)&ctx->dpartial2[i], sizeof(int) * units * ctx->nseg * 2 * ctx->ntap));
+        GC_ALLOC(ctx, &ctx->dpartial2[i], sizeof(int) * units * ctx->nseg * 2 * ctx->ntap);
     for (int i = 0; i < 2; i++) {
-        GC_HIP(hipMalloc((void **)&ctx->dunit2[i], sizeof(GcTrkUnit) * units));
-        GC_HIP(hipMalloc((void **)&ctx->dnsamp2[i], sizeof(int) * units));
-        GC_HIP(hipMalloc((void **)&ctx->drounds2[i], sizeof(GcRound) * units * ctx->nseg * GC_MAXR));
-        GC_HIP(hipMalloc((void **)&ctx->dsegs2[i], sizeof(GcUnitSegs) * units));
+        GC_ALLOC(ctx, &ctx->dunit2[i], sizeof(GcTrkUnit) * units);
+        GC_ALLOC(ctx, &ctx->dnsamp2[i], sizeof(int) * units);
+        GC_ALLOC(ctx, &ctx->drounds2[i], sizeof(GcRound) * units * ctx->nseg * GC_MAXR);
+        GC_ALLOC(ctx, &ctx->dsegs2[i], sizeof(GcUnitSegs) * units);
     }
-    GC_HIP(hipMalloc((void **)&ctx->dnco_overflow, sizeof(int)));
+    GC_ALLOC(ctx, &ctx->dnco_overflow, sizeof(int));
     GC_HIP(hipMemsetAsync(ctx->dnco_overflow, 0, sizeof(int), ctx->stream));
-    GC_HIP(hipMalloc((void **)&ctx->dring_viol, sizeof(int)));
+    GC_ALLOC(ctx, &ctx->dring_viol, sizeof(int));
     GC_HIP(hipMemsetAsync(ctx->dring_viol, 0, sizeof(int), ctx->stream));
     ctx->plan_cap = units;
+    return GNSSCORR_OK;
+}
+
+// hipMalloc; with gnsscorr_debug_poison on, the new buffer is then filled with the poison byte (and the fill is over
+// before this returns, so that it cannot race any later write on another stream)
+int gc_dev_alloc(gnsscorr_ctx *ctx, void **p, size_t bytes)
+{
+    GC_HIP(hipMalloc(p, bytes));
+    if (ctx->poison >= 0) {
+        GC_HIP(hipMemsetAsync(*p, ctx->poison, bytes, ctx->stream));
+        GC_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return GNSSCORR_OK;
+}
+
+// (tests) byte 0..255: every device buffer the context allocates from now on (tracking, closed-loop, acquisition
+// scratch, channel tables) starts out filled with it instead of whatever memory held; -1: off (the default).
+// Owned rings keep their zero fill.
+extern "C" int gnsscorr_debug_poison(gnsscorr_ctx *ctx, int byte)
+{
+    if (!ctx) return gc_fail(GNSSCORR_EINVAL, "debug_poison: null context");
+    if (byte < -1 || byte > 255) return gc_fail(GNSSCORR_EINVAL, "debug_poison: byte %d (0..255, or -1 for off)", byte);
+    ctx->poison = byte;
     return GNSSCORR_OK;
 }
 
@@ -848,11 +879,11 @@ static int ensure_step_buffers(gnsscorr_ctx *ctx)
     }
     if (nseg > 64) return gc_fail(GNSSCORR_EINVAL, "trk_run_loop: period of %d samples too long (%d rounds, 64 at most)", ctx->max_n, nseg);
     const size_t units = (size_t)ctx->nch * GC_STEP_KMAX;
-    GC_HIP(hipMalloc((void **)&ctx->dstep_meta, sizeof(GcStepMeta) * ctx->nch));
-    GC_HIP(hipMalloc((void **)&ctx->dstep_unit, sizeof(GcTrkUnit) * units));
-    GC_HIP(hipMalloc((void **)&ctx->dstep_segs, sizeof(GcUnitSegs) * units));
-    GC_HIP(hipMalloc((void **)&ctx->dstep_rounds, sizeof(GcRound) * units * nseg * 4));        // four rounds (one per wavefront) per workgroup
-    GC_HIP(hipMalloc((void **)&ctx->dstep_partial, sizeof(int) * units * nseg * 2 * ctx->ntap));
+    GC_ALLOC(ctx, &ctx->dstep_meta, sizeof(GcStepMeta) * ctx->nch);
+    GC_ALLOC(ctx, &ctx->dstep_unit, sizeof(GcTrkUnit) * units);
+    GC_ALLOC(ctx, &ctx->dstep_segs, sizeof(GcUnitSegs) * units);
+    GC_ALLOC(ctx, &ctx->dstep_rounds, sizeof(GcRound) * units * nseg * 4);        // four rounds (one per wavefront) per workgroup
+    GC_ALLOC(ctx, &ctx->dstep_partial, sizeof(int) * units * nseg * 2 * ctx->ntap);
     if (!ctx->hostflags) {
         GC_HIP(hipHostMalloc((void **)&ctx->hostflags, 64, hipHostMallocMapped));
         GC_HIP(hipHostGetDevicePointer((void **)&ctx->hostflags_dev, ctx->hostflags, 0));
@@ -878,7 +909,7 @@ extern "C" int gnsscorr_trk_run_loop(gnsscorr_ctx *ctx, int nperiod)
     if (units > ctx->looplog_cap) {
         GC_HIP(hipStreamSynchronize(ctx->stream));
         hipFree(ctx->dlooplog); ctx->dlooplog = nullptr; ctx->looplog_cap = 0;
-        GC_HIP(hipMalloc((void **)&ctx->dlooplog, sizeof(gnsscorr_trklog_t) * units));
+        GC_ALLOC(ctx, &ctx->dlooplog, sizeof(gnsscorr_trklog_t) * units);
         ctx->looplog_cap = units;
     }
     GC_HIP(hipMemsetAsync(ctx->dlooplog, 0, sizeof(gnsscorr_trklog_t) * units, ctx->stream));

@@ -124,6 +124,9 @@ struct gnsscorr_ctx {
     // timing
     int timing = 0;                                // 0: off, 1: every kernel, 2: only the two correlator kernels (trk_corr, acq_corr)
     std::map<std::string, GcTimer> timers;
+
+    // gnsscorr_debug_poison: byte (0..255) every lazily allocated device buffer is filled with before first use, -1 off
+    int poison = -1;
 };
 
 // RAII helper: brackets one kernel launch with HIP events when timing is on.
@@ -148,4 +151,11 @@ struct GcTimed {
 };
 
 void gc_acq_free(gnsscorr_ctx *ctx);
+int gc_dev_alloc(gnsscorr_ctx *ctx, void **p, size_t bytes);   // hipMalloc + the context's poison fill, if on
+
+#define GC_ALLOC(ctx, p, bytes)                                                 \
+    do {                                                                        \
+        int rc_ = gc_dev_alloc((ctx), (void **)(p), (bytes));                   \
+        if (rc_) return rc_;                                                    \
+    } while (0)
 int gc_ingest_fence(gnsscorr_ctx *ctx);      // orders the compute stream behind the last ring transfer
