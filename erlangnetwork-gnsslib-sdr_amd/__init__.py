@@ -119,6 +119,15 @@ def frame_replay(state, log_rows, cnt0=0):
         raise RuntimeError("gnsscorr_frame_replay: error %d" % rc)
 
 
+class SpecParams(C.Structure):
+    """gnsscorr_spec_t: one IF-monitor configuration (include/gnsscorr.h)."""
+    _fields_ = [("ftype", C.c_int), ("nfft", C.c_int), ("nloop", C.c_int), ("n", C.c_int), ("f_sf", C.c_double)]
+
+
+SPEC_HIST = 9          # counts per row of gnsscorr_spec_fetch's hist: bins -7,-5,...,+7 and d == maxd > 7
+SPEC_NLOOP = 100       # ref src/sdr.h:232
+
+
 class AcqRes(C.Structure):
     _fields_ = [("acqcodei", C.c_int), ("freqi", C.c_int), ("acqfreq", C.c_double),
                 ("cn0", C.c_double), ("peakr", C.c_double), ("flagacq", C.c_int),
@@ -198,13 +207,15 @@ EXPORTS_GNSSCORR = [
     "gnsscorr_num_channels", "gnsscorr_trk_set_state", "gnsscorr_trk_get_state", "gnsscorr_trk_run",
     "gnsscorr_trk_fetch", "gnsscorr_trk_fetch_sums", "gnsscorr_trk_devptrs", "gnsscorr_acq_run",
     "gnsscorr_acq_fetch", "gnsscorr_trk_start_from_acq", "gnsscorr_acq_power", "gnsscorr_fft16k", "gnsscorr_pspec",
-    "gnsscorr_timing_enable", "gnsscorr_timing_read", "gnsscorr_timing_reset", "gnsscorr_default_ctx"]
+    "gnsscorr_timing_enable", "gnsscorr_timing_read", "gnsscorr_timing_reset", "gnsscorr_default_ctx",
+    "gnsscorr_spec_run", "gnsscorr_spec_fetch"]
 EXPORTS_SDR = [
     "sdracquisition", "checkacquisition", "sdrtracking", "cumsumcorr", "clearcumsumcorr", "pll", "dll",
     "readinifile", "chk_initvalue", "initacqstruct", "inittrkprmstruct", "inittrkstruct", "initsdrch",
     "freesdrch", "cpxcpx", "cpxfft", "cpxifft", "cpxconv", "cpxpspec", "mixcarr", "rescode", "pcorrelator", "correlator",
     "maxvd", "meanvd", "ind2sub", "gencode", "rcvgetbuff", "file_pushtomembuf", "file_getbuff",
-    "sdrnavigation", "sdrini", "sdrstat", "hbuffmtx", "hreadmtx", "hfftmtx", "hobsmtx"]
+    "sdrnavigation", "sdrini", "sdrstat", "hbuffmtx", "hreadmtx", "hfftmtx", "hobsmtx",
+    "hanning", "calchistgram", "spectrumanalyzer"]
 
 
 def lib():
@@ -255,6 +266,9 @@ def lib():
     L.gnsscorr_timing_enable.argtypes = [C.c_void_p, C.c_int]
     L.gnsscorr_timing_reset.argtypes = [C.c_void_p]
     L.gnsscorr_timing_read.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
+    L.gnsscorr_spec_run.argtypes = [C.c_void_p, C.POINTER(SpecParams), C.c_int, C.c_void_p, C.c_void_p]
+    L.gnsscorr_spec_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                      C.c_size_t, C.c_void_p, C.c_size_t]
     L.gnsscorr_debug_poison.argtypes = [C.c_void_p, C.c_int]      # (tests; not part of include/gnsscorr.h)
     # reference-named symbols (bound when present; tests/test_abi.py checks that all are)
     def _sig(name, restype, argtypes):
@@ -291,6 +305,9 @@ def lib():
     _sig("rescode", C.c_double, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_void_p])
     _sig("maxvd", C.c_double, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)])
     _sig("meanvd", C.c_double, [C.c_void_p, C.c_int, C.c_int, C.c_int])
+    _sig("hanning", None, [C.c_int, C.c_void_p])
+    _sig("calchistgram", None, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+    _sig("spectrumanalyzer", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p])
     _lib = L
     return L
 
@@ -317,6 +334,33 @@ def gencode(prn, ctype):
     code = np.ctypeslib.as_array(p, shape=(n.value,)).copy()
     C.CDLL(None).free(p)
     return code, cr.value
+
+
+def _samples(data, dtype):
+    """int8 bytes of a sample block (n for dtype 1, (n, 2) or 2n interleaved for dtype 2) and n."""
+    a = np.ascontiguousarray(data, dtype=np.int8).reshape(-1)
+    if dtype not in (DTYPEI, DTYPEIQ) or a.size % dtype:
+        raise ValueError(f"dtype {dtype} with {a.size} bytes")
+    return a, a.size // dtype
+
+
+def calchistgram(data, dtype):
+    """calchistgram() of the library (ref src/sdrspec.c:170-206): (xI, yI, xQ, yQ), 8 bins each.  Host code."""
+    a, n = _samples(data, dtype)
+    xI, yI, xQ, yQ = (np.zeros(8) for _ in range(4))
+    lib().calchistgram(a.ctypes.data, dtype, n, xI.ctypes.data, yI.ctypes.data, xQ.ctypes.data, yQ.ctypes.data)
+    return xI, yI, xQ, yQ
+
+
+def spectrumanalyzer(data, dtype, f_sf, nfft=16384):
+    """spectrumanalyzer() of the library (ref src/sdrspec.c:232-296) on the default context's device: (freq MHz,
+    pspec dB), dtype*nfft each.  Its 100 segment offsets come from the C library's rand(), as in the reference."""
+    a, n = _samples(data, dtype)
+    freq = np.zeros(dtype * nfft)
+    pspec = np.zeros(dtype * nfft)
+    if lib().spectrumanalyzer(a.ctypes.data, dtype, n, float(f_sf), nfft, freq.ctypes.data, pspec.ctypes.data) != 0:
+        raise GnsscorrError(lib().gnsscorr_last_error().decode())
+    return freq, pspec
 
 
 class Channel:
@@ -407,6 +451,8 @@ class Engine:
     # -- ring
     def ring_create(self, ftype, dtype, ringlen, devptr=None):
         _check(self._L.gnsscorr_ring_create(self.h, ftype, dtype, ringlen, devptr))
+        self._ring_dtype = getattr(self, "_ring_dtype", {})
+        self._ring_dtype[ftype] = dtype
 
     def ring_push(self, ftype, samples):
         a = np.ascontiguousarray(samples, dtype=np.int8)
@@ -538,6 +584,33 @@ class Engine:
         P = np.empty((c.nfreq, c.nsamp), np.float64)
         _check(self._L.gnsscorr_acq_power(self.h, ch, P.ctypes.data))
         return P
+
+    # -- IF monitor
+    def spectrum(self, ftype, buffloc, n, f_sf, nfft=16384, nloop=SPEC_NLOOP, offsets=None, seed=None):
+        """Sample histogram and Hann-windowed averaged power spectrum of ring `ftype` (gnsscorr_spec_run/fetch):
+        what specthread() gets from calchistgram() + spectrumanalyzer() (ref src/sdrspec.c:64-102).
+        buffloc: first sample of a snapshot, or a sequence of them.  offsets: [nsnap][nloop] segment starts in
+        [0, n - nfft/2]; None draws them with numpy.random.default_rng(seed).
+        Returns (freq [dtype*nfft] MHz, pspec dB [nsnap][dtype*nfft], s linear [nsnap][2*nfft],
+        hist [nsnap][2][9]); the nsnap axis is dropped for an int buffloc."""
+        single = np.ndim(buffloc) == 0
+        loc = np.ascontiguousarray(np.atleast_1d(buffloc), dtype=np.uint64)
+        nsnap = loc.size
+        if offsets is None:
+            offsets = np.random.default_rng(seed).integers(0, n - nfft // 2 + 1, size=(nsnap, nloop))
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(nsnap, nloop)
+        sp = SpecParams(ftype, nfft, nloop, n, float(f_sf))
+        _check(self._L.gnsscorr_spec_run(self.h, C.byref(sp), nsnap, loc.ctypes.data, off.ctypes.data))
+        dtype = self._ring_dtype[ftype]
+        s = np.empty((nsnap, 2 * nfft))
+        pspec = np.empty((nsnap, dtype * nfft))
+        freq = np.empty(dtype * nfft)
+        hist = np.empty((nsnap, 2, SPEC_HIST), np.int64)
+        _check(self._L.gnsscorr_spec_fetch(self.h, s.ctypes.data, s.size, pspec.ctypes.data, pspec.size,
+                                           freq.ctypes.data, freq.size, hist.ctypes.data, hist.size))
+        if single:
+            return freq, pspec[0], s[0], hist[0]
+        return freq, pspec, s, hist
 
     # -- timing
     def timing(self, on=True):

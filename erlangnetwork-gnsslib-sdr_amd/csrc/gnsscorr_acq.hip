@@ -876,6 +876,15 @@ static int acq_tables(gnsscorr_ctx *ctx)
     return GNSSCORR_OK;
 }
 
+int gc_acq_twiddles(gnsscorr_ctx *ctx, const float2 **tw16k, const float2 **tw32k)
+{
+    int rc = acq_tables(ctx);
+    if (rc) return rc;
+    *tw16k = ctx->acq->tw16k;
+    *tw32k = ctx->acq->tw32k;
+    return GNSSCORR_OK;
+}
+
 static int acq_prepare(gnsscorr_ctx *ctx)
 {
     int rc = acq_tables(ctx);

@@ -128,6 +128,7 @@ extern "C" void gnsscorr_destroy(gnsscorr_ctx *ctx)
     if (ctx->stream3) hipStreamSynchronize(ctx->stream3);
     if (ctx->stream4) hipStreamSynchronize(ctx->stream4);
     gc_acq_free(ctx);
+    gc_spec_free(ctx);
     free_trk_buffers(ctx);
     free_channels(ctx);
     for (auto &r : ctx->ring)
@@ -486,6 +487,7 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
     if (ctx->stream3) GC_HIP(hipStreamSynchronize(ctx->stream3));
     if (ctx->stream4) GC_HIP(hipStreamSynchronize(ctx->stream4));
     gc_acq_free(ctx);
+    gc_spec_free(ctx);
     free_trk_buffers(ctx);
     free_channels(ctx);
 

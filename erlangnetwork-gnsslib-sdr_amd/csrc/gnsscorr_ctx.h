@@ -25,6 +25,7 @@ struct GcTimer {
 };
 
 struct GcAcqWork;   // gnsscorr_acq.hip
+struct GcSpecWork;  // gnsscorr_spec.hip
 
 struct gnsscorr_ctx {
     int device = 0;
@@ -121,6 +122,9 @@ struct gnsscorr_ctx {
     // acquisition
     GcAcqWork *acq = nullptr;
 
+    // IF monitor (spectrum / histogram) scratch
+    GcSpecWork *spec = nullptr;
+
     // timing
     int timing = 0;                                // 0: off, 1: every kernel, 2: only the two correlator kernels (trk_corr, acq_corr)
     std::map<std::string, GcTimer> timers;
@@ -151,6 +155,9 @@ struct GcTimed {
 };
 
 void gc_acq_free(gnsscorr_ctx *ctx);
+void gc_spec_free(gnsscorr_ctx *ctx);
+// the acquisition's forward twiddle tables (made on first use): exp(-2 pi i t/16384), exp(-2 pi i t/32768), t < 16384
+int gc_acq_twiddles(gnsscorr_ctx *ctx, const float2 **tw16k, const float2 **tw32k);
 int gc_dev_alloc(gnsscorr_ctx *ctx, void **p, size_t bytes);   // hipMalloc + the context's poison fill, if on
 
 #define GC_ALLOC(ctx, p, bytes)                                                 \

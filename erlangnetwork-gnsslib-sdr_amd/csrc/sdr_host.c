@@ -766,3 +766,49 @@ void ind2sub(int ind, int nx, int ny, int *subx, int *suby)
     *subx = ind % nx;
     *suby = ny * ind / (nx * ny);
 }
+
+/* ------------------------------------------------------------------------- */
+/* IF monitor, host part: ref src/sdrspec.c:170-219 (the spectrum itself,     */
+/* spectrumanalyzer(), runs on the device: gnsscorr_spec.hip)                 */
+/* ------------------------------------------------------------------------- */
+
+/* ref src/sdrspec.c:214-219: w[i] = 0.5 (1 - cos(2 pi (i+1) / (n+1))) in double, stored as float */
+void hanning(int n, float *win)
+{
+    for (int i = 0; i < n; i++) win[i] = (float)(0.5 * (1 - cos(2 * PI * (i + 1) / (n + 1))));
+}
+
+/* calchistgram()'s bin of sample value d (ref src/sdrspec.c:186-205): 8 levels scaled to maxd when it exceeds the
+ * 3-bit range, else the odd levels -7..+7 directly; 8 (past the end) for d == maxd > 7 */
+static int hist_bin(int d, int maxd)
+{
+    return maxd > 7 ? (int)((double)d / maxd * 4 + 4) : (d + 7) / 2;
+}
+
+/* ref src/sdrspec.c:170-206, bins 0..7 only: the reference's count at bin 8 (d == maxd > 7) lands one element past
+ * yI / yQ; here it is dropped (gnsscorr_spec_fetch reports it as a 9th count).  With maxd <= 7 the reference counts
+ * data[i], i < n, into both rows of an IQ stream -- the interleaved bytes, not the Q samples; so does this. */
+void calchistgram(char *data, int dtype, int n, double *xI, double *yI, double *xQ, double *yQ)
+{
+    int maxd = 0;
+    for (int b = 0; b < SPEC_BITN; b++) {
+        xI[b] = xQ[b] = 2 * b - 7;
+        yI[b] = yQ[b] = 0.0;
+    }
+    for (int i = 0; i < n * dtype; i++) {
+        const int a = abs((int)(signed char)data[i]);
+        if (a > maxd) maxd = a;
+    }
+    if (dtype != DTYPEI && dtype != DTYPEIQ) return;
+    for (int i = 0; i < n; i++) {
+        int bi, bq;
+        if (maxd > 7 && dtype == DTYPEIQ) {
+            bi = hist_bin((signed char)data[2 * i], maxd);
+            bq = hist_bin((signed char)data[2 * i + 1], maxd);
+        } else {
+            bi = bq = hist_bin((signed char)data[i], maxd);
+        }
+        if (bi < SPEC_BITN) yI[bi] += 1.0;
+        if (dtype == DTYPEIQ && bq < SPEC_BITN) yQ[bq] += 1.0;
+    }
+}

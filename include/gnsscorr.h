@@ -27,6 +27,7 @@
 #ifndef GNSSCORR_H
 #define GNSSCORR_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -303,9 +304,43 @@ int  gnsscorr_fft16k(gnsscorr_ctx *ctx, const void *in, void *out, int sign,
 int  gnsscorr_pspec(gnsscorr_ctx *ctx, const float *cpx, int n, int flagsum,
                     double *pspec);
 
+/* ---- IF monitor: sample histogram and averaged power spectrum on the ring --
+ * What specthread() computes every SPEC_MS (ref src/sdrspec.c:64-102) --
+ * rcvgetbuff() + calchistgram() (ref src/sdrspec.c:170-206) +
+ * spectrumanalyzer() (ref src/sdrspec.c:232-296) -- read straight from the
+ * HBM ring, for nsnap snapshots in one launch chain on the context's stream. */
+typedef struct {
+    int    ftype;   /* ring 1 or 2; dtype comes from the ring                         */
+    int    nfft;    /* 8192 or 16384 (2*nfft-point transform); ref SPEC_NFFT          */
+    int    nloop;   /* segments averaged per snapshot, >= 1; ref SPEC_NLOOP           */
+    int    n;       /* samples per snapshot, nfft/2 <= n <= ringlen; ref SPEC_LEN*nsamp */
+    double f_sf;    /* Hz, for the frequency axis                                     */
+} gnsscorr_spec_t;
+/* Snapshot s covers samples [buffloc[s], buffloc[s] + n), which the ring must
+ * hold at call time (wrpos - ringlen <= buffloc[s], buffloc[s] + n <= wrpos);
+ * segment k of it starts offsets[s*nloop + k] samples in, 0 <= offset <=
+ * n - nfft/2 (the reference's zuz).  Anything else: GNSSCORR_EINVAL naming the
+ * snapshot, and nothing is launched.  Asynchronous. */
+int  gnsscorr_spec_run(gnsscorr_ctx *ctx, const gnsscorr_spec_t *sp, int nsnap,
+                       const uint64_t *buffloc, const int *offsets);
+/* Results of the last gnsscorr_spec_run.  Any pointer may be NULL; caps are
+ * element counts, and a cap below what the run needs is GNSSCORR_EINVAL with
+ * nothing written.
+ *   s[nsnap][2*nfft]       linear segment sums in FFT order (the reference's s)
+ *   pspec[nsnap][dtype*nfft] dB, and freq[dtype*nfft] MHz, laid out as the
+ *                          reference's (ref src/sdrspec.c:280-294)
+ *   hist[nsnap][2][9]      I and Q counts of the bins {-7,-5,...,+7}; the 9th
+ *                          counts d == maxd > 7, which the reference writes one
+ *                          element past yI / yQ; the Q row is zero for dtype 1
+ * Synchronises. */
+int  gnsscorr_spec_fetch(gnsscorr_ctx *ctx, double *s, size_t s_cap,
+                         double *pspec, size_t pspec_cap, double *freq,
+                         size_t freq_cap, int64_t *hist, size_t hist_cap);
+
 /* per-kernel launch timing: enable, run, then read the accumulated HIP-event
  * time of the named kernel ("trk_corr", "trk_plan", "trk_spec", "trk_expand",
- * "trk_finish", "acq_fwd", "acq_corr", "acq_code", "acq_final").
+ * "trk_finish", "acq_fwd", "acq_corr", "acq_code", "acq_final", "spec_psd",
+ * "spec_sum", "spec_hist").
  * on = 1: every kernel; on = 2: only the two correlator kernels ("trk_corr",
  * "acq_corr"), leaving the planner and finish streams free of events; 0: off */
 int  gnsscorr_timing_enable(gnsscorr_ctx *ctx, int on);

@@ -64,6 +64,11 @@ extern "C" {
 #define CDIV          32        /* ref src/sdrcmn.c:9-11 */
 #define CMASK         0x1F
 #define CSCALE        (1.0/32.0)
+#define SPEC_MS       200       /* ref src/sdr.h:229-233 */
+#define SPEC_LEN      7
+#define SPEC_BITN     8
+#define SPEC_NLOOP    100
+#define SPEC_NFFT     16384
 
 /* ref src/sdr.h:255-269 (pthread flavour) */
 #define thread_t      pthread_t
@@ -264,6 +269,17 @@ extern double maxvd(const double *data, int n, int exinds, int exinde, int *ind)
 extern double meanvd(const double *data, int n, int exinds, int exinde);
 extern void ind2sub(int ind, int nx, int ny, int *subx, int *suby);
 extern short *gencode(int prn, int ctype, int *len, double *crate);
+
+/* ---- IF monitor: ref src/sdr.h:774-778 (src/sdrspec.c:170-296) ------------
+ * hanning() and calchistgram() are host code; calchistgram() fills bins 0..7
+ * only (the reference writes a 9th element past yI/yQ when d == maxd > 7).
+ * spectrumanalyzer() runs on the device of gnsscorr_default_ctx(); its segment
+ * offsets come from the process's rand(), drawn as the reference draws them. */
+extern void hanning(int n, float *win);
+extern void calchistgram(char *data, int dtype, int n, double *xI, double *yI,
+                         double *xQ, double *yQ);
+extern int spectrumanalyzer(const char *data, int dtype, int n, double f_sf,
+                            int nfft, double *freq, double *pspec);
 
 /* ---- sample ring: ref src/sdr.h (sdrrcv.c section), src/sdrrcv.c:406-532 -- */
 extern int rcvgetbuff(sdrini_t *ini, uint64_t buffloc, int n, int ftype,
