@@ -1370,6 +1370,7 @@ struct GcCodeStepC {
     double d[ITOP + 1], pre[ITOP + 1];                     // step, the tie binade's own addition (ci or 0)
     double ci, dlen, b0, smaxci;
     int    ex_top;                                          // biased exponent the start value must have (binade ITOP's)
+    int    it;                                              // the tie binade (pre != 0), or -1
 };
 
 template <int ITOP>
@@ -1380,6 +1381,7 @@ GC_HD void gc_code_stepc_init(GcCodeStepC<ITOP> &C, const GcCodePlan &P)
     C.b0 = gc_u2d((uint64_t)P.f.ex0 << 52);
     C.smaxci = P.smaxci;
     C.ex_top = P.f.ex0 + ITOP;
+    C.it = P.it;
 #pragma unroll
     for (int i = 0; i <= ITOP; i++) {
         C.d[i] = P.f.d[i];
@@ -1551,6 +1553,7 @@ struct GcCarStepC {
     double d[GC_CLAIM_CWIN], pre[GC_CLAIM_CWIN];   // step, the tie binade's own addition (s or 0)
     double s;
     int    ilo, ex0;                // first binade of the window; biased exponent of table binade 0
+    int    ptie;                    // window position of the tie binade (pre != 0), or -1
 };
 
 // nmax: the longest period the channel is expected to have (samples); a longer one only loses the fast path
@@ -1561,6 +1564,7 @@ GC_HD void gc_car_stepc_init(GcCarStepC &C, const GcCarPlan &P, int nmax)
     C.s = f.s;
     C.ex0 = f.ex0;
     C.ilo = 0;
+    C.ptie = -1;
     if (f.ex0 != 0x7FFFFFF) {
         const double xmax = fma((double)nmax, fabs(f.s), GC_NCO_CDIV);
         int imax = gc_expo(xmax) - f.ex0;
@@ -1576,6 +1580,7 @@ GC_HD void gc_car_stepc_init(GcCarStepC &C, const GcCarPlan &P, int nmax)
             if (i != C.ilo + p) continue;
             C.d[p] = f.d[i];
             C.pre[p] = ((f.tie >> i) & 1) ? f.s : 0.0;
+            if ((f.tie >> i) & 1) C.ptie = p;
         }
         GC_PIN_V(C.d[p]);
         GC_PIN_V(C.pre[p]);
@@ -1686,6 +1691,157 @@ GC_HD bool gc_carrier_claims_step(const GcCarPlan &P, const GcCarStepC &C, doubl
     *remcarr_out = p;
     if (DISCOVER && !ok) cl.tag = 0;
     return ok;
+}
+
+// ---------------------------------------------------------------------------
+// value-only period steps (the chains' bracketed path)
+// ---------------------------------------------------------------------------
+// The claims steps above evaluate a fixed worst-case shape -- every window position, every literal and tail
+// addition, every subtraction of DPI -- and pick the claimed result, because their checks and the discovery need
+// all of it.  A chain whose start lies inside a bracket the discovery checked at both ends holds its proof already
+// and wants the value only: the steps below perform exactly the operations the claims name, the same ones in the
+// same order, so they are bit-identical to the claims steps (tests/test_nco_value_step.py holds them to those and to
+// the oracle's literal loops).  Every count is the same in all lanes (GC_UNIFORM_INT): the evaluation branches on
+// them with scalar tests beside the fp64 operations, whose table indices stay compile-time constants, so the
+// per-channel constants stay in registers.  A channel without a tie binade (nearly all) makes no addition of zero.
+
+// Control flow, not selects: a block that the compiler could compute unconditionally and then select (one fp64
+// addition, say) would put the selects back on the dependent path; GC_KEEP_V pins the block's value so that the
+// block stays a branch around it.  Branches are not free either (a lone wavefront pays for every scalar test and
+// branch it issues), so there are few of them: k equal additions go in blocks of 2^b by the bits of k -- every
+// addition is the same operation, so the grouping leaves the sequence as it is -- and the tie binade's own
+// addition is decided once per channel, not once per binade.
+#define GC_KEEP_V(x) GC_PIN_V(x)
+
+template <int N>
+struct GcPow2Floor { static constexpr int value = N < 2 ? 1 : 2 * GcPow2Floor<N / 2>::value; };
+template <>
+struct GcPow2Floor<0> { static constexpr int value = 1; };
+
+// y after k additions of a, k in 0..N (bits of k above N's are never a claim these steps are given)
+template <int N>
+GC_HD double gc_add_n(double y, double a, int k)
+{
+    GC_FP_STRICT
+    constexpr int TOP = GcPow2Floor<N>::value;
+#pragma unroll
+    for (int b = TOP; b >= 1; b >>= 1) {
+        if (k & b) {
+#pragma unroll
+            for (int j = 0; j < b; j++) y = y + a;
+            GC_KEEP_V(y);
+        }
+    }
+    return y;
+}
+
+// the phase remainder (ref src/sdrcmn.c:666-668) with the claimed number of subtractions (the reference subtracts
+// DPI: the sum with -DPI is the same rounded difference)
+GC_HD double gc_prem_value(double x, int kprem)
+{
+    GC_FP_STRICT
+    const double p = x * GC_NCO_DPI * (1.0 / GC_NCO_CDIV);
+    return gc_add_n<GC_CLAIM_PREM>(p, -GC_NCO_DPI, kprem);
+}
+
+// ... and with the claim checked: *held when the last subtraction started above DPI and the result is not above it
+GC_HD double gc_prem_checked(double x, int kprem, bool *held)
+{
+    GC_FP_STRICT
+    double p = x * GC_NCO_DPI * (1.0 / GC_NCO_CDIV);
+    double prev = p;
+    if (kprem >= 1) {
+        p = gc_add_n<GC_CLAIM_PREM>(p, -GC_NCO_DPI, kprem - 1);
+        prev = p;
+        p = p - GC_NCO_DPI;
+    }
+    *held = (p < 1.0e300) & (kprem >= 0) & (kprem <= GC_CLAIM_PREM) & ((kprem == 0) | (prev > GC_NCO_DPI)) & !(p > GC_NCO_DPI);
+    return p;
+}
+
+// Code, as gc_code_claims_step<ITOP, TMAX, false> on claims (q, nl, i0, jsum) with dmd[i] = (double)dm[i]:
+// the head, nl literal additions, the climb from binade i0, nt - jsum tail additions.
+template <int ITOP, int TMAX>
+GC_HD double gc_code_value_step(const GcCodeStepC<ITOP> &C, double remcode, int nt, int q, int nl, int i0, int jsum,
+                                const double *dmd)
+{
+    GC_FP_STRICT
+    const double ci = C.ci, dlen = C.dlen;
+    const int it = GC_UNIFORM_INT(C.it);
+    const double cs = remcode - C.smaxci;
+    const double c0 = cs < 0.0 ? cs + dlen : cs;
+    double y = fma((double)q + 1.0, C.d[ITOP], c0);
+    y = y - dlen;
+    y = gc_add_n<GC_CLAIM_LIT>(y, ci, nl);
+    if (i0 == 0) {
+        if (it == 0) y = y + ci;                    // (the tie binade's own addition: C.pre[it] = ci)
+        y = fma(dmd[0], C.d[0], y);
+        y = y + ci;
+        GC_KEEP_V(y);
+    }
+    if (it <= 0) {                                  // no tie binade above binade 0: the climb is one fma and one addition per binade
+#pragma unroll
+        for (int i = 1; i <= ITOP; i++) {
+            y = fma(dmd[i], C.d[i], y);
+            y = y + ci;
+        }
+    } else {
+#pragma unroll
+        for (int i = 1; i <= ITOP; i++) {
+            y = y + C.pre[i];
+            y = fma(dmd[i], C.d[i], y);
+            y = y + ci;
+        }
+    }
+    y = y - dlen;
+    y = gc_add_n<TMAX>(y, ci, nt - jsum);
+    return y - C.smaxci;
+}
+
+// Carrier, window shape (claims tag 1), as gc_carrier_claims_step<false, false, 1>: window positions p0 .. plast
+// (p0 = claimed entry binade - C.ilo, plast = p0 + nseg - 1, both in 0 .. GC_CLAIM_CWIN - 1), dmd[p] =
+// (double)dm[p]; then kprem subtractions of DPI.
+GC_HD double gc_carrier_value_step(const GcCarPlan &P, const GcCarStepC &C, double remcarr, int p0, int plast, int kprem,
+                                   const double *dmd)
+{
+    GC_FP_STRICT
+    static_assert(GC_CLAIM_CWIN <= 32, "gc_carrier_value_step: one bit per window position");
+    const int ptie = GC_UNIFORM_INT(C.ptie);
+    double x = gc_div_y(remcarr * GC_NCO_CDIV, GC_NCO_DPI, P.ydpi);      // ref src/sdrcmn.c:649
+    // positions p0 .. plast: one bit each; the low half of the window is looked at only when the period starts in it
+    const unsigned act = ((2u << (plast - p0)) - 1u) << p0;
+    constexpr int PH = GC_CLAIM_CWIN / 2;
+    if (ptie < 0) {
+        if (p0 < PH) {
+#pragma unroll
+            for (int p = 0; p < PH; p++)
+                if ((act >> p) & 1u) { x = fma(dmd[p], C.d[p], x); x = x + C.s; GC_KEEP_V(x); }
+        }
+#pragma unroll
+        for (int p = PH; p < GC_CLAIM_CWIN; p++)
+            if ((act >> p) & 1u) { x = fma(dmd[p], C.d[p], x); x = x + C.s; GC_KEEP_V(x); }
+    } else {                                        // a tie binade in the window: its own addition (C.pre) at every position
+#pragma unroll
+        for (int p = 0; p < GC_CLAIM_CWIN; p++)
+            if ((act >> p) & 1u) { x = x + C.pre[p]; x = fma(dmd[p], C.d[p], x); x = x + C.s; GC_KEEP_V(x); }
+    }
+    return gc_prem_value(x, kprem);
+}
+
+// Carrier, one-binade shape (claims tag 2), as gc_carrier_claims_step<false, false, 2>: judged by its own
+// conditions (gc_one_binade_walk) and the remainder's claim, which it checks; false: *remcarr_out not written.
+GC_HD bool gc_carrier_value_step_one(const GcCarPlan &P, const GcCarStepC &C, double remcarr, int n, int kprem,
+                                     double *remcarr_out)
+{
+    GC_FP_STRICT
+    if (C.ex0 == 0x7FFFFFF || n < 1) return false;
+    double x = gc_div_y(remcarr * GC_NCO_CDIV, GC_NCO_DPI, P.ydpi);      // ref src/sdrcmn.c:649
+    if (!gc_one_binade_walk(x, C.s, n, &x)) return false;
+    bool held;
+    const double p = gc_prem_checked(x, kprem, &held);
+    if (!held) return false;
+    *remcarr_out = p;
+    return true;
 }
 
 #if defined(__HIPCC__)

@@ -638,20 +638,14 @@ __device__ __attribute__((noinline)) void plan4_code_wave(double ci_, double spc
             const int n = plan2_uni((qn > -2147483648.0 && qn < 2147483648.0) ? (int)qn : 0);
             const int tag = row.tag;
             const bool inside = tag == 1 && remcode >= row.lo && remcode <= row.hi && n == row.n;
-            GcCodeClaims c2;
             double dmd[ITOP + 1];
-            c2.tag = 1;
-            c2.i0 = 0;
-            c2.q = plan4_scopy(row.q);
-            c2.nl = plan4_scopy(row.nl);
-            c2.jsum = plan4_scopy(row.jsum);
+            const int q = plan4_scopy(row.q), nl = plan4_scopy(row.nl), i0 = plan4_scopy(row.i0);
+            const int jsum = plan4_scopy(row.jsum);
 #pragma unroll
             for (int k = 0; k <= ITOP; k++) {
                 dmd[k] = (double)row.dm[k];
                 GC_PIN_V(dmd[k]);
             }
-#pragma unroll
-            for (int k = 0; k < 13; k++) c2.dm[k] = 0;
             const bool inside_u = plan4_bcopy(inside);
             const bool claims_u = plan4_bcopy(tag == 1);
             __builtin_amdgcn_sched_barrier(0);
@@ -666,7 +660,7 @@ __device__ __attribute__((noinline)) void plan4_code_wave(double ci_, double spc
             if (n > 0 && n <= (1 << 24)) {
                 double rc = remcode;
                 if (inside_u && !J.verify) {
-                    (void)gc_code_claims_step<ITOP, TMAX, false>(PC, SC, remcode, n + 2 * smax, c2, &rc, dmd);     // the value; the bracket is the proof
+                    rc = gc_code_value_step<ITOP, TMAX>(SC, remcode, n + 2 * smax, q, nl, i0, jsum, dmd);     // the value; the bracket is the proof
                     tally0++;
                 } else {                        // (its own result variable: what a called function gets the address of lives in memory)
                     double rs;
@@ -807,6 +801,7 @@ __device__ __attribute__((noinline)) void plan4_car_wave(double ps_, int nsamp_,
     gc_car_plan_init(PK, ps, false, false);
     GcCarStepC CK;
     gc_car_stepc_init(CK, PK, nsamp + 16);
+    const int ilo = plan2_uni(CK.ilo);
     unsigned tally0 = 0, tally1 = 0, tally2 = 0, miss = 0, mism = 0;    // (scalars: an array indexed by a variable lives in memory)
     GC_GLOBAL GcTrkPlan *out = (GC_GLOBAL GcTrkPlan *)J.out;
     double remcarr = J.s.remcarr;
@@ -831,20 +826,15 @@ __device__ __attribute__((noinline)) void plan4_car_wave(double ps_, int nsamp_,
             __builtin_amdgcn_s_waitcnt(0xC07F);        // lgkmcnt(0): n and the row are here
             const int tag = row.tag;
             const bool inside = tag == 1 && remcarr >= row.lo && remcarr <= row.hi && n == row.nl;
-            GcCarClaims c2;
             double dmd[GC_CLAIM_CWIN];
-            c2.tag = tag == 2 ? 2 : 1;
-            c2.nl = n;
-            c2.i0 = plan4_scopy(row.i0);
-            c2.nseg = plan4_scopy(row.nseg);
-            c2.kprem = plan4_scopy(row.kprem);
+            const int p0 = plan4_scopy(row.i0 - ilo);
+            const int plast = plan4_scopy(row.i0 - ilo + row.nseg - 1);
+            const int kprem = plan4_scopy(row.kprem);
 #pragma unroll
             for (int k = 0; k < GC_CLAIM_CWIN; k++) {
                 dmd[k] = (double)row.dm[k];
                 GC_PIN_V(dmd[k]);
             }
-#pragma unroll
-            for (int k = 0; k < GC_CLAIM_CSEG; k++) c2.dm[k] = 0;
             const bool inside_u = plan4_bcopy(inside);
             const int tag_u = plan4_scopy(tag);
             __builtin_amdgcn_sched_barrier(0);
@@ -857,13 +847,13 @@ __device__ __attribute__((noinline)) void plan4_car_wave(double ps_, int nsamp_,
                 double rp = remcarr;
                 bool done = false;
                 if (inside_u && !J.verify) {
-                    (void)gc_carrier_claims_step<false, false, 1>(PK, CK, remcarr, n, c2, &rp, dmd);
+                    rp = gc_carrier_value_step(PK, CK, remcarr, p0, plast, kprem, dmd);     // the value; the bracket is the proof
                     done = true;
                 } else if (tag_u == 2) {
                     // a period inside one binade: the step carries its own conditions (gc_one_binade_walk) and is judged by
                     // them; the remainder's one claim is checked
                     double r2 = remcarr;
-                    done = gc_carrier_claims_step<false, false, 2>(PK, CK, remcarr, n, c2, &r2);
+                    done = gc_carrier_value_step_one(PK, CK, remcarr, n, kprem, &r2);
                     rp = done ? r2 : rp;
                 }
                 if (done) {
