@@ -25,6 +25,7 @@ CTYPE_L1CA, CTYPE_G1, CTYPE_L1SBAS = 1, 20, 27
 SYS_GPS, SYS_SBS, SYS_GLO = 1, 2, 4
 DTYPEI, DTYPEIQ = 1, 2
 FTYPE1, FTYPE2 = 1, 2
+FEND_RTLSDR, FEND_FRTLSDR, FEND_FILE = 3, 8, 10
 MEMBUFFLEN, FILE_BUFFSIZE = 5000, 65536      # ref src/sdr.h:134,137
 ACQTH = 3.0                                  # ref src/sdr.h:148
 
@@ -365,10 +366,12 @@ def spectrumanalyzer(data, dtype, f_sf, nfft=16384):
 
 class Channel:
     """Constants of one receiver channel, derived exactly as initsdrch() does
-    (ref src/sdrinit.c:583-657, acquisition grid :385-394,:633-635, taps :446-455)."""
+    (ref src/sdrinit.c:583-657, acquisition grid :385-394,:633-635, taps :446-455).  fend / ppmerr stand for
+    sdrini.fend / sdrini.rtlsdrppmerr: RTL-SDR file replay (FEND_FRTLSDR) offsets the channel by f_cf*ppmerr*1e-6."""
 
     def __init__(self, prn, ctype=CTYPE_L1CA, dtype=DTYPEIQ, ftype=FTYPE1, f_cf=1575.42e6,
-                 f_sf=16.368e6, f_if=0.0, corrn=2, corrd=3, corrp=3, hband=7000, step=200, intg=10):
+                 f_sf=16.368e6, f_if=0.0, corrn=2, corrd=3, corrp=3, hband=7000, step=200, intg=10,
+                 fend=FEND_FILE, ppmerr=0):
         self.prn, self.ctype, self.dtype, self.ftype = prn, ctype, dtype, ftype
         self.code, self.crate = gencode(prn, ctype)
         self.clen = len(self.code)
@@ -381,6 +384,8 @@ class Channel:
         if ctype == CTYPE_G1:
             self.f_cf = 1.60200e9 + 0.56250e6 * prn
             self.foffset = 0.56250e6 * prn
+        elif fend == FEND_FRTLSDR:
+            self.f_cf, self.foffset = f_cf, f_cf * ppmerr * 1e-6
         else:
             self.f_cf, self.foffset = f_cf, 0.0
         self.intg = intg

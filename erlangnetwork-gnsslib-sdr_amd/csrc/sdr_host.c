@@ -414,6 +414,12 @@ int initsdrch(int chno, int sys, int prn, int ctype, int dtype, int ftype, doubl
         snprintf(sdr->satstr, 5, "R%d", prn);
         sdr->f_cf = FREQ1_GLO + DFRQ1_GLO * prn;
         sdr->foffset = DFRQ1_GLO * prn;
+    } else if (sdrini.fend == FEND_FRTLSDR) {
+        /* RTL-SDR file replay: the acquisition grid is shifted by the front end's clock error (ref :616-617).
+         * f_cf keeps the front end's CF: the reference leaves it 0 here, and dll() divides by f_cf/crate
+         *  */
+        sdr->f_cf = f_cf;
+        sdr->foffset = f_cf * sdrini.rtlsdrppmerr * 1e-6;
     } else {
         sdr->f_cf = f_cf;
         sdr->foffset = 0.0;

@@ -32,6 +32,8 @@ extern "C" {
 #define DPI           (2.0*PI)
 #define ON            1
 #define OFF           0
+#define FEND_RTLSDR   3
+#define FEND_FRTLSDR  8
 #define FEND_FILE     10
 #define FTYPE1        1
 #define FTYPE2        2

@@ -267,6 +267,29 @@ static const double complex *roots(int n, int sign)
     return g_tw[slot].w;
 }
 
+/* root_p^(r q) = w[wp * (r q mod p)] as [r][re row | im row][q], for w = roots(wp * p, sign): one table per
+ * (p, wp, sign) and thread, as roots() keeps its own */
+static const double *prime_table(const double complex *w, int wp, int p)
+{
+    static __thread struct { int p, wp, neg; double *tab; } c[8];
+    const int neg = cimag(w[wp]) < 0;
+    int i, r, q;
+    for (i = 0; i < 8; i++)
+        if (c[i].tab && c[i].p == p && c[i].wp == wp && c[i].neg == neg) return c[i].tab;
+    for (i = 0; i < 7 && c[i].tab; i++) ;
+    free(c[i].tab);
+    c[i].tab = (double *)malloc(sizeof(double) * 2 * (size_t)p * (size_t)p);
+    if (!c[i].tab) abort();
+    c[i].p = p; c[i].wp = wp; c[i].neg = neg;
+    for (r = 0; r < p; r++)
+        for (q = 0; q < p; q++) {
+            const double complex y = w[(size_t)wp * (((size_t)r * q) % p)];
+            c[i].tab[(size_t)2 * r * p + q] = creal(y);
+            c[i].tab[(size_t)2 * r * p + p + q] = cimag(y);
+        }
+    return c[i].tab;
+}
+
 static int small_factor(int n)
 {
     int p;
@@ -291,8 +314,10 @@ static void dft_rec(const double complex *in, int stride, int n,
     {
         int ws = wn / n;              /* w[ws*t] = root_n^t   */
         int wp = wn / p;              /* w[wp*t] = root_p^t   */
-        double complex t[64];
-        if (p > 64) return;           /* primes above 64 are not needed here */
+        /* any prime: 2*nsamp = 16366 at 8.1838 Msps has the factor 167 */
+        double complex t64[64], *t = p <= 64 ? t64 : (double complex *)malloc(sizeof(double complex) * (size_t)p);
+        double *accr = p <= 64 ? NULL : (double *)malloc(sizeof(double) * 2 * (size_t)p), *acci = accr ? accr + p : NULL;
+        if (!t || (p > 64 && !accr)) abort();
         for (k = 0; k < m; k++) {
             for (r = 0; r < p; r++)
                 t[r] = scratch[(size_t)r * m + k] * w[(size_t)ws * ((size_t)r * k % n)];
@@ -307,15 +332,32 @@ static void dft_rec(const double complex *in, int stride, int n,
                 out[k + m] = b + d;
                 out[k + 2 * m] = a - c;
                 out[k + 3 * m] = b - d;
-            } else {
+            } else if (p <= 64) {
                 for (q = 0; q < p; q++) {
                     double complex acc = t[0];
                     for (r = 1; r < p; r++)
                         acc += t[r] * w[(size_t)wp * ((r * q) % p)];
                     out[k + (size_t)q * m] = acc;
                 }
+            } else {
+                /* out[k + q m] = sum_r t[r] root_p^(r q), r in order, in real arithmetic (what the complex product
+                 * gives for finite values, without the C99 Annex G library call) over a table of root_p^(r q):
+                 * large primes make this the oracle's hot loop */
+                const double *tab = prime_table(w, wp, p);
+                for (q = 0; q < p; q++) { accr[q] = creal(t[0]); acci[q] = cimag(t[0]); }
+                for (r = 1; r < p; r++) {
+                    const double xr = creal(t[r]), xi = cimag(t[r]);
+                    const double *yr = tab + (size_t)2 * r * p, *yi = yr + p;
+                    for (q = 0; q < p; q++) {
+                        accr[q] += xr * yr[q] - xi * yi[q];
+                        acci[q] += xr * yi[q] + xi * yr[q];
+                    }
+                }
+                for (q = 0; q < p; q++) out[k + (size_t)q * m] = accr[q] + _Complex_I * acci[q];
             }
         }
+        if (t != t64) free(t);
+        free(accr);
     }
 }
 
@@ -505,7 +547,7 @@ void orc_getbuff(const orc_ring_t *ring, uint64_t buffloc, int n, int dtype,
  * :432-480 (taps).  GLONASS FDMA offsets as :612-615. */
 int orc_initchan(orc_chan_t *ch, int prn, int ctype, int dtype, double f_cf,
                  double f_sf, double f_if, int corrn, int corrd, int corrp,
-                 const double *dllb, const double *pllb, const double *fllb)
+                 const double *dllb, const double *pllb, const double *fllb, int fend, int ppmerr)
 {
     int i;
     memset(ch, 0, sizeof(*ch));
@@ -521,6 +563,9 @@ int orc_initchan(orc_chan_t *ch, int prn, int ctype, int dtype, double f_cf,
     if (ctype == ORC_CTYPE_G1) {
         ch->f_cf = 1.60200E9 + 0.56250E6 * prn;
         ch->foffset = 0.56250E6 * prn;
+    } else if (fend == 8) {              /* FEND_FRTLSDR: ref :616-617 (f_cf kept, see gnss_oracle.h) */
+        ch->f_cf = f_cf;
+        ch->foffset = f_cf * ppmerr * 1e-6;
     } else {
         ch->f_cf = f_cf;
         ch->foffset = 0.0;

@@ -145,10 +145,12 @@ typedef struct {
     int    flagremcarradd, flagpolarityadd, flagsyncf, polarity, obs_n, obs_nsnr;
 } orc_chan_t;
 
-/* ref src/sdrinit.c:583-657 (+ :385-394, :402-480); xcode left NULL */
+/* ref src/sdrinit.c:583-657 (+ :385-394, :402-480); xcode left NULL.  fend / ppmerr: sdrini.fend and
+ * sdrini.rtlsdrppmerr -- RTL-SDR file replay (fend 8) shifts foffset by f_cf*ppmerr*1e-6 (ref :616-617); f_cf
+ * is kept there, where the reference leaves it 0 and dll() would divide by it (ref src/sdrtrk.c:147-148) */
 int orc_initchan(orc_chan_t *ch, int prn, int ctype, int dtype, double f_cf,
                  double f_sf, double f_if, int corrn, int corrd, int corrp,
-                 const double *dllb, const double *pllb, const double *fllb);
+                 const double *dllb, const double *pllb, const double *fllb, int fend, int ppmerr);
 /* ref src/sdracq.c:14-62 (no sleep, no printf); power = nsamp*nfreq zeroed
  * doubles; returns buffloc */
 uint64_t orc_sdracquisition(orc_chan_t *ch, const orc_ring_t *ring,

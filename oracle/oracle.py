@@ -87,7 +87,7 @@ def lib():
     L.orc_meanvd.argtypes = [vp, i, i, i]
     L.orc_checkacquisition.argtypes = [vp, i, i, i, d, vp, C.POINTER(AcqRes)]
     L.orc_getbuff.argtypes = [C.POINTER(Ring), C.c_uint64, i, i, vp]
-    L.orc_initchan.argtypes = [C.POINTER(Chan), i, i, i, d, d, d, i, i, i, vp, vp, vp]
+    L.orc_initchan.argtypes = [C.POINTER(Chan), i, i, i, d, d, d, i, i, i, vp, vp, vp, i, i]
     L.orc_sdracquisition.restype = C.c_uint64
     L.orc_sdracquisition.argtypes = [C.POINTER(Chan), C.POINTER(Ring), vp, C.POINTER(i)]
     L.orc_sdrtracking.restype = C.c_uint64
@@ -130,11 +130,13 @@ def correlator(data, dtype, ti, n, freq, phi0, crate, coff, s, code):
 
 
 def make_chan(prn, ctype=1, dtype=2, f_cf=1575.42e6, f_sf=16.368e6, f_if=0.0, corrn=2, corrd=3, corrp=3,
-              dllb=(5.0, 1.0), pllb=(30.0, 10.0), fllb=(200.0, 50.0)):
+              dllb=(5.0, 1.0), pllb=(30.0, 10.0), fllb=(200.0, 50.0), fend=10, ppmerr=0):
+    """fend / ppmerr: the receiver's front-end type and RTL-SDR clock error (sdrini.fend / .rtlsdrppmerr); fend 8
+    (RTL-SDR file replay) gives the channel a frequency offset of f_cf*ppmerr*1e-6."""
     ch = Chan()
     a = [np.array(x, np.float64) for x in (dllb, pllb, fllb)]
     if lib().orc_initchan(C.byref(ch), prn, ctype, dtype, f_cf, f_sf, f_if, corrn, corrd, corrp,
-                          a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data) < 0:
+                          a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, fend, ppmerr) < 0:
         raise ValueError("orc_initchan")
     return ch
 

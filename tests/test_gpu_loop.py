@@ -242,11 +242,18 @@ def test_closed_loop_random_states_across_front_ends(gc, orc, engine, seed, dtyp
     planned from claims discovered for brackets around the closed-form period starts, gnsscorr_loop.hip).  Starts
     include a remainder of exactly 0, remainders within 1e-6 of 0 and of 1 chip, a carrier phase of 0 and Doppler up
     to +-9 kHz.  12 channels x 130 periods in two runs, everything bit for bit against orc_sdrthread_step."""
-    corrn, corrd, corrp = taps
     ctype = gc.CTYPE_L1CA
     if flagsync < 0:                                    # (negative: the G1 cases)
         ctype, flagsync = gc.CTYPE_G1, -flagsync - 1
-    nper, nch = 130, 12
+    _random_states_case(gc, orc, engine, seed, dtype, f_if, f_sf, taps, flagsync, ctype=ctype)
+
+
+def _random_states_case(gc, orc, engine, seed, dtype, f_if, f_sf, taps, flagsync, ctype=1, nper=130, nch=12,
+                        chunks=(97, 33)):
+    """test_closed_loop_random_states_across_front_ends for one front end / tap set: nch channels from random start
+    states on noise, nper periods in len(chunks) runs, every period against orc_sdrthread_step."""
+    corrn, corrd, corrp = taps
+    assert sum(chunks) == nper
     nsamp = int(f_sf * 1e-3)
     rng = np.random.default_rng(seed)
     nsamples = nsamp * (nper + 4)
@@ -278,8 +285,10 @@ def test_closed_loop_random_states_across_front_ends(gc, orc, engine, seed, dtyp
     ntap = 1 + 2 * corrn
     # (filter outputs: the device's atan / atan2 and glibc's differ by an ulp now and then, times the loop gains -- 1e-13
     # relative here, north_star's bound is 1e-4; everything the correlators return stays exact)
-    _check_against_oracle(orc, engine, ochs, ring, bufflocs, 97, ntap, tol=1e-12)
-    _check_against_oracle(orc, engine, ochs, ring, bufflocs, 33, ntap, done=97, tol=1e-12)
+    done = 0
+    for nrun in chunks:
+        _check_against_oracle(orc, engine, ochs, ring, bufflocs, nrun, ntap, done=done, tol=1e-12)
+        done += nrun
     fin = engine.trk_get_state()
     for i, o in enumerate(ochs):
         assert fin[i]["buffloc"] == bufflocs[i].value and fin[i]["remcode"] == o.remcode and fin[i]["remcarr"] == o.remcarr

@@ -103,6 +103,50 @@ def test_initsdrch_matches_reference_shapes(gc, orc):
     L.freesdrch(C.byref(s))
 
 
+def test_initsdrch_rtlsdr_file_replay_frequency_offset(gc, orc, tmp_path):
+    """RTL-SDR file replay (FEND = FILERTLSDR, 8) shifts every channel by the front end's clock error,
+    foffset = f_cf*PPMERR*1e-6, and the acquisition grid with it (ref src/sdrinit.c:616-617, :632-635); the live
+    RTL-SDR front end (3) and every other type leave it 0, GLONASS keeps its FDMA offset.  f_cf stays the front
+    end's CF (the reference leaves it 0, and dll() divides by f_cf/crate: DESIGN.md section 4)."""
+    L = gc.lib()
+    ini = gc.sdrini()
+    saved = gc.SdrIni.from_buffer_copy(ini)
+    try:
+        dat = tmp_path / "rtl.bin"
+        dat.write_bytes(b"\x80" * 64)
+        fe = tmp_path / "fe.ini"
+        fe.write_text(open(os.path.join(HERE, "golden", "frontend_filertlsdr.ini")).read().replace("@FILE1@", str(dat)))
+        rcv = tmp_path / "gnss-sdrcli.ini"
+        rcv.write_text(open(os.path.join(HERE, "golden", "gnss-sdrcli.ini")).read().replace("@FENDCONF@", str(fe)))
+        assert L.readinifile_at(C.byref(ini), str(rcv).encode()) == 0 and L.chk_initvalue(C.byref(ini)) == 0
+        assert (ini.fend, ini.rtlsdrppmerr, ini.f_sf[0], ini.f_if[0], ini.dtype[0]) == (8, 30, 2.048e6, 0.0, 2)
+        assert (ini.trkcorrn, ini.trkcorrd, ini.trkcorrp) == (4, 1, 1)
+        foff = 1575.42e6 * 30 * 1e-6
+        for fend, want in ((gc.FEND_FRTLSDR, foff), (gc.FEND_RTLSDR, 0.0), (gc.FEND_FILE, 0.0)):
+            ini.fend = fend
+            sdr = gc.SdrCh()
+            assert L.initsdrch(1, gc.SYS_GPS, 7, gc.CTYPE_L1CA, 2, 1, ini.f_cf[0], ini.f_sf[0], ini.f_if[0],
+                               C.byref(sdr)) == 0
+            assert sdr.foffset == want and sdr.f_cf == 1575.42e6, fend
+            assert (sdr.nsamp, sdr.nsampchip, sdr.acq.nfft, sdr.trk.ne, sdr.trk.nl) == (2048, 2, 4096, 1, 2)
+            freq = np.ctypeslib.as_array(sdr.acq.freq, shape=(71,))
+            assert freq[0] == -7000.0 + want and freq[35] == want and freq[70] == 7000.0 + want, fend
+            # the Python mirror and the oracle carry the same offset and grid
+            ch = gc.Channel(7, dtype=2, f_sf=2.048e6, f_if=0.0, corrn=4, corrd=1, corrp=1, fend=fend, ppmerr=30)
+            o = orc.make_chan(7, dtype=2, f_sf=2.048e6, f_if=0.0, corrn=4, corrd=1, corrp=1, fend=fend, ppmerr=30)
+            assert ch.foffset == o.foffset == want and ch.f_cf == o.f_cf == sdr.f_cf, fend
+            assert np.array_equal(ch.freq, freq) and np.array_equal(np.ctypeslib.as_array(o.freq)[:71], freq), fend
+            L.freesdrch(C.byref(sdr))
+        # GLONASS keeps its FDMA carrier and offset under RTL-SDR file replay (the G1 branch comes first)
+        ini.fend = gc.FEND_FRTLSDR
+        g = gc.SdrCh()
+        assert L.initsdrch(2, gc.SYS_GLO, -3, gc.CTYPE_G1, 2, 1, 1602e6, 20e6, 0.0, C.byref(g)) == 0
+        assert g.foffset == -3 * 0.5625e6 and g.f_cf == 1602e6 - 3 * 0.5625e6
+        L.freesdrch(C.byref(g))
+    finally:
+        C.memmove(C.addressof(ini), C.addressof(saved), C.sizeof(gc.SdrIni))
+
+
 def test_loop_filters_product_vs_oracle(gc, orc):
     L = gc.lib()
     ini = gc.sdrini()

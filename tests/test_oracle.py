@@ -50,7 +50,9 @@ def test_carrier_lut(orc):
     assert np.array_equal(cost, np.roll(sint, -8))
 
 
-@pytest.mark.parametrize("n", [8, 12, 33, 341, 1024, 4092, 32736, 32768])
+# (4096 and 16366: the acquisition transforms 2*nsamp of the 2.048 and 8.1838 Msps front ends; 16366 = 2*7*7*167 and
+# 334 hold a prime factor above 64)
+@pytest.mark.parametrize("n", [8, 12, 33, 334, 341, 1024, 4092, 4096, 16366, 32736, 32768])
 def test_fft_matches_numpy(orc, n):
     rng = np.random.default_rng(n)
     x = (rng.standard_normal(n) + 1j * rng.standard_normal(n)).astype(np.complex64)
