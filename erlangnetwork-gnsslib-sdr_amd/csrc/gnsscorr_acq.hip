@@ -51,27 +51,25 @@ struct GcAcqCar {
 #define GC_ACQ_CARLDS (((GC_NCAR * 4 + 15) & ~15) + GC_NCAR * (int)sizeof(GcCarSeg))
 
 struct GcAcqWork {
-    GcAcqCar *car = nullptr;    // [grid][bin]
-    int *car_overflow = nullptr;
-    float2 *tw16k = nullptr;    // exp(-2 pi i t/16384), t < 16384
-    float2 *tw32k = nullptr;    // exp(-2 pi i t/32768), t < 16384
-    float2 *tw32p = nullptr;    // the same twiddles in pass order: exp(-2 pi i freq_of(p)/32768), p < 16384
-    float2 *tw64p1 = nullptr;   // exp(-2 pi i freq_of(p)/65536) and
-    float2 *tw64p3 = nullptr;   // exp(-2 pi i 3 freq_of(p)/65536), pass order (the 65536-point path)
+    GcDevBuf<GcAcqCar> car;     // [grid][bin]
+    GcDevBuf<int> car_overflow;
+    GcDevBuf<float2> tw16k;     // exp(-2 pi i t/16384), t < 16384
+    GcDevBuf<float2> tw32k;     // exp(-2 pi i t/32768), t < 16384
+    GcDevBuf<float2> tw32p;     // the same twiddles in pass order: exp(-2 pi i freq_of(p)/32768), p < 16384
+    GcDevBuf<float2> tw64p1;    // exp(-2 pi i freq_of(p)/65536) and
+    GcDevBuf<float2> tw64p3;    // exp(-2 pi i 3 freq_of(p)/65536), pass order (the 65536-point path)
     int L = GC_L;               // transform length of this channel set: 32768, or 65536 when a period exceeds 16384 samples
-    float2 *X = nullptr;        // [grid][iter][bin][2][16384]: X[f] and X[f + 16384] at the pass position of f
-    size_t  X_elems = 0;
-    float2 *C = nullptr;        // [ch][2][16384]
-    GcAcqRow *rows = nullptr;   // [ch][iter][bin]
-    int *arrive = nullptr;      // [ch][iter] workgroups done with the iteration, then [ch] "acquired" flags
-    int *iters = nullptr;       // [ch] iteration limit for acq_corr
-    gnsscorr_acqres_t *res = nullptr;   // [ch]
-    double *P = nullptr;        // one channel's power array (on demand)
-    size_t P_elems = 0;
+    GcDevBuf<float2> X;         // [grid][iter][bin][2][16384]: X[f] and X[f + 16384] at the pass position of f
+    GcDevBuf<float2> C;         // [ch][2][16384]
+    GcDevBuf<GcAcqRow> rows;    // [ch][iter][bin]
+    GcDevBuf<int> arrive;       // [ch][iter] workgroups done with the iteration, then [ch] "acquired" flags
+    GcDevBuf<int> iters;        // [ch] iteration limit for acq_corr
+    GcDevBuf<gnsscorr_acqres_t> res;    // [ch]
+    GcDevBuf<double> P;         // one channel's power array (on demand)
     int ngrid = 0, maxfreq = 0, maxintg = 0;
     std::vector<int> grid_chan;         // a representative channel per grid
-    int *d_grid_chan = nullptr;         // device copy of grid_chan
-    uint64_t *d_grid_wrpos = nullptr;   // ring write position seen by each grid
+    GcDevBuf<int> d_grid_chan;          // device copy of grid_chan
+    GcDevBuf<uint64_t> d_grid_wrpos;    // ring write position seen by each grid
     bool code_ready = false;
     uint64_t last_wrpos[2] = {0, 0};
     bool ran = false;
@@ -839,13 +837,7 @@ __global__ __launch_bounds__(GC_FFT_THREADS) void pspec_kernel(const float2 *__r
 // ---------------------------------------------------------------------------
 void gc_acq_free(gnsscorr_ctx *ctx)
 {
-    GcAcqWork *w = ctx->acq;
-    if (!w) return;
-    hipFree(w->tw16k); hipFree(w->tw32k); hipFree(w->tw32p); hipFree(w->tw64p1); hipFree(w->tw64p3);
-    hipFree(w->X); hipFree(w->C); hipFree(w->rows); hipFree(w->arrive);
-    hipFree(w->iters); hipFree(w->res); hipFree(w->P);
-    hipFree(w->d_grid_chan); hipFree(w->d_grid_wrpos); hipFree(w->car); hipFree(w->car_overflow);
-    delete w;
+    delete ctx->acq;
     ctx->acq = nullptr;
 }
 
@@ -854,11 +846,11 @@ static int acq_tables(gnsscorr_ctx *ctx)
     if (!ctx->acq) ctx->acq = new GcAcqWork();
     GcAcqWork *w = ctx->acq;
     if (w->tw16k) return GNSSCORR_OK;
-    GC_ALLOC(ctx, &w->tw16k, sizeof(float2) * GC_LH);
-    GC_ALLOC(ctx, &w->tw32k, sizeof(float2) * GC_LH);
-    GC_ALLOC(ctx, &w->tw32p, sizeof(float2) * GC_LH);
-    GC_ALLOC(ctx, &w->tw64p1, sizeof(float2) * GC_LH);
-    GC_ALLOC(ctx, &w->tw64p3, sizeof(float2) * GC_LH);
+    GC_RESERVE(ctx, w->tw32k, GC_LH);
+    GC_RESERVE(ctx, w->tw32p, GC_LH);
+    GC_RESERVE(ctx, w->tw64p1, GC_LH);
+    GC_RESERVE(ctx, w->tw64p3, GC_LH);
+    GC_RESERVE(ctx, w->tw16k, GC_LH);              // last: the test above
     hipLaunchKernelGGL(tw_init_kernel, dim3(GC_LH / 256), dim3(256), 0, ctx->stream, w->tw16k, w->tw32k, w->tw32p);
     hipLaunchKernelGGL(tw64_init_kernel, dim3(GC_LH / 256), dim3(256), 0, ctx->stream, w->tw64p1, w->tw64p3);
     GC_HIP(hipGetLastError());
@@ -906,19 +898,18 @@ static int acq_prepare(gnsscorr_ctx *ctx)
         if (c.nfreq > w->maxfreq) w->maxfreq = c.nfreq;
         if (c.intg > w->maxintg) w->maxintg = c.intg;
     }
-    w->X_elems = (size_t)w->ngrid * w->maxintg * w->maxfreq * w->L;
-    GC_ALLOC(ctx, &w->X, sizeof(float2) * w->X_elems);
-    GC_ALLOC(ctx, &w->C, sizeof(float2) * (size_t)nch * w->L);
-    GC_ALLOC(ctx, &w->rows, sizeof(GcAcqRow) * (size_t)nch * w->maxintg * w->maxfreq);
-    GC_ALLOC(ctx, &w->arrive, sizeof(int) * ((size_t)nch * w->maxintg + nch));
-    GC_ALLOC(ctx, &w->iters, sizeof(int) * nch);
-    GC_ALLOC(ctx, &w->res, sizeof(gnsscorr_acqres_t) * nch);
-    GC_ALLOC(ctx, &w->d_grid_chan, sizeof(int) * w->ngrid);
-    GC_ALLOC(ctx, &w->d_grid_wrpos, sizeof(uint64_t) * w->ngrid);
+    GC_RESERVE(ctx, w->X, (size_t)w->ngrid * w->maxintg * w->maxfreq * w->L);
+    GC_RESERVE(ctx, w->rows, (size_t)nch * w->maxintg * w->maxfreq);
+    GC_RESERVE(ctx, w->arrive, (size_t)nch * w->maxintg + nch);
+    GC_RESERVE(ctx, w->iters, nch);
+    GC_RESERVE(ctx, w->res, nch);
+    GC_RESERVE(ctx, w->d_grid_chan, w->ngrid);
+    GC_RESERVE(ctx, w->d_grid_wrpos, w->ngrid);
     GC_HIP(hipMemcpyAsync(w->d_grid_chan, w->grid_chan.data(), sizeof(int) * w->ngrid, hipMemcpyHostToDevice,
                           ctx->stream));
-    GC_ALLOC(ctx, &w->car, sizeof(GcAcqCar) * (size_t)w->ngrid * w->maxfreq);
-    GC_ALLOC(ctx, &w->car_overflow, sizeof(int));
+    GC_RESERVE(ctx, w->car, (size_t)w->ngrid * w->maxfreq);
+    GC_RESERVE(ctx, w->car_overflow, 1);
+    GC_RESERVE(ctx, w->C, (size_t)nch * w->L);     // last: the test above
     GC_HIP(hipMemsetAsync(w->car_overflow, 0, sizeof(int), ctx->stream));
     hipLaunchKernelGGL(acq_nco_kernel, dim3((w->ngrid * w->maxfreq + 63) / 64), dim3(64), 0, ctx->stream, ctx->dchan,
                        w->d_grid_chan, ctx->dfreqs, w->car, w->ngrid, w->maxfreq, w->car_overflow);
@@ -933,7 +924,7 @@ static int acq_prepare(gnsscorr_ctx *ctx)
     GC_HIP(hipMemcpyAsync(&over, w->car_overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
     if (over) {
-        hipFree(w->C); w->C = nullptr;       // not prepared
+        w->C.reset();       // not prepared
         return gc_fail(GNSSCORR_EINVAL, "acquisition: %d Doppler bins need more carrier NCO pieces than the tables hold", over);
     }
     return GNSSCORR_OK;
@@ -1040,10 +1031,8 @@ extern "C" int gnsscorr_trk_start_from_acq(gnsscorr_ctx *ctx)
 {
     if (!ctx || !ctx->acq || !ctx->acq->ran) return gc_fail(GNSSCORR_ESTATE, "trk_start_from_acq: no acq_run yet");
     GC_HIP(hipSetDevice(ctx->device));
-    if (ctx->stream2) GC_HIP(hipStreamSynchronize(ctx->stream2));     // a look-ahead plan may be in flight
-    if (ctx->stream3) GC_HIP(hipStreamSynchronize(ctx->stream3));
-    ctx->ahead_valid = false;                                         // ... and is dropped
-    ctx->state_touched = true;
+    int rc = gc_quiesce(ctx);
+    if (rc) return rc;
     hipLaunchKernelGGL(acq_to_trk_kernel, dim3((ctx->nch + 63) / 64), dim3(64), 0, ctx->stream, ctx->dchan,
                        ctx->acq->res, ctx->dstate2[ctx->state_cur], ctx->nch);
     GC_HIP(hipGetLastError());
@@ -1058,11 +1047,7 @@ extern "C" int gnsscorr_acq_power(gnsscorr_ctx *ctx, int ch, double *power)
     GcAcqWork *w = ctx->acq;
     const GcChan &c = ctx->hchan[ch];
     const size_t elems = (size_t)c.nfreq * c.nsamp;
-    if (elems > w->P_elems) {
-        hipFree(w->P); w->P = nullptr; w->P_elems = 0;
-        GC_ALLOC(ctx, &w->P, sizeof(double) * elems);
-        w->P_elems = elems;
-    }
+    GC_RESERVE(ctx, w->P, elems);
     // iteration count of the last run is still in w->iters[ch]; rows of this channel are rewritten
     // with identical values
     if (w->L == 2 * GC_L)
@@ -1105,10 +1090,10 @@ extern "C" int gnsscorr_pspec(gnsscorr_ctx *ctx, const float *cpx, int n, int fl
     int rc = acq_tables(ctx);
     if (rc) return rc;
     GcAcqWork *w = ctx->acq;
-    float2 *din = nullptr;
-    double *dps = nullptr;
-    GC_HIP(hipMalloc((void **)&din, sizeof(float2) * n));
-    if (hipMalloc((void **)&dps, sizeof(double) * n) != hipSuccess) { hipFree(din); return gc_fail(GNSSCORR_EHIP, "pspec: hipMalloc"); }
+    GcDevBuf<float2> din;
+    GcDevBuf<double> dps;
+    GC_RESERVE(ctx, din, n);
+    GC_RESERVE(ctx, dps, n);
     hipMemcpyAsync(din, cpx, sizeof(float2) * n, hipMemcpyHostToDevice, ctx->stream);
     if (flagsum) hipMemcpyAsync(dps, pspec, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream);
     hipLaunchKernelGGL(pspec_kernel, dim3(1), dim3(GC_FFT_THREADS), GC_FFT_LDS + 256, ctx->stream, din, n,
@@ -1116,7 +1101,6 @@ extern "C" int gnsscorr_pspec(gnsscorr_ctx *ctx, const float *cpx, int n, int fl
     hipError_t e = hipGetLastError();
     hipMemcpyAsync(pspec, dps, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream);
     hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    hipFree(din); hipFree(dps);
     if (e != hipSuccess) return gc_fail_hip(e, "pspec_kernel", __FILE__, __LINE__);
     if (e2 != hipSuccess) return gc_fail_hip(e2, "pspec sync", __FILE__, __LINE__);
     return GNSSCORR_OK;

@@ -36,6 +36,21 @@ extern "C" int gnsscorr_device_count(void)
     return n;
 }
 
+// every stream and event of the context (of a failed create: those made so far)
+static void destroy_handles(gnsscorr_ctx *ctx)
+{
+    for (auto &kv : ctx->timers)
+        for (auto &p : kv.second.pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
+    for (GcPlanSlot &s : ctx->slot)
+        for (hipEvent_t e : {s.ev_plan, s.ev_used, s.ev_corr, s.ev_fin})
+            if (e) hipEventDestroy(e);
+    for (hipEvent_t e : {ctx->ev_spec, ctx->ev_chain, ctx->ev_pin[0], ctx->ev_pin[1], ctx->ev_in})
+        if (e) hipEventDestroy(e);
+    for (hipStream_t s : {ctx->stream_plan, ctx->stream_finish, ctx->stream_discover, ctx->stream_in})
+        if (s) hipStreamDestroy(s);
+    if (ctx->own_stream) hipStreamDestroy(ctx->stream);
+}
+
 extern "C" int gnsscorr_create(gnsscorr_ctx **out, int device, void *stream)
 {
     if (!out) return gc_fail(GNSSCORR_EINVAL, "gnsscorr_create: null out pointer");
@@ -46,114 +61,70 @@ extern "C" int gnsscorr_create(gnsscorr_ctx **out, int device, void *stream)
     GC_HIP(hipSetDevice(device));
     gnsscorr_ctx *ctx = new gnsscorr_ctx();
     ctx->device = device;
+    hipError_t e = hipSuccess;
     if (stream) {
         ctx->stream = (hipStream_t)stream;
     } else {
-        hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) { delete ctx; return gc_fail_hip(e, "hipStreamCreate", __FILE__, __LINE__); }
-        ctx->own_stream = true;
+        e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
+        ctx->own_stream = e == hipSuccess;
     }
-    if (hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking) != hipSuccess) ctx->stream2 = nullptr;
-    if (!ctx->stream2 || hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking) != hipSuccess) ctx->stream3 = nullptr;
-    if (ctx->stream2 && (hipStreamCreateWithFlags(&ctx->stream4, hipStreamNonBlocking) != hipSuccess ||
-                         hipEventCreateWithFlags(&ctx->ev_spec, hipEventDisableTiming) != hipSuccess ||
-                         hipEventCreateWithFlags(&ctx->ev_chain, hipEventDisableTiming) != hipSuccess)) {
-        if (ctx->stream4) hipStreamDestroy(ctx->stream4);
-        ctx->stream4 = nullptr;
-    }
-    for (int i = 0; i < 2 && ctx->stream2; i++) {
-        hipEventCreateWithFlags(&ctx->ev_plan[i], hipEventDisableTiming);
-        hipEventCreateWithFlags(&ctx->ev_used[i], hipEventDisableTiming);
-        hipEventCreateWithFlags(&ctx->ev_corr[i], hipEventDisableTiming);
-        hipEventCreateWithFlags(&ctx->ev_fin[i], hipEventDisableTiming);
+    for (hipStream_t *s : {&ctx->stream_plan, &ctx->stream_finish, &ctx->stream_discover})
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+    for (hipEvent_t *ev : {&ctx->ev_spec, &ctx->ev_chain, &ctx->slot[0].ev_plan, &ctx->slot[0].ev_used, &ctx->slot[0].ev_corr,
+                           &ctx->slot[0].ev_fin, &ctx->slot[1].ev_plan, &ctx->slot[1].ev_used, &ctx->slot[1].ev_corr,
+                           &ctx->slot[1].ev_fin})
+        if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        destroy_handles(ctx);
+        delete ctx;
+        return gc_fail_hip(e, "gnsscorr_create: stream / event", __FILE__, __LINE__);
     }
     *out = ctx;
     return GNSSCORR_OK;
 }
 
-static void free_channels(gnsscorr_ctx *ctx)
+int gc_quiesce(gnsscorr_ctx *ctx, bool ingest)
 {
-    hipFree(ctx->dchan);  ctx->dchan = nullptr;
-    hipFree(ctx->dcodes); ctx->dcodes = nullptr;
-    hipFree(ctx->dfreqs); ctx->dfreqs = nullptr;
-    for (int i = 0; i < 2; i++) { hipFree(ctx->dstate2[i]); ctx->dstate2[i] = nullptr; }
-    hipFree(ctx->dloop); ctx->dloop = nullptr;
-    hipFree(ctx->dloopdone); ctx->dloopdone = nullptr;
-    hipFree(ctx->dlooplog); ctx->dlooplog = nullptr;
-    hipFree(ctx->dstep_meta); ctx->dstep_meta = nullptr;
-    hipFree(ctx->dstep_unit); ctx->dstep_unit = nullptr;
-    hipFree(ctx->dstep_segs); ctx->dstep_segs = nullptr;
-    hipFree(ctx->dstep_rounds); ctx->dstep_rounds = nullptr;
-    hipFree(ctx->dstep_partial); ctx->dstep_partial = nullptr;
-    ctx->step_nseg = 0;
-    ctx->looplog_cap = 0;
-    ctx->last_loop_nper = 0;
-    ctx->state_cur = 0;
-    ctx->ahead_valid = false;
+    if (ingest && ctx->stream_in) GC_HIP(hipStreamSynchronize(ctx->stream_in));
+    for (hipStream_t s : {ctx->stream_plan, ctx->stream_finish, ctx->stream_discover, ctx->stream})
+        GC_HIP(hipStreamSynchronize(s));
+    ctx->ahead_valid = false;          // a look-ahead plan may have been in flight: it is dropped
     ctx->state_touched = true;
+    return GNSSCORR_OK;
 }
 
-static void free_trk_buffers(gnsscorr_ctx *ctx)
+// the channel set's device buffers; the next set starts from nothing
+static void drop_channel_buffers(gnsscorr_ctx *ctx)
 {
-    for (int i = 0; i < 2; i++) { hipFree(ctx->dplan2[i]); ctx->dplan2[i] = nullptr; }
-    for (int i = 0; i < 2; i++) { hipFree(ctx->dspec2[i]); ctx->dspec2[i] = nullptr; }
-    hipFree(ctx->detab); ctx->detab = nullptr;
-    ctx->spec_ahead_valid = false;
-    ctx->ahead_valid = false;
-    hipFree(ctx->dcorrI); ctx->dcorrI = nullptr;
-    hipFree(ctx->dcorrQ); ctx->dcorrQ = nullptr;
-    hipFree(ctx->dsumI);  ctx->dsumI = nullptr;
-    hipFree(ctx->dfinish); ctx->dfinish = nullptr;
-    hipFree(ctx->dsumQ);  ctx->dsumQ = nullptr;
-    for (int i = 0; i < 2; i++) { hipFree(ctx->dpartial2[i]); ctx->dpartial2[i] = nullptr; }
-    ctx->fin_pending[0] = ctx->fin_pending[1] = false;
-    for (int i = 0; i < 2; i++) {
-        hipFree(ctx->dunit2[i]); ctx->dunit2[i] = nullptr;
-        hipFree(ctx->drounds2[i]); ctx->drounds2[i] = nullptr;
-        hipFree(ctx->dsegs2[i]); ctx->dsegs2[i] = nullptr;
-        hipFree(ctx->dnsamp2[i]); ctx->dnsamp2[i] = nullptr;
+    gc_acq_free(ctx);
+    gc_spec_free(ctx);
+    for (GcPlanSlot &s : ctx->slot) {
+        s.plan.reset(); s.unit.reset(); s.rounds.reset(); s.segs.reset(); s.nsamp.reset(); s.partial.reset();
+        s.fin_pending = false;
     }
-    hipFree(ctx->dnco_overflow); ctx->dnco_overflow = nullptr;
-    hipFree(ctx->dring_viol); ctx->dring_viol = nullptr;
-    ctx->plan_cap = 0;
+    for (int i = 0; i < 2; i++) { ctx->dstate2[i].reset(); ctx->dspec2[i].reset(); }
+    ctx->dchan.reset(); ctx->dcodes.reset(); ctx->dfreqs.reset(); ctx->detab.reset();
+    ctx->dcorrI.reset(); ctx->dcorrQ.reset(); ctx->dsumI.reset(); ctx->dsumQ.reset(); ctx->dfinish.reset();
+    ctx->dnco_overflow.reset(); ctx->dring_viol.reset();
+    ctx->dloop.reset(); ctx->dloopdone.reset(); ctx->dlooplog.reset();
+    ctx->dstep_meta.reset(); ctx->dstep_unit.reset(); ctx->dstep_segs.reset(); ctx->dstep_rounds.reset();
+    ctx->dstep_partial.reset();
+    ctx->spec_ahead_valid = false;
+    ctx->trk_units = 0;
+    ctx->step_nseg = 0;
+    ctx->last_loop_nper = 0;
+    ctx->state_cur = 0;
 }
 
 extern "C" void gnsscorr_destroy(gnsscorr_ctx *ctx)
 {
     if (!ctx) return;
     hipSetDevice(ctx->device);
-    if (ctx->stream_in) hipStreamSynchronize(ctx->stream_in);
-    hipStreamSynchronize(ctx->stream);
-    if (ctx->stream2) hipStreamSynchronize(ctx->stream2);
-    if (ctx->stream3) hipStreamSynchronize(ctx->stream3);
-    if (ctx->stream4) hipStreamSynchronize(ctx->stream4);
+    gc_quiesce(ctx, true);
     gc_acq_free(ctx);
     gc_spec_free(ctx);
-    free_trk_buffers(ctx);
-    free_channels(ctx);
-    for (auto &r : ctx->ring)
-        if (r.owned && r.mem) hipFree(r.mem);
-    for (auto &kv : ctx->timers)
-        for (auto &p : kv.second.pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-    for (int i = 0; i < 2; i++) {
-        if (ctx->ev_plan[i]) hipEventDestroy(ctx->ev_plan[i]);
-        if (ctx->ev_used[i]) hipEventDestroy(ctx->ev_used[i]);
-        if (ctx->ev_corr[i]) hipEventDestroy(ctx->ev_corr[i]);
-        if (ctx->ev_fin[i]) hipEventDestroy(ctx->ev_fin[i]);
-    }
-    if (ctx->stream_in) {
-        hipStreamSynchronize(ctx->stream_in);
-        for (int i = 0; i < 2; i++) { hipHostFree(ctx->pin[i]); hipFree(ctx->dstage[i]); if (ctx->ev_pin[i]) hipEventDestroy(ctx->ev_pin[i]); }
-        if (ctx->ev_in) hipEventDestroy(ctx->ev_in);
-        hipStreamDestroy(ctx->stream_in);
-    }
-    if (ctx->stream2) hipStreamDestroy(ctx->stream2);
-    if (ctx->stream3) hipStreamDestroy(ctx->stream3);
-    if (ctx->stream4) { hipStreamSynchronize(ctx->stream4); hipStreamDestroy(ctx->stream4); }
-    if (ctx->ev_spec) hipEventDestroy(ctx->ev_spec);
-    if (ctx->ev_chain) hipEventDestroy(ctx->ev_chain);
-    if (ctx->own_stream) hipStreamDestroy(ctx->stream);
-    delete ctx;
+    destroy_handles(ctx);
+    delete ctx;                        // the buffers it owns go with it
 }
 
 extern "C" void *gnsscorr_stream(gnsscorr_ctx *ctx) { return ctx ? (void *)ctx->stream : nullptr; }
@@ -162,8 +133,8 @@ extern "C" void *gnsscorr_stream(gnsscorr_ctx *ctx) { return ctx ? (void *)ctx->
 // of its own).
 static int outputs_ready(gnsscorr_ctx *ctx)
 {
-    if (ctx->fin_pending[ctx->last_slot])
-        GC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_fin[ctx->last_slot], 0));
+    const GcPlanSlot &last = ctx->slot[ctx->last_slot];
+    if (last.fin_pending) GC_HIP(hipStreamWaitEvent(ctx->stream, last.ev_fin, 0));
     return GNSSCORR_OK;
 }
 
@@ -204,18 +175,17 @@ extern "C" int gnsscorr_ring_create(gnsscorr_ctx *ctx, int ftype, int dtype, uin
         // transfers into the old ring (ingest stream) and kernels reading it (compute stream) are over before it goes
         if (ctx->stream_in) GC_HIP(hipStreamSynchronize(ctx->stream_in));
         GC_HIP(hipStreamSynchronize(ctx->stream));
-        if (r->owned && r->mem) hipFree(r->mem);
+        r->own.reset();
         r->mem = nullptr;
-        r->owned = false;
         if (devmem) {
             r->mem = (int8_t *)devmem;
         } else {
-            GC_HIP(hipMalloc((void **)&r->mem, (size_t)dtype * ringlen));
+            GC_RESERVE(ctx, r->own, (size_t)dtype * ringlen);
+            r->mem = r->own;
             // the zero fill is over before the first push: pushes run on the ingest stream, which nothing orders
             // behind the compute stream
             GC_HIP(hipMemsetAsync(r->mem, 0, (size_t)dtype * ringlen, ctx->stream));
             GC_HIP(hipStreamSynchronize(ctx->stream));
-            r->owned = true;
         }
         r->dtype = dtype;
         r->ringlen = ringlen;
@@ -232,12 +202,13 @@ int gc_ingest_fence(gnsscorr_ctx *ctx);
 
 static int ingest_init(gnsscorr_ctx *ctx)
 {
-    if (ctx->stream_in) return GNSSCORR_OK;
-    GC_HIP(hipStreamCreateWithFlags(&ctx->stream_in, hipStreamNonBlocking));
+    if (ctx->ev_in) return GNSSCORR_OK;           // made last (a failed init is completed by the next call)
+    if (!ctx->stream_in) GC_HIP(hipStreamCreateWithFlags(&ctx->stream_in, hipStreamNonBlocking));
     for (int i = 0; i < 2; i++) {
-        GC_HIP(hipHostMalloc((void **)&ctx->pin[i], GC_PIN_BYTES));
-        GC_HIP(hipMalloc((void **)&ctx->dstage[i], GC_PIN_BYTES));
-        GC_HIP(hipEventCreateWithFlags(&ctx->ev_pin[i], hipEventDisableTiming));
+        int rc = ctx->pin[i].reserve(GC_PIN_BYTES);
+        if (rc) return rc;
+        GC_RESERVE(ctx, ctx->dstage[i], GC_PIN_BYTES);
+        if (!ctx->ev_pin[i]) GC_HIP(hipEventCreateWithFlags(&ctx->ev_pin[i], hipEventDisableTiming));
     }
     GC_HIP(hipEventCreateWithFlags(&ctx->ev_in, hipEventDisableTiming));
     return GNSSCORR_OK;
@@ -482,14 +453,9 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
             return gc_fail(GNSSCORR_EINVAL, "channel %d: ring %d (%llu samples) is shorter than a code period (%d + 100 + %d)",
                            i, c.ftype, (unsigned long long)r.ringlen, c.nsamp, 32 / c.dtype);
     }
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->stream2) GC_HIP(hipStreamSynchronize(ctx->stream2));
-    if (ctx->stream3) GC_HIP(hipStreamSynchronize(ctx->stream3));
-    if (ctx->stream4) GC_HIP(hipStreamSynchronize(ctx->stream4));
-    gc_acq_free(ctx);
-    gc_spec_free(ctx);
-    free_trk_buffers(ctx);
-    free_channels(ctx);
+    int rc = gc_quiesce(ctx);
+    if (rc) return rc;
+    drop_channel_buffers(ctx);
 
     ctx->nch = nch;
     ctx->hdesc.assign(ch, ch + nch);
@@ -535,16 +501,16 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
         if (g.smax > ctx->smax_max) ctx->smax_max = g.smax;
         if (d.nsamp + 100 > ctx->max_n) ctx->max_n = d.nsamp + 100;   // ref src/sdrtrk.c:23
     }
-    GC_ALLOC(ctx, &ctx->dchan, sizeof(GcChan) * nch);
-    GC_ALLOC(ctx, &ctx->dcodes, codes.size());
-    GC_ALLOC(ctx, &ctx->dfreqs, sizeof(double) * freqs.size());
+    GC_RESERVE(ctx, ctx->dchan, nch);
+    GC_RESERVE(ctx, ctx->dcodes, codes.size());
+    GC_RESERVE(ctx, ctx->dfreqs, freqs.size());
     for (int i = 0; i < 2; i++) {
-        GC_ALLOC(ctx, &ctx->dstate2[i], sizeof(GcTrkState) * nch);
+        GC_RESERVE(ctx, ctx->dstate2[i], nch);
         GC_HIP(hipMemsetAsync(ctx->dstate2[i], 0, sizeof(GcTrkState) * nch, ctx->stream));
     }
-    GC_ALLOC(ctx, &ctx->dloop, sizeof(gnsscorr_loop_t) * nch);
+    GC_RESERVE(ctx, ctx->dloop, nch);
     GC_HIP(hipMemsetAsync(ctx->dloop, 0, sizeof(gnsscorr_loop_t) * nch, ctx->stream));
-    GC_ALLOC(ctx, &ctx->dloopdone, sizeof(int) * nch + sizeof(uint64_t) * nch + 8);
+    GC_RESERVE(ctx, ctx->dloopdone, 3 * (size_t)nch + 2);        // int [nch], then uint64 [nch] + 8 bytes
     GC_HIP(hipMemsetAsync(ctx->dloopdone, 0, sizeof(int) * nch + sizeof(uint64_t) * nch + 8, ctx->stream));
     GC_HIP(hipMemcpyAsync(ctx->dcodes, codes.data(), codes.size(), hipMemcpyHostToDevice, ctx->stream));
     GC_HIP(hipMemcpyAsync(ctx->dfreqs, freqs.data(), sizeof(double) * freqs.size(), hipMemcpyHostToDevice,
@@ -571,12 +537,8 @@ extern "C" int gnsscorr_trk_set_state(gnsscorr_ctx *ctx, int ch0, int nch, const
         return gc_fail(GNSSCORR_EINVAL, "trk_set_state: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
     static_assert(sizeof(gnsscorr_trkstate_t) == sizeof(GcTrkState), "state layout");
     GC_HIP(hipSetDevice(ctx->device));
-    if (ctx->stream2) GC_HIP(hipStreamSynchronize(ctx->stream2));     // a look-ahead plan may be in flight
-    if (ctx->stream3) GC_HIP(hipStreamSynchronize(ctx->stream3));
-    if (ctx->stream4) GC_HIP(hipStreamSynchronize(ctx->stream4));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->ahead_valid = false;                                         // ... and is dropped
-    ctx->state_touched = true;
+    int rc = gc_quiesce(ctx);
+    if (rc) return rc;
     GC_HIP(hipMemcpyAsync(ctx->dstate2[ctx->state_cur] + ch0, st, sizeof(GcTrkState) * nch, hipMemcpyHostToDevice,
                           ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
@@ -588,10 +550,9 @@ extern "C" int gnsscorr_trk_get_state(gnsscorr_ctx *ctx, int ch0, int nch, gnssc
     if (!ctx || !st || ch0 < 0 || nch <= 0 || ch0 + nch > ctx->nch)
         return gc_fail(GNSSCORR_EINVAL, "trk_get_state: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
     GC_HIP(hipSetDevice(ctx->device));
-    if (ctx->stream2) GC_HIP(hipStreamSynchronize(ctx->stream2));
-    if (ctx->stream3) GC_HIP(hipStreamSynchronize(ctx->stream3));
-    if (ctx->stream4) GC_HIP(hipStreamSynchronize(ctx->stream4));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
+    // (drains like gc_quiesce but keeps the look-ahead: reading the committed state leaves it valid)
+    for (hipStream_t s : {ctx->stream_plan, ctx->stream_finish, ctx->stream_discover, ctx->stream})
+        GC_HIP(hipStreamSynchronize(s));
     GC_HIP(hipMemcpyAsync(st, ctx->dstate2[ctx->state_cur] + ch0, sizeof(GcTrkState) * nch, hipMemcpyDeviceToHost,
                           ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
@@ -601,43 +562,40 @@ extern "C" int gnsscorr_trk_get_state(gnsscorr_ctx *ctx, int ch0, int nch, gnssc
 static int ensure_trk_buffers(gnsscorr_ctx *ctx, int nepoch)
 {
     const size_t units = (size_t)ctx->nch * nepoch;
-    if (units <= ctx->plan_cap) return GNSSCORR_OK;
-    if (ctx->stream2) GC_HIP(hipStreamSynchronize(ctx->stream2));
-    if (ctx->stream3) GC_HIP(hipStreamSynchronize(ctx->stream3));
-    if (ctx->stream4) GC_HIP(hipStreamSynchronize(ctx->stream4));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->ahead_valid) {            // a look-ahead plan advanced the state one batch: roll it back
-        ctx->ahead_valid = false;
-    }
-    free_trk_buffers(ctx);
-    for (int i = 0; i < 2; i++) GC_ALLOC(ctx, &ctx->dplan2[i], sizeof(GcTrkPlan) * units);
-    for (int i = 0; i < 2; i++) GC_ALLOC(ctx, &ctx->dspec2[i], sizeof(int) * gc_trk_spec_ints(units));
-    GC_ALLOC(ctx, &ctx->detab, sizeof(unsigned short) * units * GC_EDGTAB);
+    if (units <= ctx->trk_units) return GNSSCORR_OK;
+    // drains like gc_quiesce but leaves state_touched: the committed state is unchanged, so this batch still plans ahead
+    for (hipStream_t s : {ctx->stream_plan, ctx->stream_finish, ctx->stream_discover, ctx->stream})
+        GC_HIP(hipStreamSynchronize(s));
+    ctx->ahead_valid = false;          // (a look-ahead plan advanced the uncommitted state one batch: it is dropped)
     ctx->spec_ahead_valid = false;
-    GC_ALLOC(ctx, &ctx->dcorrI, sizeof(double) * units * ctx->ntap);
-    GC_ALLOC(ctx, &ctx->dcorrQ, sizeof(double) * units * ctx->ntap);
-    GC_ALLOC(ctx, &ctx->dsumI, sizeof(double) * ctx->nch * ctx->ntap);
-    GC_ALLOC(ctx, &ctx->dsumQ, sizeof(double) * ctx->nch * ctx->ntap);
-    GC_ALLOC(ctx, &ctx->dfinish, sizeof(unsigned long long) * ctx->nch * GC_FINISH_SCRATCH);
-    GC_HIP(hipMemsetAsync(ctx->dfinish, 0, sizeof(unsigned long long) * ctx->nch * GC_FINISH_SCRATCH, ctx->stream));
+    ctx->trk_units = 0;                // until every buffer below has its size
     ctx->nseg = 1;
     for (int i = 0; i < ctx->nch; i++) {
         const int s = gc_trk_nseg(ctx->hchan[i].dtype, ctx->max_n);
         if (s > ctx->nseg) ctx->nseg = s;
     }
-    for (int i = 0; i < 2; i++)
-        GC_ALLOC(ctx, &ctx->dpartial2[i], sizeof(int) * units * ctx->nseg * 2 * ctx->ntap);
-    for (int i = 0; i < 2; i++) {
-        GC_ALLOC(ctx, &ctx->dunit2[i], sizeof(GcTrkUnit) * units);
-        GC_ALLOC(ctx, &ctx->dnsamp2[i], sizeof(int) * units);
-        GC_ALLOC(ctx, &ctx->drounds2[i], sizeof(GcRound) * units * ctx->nseg * GC_MAXR);
-        GC_ALLOC(ctx, &ctx->dsegs2[i], sizeof(GcUnitSegs) * units);
+    for (GcPlanSlot &s : ctx->slot) {
+        GC_RESERVE(ctx, s.plan, units);
+        GC_RESERVE(ctx, s.partial, units * ctx->nseg * 2 * ctx->ntap);
+        GC_RESERVE(ctx, s.unit, units);
+        GC_RESERVE(ctx, s.nsamp, units);
+        GC_RESERVE(ctx, s.rounds, units * ctx->nseg * GC_MAXR);
+        GC_RESERVE(ctx, s.segs, units);
+        s.fin_pending = false;
     }
-    GC_ALLOC(ctx, &ctx->dnco_overflow, sizeof(int));
+    for (int i = 0; i < 2; i++) GC_RESERVE(ctx, ctx->dspec2[i], gc_trk_spec_ints(units));
+    GC_RESERVE(ctx, ctx->detab, units * GC_EDGTAB);
+    GC_RESERVE(ctx, ctx->dcorrI, units * ctx->ntap);
+    GC_RESERVE(ctx, ctx->dcorrQ, units * ctx->ntap);
+    GC_RESERVE(ctx, ctx->dsumI, (size_t)ctx->nch * ctx->ntap);
+    GC_RESERVE(ctx, ctx->dsumQ, (size_t)ctx->nch * ctx->ntap);
+    GC_RESERVE(ctx, ctx->dfinish, (size_t)ctx->nch * GC_FINISH_SCRATCH);
+    GC_HIP(hipMemsetAsync(ctx->dfinish, 0, sizeof(unsigned long long) * ctx->nch * GC_FINISH_SCRATCH, ctx->stream));
+    GC_RESERVE(ctx, ctx->dnco_overflow, 1);
     GC_HIP(hipMemsetAsync(ctx->dnco_overflow, 0, sizeof(int), ctx->stream));
-    GC_ALLOC(ctx, &ctx->dring_viol, sizeof(int));
+    GC_RESERVE(ctx, ctx->dring_viol, 1);
     GC_HIP(hipMemsetAsync(ctx->dring_viol, 0, sizeof(int), ctx->stream));
-    ctx->plan_cap = units;
+    ctx->trk_units = units;
     return GNSSCORR_OK;
 }
 
@@ -696,17 +654,17 @@ extern "C" int gnsscorr_trk_run(gnsscorr_ctx *ctx, int nepoch)
     }
     // ---- planner: use the look-ahead plan if it matches, else plan now ----
     // plan = the sequential NCO chain per channel (discovery pass + chain), on the planner stream into the
-    // slot's plan buffer; ev_plan[slot] marks it ready
-    hipStream_t ps = ctx->stream2 ? ctx->stream2 : ctx->stream;
-    auto plan_into = [&](int s) -> int {
+    // slot's plan buffer; ev_plan marks it ready
+    hipStream_t ps = ctx->stream_plan;
+    auto plan_into = [&](GcPlanSlot &sl) -> int {
         // the slot's partial sums were last read by the finish of two batches ago: ordering the plan
-        // behind it lets ev_plan[s] stand for "slot s is free and planned" on the main stream
-        if (ctx->stream2 && ctx->fin_pending[s]) GC_HIP(hipStreamWaitEvent(ps, ctx->ev_fin[s], 0));
+        // behind it lets ev_plan stand for "the slot is free and planned" on the main stream
+        if (sl.fin_pending) GC_HIP(hipStreamWaitEvent(ps, sl.ev_fin, 0));
         // claims of this batch: discovered ahead (while the previous batch's chain ran, from that batch's
         // input state) if nothing has touched the state since, else discovered now from the state itself
         const GcTrkState *sin = ctx->dstate2[ctx->state_cur];
         int buf;
-        if (ctx->stream4 && ctx->spec_pending) GC_HIP(hipStreamWaitEvent(ps, ctx->ev_spec, 0));
+        if (ctx->spec_pending) GC_HIP(hipStreamWaitEvent(ps, ctx->ev_spec, 0));
         if (ctx->spec_ahead_valid && !ctx->state_touched && ctx->spec_ahead_nepoch == nepoch && ctx->spec_ahead_state == (const void *)sin) {
             buf = ctx->spec_ahead_buf;
         } else {
@@ -719,102 +677,98 @@ extern "C" int gnsscorr_trk_run(gnsscorr_ctx *ctx, int nepoch)
         ctx->spec_pending = false;
         ctx->spec_last_buf = buf;
         ctx->spec_last_units = ctx->nch * nepoch;
-        if (ctx->stream4) {
-            // the next batch's claims, from the same input state, beside this batch's chain (the other buffer
-            // was last read by the chain in front of this one on the planner stream)
-            GC_HIP(hipEventRecord(ctx->ev_chain, ps));
-            GC_HIP(hipStreamWaitEvent(ctx->stream4, ctx->ev_chain, 0));
-            GcTimed t(ctx, "trk_spec", ctx->stream4);
-            int r2 = gc_launch_trk_spec(ctx->stream4, ctx->dchan, sin, ctx->nch, nepoch, ctx->dspec2[buf ^ 1], nepoch);
+        // the next batch's claims, from the same input state, beside this batch's chain (the other buffer
+        // was last read by the chain in front of this one on the planner stream)
+        GC_HIP(hipEventRecord(ctx->ev_chain, ps));
+        GC_HIP(hipStreamWaitEvent(ctx->stream_discover, ctx->ev_chain, 0));
+        {
+            GcTimed t(ctx, "trk_spec", ctx->stream_discover);
+            int r2 = gc_launch_trk_spec(ctx->stream_discover, ctx->dchan, sin, ctx->nch, nepoch, ctx->dspec2[buf ^ 1], nepoch);
             if (r2) return r2;
-            GC_HIP(hipEventRecord(ctx->ev_spec, ctx->stream4));
-            ctx->spec_pending = true;
-            ctx->spec_ahead_valid = true;
-            ctx->spec_ahead_buf = buf ^ 1;
-            ctx->spec_ahead_nepoch = nepoch;
-            ctx->spec_ahead_state = (const void *)ctx->dstate2[ctx->state_cur ^ 1];
+            GC_HIP(hipEventRecord(ctx->ev_spec, ctx->stream_discover));
         }
+        ctx->spec_pending = true;
+        ctx->spec_ahead_valid = true;
+        ctx->spec_ahead_buf = buf ^ 1;
+        ctx->spec_ahead_nepoch = nepoch;
+        ctx->spec_ahead_state = (const void *)ctx->dstate2[ctx->state_cur ^ 1];
         {
             GcTimed t(ctx, "trk_plan", ps);
             int r2 = gc_launch_trk_plan(ps, ctx->dchan, sin, ctx->dstate2[ctx->state_cur ^ 1],
-                                        ctx->dplan2[s], ctx->nch, nepoch, ctx->dspec2[buf]);
+                                        sl.plan, ctx->nch, nepoch, ctx->dspec2[buf]);
             if (r2) return r2;
         }
-        if (ctx->stream2) GC_HIP(hipEventRecord(ctx->ev_plan[s], ps));
+        GC_HIP(hipEventRecord(sl.ev_plan, ps));
         return 0;
     };
     const int slot = ctx->plan_slot;
+    GcPlanSlot &cur = ctx->slot[slot];
     if (!(ctx->ahead_valid && ctx->ahead_nepoch == nepoch)) {
         if (ctx->ahead_valid) {        // planned for another batch length: the committed state is untouched
             GC_HIP(hipStreamSynchronize(ps));
             ctx->ahead_valid = false;
         }
-        if (ctx->stream2) {            // order after whatever the main stream did to the state / buffers
-            GC_HIP(hipEventRecord(ctx->ev_used[slot], ctx->stream));
-            GC_HIP(hipStreamWaitEvent(ps, ctx->ev_used[slot], 0));
-        }
-        rc = plan_into(slot);
+        // order after whatever the main stream did to the state / buffers
+        GC_HIP(hipEventRecord(cur.ev_used, ctx->stream));
+        GC_HIP(hipStreamWaitEvent(ps, cur.ev_used, 0));
+        rc = plan_into(cur);
         if (rc) return rc;
     }
-    if (ctx->stream2) GC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_plan[slot], 0));
+    GC_HIP(hipStreamWaitEvent(ctx->stream, cur.ev_plan, 0));
     // the per-unit constants and NCO tables of the planned periods: on the main stream, in front of the
     // correlator that reads them (the planner stream carries nothing but the sequential chain)
     {
-        const int s = slot;
         GcTimed t(ctx, "trk_expand");
-        int r2 = gc_launch_trk_expand(ctx->stream, ctx->dchan, ctx->dplan2[s], ctx->dunit2[s], ctx->dsegs2[s], ctx->dnsamp2[s],
-                                      ctx->nch, nepoch, ctx->drounds2[s], ctx->nseg, ctx->max_n, ctx->dnco_overflow);
+        int r2 = gc_launch_trk_expand(ctx->stream, ctx->dchan, cur.plan, cur.unit, cur.segs, cur.nsamp,
+                                      ctx->nch, nepoch, cur.rounds, ctx->nseg, ctx->max_n, ctx->dnco_overflow);
         if (r2) return r2;
     }
     // the planned periods against what the rings hold now
     // (the write positions travel as kernel arguments: no copy, no host synchronisation per batch)
-    rc = gc_launch_trk_ringcheck(ctx->stream, ctx->dchan, ctx->dplan2[slot], (const int8_t *)ctx->ring[0].mem, wr0, wr1, ctx->nch,
+    rc = gc_launch_trk_ringcheck(ctx->stream, ctx->dchan, cur.plan, (const int8_t *)ctx->ring[0].mem, wr0, wr1, ctx->nch,
                                  nepoch, ctx->dring_viol);
     if (rc) return rc;
     bool have[3] = {false, false, false};
     for (int i = 0; i < ctx->nch; i++) have[ctx->hchan[i].dtype] = true;
-    if (!ctx->stream2 && ctx->fin_pending[slot]) GC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_fin[slot], 0));
     {
         // start samples of the periods' chip edges, for the correlator's look-up phase
         GcTimed t(ctx, "trk_edges");
-        rc = gc_launch_trk_edges(ctx->stream, ctx->dchan, ctx->dunit2[slot], ctx->dsegs2[slot], ctx->detab, ctx->nch, nepoch);
+        rc = gc_launch_trk_edges(ctx->stream, ctx->dchan, cur.unit, cur.segs, ctx->detab, ctx->nch, nepoch);
         if (rc) return rc;
     }
     for (int dtype = 1; dtype <= 2; dtype++) {
         if (!have[dtype]) continue;
         GcTimed t(ctx, "trk_corr");
-        rc = gc_launch_trk_corr(ctx->stream, ctx->dchan, ctx->dunit2[slot], ctx->dsegs2[slot], ctx->drounds2[slot], ctx->dpartial2[slot],
+        rc = gc_launch_trk_corr(ctx->stream, ctx->dchan, cur.unit, cur.segs, cur.rounds, cur.partial,
                                 ctx->nch, nepoch, ctx->nseg, ctx->ntap, dtype, ctx->ntap, ctx->max_n, ctx->smax_max, ctx->detab);
         if (rc) return rc;
     }
-    if (ctx->stream2) GC_HIP(hipEventRecord(ctx->ev_corr[slot], ctx->stream));     // slot buffers consumed, partials ready
+    GC_HIP(hipEventRecord(cur.ev_corr, ctx->stream));     // slot buffers consumed, partials ready
     // every launch of the batch was issued: only now the plan's output state becomes the committed one
     ctx->ahead_valid = false;
     ctx->state_cur ^= 1;
     ctx->plan_slot ^= 1;
     // ---- look ahead: plan the next batch of the same length while this one is correlated ----
-    if (ctx->stream2 && !ctx->state_touched) {
-        const int ns = ctx->plan_slot;
-        GC_HIP(hipStreamWaitEvent(ps, ctx->ev_corr[ns], 0));        // its previous contents were consumed
-        rc = plan_into(ns);
+    if (!ctx->state_touched) {
+        GcPlanSlot &next = ctx->slot[ctx->plan_slot];
+        GC_HIP(hipStreamWaitEvent(ps, next.ev_corr, 0));        // its previous contents were consumed
+        rc = plan_into(next);
         if (rc) return rc;
         ctx->ahead_valid = true;
         ctx->ahead_nepoch = nepoch;
     }
     ctx->state_touched = false;
     // ---- finish on its own stream: the main stream goes straight from this batch's correlator to the
-    // next one's, the outputs become valid at ev_fin[slot] ----
+    // next one's, the outputs become valid at the slot's ev_fin ----
     {
-        hipStream_t fs = ctx->stream3 ? ctx->stream3 : ctx->stream;
-        if (ctx->stream3) GC_HIP(hipStreamWaitEvent(fs, ctx->ev_corr[slot], 0));
+        hipStream_t fs = ctx->stream_finish;
+        GC_HIP(hipStreamWaitEvent(fs, cur.ev_corr, 0));
         GcTimed t(ctx, "trk_finish", fs);
-        rc = gc_launch_trk_finish(fs, ctx->dpartial2[slot], ctx->dcorrI, ctx->dcorrQ, ctx->dsumI, ctx->dsumQ,
+        rc = gc_launch_trk_finish(fs, cur.partial, ctx->dcorrI, ctx->dcorrQ, ctx->dsumI, ctx->dsumQ,
                                   ctx->dfinish, ctx->nch, nepoch, ctx->nseg, ctx->ntap);
         if (rc) return rc;
-        if (ctx->stream3) {
-            GC_HIP(hipEventRecord(ctx->ev_fin[slot], fs));
-            ctx->fin_pending[slot] = true;
-        }
+        GC_HIP(hipEventRecord(cur.ev_fin, fs));
+        cur.fin_pending = true;
     }
     ctx->last_slot = slot;
     ctx->last_nepoch = nepoch;
@@ -825,17 +779,6 @@ extern "C" int gnsscorr_trk_run(gnsscorr_ctx *ctx, int nepoch)
 // ---------------------------------------------------------------------------
 // tracking, closed loop
 // ---------------------------------------------------------------------------
-static int loop_quiesce(gnsscorr_ctx *ctx)
-{
-    if (ctx->stream2) GC_HIP(hipStreamSynchronize(ctx->stream2));     // a look-ahead plan may be in flight
-    if (ctx->stream3) GC_HIP(hipStreamSynchronize(ctx->stream3));
-    if (ctx->stream4) GC_HIP(hipStreamSynchronize(ctx->stream4));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->ahead_valid = false;                                         // ... and is dropped
-    ctx->state_touched = true;
-    return GNSSCORR_OK;
-}
-
 extern "C" int gnsscorr_loop_set(gnsscorr_ctx *ctx, int ch0, int nch, const gnsscorr_loop_t *lp)
 {
     if (!ctx || !lp || ch0 < 0 || nch <= 0 || ch0 + nch > ctx->nch)
@@ -849,7 +792,7 @@ extern "C" int gnsscorr_loop_set(gnsscorr_ctx *ctx, int ch0, int nch, const gnss
             return gc_fail(GNSSCORR_EINVAL, "loop_set: channel %d: loopms %d, rate %d (rate 1..20)", ch0 + i, l.loopms, l.rate);
     }
     GC_HIP(hipSetDevice(ctx->device));
-    { int rc = loop_quiesce(ctx); if (rc) return rc; }
+    { int rc = gc_quiesce(ctx); if (rc) return rc; }
     GC_HIP(hipMemcpyAsync(ctx->dloop + ch0, lp, sizeof(gnsscorr_loop_t) * nch, hipMemcpyHostToDevice, ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < nch; i++) {
@@ -864,7 +807,7 @@ extern "C" int gnsscorr_loop_get(gnsscorr_ctx *ctx, int ch0, int nch, gnsscorr_l
     if (!ctx || !lp || ch0 < 0 || nch <= 0 || ch0 + nch > ctx->nch)
         return gc_fail(GNSSCORR_EINVAL, "loop_get: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
     GC_HIP(hipSetDevice(ctx->device));
-    { int rc = loop_quiesce(ctx); if (rc) return rc; }
+    { int rc = gc_quiesce(ctx); if (rc) return rc; }
     GC_HIP(hipMemcpyAsync(lp, ctx->dloop + ch0, sizeof(gnsscorr_loop_t) * nch, hipMemcpyDeviceToHost, ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
     return GNSSCORR_OK;
@@ -881,15 +824,13 @@ static int ensure_step_buffers(gnsscorr_ctx *ctx)
     }
     if (nseg > 64) return gc_fail(GNSSCORR_EINVAL, "trk_run_loop: period of %d samples too long (%d rounds, 64 at most)", ctx->max_n, nseg);
     const size_t units = (size_t)ctx->nch * GC_STEP_KMAX;
-    GC_ALLOC(ctx, &ctx->dstep_meta, sizeof(GcStepMeta) * ctx->nch);
-    GC_ALLOC(ctx, &ctx->dstep_unit, sizeof(GcTrkUnit) * units);
-    GC_ALLOC(ctx, &ctx->dstep_segs, sizeof(GcUnitSegs) * units);
-    GC_ALLOC(ctx, &ctx->dstep_rounds, sizeof(GcRound) * units * nseg * 4);        // four rounds (one per wavefront) per workgroup
-    GC_ALLOC(ctx, &ctx->dstep_partial, sizeof(int) * units * nseg * 2 * ctx->ntap);
-    if (!ctx->hostflags) {
-        GC_HIP(hipHostMalloc((void **)&ctx->hostflags, 64, hipHostMallocMapped));
-        GC_HIP(hipHostGetDevicePointer((void **)&ctx->hostflags_dev, ctx->hostflags, 0));
-    }
+    GC_RESERVE(ctx, ctx->dstep_unit, units);
+    GC_RESERVE(ctx, ctx->dstep_segs, units);
+    GC_RESERVE(ctx, ctx->dstep_rounds, units * nseg * 4);        // four rounds (one per wavefront) per workgroup
+    GC_RESERVE(ctx, ctx->dstep_partial, units * nseg * 2 * ctx->ntap);
+    int rc = ctx->hostflags.reserve(16, hipHostMallocMapped);
+    if (rc) return rc;
+    GC_RESERVE(ctx, ctx->dstep_meta, ctx->nch);                   // last: the test above
     ctx->step_nseg = nseg;
     return GNSSCORR_OK;
 }
@@ -904,20 +845,15 @@ extern "C" int gnsscorr_trk_run_loop(gnsscorr_ctx *ctx, int nperiod)
     rc = ensure_step_buffers(ctx);
     if (rc) return rc;
     // the look-ahead planner of the batched interface works on the same state: stop it, drop its plan
-    if (ctx->ahead_valid || ctx->fin_pending[0] || ctx->fin_pending[1]) { rc = loop_quiesce(ctx); if (rc) return rc; }
+    if (ctx->ahead_valid || ctx->slot[0].fin_pending || ctx->slot[1].fin_pending) { rc = gc_quiesce(ctx); if (rc) return rc; }
     ctx->ahead_valid = false;
     ctx->state_touched = true;
     const size_t units = (size_t)ctx->nch * nperiod;
-    if (units > ctx->looplog_cap) {
-        GC_HIP(hipStreamSynchronize(ctx->stream));
-        hipFree(ctx->dlooplog); ctx->dlooplog = nullptr; ctx->looplog_cap = 0;
-        GC_ALLOC(ctx, &ctx->dlooplog, sizeof(gnsscorr_trklog_t) * units);
-        ctx->looplog_cap = units;
-    }
+    GC_RESERVE(ctx, ctx->dlooplog, units);
     GC_HIP(hipMemsetAsync(ctx->dlooplog, 0, sizeof(gnsscorr_trklog_t) * units, ctx->stream));
     GC_HIP(hipMemsetAsync(ctx->dcorrI, 0, sizeof(double) * units * ctx->ntap, ctx->stream));
     GC_HIP(hipMemsetAsync(ctx->dcorrQ, 0, sizeof(double) * units * ctx->ntap, ctx->stream));
-    GC_HIP(hipMemsetAsync(ctx->dnsamp2[0], 0, sizeof(int) * units, ctx->stream));
+    GC_HIP(hipMemsetAsync(ctx->slot[0].nsamp, 0, sizeof(int) * units, ctx->stream));
     GC_HIP(hipMemsetAsync(ctx->dstep_meta, 0, sizeof(GcStepMeta) * ctx->nch, ctx->stream));
     // write position of each channel's ring (ref src/sdrtrk.c:26-28: fendbuffsize*buffcnt), read together with the
     // ingest fence under the lock: the positions cover only samples whose transfer the compute stream is ordered behind
@@ -960,8 +896,8 @@ extern "C" int gnsscorr_trk_run_loop(gnsscorr_ctx *ctx, int nperiod)
                 GcTimed t(ctx, "trk_step_tail");
                 rc = gc_launch_step_tail(ctx->stream, ctx->dchan, ctx->dstate2[ctx->state_cur], ctx->dloop, ctx->dstep_meta, dwp,
                                          ctx->dstep_partial, ctx->dstep_unit, ctx->dstep_segs, ctx->dstep_rounds, ctx->dcorrI,
-                                         ctx->dcorrQ, ctx->dnsamp2[0], ctx->dlooplog, ctx->dloopdone, ctx->dnco_overflow,
-                                         ctx->hostflags_dev, ctx->nch, nperiod, ctx->step_nseg, ctx->ntap, ctx->max_n, kcap, 1);
+                                         ctx->dcorrQ, ctx->slot[0].nsamp, ctx->dlooplog, ctx->dloopdone, ctx->dnco_overflow,
+                                         ctx->hostflags.dev, ctx->nch, nperiod, ctx->step_nseg, ctx->ntap, ctx->max_n, kcap, 1);
                 if (rc) { cleanup(); return rc; }
             }
             for (int dtype = 1; dtype <= 2; dtype++) {
@@ -979,14 +915,14 @@ extern "C" int gnsscorr_trk_run_loop(gnsscorr_ctx *ctx, int nperiod)
     }
     // close whatever the last correlator launch produced
     rc = gc_launch_step_tail(ctx->stream, ctx->dchan, ctx->dstate2[ctx->state_cur], ctx->dloop, ctx->dstep_meta, dwp, ctx->dstep_partial,
-                             ctx->dstep_unit, ctx->dstep_segs, ctx->dstep_rounds, ctx->dcorrI, ctx->dcorrQ, ctx->dnsamp2[0],
-                             ctx->dlooplog, ctx->dloopdone, ctx->dnco_overflow, ctx->hostflags_dev, ctx->nch, nperiod, ctx->step_nseg,
+                             ctx->dstep_unit, ctx->dstep_segs, ctx->dstep_rounds, ctx->dcorrI, ctx->dcorrQ, ctx->slot[0].nsamp,
+                             ctx->dlooplog, ctx->dloopdone, ctx->dnco_overflow, ctx->hostflags.dev, ctx->nch, nperiod, ctx->step_nseg,
                              ctx->ntap, ctx->max_n, 1, 0);
     cleanup();
     if (rc) return rc;
     if (ctx->hostflags[1]) ctx->loop_sync_hint = true;
     ctx->last_slot = 0;
-    ctx->fin_pending[0] = ctx->fin_pending[1] = false;
+    ctx->slot[0].fin_pending = ctx->slot[1].fin_pending = false;
     ctx->last_nepoch = nperiod;
     ctx->last_loop_nper = nperiod;
     return GNSSCORR_OK;
@@ -1034,7 +970,7 @@ extern "C" int gnsscorr_trk_fetch(gnsscorr_ctx *ctx, double *trkII, double *trkQ
     if (trkQQ)
         GC_HIP(hipMemcpyAsync(trkQQ, ctx->dcorrI, sizeof(double) * units * ctx->ntap, hipMemcpyDeviceToHost, ctx->stream));
     if (nsamp_out)
-        GC_HIP(hipMemcpyAsync(nsamp_out, ctx->dnsamp2[ctx->last_slot], sizeof(int) * units, hipMemcpyDeviceToHost, ctx->stream));
+        GC_HIP(hipMemcpyAsync(nsamp_out, ctx->slot[ctx->last_slot].nsamp, sizeof(int) * units, hipMemcpyDeviceToHost, ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
     return nco_check(ctx);
 }

@@ -16,36 +16,37 @@
 
 #define SDRPRINTF printf
 
-// per-call scratch on the default context (guarded by ctx->mtx)
+// per-call scratch on the default context (guarded by ctx->mtx).  Never deleted: no hipFree runs during static
+// destruction, after the HIP runtime may have gone.
 struct GcOnce {
-    int8_t *data = nullptr;  size_t data_cap = 0;    // scratch "ring" for host-supplied samples
-    int8_t *code = nullptr;                          // one code block
-    GcChan *chan = nullptr;
-    GcTrkPlan *plan = nullptr;
-    GcTrkUnit *unit = nullptr;
-    GcUnitSegs *segs = nullptr;
-    int *overflow = nullptr;
-    double *out = nullptr;                           // 4*GNSSCORR_MAXTAPS: corrI, corrQ, sumI, sumQ
-    int *partial = nullptr;  int partial_cap = 0;    // nseg*2*ntap
-    GcRound *rounds = nullptr;  int rounds_cap = 0;  // nseg*GC_MAXR
-    unsigned long long *finish = nullptr;            // GC_FINISH_SCRATCH words, zero between launches
+    GcDevBuf<int8_t> data;                           // scratch "ring" for host-supplied samples
+    GcDevBuf<int8_t> code;                           // one code block
+    GcDevBuf<GcChan> chan;
+    GcDevBuf<GcTrkPlan> plan;
+    GcDevBuf<GcTrkUnit> unit;
+    GcDevBuf<GcUnitSegs> segs;
+    GcDevBuf<int> overflow;
+    GcDevBuf<double> out;                            // 4*GNSSCORR_MAXTAPS: corrI, corrQ, sumI, sumQ
+    GcDevBuf<int> partial;                           // nseg*2*ntap
+    GcDevBuf<GcRound> rounds;                        // nseg*GC_MAXR
+    GcDevBuf<unsigned long long> finish;             // GC_FINISH_SCRATCH words, zero between launches
 };
-static GcOnce g_once;
+static GcOnce &g_once = *new GcOnce();
 
 static int once_init(gnsscorr_ctx *ctx)
 {
     if (g_once.chan) return 0;
     GC_HIP(hipSetDevice(ctx->device));
-    GC_HIP(hipMalloc((void **)&g_once.code, GC_CODEBLOCK));
-    GC_HIP(hipMalloc((void **)&g_once.chan, sizeof(GcChan)));
-    GC_HIP(hipMalloc((void **)&g_once.plan, sizeof(GcTrkPlan)));
-    GC_HIP(hipMalloc((void **)&g_once.unit, sizeof(GcTrkUnit)));
-    GC_HIP(hipMalloc((void **)&g_once.segs, sizeof(GcUnitSegs)));
-    GC_HIP(hipMalloc((void **)&g_once.overflow, sizeof(int)));
+    GC_RESERVE(ctx, g_once.code, GC_CODEBLOCK);
+    GC_RESERVE(ctx, g_once.plan, 1);
+    GC_RESERVE(ctx, g_once.unit, 1);
+    GC_RESERVE(ctx, g_once.segs, 1);
+    GC_RESERVE(ctx, g_once.overflow, 1);
     GC_HIP(hipMemsetAsync(g_once.overflow, 0, sizeof(int), ctx->stream));
-    GC_HIP(hipMalloc((void **)&g_once.out, sizeof(double) * 4 * GNSSCORR_MAXTAPS));
-    GC_HIP(hipMalloc((void **)&g_once.finish, sizeof(unsigned long long) * GC_FINISH_SCRATCH));
+    GC_RESERVE(ctx, g_once.out, 4 * GNSSCORR_MAXTAPS);
+    GC_RESERVE(ctx, g_once.finish, GC_FINISH_SCRATCH);
     GC_HIP(hipMemsetAsync(g_once.finish, 0, sizeof(unsigned long long) * GC_FINISH_SCRATCH, ctx->stream));
+    GC_RESERVE(ctx, g_once.chan, 1);                 // last: the guard above
     return 0;
 }
 
@@ -98,18 +99,8 @@ static int corr_unit(gnsscorr_ctx *ctx, const int8_t *ring, uint64_t ringlen, in
     GC_HIP(hipMemcpyAsync(g_once.chan, &c, sizeof(c), hipMemcpyHostToDevice, ctx->stream));
     GC_HIP(hipMemcpyAsync(g_once.plan, &p, sizeof(p), hipMemcpyHostToDevice, ctx->stream));
     const int nseg = gc_trk_nseg(dtype, n);
-    if (nseg * 2 * c.ntap > g_once.partial_cap) {
-        if (g_once.partial) hipFree(g_once.partial);
-        g_once.partial = nullptr; g_once.partial_cap = 0;
-        GC_HIP(hipMalloc((void **)&g_once.partial, sizeof(int) * nseg * 2 * c.ntap));
-        g_once.partial_cap = nseg * 2 * c.ntap;
-    }
-    if (nseg > g_once.rounds_cap) {
-        if (g_once.rounds) hipFree(g_once.rounds);
-        g_once.rounds = nullptr; g_once.rounds_cap = 0;
-        GC_HIP(hipMalloc((void **)&g_once.rounds, sizeof(GcRound) * nseg * GC_MAXR));
-        g_once.rounds_cap = nseg;
-    }
+    GC_RESERVE(ctx, g_once.partial, (size_t)nseg * 2 * c.ntap);
+    GC_RESERVE(ctx, g_once.rounds, (size_t)nseg * GC_MAXR);
     rc = gc_launch_trk_expand(ctx->stream, g_once.chan, g_once.plan, g_once.unit, g_once.segs, nullptr, 1, 1, g_once.rounds,
                               nseg, n, g_once.overflow);
     if (rc) return rc;
@@ -148,21 +139,16 @@ void correlator(const char *data, int dtype, double ti, int n, double freq, doub
     std::lock_guard<std::mutex> lk(ctx->mtx);
     if (hipSetDevice(ctx->device) != hipSuccess) { SDRPRINTF("error: correlator: hipSetDevice\n"); return; }
     const size_t bytes = (((size_t)n * dtype + 15) & ~(size_t)15) + 32;
-    if (bytes > g_once.data_cap) {
-        if (g_once.data) hipFree(g_once.data);
-        g_once.data = nullptr; g_once.data_cap = 0;
-        if (hipMalloc((void **)&g_once.data, bytes) != hipSuccess) {
-            SDRPRINTF("error: correlator memory allocation\n");
-            return;
-        }
-        g_once.data_cap = bytes;
+    if (g_once.data.reserve(ctx, bytes)) {
+        SDRPRINTF("error: correlator memory allocation\n");
+        return;
     }
     if (hipMemcpyAsync(g_once.data, data, (size_t)n * dtype, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
         SDRPRINTF("error: correlator: sample upload failed\n");
         return;
     }
     double cI[GNSSCORR_MAXTAPS], cQ[GNSSCORR_MAXTAPS];
-    const uint64_t ringlen = g_once.data_cap / dtype;      // multiple of 16 bytes by construction
+    const uint64_t ringlen = g_once.data.n / dtype;      // multiple of 16 bytes by construction
     if (corr_unit(ctx, g_once.data, ringlen, dtype, ti, n, freq, phi0, crate, coff, s, ns, codein, coden, 0,
                   cI, cQ)) {
         SDRPRINTF("error: correlator: %s\n", gnsscorr_last_error());
@@ -199,7 +185,7 @@ struct TrkReq {
     char err[200];
 };
 
-struct CodeSlot { int8_t *dcode = nullptr; unsigned long sum = ~0ul; int clen = 0, nedge = 0, pm1 = 0; };
+struct CodeSlot { GcDevBuf<int8_t> dcode; unsigned long sum = ~0ul; int clen = 0, nedge = 0, pm1 = 0; };
 
 struct TrkCombiner {
     std::mutex qm;
@@ -210,18 +196,20 @@ struct TrkCombiner {
     // device / pinned staging for `cap` requests.  One pinned block goes down per launch chain (the requests' GcChan
     // and GcTrkPlan records, side by side); the results come back without a copy: trk_finish writes the sums into
     // pinned host memory (hres), and the piece-table overflow counter lives there too (hover).
-    int cap = 0, nseg_cap = 0, ntap_cap = 0;
-    char *dstage = nullptr, *hstage = nullptr;
-    GcTrkUnit *dunit = nullptr;
-    GcUnitSegs *dsegs = nullptr;
-    GcRound *drounds = nullptr;
-    int *dpartial = nullptr;
-    double *dsum = nullptr;                             // sumI[cap][ntap], sumQ[cap][ntap] (device; unused by sdrtracking)
-    double *hres = nullptr, *hres_dev = nullptr;        // corrI[cap][ntap], corrQ[cap][ntap] (pinned, written by the device)
-    int *hover = nullptr, *hover_dev = nullptr;         // NCO piece-table overflow (pinned)
-    unsigned long long *dfinish = nullptr;
+    // (never deleted, like g_once)
+    int cap = 0, nseg_cap = 0;
+    GcDevBuf<char> dstage;
+    GcPinBuf<char> hstage;
+    GcDevBuf<GcTrkUnit> dunit;
+    GcDevBuf<GcUnitSegs> dsegs;
+    GcDevBuf<GcRound> drounds;
+    GcDevBuf<int> dpartial;
+    GcDevBuf<double> dsum;                              // sumI[cap][ntap], sumQ[cap][ntap] (device; unused by sdrtracking)
+    GcPinBuf<double> hres;                              // corrI[cap][ntap], corrQ[cap][ntap] (mapped, written by the device)
+    GcPinBuf<int> hover;                                // NCO piece-table overflow (mapped)
+    GcDevBuf<unsigned long long> dfinish;
 };
-TrkCombiner g_cmb;
+TrkCombiner &g_cmb = *new TrkCombiner();
 
 // GNSSCORR_CMB_PROF=1: where a combined launch chain's host time goes, printed when the process ends
 struct CmbProf {
@@ -239,37 +227,28 @@ struct CmbProf {
 };
 CmbProf g_cprof;
 
-int cmb_reserve(gnsscorr_ctx *ctx, int k, int nseg, int ntap)
+int cmb_reserve(gnsscorr_ctx *ctx, int k, int nseg)
 {
     TrkCombiner &q = g_cmb;
-    if (k <= q.cap && nseg <= q.nseg_cap && ntap <= q.ntap_cap) return 0;
+    if (k <= q.cap && nseg <= q.nseg_cap) return 0;
     GC_HIP(hipStreamSynchronize(ctx->stream));
-    // (every pointer is cleared as it is freed: an allocation that fails below leaves nothing dangling, and the next
-    // call -- capacities are zero -- starts over)
-    auto dfree = [](auto *&p) { if (p) hipFree(p); p = nullptr; };
-    auto hfree = [](auto *&p) { if (p) hipHostFree(p); p = nullptr; };
-    dfree(q.dstage); dfree(q.dunit); dfree(q.dsegs); dfree(q.drounds); dfree(q.dpartial);
-    dfree(q.dsum); dfree(q.dfinish);
-    hfree(q.hstage); hfree(q.hres); hfree(q.hover);
-    q.hres_dev = nullptr; q.hover_dev = nullptr;
     const int cap = k > 64 ? k : 64, ns = nseg > 1 ? nseg : 1, nt = GNSSCORR_MAXTAPS;
-    q.cap = q.nseg_cap = q.ntap_cap = 0;
+    q.cap = q.nseg_cap = 0;            // (until every buffer below is there)
     const size_t stage = (sizeof(GcChan) + sizeof(GcTrkPlan)) * cap + 64;
-    GC_HIP(hipMalloc((void **)&q.dstage, stage));
-    GC_HIP(hipMalloc((void **)&q.dunit, sizeof(GcTrkUnit) * cap));
-    GC_HIP(hipMalloc((void **)&q.dsegs, sizeof(GcUnitSegs) * cap));
-    GC_HIP(hipMalloc((void **)&q.drounds, sizeof(GcRound) * cap * ns * GC_MAXR));
-    GC_HIP(hipMalloc((void **)&q.dpartial, sizeof(int) * cap * ns * 2 * nt));
-    GC_HIP(hipMalloc((void **)&q.dsum, sizeof(double) * cap * 2 * nt));
-    GC_HIP(hipMalloc((void **)&q.dfinish, sizeof(unsigned long long) * cap * GC_FINISH_SCRATCH));
+    GC_RESERVE(ctx, q.dstage, stage);
+    GC_RESERVE(ctx, q.dunit, cap);
+    GC_RESERVE(ctx, q.dsegs, cap);
+    GC_RESERVE(ctx, q.drounds, (size_t)cap * ns * GC_MAXR);
+    GC_RESERVE(ctx, q.dpartial, (size_t)cap * ns * 2 * nt);
+    GC_RESERVE(ctx, q.dsum, (size_t)cap * 2 * nt);
+    GC_RESERVE(ctx, q.dfinish, (size_t)cap * GC_FINISH_SCRATCH);
     GC_HIP(hipMemsetAsync(q.dfinish, 0, sizeof(unsigned long long) * cap * GC_FINISH_SCRATCH, ctx->stream));
-    GC_HIP(hipHostMalloc((void **)&q.hstage, stage));
-    GC_HIP(hipHostMalloc((void **)&q.hres, sizeof(double) * cap * 2 * nt, hipHostMallocMapped));
-    GC_HIP(hipHostGetDevicePointer((void **)&q.hres_dev, q.hres, 0));
-    GC_HIP(hipHostMalloc((void **)&q.hover, 64, hipHostMallocMapped));
-    GC_HIP(hipHostGetDevicePointer((void **)&q.hover_dev, q.hover, 0));
+    int rc = q.hstage.reserve(stage);
+    if (!rc) rc = q.hres.reserve((size_t)cap * 2 * nt, hipHostMallocMapped);
+    if (!rc) rc = q.hover.reserve(16, hipHostMallocMapped);
+    if (rc) return rc;
     *q.hover = 0;
-    q.cap = cap; q.nseg_cap = ns; q.ntap_cap = nt;
+    q.cap = cap; q.nseg_cap = ns;
     return 0;
 }
 
@@ -279,12 +258,11 @@ int cmb_code(gnsscorr_ctx *ctx, sdrch_t *sdr, unsigned long sum, CodeSlot **out)
     // (keyed by the caller's sdrch_t: a receiver has at most MAXSAT of them; a caller that keeps handing in new structs
     // gets the table emptied instead of growing without bound -- the stream is idle here, every call ends synchronised)
     if (g_cmb.codes.size() > 256 && !g_cmb.codes.count(sdr)) {
-        for (auto &kv : g_cmb.codes) if (kv.second.dcode) hipFree(kv.second.dcode);
         g_cmb.codes.clear();
     }
     CodeSlot &cs = g_cmb.codes[sdr];
     if (!cs.dcode || cs.sum != sum || cs.clen != sdr->clen) {
-        if (!cs.dcode) GC_HIP(hipMalloc((void **)&cs.dcode, GC_CODEBLOCK));
+        GC_RESERVE(ctx, cs.dcode, GC_CODEBLOCK);
         int8_t block[GC_CODEBLOCK];
         gc_build_codeblock(sdr->code, sdr->clen, block, &cs.nedge, &cs.pm1);
         GC_HIP(hipMemcpy(cs.dcode, block, GC_CODEBLOCK, hipMemcpyHostToDevice));
@@ -308,12 +286,12 @@ int cmb_run_group(gnsscorr_ctx *ctx, std::vector<TrkReq *> &grp)
         if (sm > smax_max) smax_max = sm;
     }
     const int nseg = gc_trk_nseg(dtype, max_n);
-    int rc = cmb_reserve(ctx, k, nseg, ntap);
+    int rc = cmb_reserve(ctx, k, nseg);
     if (rc) return rc;
     const double tp0 = g_cprof.on ? CmbProf::now() : 0.0;
     const size_t plan_off = (sizeof(GcChan) * (size_t)k + 63) & ~(size_t)63;
-    GcChan *hchan = reinterpret_cast<GcChan *>(q.hstage), *dchan = reinterpret_cast<GcChan *>(q.dstage);
-    GcTrkPlan *hplan = reinterpret_cast<GcTrkPlan *>(q.hstage + plan_off), *dplan = reinterpret_cast<GcTrkPlan *>(q.dstage + plan_off);
+    GcChan *hchan = reinterpret_cast<GcChan *>(q.hstage.p), *dchan = reinterpret_cast<GcChan *>(q.dstage.p);
+    GcTrkPlan *hplan = reinterpret_cast<GcTrkPlan *>(q.hstage.p + plan_off), *dplan = reinterpret_cast<GcTrkPlan *>(q.dstage.p + plan_off);
     for (int i = 0; i < k; i++) {
         sdrch_t *sdr = grp[i]->sdr;
         const GcRing &ring = ctx->ring[sdr->ftype == FTYPE2 ? 1 : 0];
@@ -337,12 +315,12 @@ int cmb_run_group(gnsscorr_ctx *ctx, std::vector<TrkReq *> &grp)
     hipStream_t st = ctx->stream;
     const double tp1 = g_cprof.on ? CmbProf::now() : 0.0;
     GC_HIP(hipMemcpyAsync(q.dstage, q.hstage, plan_off + sizeof(GcTrkPlan) * k, hipMemcpyHostToDevice, st));
-    rc = gc_launch_trk_expand(st, dchan, dplan, q.dunit, q.dsegs, nullptr, k, 1, q.drounds, nseg, max_n, q.hover_dev);
+    rc = gc_launch_trk_expand(st, dchan, dplan, q.dunit, q.dsegs, nullptr, k, 1, q.drounds, nseg, max_n, q.hover.dev);
     if (rc) return rc;
     rc = gc_launch_trk_corr(st, dchan, q.dunit, q.dsegs, q.drounds, q.dpartial, k, 1, nseg, ntap, dtype, ntap, max_n, smax_max, nullptr);
     if (rc) return rc;
     // (the period's sums straight into pinned host memory: no copy back)
-    double *cI = q.hres_dev, *cQ = q.hres_dev + (size_t)q.cap * ntap, *sI = q.dsum, *sQ = q.dsum + (size_t)q.cap * ntap;
+    double *cI = q.hres.dev, *cQ = q.hres.dev + (size_t)q.cap * ntap, *sI = q.dsum, *sQ = q.dsum + (size_t)q.cap * ntap;
     rc = gc_launch_trk_finish(st, q.dpartial, cI, cQ, sI, sQ, q.dfinish, k, 1, nseg, ntap);
     if (rc) return rc;
     const double tp2 = g_cprof.on ? CmbProf::now() : 0.0;

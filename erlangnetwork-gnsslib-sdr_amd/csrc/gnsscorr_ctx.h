@@ -10,9 +10,81 @@
 #include <cstring>
 #include "gnsscorr_internal.h"
 
+struct gnsscorr_ctx;
+int gc_dev_alloc(gnsscorr_ctx *ctx, void **p, size_t bytes);   // hipMalloc + the context's poison fill, if on
+
+// Owning device buffer (hipMalloc / hipFree), move-only.  reserve() only grows: a larger request frees the old buffer
+// (hipFree synchronises the device, so no launch still reads it) and allocates through gc_dev_alloc.
+template <class T>
+struct GcDevBuf {
+    T *p = nullptr;
+    size_t n = 0;               // elements
+    GcDevBuf() = default;
+    GcDevBuf(GcDevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    GcDevBuf &operator=(GcDevBuf &&o) noexcept
+    {
+        if (this != &o) { reset(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
+        return *this;
+    }
+    ~GcDevBuf() { reset(); }
+    void reset()
+    {
+        if (p) hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
+    int reserve(gnsscorr_ctx *ctx, size_t elems)
+    {
+        if (elems <= n) return 0;
+        reset();
+        int rc = gc_dev_alloc(ctx, (void **)&p, sizeof(T) * elems);
+        if (!rc) n = elems;
+        return rc;
+    }
+    operator T *() const { return p; }
+};
+
+// Owning pinned host buffer (hipHostMalloc / hipHostFree), move-only and grow-only like GcDevBuf; dev is the device
+// pointer of a mapped one.
+template <class T>
+struct GcPinBuf {
+    T *p = nullptr, *dev = nullptr;
+    size_t n = 0;
+    GcPinBuf() = default;
+    GcPinBuf(GcPinBuf &&o) noexcept : p(o.p), dev(o.dev), n(o.n) { o.p = o.dev = nullptr; o.n = 0; }
+    GcPinBuf &operator=(GcPinBuf &&o) noexcept
+    {
+        if (this != &o) { reset(); p = o.p; dev = o.dev; n = o.n; o.p = o.dev = nullptr; o.n = 0; }
+        return *this;
+    }
+    ~GcPinBuf() { reset(); }
+    void reset()
+    {
+        if (p) hipHostFree(p);
+        p = dev = nullptr;
+        n = 0;
+    }
+    int reserve(size_t elems, unsigned flags = hipHostMallocDefault)
+    {
+        if (elems <= n) return 0;
+        reset();
+        GC_HIP(hipHostMalloc((void **)&p, sizeof(T) * elems, flags));
+        if (flags & hipHostMallocMapped) GC_HIP(hipHostGetDevicePointer((void **)&dev, p, 0));
+        n = elems;
+        return 0;
+    }
+    operator T *() const { return p; }
+};
+
+#define GC_RESERVE(ctx, buf, elems)                                             \
+    do {                                                                        \
+        int rc_ = (buf).reserve((ctx), (elems));                                \
+        if (rc_) return rc_;                                                    \
+    } while (0)
+
 struct GcRing {
-    int8_t  *mem = nullptr;
-    bool     owned = false;
+    int8_t  *mem = nullptr;   // own, or the caller's buffer
+    GcDevBuf<int8_t> own;
     int      dtype = 0;
     uint64_t ringlen = 0;     // samples
     uint64_t wrpos = 0;       // samples written so far (fendbuffsize*buffcnt)
@@ -27,6 +99,21 @@ struct GcTimer {
 struct GcAcqWork;   // gnsscorr_acq.hip
 struct GcSpecWork;  // gnsscorr_spec.hip
 
+// One plan slot: the planner stream expands batch k+1 into one slot while batch k is correlated from the other
+struct GcPlanSlot {
+    GcDevBuf<GcTrkPlan> plan;      // [unit]
+    GcDevBuf<GcTrkUnit> unit;      // [unit] per-unit constants
+    GcDevBuf<GcRound> rounds;      // [unit][nseg][GC_MAXR]
+    GcDevBuf<GcUnitSegs> segs;     // [unit]: the unit's carrier / code NCO piece tables
+    GcDevBuf<int> nsamp;           // [unit]
+    GcDevBuf<int> partial;         // [ch][epoch][segment][2*ntap] int32 partial sums
+    hipEvent_t ev_plan = nullptr;  // plan finished (planner stream)
+    hipEvent_t ev_used = nullptr;  // the main stream is done with what the slot held before: the planner may write it
+    hipEvent_t ev_corr = nullptr;  // correlator finished (main stream): slot consumed, partials ready
+    hipEvent_t ev_fin = nullptr;   // finish done (finish stream): outputs valid
+    bool fin_pending = false;      // ev_fin has been recorded
+};
+
 struct gnsscorr_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -38,8 +125,8 @@ struct gnsscorr_ctx {
     // ingest: copy stream + two pinned staging buffers (and device staging for packed formats); ev_in marks
     // the last transfer, the compute stream waits on it before it reads the ring
     hipStream_t stream_in = nullptr;
-    int8_t *pin[2] = {nullptr, nullptr};
-    uint8_t *dstage[2] = {nullptr, nullptr};
+    GcPinBuf<int8_t> pin[2];
+    GcDevBuf<uint8_t> dstage[2];
     hipEvent_t ev_pin[2] = {nullptr, nullptr};
     bool pin_busy[2] = {false, false};
     int pin_next = 0;
@@ -53,69 +140,56 @@ struct gnsscorr_ctx {
     std::vector<std::vector<short>> hcode;
     std::vector<std::vector<double>> hfreq;
     std::vector<std::vector<int>> hcorrp;
-    GcChan *dchan = nullptr;
-    int8_t *dcodes = nullptr;
-    double *dfreqs = nullptr;
+    GcDevBuf<GcChan> dchan;
+    GcDevBuf<int8_t> dcodes;
+    GcDevBuf<double> dfreqs;
     int ntap = 0, smax_max = 0, max_n = 0;
 
     // tracking.  The planner (a short sequential NCO chain per channel) runs one batch ahead on
     // its own stream: plan entries and the chained state are double buffered, so batch k+1 is
     // planned while batch k is correlated.  A look-ahead plan is dropped when the caller changes
-    // the state or the batch length.
-    GcTrkState *dstate2[2] = {nullptr, nullptr};   // ping-pong; cur = index of the committed state
+    // the state or the batch length.  Every stream and event below exists for the context's lifetime.
+    hipStream_t stream_plan = nullptr;             // planner: the sequential chain (and the direct discovery)
+    hipStream_t stream_finish = nullptr;           // finish: partial sums -> outputs
+    hipStream_t stream_discover = nullptr;         // discovery of the next batch's claims, beside the chain
+    GcDevBuf<GcTrkState> dstate2[2];               // ping-pong; cur = index of the committed state
     int state_cur = 0;
-    GcTrkPlan *dplan2[2] = {nullptr, nullptr};
+    GcPlanSlot slot[2];
+    size_t trk_units = 0;                          // (channel, period) units every tracking buffer below is sized for
     // claims of the batch being planned (discovery pass -> chain), two buffers: while the chain of one batch reads
     // its claims the discovery pass of the NEXT batch fills the other one from the same input state, on its own stream
-    int *dspec2[2] = {nullptr, nullptr};
-    unsigned short *detab = nullptr;               // [unit][GC_EDGTAB] start samples of the batch's chip edges (main stream: trk_edges -> trk_corr)
-    hipStream_t stream4 = nullptr;                 // discovery-ahead stream
+    GcDevBuf<int> dspec2[2];
+    GcDevBuf<unsigned short> detab;                // [unit][GC_EDGTAB] start samples of the batch's chip edges (main stream: trk_edges -> trk_corr)
     hipEvent_t ev_spec = nullptr, ev_chain = nullptr;
-    bool spec_pending = false;                     // stream4 has work whose end ev_spec marks
+    bool spec_pending = false;                     // the discovery stream has work whose end ev_spec marks
     bool spec_ahead_valid = false;                 // dspec2[spec_ahead_buf] holds claims for the batch that starts at spec_ahead_state
     int spec_ahead_buf = 0, spec_ahead_nepoch = 0;
     int spec_last_buf = 0, spec_last_units = 0;     // (tools/debug) the claims the last planned batch used
     const void *spec_ahead_state = nullptr;
     int plan_slot = 0;                             // slot the next trk_run consumes
-    bool ahead_valid = false;                      // dplan2[plan_slot] already planned (look-ahead)
+    bool ahead_valid = false;                      // slot[plan_slot] already planned (look-ahead)
     int ahead_nepoch = 0;
     bool state_touched = true;                     // set_state since the last run: do not look ahead
-    hipStream_t stream2 = nullptr;                 // planner stream
-    hipStream_t stream3 = nullptr;                 // finish stream
-    hipEvent_t ev_plan[2] = {nullptr, nullptr};    // plan of slot s finished
-    hipEvent_t ev_used[2] = {nullptr, nullptr};    // expand consumed slot s
-    // per-unit constants, one set per plan slot: the planner stream expands batch k+1 while batch k is correlated
-    GcTrkUnit *dunit2[2] = {nullptr, nullptr};
-    GcRound *drounds2[2] = {nullptr, nullptr};     // [unit][nseg][GC_MAXR]
-    GcUnitSegs *dsegs2[2] = {nullptr, nullptr};    // [unit]: the unit's carrier / code NCO piece tables
-    int *dnco_overflow = nullptr;
-    int *dring_viol = nullptr;                     // planned periods outside what the ring holds, since the last fetch
+    GcDevBuf<int> dnco_overflow;                   // units whose NCO tables overflowed since the last fetch
+    GcDevBuf<int> dring_viol;                      // planned periods outside what the ring holds, since the last fetch
     // closed loop (gnsscorr_trk_run_loop): per channel loop state, one log row per period; the step buffers hold one
     // filter interval per channel (GC_STEP_KMAX periods at most): unit constants, NCO tables, rounds, partial sums
-    gnsscorr_loop_t *dloop = nullptr;              // [nch]
-    GcStepMeta *dstep_meta = nullptr;              // [nch]
-    GcTrkUnit *dstep_unit = nullptr;               // [nch][GC_STEP_KMAX]
-    GcUnitSegs *dstep_segs = nullptr;
-    GcRound *dstep_rounds = nullptr;               // [nch][GC_STEP_KMAX][step_nseg][4]
-    int *dstep_partial = nullptr;                  // [nch][GC_STEP_KMAX][step_nseg][2*ntap]
+    GcDevBuf<gnsscorr_loop_t> dloop;               // [nch]
+    GcDevBuf<GcStepMeta> dstep_meta;               // [nch]
+    GcDevBuf<GcTrkUnit> dstep_unit;                // [nch][GC_STEP_KMAX]
+    GcDevBuf<GcUnitSegs> dstep_segs;
+    GcDevBuf<GcRound> dstep_rounds;                // [nch][GC_STEP_KMAX][step_nseg][4]
+    GcDevBuf<int> dstep_partial;                   // [nch][GC_STEP_KMAX][step_nseg][2*ntap]
     int step_nseg = 0;
-    unsigned *hostflags = nullptr;                 // pinned, device-visible: [0] channels whose run is over, [1] some channel has its nav bit synchronised
-    unsigned *hostflags_dev = nullptr;
+    GcPinBuf<unsigned> hostflags;                  // mapped: [0] channels whose run is over, [1] some channel has its nav bit synchronised
     bool loop_sync_hint = false;                   // some channel had its nav bit synchronised when last seen
     int loop_kmax = 1;                             // largest loopms among the channels' loop states (gnsscorr_loop_set)
-    gnsscorr_trklog_t *dlooplog = nullptr;         // [nch][looplog_cap]
-    int *dloopdone = nullptr;                      // [nch]
-    size_t looplog_cap = 0;
-    int last_loop_nper = 0;                        // > 0: the last run was a closed-loop one of that many periods                  // units whose NCO tables overflowed since the last fetch
-    int *dnsamp2[2] = {nullptr, nullptr};
+    GcDevBuf<gnsscorr_trklog_t> dlooplog;          // [nch][nperiod]
+    GcDevBuf<int> dloopdone;                       // [nch], then the rings' write positions [nch] (uint64)
+    int last_loop_nper = 0;                        // > 0: the last run was a closed-loop one of that many periods
     int last_slot = 0;                             // slot of the last completed trk_run
-    size_t plan_cap = 0;
-    double *dcorrI = nullptr, *dcorrQ = nullptr, *dsumI = nullptr, *dsumQ = nullptr;
-    unsigned long long *dfinish = nullptr;     // batch-sum scratch of trk_finish
-    int *dpartial2[2] = {nullptr, nullptr};    // per slot: [ch][epoch][segment][2*ntap] int32 partial sums
-    hipEvent_t ev_corr[2] = {nullptr, nullptr};   // correlator of slot s finished (main stream)
-    hipEvent_t ev_fin[2] = {nullptr, nullptr};    // finish of slot s done (finish stream): outputs valid
-    bool fin_pending[2] = {false, false};         // ev_fin[s] has been recorded
+    GcDevBuf<double> dcorrI, dcorrQ, dsumI, dsumQ;
+    GcDevBuf<unsigned long long> dfinish;          // batch-sum scratch of trk_finish
     int nseg = 1;
     int last_nepoch = 0;
 
@@ -156,13 +230,8 @@ struct GcTimed {
 
 void gc_acq_free(gnsscorr_ctx *ctx);
 void gc_spec_free(gnsscorr_ctx *ctx);
+// drains the helper streams and the main stream (and the ingest stream when `ingest`), then drops the look-ahead plan
+int gc_quiesce(gnsscorr_ctx *ctx, bool ingest = false);
 // the acquisition's forward twiddle tables (made on first use): exp(-2 pi i t/16384), exp(-2 pi i t/32768), t < 16384
 int gc_acq_twiddles(gnsscorr_ctx *ctx, const float2 **tw16k, const float2 **tw32k);
-int gc_dev_alloc(gnsscorr_ctx *ctx, void **p, size_t bytes);   // hipMalloc + the context's poison fill, if on
-
-#define GC_ALLOC(ctx, p, bytes)                                                 \
-    do {                                                                        \
-        int rc_ = gc_dev_alloc((ctx), (void **)(p), (bytes));                   \
-        if (rc_) return rc_;                                                    \
-    } while (0)
 int gc_ingest_fence(gnsscorr_ctx *ctx);      // orders the compute stream behind the last ring transfer

@@ -190,20 +190,12 @@ __global__ __launch_bounds__(1024) void vstat_kernel(const double *__restrict__ 
     }
 }
 
-struct Scratch {           // per-call device scratch of the default context
-    void *p[8] = {nullptr};
-    size_t cap[8] = {0};
-};
-Scratch g_s;
+// per-call device scratch of the default context, never deleted: no hipFree runs during static destruction
+GcDevBuf<char> *const g_s = new GcDevBuf<char>[8];
 
-void *need(int slot, size_t bytes)
+void *need(gnsscorr_ctx *ctx, int slot, size_t bytes)
 {
-    if (bytes <= g_s.cap[slot]) return g_s.p[slot];
-    if (g_s.p[slot]) hipFree(g_s.p[slot]);
-    g_s.p[slot] = nullptr; g_s.cap[slot] = 0;
-    if (hipMalloc(&g_s.p[slot], bytes) != hipSuccess) return nullptr;
-    g_s.cap[slot] = bytes;
-    return g_s.p[slot];
+    return g_s[slot].reserve(ctx, bytes) ? nullptr : g_s[slot].p;
 }
 
 int dft(gnsscorr_ctx *ctx, const float2 *in, float2 *out, int m, int sign)
@@ -240,19 +232,19 @@ struct Guard {             // default context + lock + device, or a printed erro
     explicit operator bool() const { return ctx != nullptr; }
 };
 
-GcOpTables *g_optab = nullptr;
+GcDevBuf<GcOpTables> &g_optab = *new GcDevBuf<GcOpTables>();      // (never deleted, like g_s)
 
 // builds the call's tables on the device; returns nonzero (and prints) when they do not fit
 int op_tables(gnsscorr_ctx *ctx, const char *who, int n, double phi0, double freq, double ti, int nt, double coff,
               int smax, double ci, int len)
 {
-    if (!g_optab && hipMalloc((void **)&g_optab, sizeof(GcOpTables)) != hipSuccess) {
+    if (g_optab.reserve(ctx, 1)) {
         SDRPRINTF("error: %s memory allocation\n", who);
         return -1;
     }
     hipLaunchKernelGGL(op_tables_kernel, dim3(1), dim3(1), 0, ctx->stream, g_optab, n, phi0, freq, ti, nt, coff, smax, ci, len);
     int over = 0;
-    if (hipMemcpyAsync(&over, &g_optab->overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+    if (hipMemcpyAsync(&over, &g_optab.p->overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess) {
         SDRPRINTF("error: %s: HIP failure\n", who);
         return -1;
@@ -270,8 +262,8 @@ void cpxcpx(const short *II, const short *QQ, double scale, int n, cpx_t *cpx)
 {
     Guard g("cpxcpx");
     if (!g || n <= 0) return;
-    short *dI = (short *)need(0, sizeof(short) * n), *dQ = QQ ? (short *)need(1, sizeof(short) * n) : nullptr;
-    float2 *dc = (float2 *)need(2, sizeof(float2) * n);
+    short *dI = (short *)need(g.ctx, 0, sizeof(short) * n), *dQ = QQ ? (short *)need(g.ctx, 1, sizeof(short) * n) : nullptr;
+    float2 *dc = (float2 *)need(g.ctx, 2, sizeof(float2) * n);
     if (!dI || (QQ && !dQ) || !dc) { SDRPRINTF("error: cpxcpx memory allocation\n"); return; }
     hipMemcpyAsync(dI, II, sizeof(short) * n, hipMemcpyHostToDevice, g.ctx->stream);
     if (QQ) hipMemcpyAsync(dQ, QQ, sizeof(short) * n, hipMemcpyHostToDevice, g.ctx->stream);
@@ -286,7 +278,7 @@ void cpxfft(void *plan, cpx_t *cpx, int n)
     (void)plan;
     Guard g("cpxfft");
     if (!g || n <= 0) return;
-    float2 *a = (float2 *)need(2, sizeof(float2) * n), *b = (float2 *)need(3, sizeof(float2) * n);
+    float2 *a = (float2 *)need(g.ctx, 2, sizeof(float2) * n), *b = (float2 *)need(g.ctx, 3, sizeof(float2) * n);
     if (!a || !b) { SDRPRINTF("error: cpxfft memory allocation\n"); return; }
     hipMemcpyAsync(a, cpx, sizeof(float2) * n, hipMemcpyHostToDevice, g.ctx->stream);
     if (dft(g.ctx, a, b, n, -1)) { SDRPRINTF("error: cpxfft: %s\n", gnsscorr_last_error()); return; }
@@ -299,7 +291,7 @@ void cpxifft(void *plan, cpx_t *cpx, int n)
     (void)plan;
     Guard g("cpxifft");
     if (!g || n <= 0) return;
-    float2 *a = (float2 *)need(2, sizeof(float2) * n), *b = (float2 *)need(3, sizeof(float2) * n);
+    float2 *a = (float2 *)need(g.ctx, 2, sizeof(float2) * n), *b = (float2 *)need(g.ctx, 3, sizeof(float2) * n);
     if (!a || !b) { SDRPRINTF("error: cpxifft memory allocation\n"); return; }
     hipMemcpyAsync(a, cpx, sizeof(float2) * n, hipMemcpyHostToDevice, g.ctx->stream);
     if (dft(g.ctx, a, b, n, +1)) { SDRPRINTF("error: cpxifft: %s\n", gnsscorr_last_error()); return; }
@@ -313,9 +305,9 @@ void cpxconv(void *plan, void *iplan, cpx_t *cpxa, cpx_t *cpxb, int m, int n, in
     (void)plan; (void)iplan;
     Guard g("cpxconv");
     if (!g || m <= 0 || n <= 0 || n > m) return;
-    float2 *a = (float2 *)need(2, sizeof(float2) * m), *t = (float2 *)need(3, sizeof(float2) * m);
-    float2 *b = (float2 *)need(4, sizeof(float2) * m);
-    double *c = (double *)need(5, sizeof(double) * n);
+    float2 *a = (float2 *)need(g.ctx, 2, sizeof(float2) * m), *t = (float2 *)need(g.ctx, 3, sizeof(float2) * m);
+    float2 *b = (float2 *)need(g.ctx, 4, sizeof(float2) * m);
+    double *c = (double *)need(g.ctx, 5, sizeof(double) * n);
     if (!a || !t || !b || !c) { SDRPRINTF("error: cpxconv memory allocation\n"); return; }
     hipStream_t st = g.ctx->stream;
     hipMemcpyAsync(a, cpxa, sizeof(float2) * m, hipMemcpyHostToDevice, st);
@@ -341,8 +333,8 @@ void cpxpspec(void *plan, cpx_t *cpx, int n, int flagsum, double *pspec)
     }
     Guard g("cpxpspec");
     if (!g || n <= 0) return;
-    float2 *a = (float2 *)need(2, sizeof(float2) * n), *b = (float2 *)need(3, sizeof(float2) * n);
-    double *c = (double *)need(5, sizeof(double) * n);
+    float2 *a = (float2 *)need(g.ctx, 2, sizeof(float2) * n), *b = (float2 *)need(g.ctx, 3, sizeof(float2) * n);
+    double *c = (double *)need(g.ctx, 5, sizeof(double) * n);
     if (!a || !b || !c) { SDRPRINTF("error: cpxpspec memory allocation\n"); return; }
     hipStream_t st = g.ctx->stream;
     hipMemcpyAsync(a, cpx, sizeof(float2) * n, hipMemcpyHostToDevice, st);
@@ -359,8 +351,8 @@ double mixcarr(const char *data, int dtype, double ti, int n, double freq, doubl
 {
     Guard g("mixcarr");
     if (!g || n <= 0 || (dtype != 1 && dtype != 2)) return 0.0;
-    int8_t *d = (int8_t *)need(0, (size_t)n * dtype);
-    short *dI = (short *)need(1, sizeof(short) * n), *dQ = (short *)need(6, sizeof(short) * n);
+    int8_t *d = (int8_t *)need(g.ctx, 0, (size_t)n * dtype);
+    short *dI = (short *)need(g.ctx, 1, sizeof(short) * n), *dQ = (short *)need(g.ctx, 6, sizeof(short) * n);
     if (!d || !dI || !dQ) { SDRPRINTF("error: mixcarr memory allocation\n"); return 0.0; }
     hipStream_t st = g.ctx->stream;
     hipMemcpyAsync(d, data, (size_t)n * dtype, hipMemcpyHostToDevice, st);
@@ -380,7 +372,7 @@ double rescode(const short *code, int len, double coff, int smax, double ci, int
     Guard g("rescode");
     const int nt = n + 2 * smax;
     if (!g || nt <= 0 || len <= 0) return 0.0;
-    short *dc = (short *)need(1, sizeof(short) * len), *dr = (short *)need(6, sizeof(short) * nt);
+    short *dc = (short *)need(g.ctx, 1, sizeof(short) * len), *dr = (short *)need(g.ctx, 6, sizeof(short) * nt);
     if (!dc || !dr) { SDRPRINTF("error: rescode memory allocation\n"); return 0.0; }
     hipStream_t st = g.ctx->stream;
     hipMemcpyAsync(dc, code, sizeof(short) * len, hipMemcpyHostToDevice, st);
@@ -404,10 +396,10 @@ void pcorrelator(const char *data, int dtype, double ti, int n, double *freq, in
         SDRPRINTF("error: pcorrelator: unsupported shape n=%d m=%d dtype=%d\n", n, m, dtype);
         return;
     }
-    int8_t *d = (int8_t *)need(0, (size_t)m * dtype);
-    float2 *x = (float2 *)need(2, sizeof(float2) * m), *t = (float2 *)need(3, sizeof(float2) * m);
-    float2 *cx = (float2 *)need(4, sizeof(float2) * m);
-    double *dP = (double *)need(5, sizeof(double) * (size_t)n * nfreq);
+    int8_t *d = (int8_t *)need(g.ctx, 0, (size_t)m * dtype);
+    float2 *x = (float2 *)need(g.ctx, 2, sizeof(float2) * m), *t = (float2 *)need(g.ctx, 3, sizeof(float2) * m);
+    float2 *cx = (float2 *)need(g.ctx, 4, sizeof(float2) * m);
+    double *dP = (double *)need(g.ctx, 5, sizeof(double) * (size_t)n * nfreq);
     if (!d || !x || !t || !cx || !dP) { SDRPRINTF("error: pcorrelator memory allocation\n"); return; }
     hipStream_t st = g.ctx->stream;
     hipMemsetAsync(d, 0, (size_t)m * dtype, st);                       // zero padding (:756)
@@ -430,7 +422,7 @@ void pcorrelator(const char *data, int dtype, double ti, int n, double *freq, in
 
 static int vstat(gnsscorr_ctx *ctx, const double *ddev, int n, int exs, int exe, double *o3, int *oi)
 {
-    double *out = (double *)need(7, 64);
+    double *out = (double *)need(ctx, 7, 64);
     if (!out) return gc_fail(GNSSCORR_EHIP, "vstat: hipMalloc");
     hipLaunchKernelGGL(vstat_kernel, dim3(1), dim3(1024), 0, ctx->stream, ddev, n, exs, exe, out, (int *)(out + 4));
     GC_HIP(hipGetLastError());
@@ -447,7 +439,7 @@ double maxvd(const double *data, int n, int exinds, int exinde, int *ind)
 {
     Guard g("maxvd");
     if (!g || n <= 0) return 0.0;
-    double *d = (double *)need(5, sizeof(double) * n);
+    double *d = (double *)need(g.ctx, 5, sizeof(double) * n);
     if (!d) { SDRPRINTF("error: maxvd memory allocation\n"); return 0.0; }
     hipMemcpyAsync(d, data, sizeof(double) * n, hipMemcpyHostToDevice, g.ctx->stream);
     double o[3]; int oi = 0;
@@ -461,7 +453,7 @@ double meanvd(const double *data, int n, int exinds, int exinde)
 {
     Guard g("meanvd");
     if (!g || n <= 0) return 0.0;
-    double *d = (double *)need(5, sizeof(double) * n);
+    double *d = (double *)need(g.ctx, 5, sizeof(double) * n);
     if (!d) { SDRPRINTF("error: meanvd memory allocation\n"); return 0.0; }
     hipMemcpyAsync(d, data, sizeof(double) * n, hipMemcpyHostToDevice, g.ctx->stream);
     double o[3]; int oi = 0;
@@ -475,7 +467,7 @@ int checkacquisition(double *P, sdrch_t *sdr)
     Guard g("checkacquisition");
     const int n = sdr->nsamp, nf = sdr->acq.nfreq;
     if (!g || n <= 0 || nf <= 0) return 0;
-    double *d = (double *)need(5, sizeof(double) * (size_t)n * nf);
+    double *d = (double *)need(g.ctx, 5, sizeof(double) * (size_t)n * nf);
     if (!d) { SDRPRINTF("error: checkacquisition memory allocation\n"); return 0; }
     hipMemcpyAsync(d, P, sizeof(double) * (size_t)n * nf, hipMemcpyHostToDevice, g.ctx->stream);
     double o[3]; int maxi = 0, dummy = 0;

@@ -30,20 +30,15 @@
 #define GC_SPEC_HT   256        // threads of the histogram kernels
 
 struct GcSpecWork {
-    float *psd = nullptr;       // [nsnap][nloop][2*nfft] fp32 power per segment
-    size_t psd_elems = 0;
-    double *sum = nullptr;      // [nsnap][2*nfft]
-    size_t sum_elems = 0;
-    unsigned *hist = nullptr;   // [nsnap][2][GC_SPEC_HIST]
-    int *maxd = nullptr;        // [nsnap]
-    int hist_snaps = 0;
-    float *win = nullptr;       // Hann window of the last nfft (hanning(nfft/2), computed on the host)
+    GcDevBuf<float> psd;        // [nsnap][nloop][2*nfft] fp32 power per segment
+    GcDevBuf<double> sum;       // [nsnap][2*nfft]
+    GcDevBuf<unsigned> hist;    // [nsnap][2][GC_SPEC_HIST]
+    GcDevBuf<int> maxd;         // [nsnap]
+    GcDevBuf<float> win;        // Hann window of the last nfft (hanning(nfft/2), computed on the host)
     int win_n = 0;
-    uint64_t *loc = nullptr;    // [nsnap] first sample of each snapshot
-    int *off = nullptr;         // [nsnap][nloop] segment offsets
-    size_t loc_cap = 0, off_cap = 0;
-    int8_t *stage = nullptr;    // the drop-in's copy of the caller's samples
-    size_t stage_bytes = 0;
+    GcDevBuf<uint64_t> loc;     // [nsnap] first sample of each snapshot
+    GcDevBuf<int> off;          // [nsnap][nloop] segment offsets
+    GcDevBuf<int8_t> stage;     // the drop-in's copy of the caller's samples
     std::vector<uint64_t> hloc;
     std::vector<int> hoff;
     // the last run, for fetch
@@ -185,43 +180,26 @@ GcSpecWork *spec_work(gnsscorr_ctx *ctx)
     return ctx->spec;
 }
 
-template <class T>
-int spec_grow(gnsscorr_ctx *ctx, T **p, size_t *cap, size_t elems)
-{
-    if (elems <= *cap) return GNSSCORR_OK;
-    hipFree(*p);        // synchronises: no launch still reads the old buffer
-    *p = nullptr;
-    *cap = 0;
-    GC_ALLOC(ctx, p, sizeof(T) * elems);
-    *cap = elems;
-    return GNSSCORR_OK;
-}
-
 // everything spec_enqueue needs that does not depend on the samples
 int spec_prepare(gnsscorr_ctx *ctx, int nsnap, int nfft, int nloop)
 {
     GcSpecWork *w = spec_work(ctx);
     const size_t L = 2 * (size_t)nfft;
-    int rc = spec_grow(ctx, &w->psd, &w->psd_elems, (size_t)nsnap * nloop * L);
-    if (!rc) rc = spec_grow(ctx, &w->sum, &w->sum_elems, (size_t)nsnap * L);
-    if (!rc) rc = spec_grow(ctx, &w->loc, &w->loc_cap, (size_t)nsnap);
-    if (!rc) rc = spec_grow(ctx, &w->off, &w->off_cap, (size_t)nsnap * nloop);
-    if (rc) return rc;
-    if (nsnap > w->hist_snaps) {
-        hipFree(w->hist); hipFree(w->maxd);
-        w->hist = nullptr; w->maxd = nullptr; w->hist_snaps = 0;
-        GC_ALLOC(ctx, &w->hist, sizeof(unsigned) * 2 * GC_SPEC_HIST * nsnap);
-        GC_ALLOC(ctx, &w->maxd, sizeof(int) * nsnap);
-        w->hist_snaps = nsnap;
-    }
+    GC_RESERVE(ctx, w->psd, (size_t)nsnap * nloop * L);
+    GC_RESERVE(ctx, w->sum, (size_t)nsnap * L);
+    GC_RESERVE(ctx, w->loc, (size_t)nsnap);
+    GC_RESERVE(ctx, w->off, (size_t)nsnap * nloop);
+    GC_RESERVE(ctx, w->hist, (size_t)2 * GC_SPEC_HIST * nsnap);
+    GC_RESERVE(ctx, w->maxd, (size_t)nsnap);
     const int nwin = nfft / 2;
     if (w->win_n != nwin) {
-        hipFree(w->win);
-        w->win = nullptr; w->win_n = 0;
-        GC_ALLOC(ctx, &w->win, sizeof(float) * nwin);
+        w->win_n = 0;
+        GC_RESERVE(ctx, w->win, nwin);
         std::vector<float> hw(nwin);
         hanning(nwin, hw.data());       // the reference's double formula (ref src/sdrspec.c:214-219)
-        GC_HIP(hipMemcpy(w->win, hw.data(), sizeof(float) * nwin, hipMemcpyHostToDevice));
+        // in stream order behind any spec_psd still reading the window, and done before hw goes
+        GC_HIP(hipMemcpyAsync(w->win, hw.data(), sizeof(float) * nwin, hipMemcpyHostToDevice, ctx->stream));
+        GC_HIP(hipStreamSynchronize(ctx->stream));
         w->win_n = nwin;
     }
     GC_HIP(hipFuncSetAttribute((const void *)spec_psd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -297,11 +275,7 @@ bool spec_nfft_ok(int nfft) { return nfft == 8192 || nfft == 16384; }
 
 void gc_spec_free(gnsscorr_ctx *ctx)
 {
-    GcSpecWork *w = ctx->spec;
-    if (!w) return;
-    hipFree(w->psd); hipFree(w->sum); hipFree(w->hist); hipFree(w->maxd); hipFree(w->win);
-    hipFree(w->loc); hipFree(w->off); hipFree(w->stage);
-    delete w;
+    delete ctx->spec;
     ctx->spec = nullptr;
 }
 
@@ -427,7 +401,7 @@ extern "C" int spectrumanalyzer(const char *data, int dtype, int n, double f_sf,
     if (!rc) rc = spec_prepare(ctx, 1, nfft, SPEC_NLOOP);
     GcSpecWork *w = ctx->spec;
     const size_t bytes = (size_t)dtype * n;
-    if (!rc) rc = spec_grow(ctx, &w->stage, &w->stage_bytes, (bytes + 15) & ~(size_t)15);
+    if (!rc) rc = w->stage.reserve(ctx, (bytes + 15) & ~(size_t)15);
     if (!rc) {
         w->hloc.assign(1, 0);
         w->hoff = zuz;
