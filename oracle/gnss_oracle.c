@@ -468,6 +468,32 @@ void orc_pcorrelator_td(const signed char *data, int dtype, double ti, int n,
     free(dI); free(dQ); free(rc);
 }
 
+/* the same closed form at a list of lags: P[b*nlags + i] += |sum_j w[lags[i]+j] r[j]|^2/(32 m)^2 */
+void orc_pcorrelator_td_lags(const signed char *data, int dtype, double ti, int n,
+                             const double *freq, int nfreq, int m,
+                             const short *code, int clen, double ci,
+                             const int *lags, int nlags, double *P)
+{
+    short *dI = (short *)malloc(sizeof(short) * (size_t)(m + 64));
+    short *dQ = (short *)malloc(sizeof(short) * (size_t)(m + 64));
+    short *rc = (short *)malloc(sizeof(short) * (size_t)n);
+    int b, i, j;
+    orc_rescode_seq(code, clen, 0.0, 0, ci, n, rc);
+    for (b = 0; b < nfreq; b++) {
+        orc_mixcarr_seq(data, dtype, ti, m, freq[b], 0.0, dI, dQ);
+        for (i = 0; i < nlags; i++) {
+            const int k = lags[i];
+            double sr = 0.0, si = 0.0, sc = 32.0 * (double)m;
+            for (j = 0; j < n; j++) {
+                sr += dI[k + j] * rc[j];
+                si += dQ[k + j] * rc[j];
+            }
+            P[(size_t)b * nlags + i] += (sr * sr + si * si) / (sc * sc);
+        }
+    }
+    free(dI); free(dQ); free(rc);
+}
+
 /* ------------------------------------------------------------------------- */
 /* acquisition decision                                                      */
 /* ------------------------------------------------------------------------- */

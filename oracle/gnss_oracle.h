@@ -79,6 +79,11 @@ void orc_pcorrelator_td(const signed char *data, int dtype, double ti, int n,
                         const double *freq, int nfreq, int m,
                         const short *code, int clen, double ci,
                         int k0, int k1, double *P);
+/* the same at the lags lags[0..nlags) (each in [0, m-n]): P[b*nlags + i] */
+void orc_pcorrelator_td_lags(const signed char *data, int dtype, double ti, int n,
+                             const double *freq, int nfreq, int m,
+                             const short *code, int clen, double ci,
+                             const int *lags, int nlags, double *P);
 
 /* ref src/sdrcmn.c:461-497, :574-578 */
 double orc_maxvd(const double *d, int n, int exinds, int exinde, int *ind);

@@ -81,6 +81,7 @@ def lib():
     L.orc_codespectrum.argtypes = [vp, i, d, i, i, vp]
     L.orc_pcorrelator.argtypes = [vp, i, d, i, vp, i, d, i, vp, vp]
     L.orc_pcorrelator_td.argtypes = [vp, i, d, i, vp, i, i, vp, i, d, i, i, vp]
+    L.orc_pcorrelator_td_lags.argtypes = [vp, i, d, i, vp, i, i, vp, i, d, vp, i, vp]
     L.orc_maxvd.restype = d
     L.orc_maxvd.argtypes = [vp, i, i, i, C.POINTER(i)]
     L.orc_meanvd.restype = d

@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from acq_cases import _cn0_restated
 from conftest import rel_err
 from test_gpu_loop import _check_against_oracle
 from test_gpu_tracking import _oracle_run
@@ -79,20 +80,6 @@ def _acquire(orc, ochs, data, wrpos):
         o.xcode = None
         out.append((buffloc, iters.value, power))
     return out
-
-
-def _cn0_restated(P, codei, freqi, nsampchip, ctime):
-    """checkacquisition()'s C/N0 (ref src/sdracq.c:71-95): the peak over the mean of its Doppler row outside
-    codei +- 2*nsampchip (wrapping), with an exactly rounded sum.  The peak ratio and the 1e-4 bar on cn0 cannot see
-    that window's width at these shapes (one more sample per side moves cn0 by ~2e-5 relative): this can."""
-    import math
-    nsamp = P.shape[1]
-    s, e = codei - 2 * nsampchip, codei + 2 * nsampchip
-    s, e = s + nsamp if s < 0 else s, e - nsamp if e >= nsamp else e
-    i = np.arange(nsamp)
-    out = ((i < s) | (i > e)) if s <= e else ((i < s) & (i > e))
-    meanP = math.fsum(P[freqi][out]) / int(out.sum())
-    return 10 * math.log10(P[freqi, codei] / meanP / ctime)
 
 
 def _check_acq(r, o, buffloc, iters, where):
