@@ -209,7 +209,7 @@ EXPORTS_GNSSCORR = [
     "gnsscorr_trk_fetch", "gnsscorr_trk_fetch_sums", "gnsscorr_trk_devptrs", "gnsscorr_acq_run",
     "gnsscorr_acq_fetch", "gnsscorr_trk_start_from_acq", "gnsscorr_acq_power", "gnsscorr_fft16k", "gnsscorr_pspec",
     "gnsscorr_timing_enable", "gnsscorr_timing_read", "gnsscorr_timing_reset", "gnsscorr_default_ctx",
-    "gnsscorr_spec_run", "gnsscorr_spec_fetch"]
+    "gnsscorr_spec_run", "gnsscorr_spec_fetch", "gnsscorr_trk_loop_lapped"]
 EXPORTS_SDR = [
     "sdracquisition", "checkacquisition", "sdrtracking", "cumsumcorr", "clearcumsumcorr", "pll", "dll",
     "readinifile", "chk_initvalue", "initacqstruct", "inittrkprmstruct", "inittrkstruct", "initsdrch",
@@ -258,6 +258,7 @@ def lib():
     L.gnsscorr_loop_get.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(LoopState)]
     L.gnsscorr_trk_run_loop.argtypes = [C.c_void_p, C.c_int]
     L.gnsscorr_trk_fetch_log.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gnsscorr_trk_loop_lapped.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     L.gnsscorr_acq_run.argtypes = [C.c_void_p, C.c_uint64]
     L.gnsscorr_acq_fetch.argtypes = [C.c_void_p, C.POINTER(AcqRes)]
     L.gnsscorr_trk_start_from_acq.argtypes = [C.c_void_p]
@@ -570,6 +571,12 @@ class Engine:
         ndone = np.zeros(nch, np.int32)
         _check(self._L.gnsscorr_trk_fetch_log(self.h, log.ctypes.data, ndone.ctypes.data))
         return log, ndone
+
+    def trk_loop_lapped(self):
+        """Periods of the last trk_run_loop that read samples the writer had overwritten since."""
+        n = C.c_int()
+        _check(self._L.gnsscorr_trk_loop_lapped(self.h, C.byref(n)))
+        return n.value
 
     # -- acquisition
     def acq_run(self, wrpos=0):

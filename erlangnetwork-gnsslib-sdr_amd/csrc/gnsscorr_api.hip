@@ -106,7 +106,7 @@ static void drop_channel_buffers(gnsscorr_ctx *ctx)
     ctx->dchan.reset(); ctx->dcodes.reset(); ctx->dfreqs.reset(); ctx->detab.reset();
     ctx->dcorrI.reset(); ctx->dcorrQ.reset(); ctx->dsumI.reset(); ctx->dsumQ.reset(); ctx->dfinish.reset();
     ctx->dnco_overflow.reset(); ctx->dring_viol.reset();
-    ctx->dloop.reset(); ctx->dloopdone.reset(); ctx->dlooplog.reset();
+    ctx->dloop.reset(); ctx->dloopdone.reset(); ctx->dloop_lapped.reset(); ctx->dlooplog.reset();
     ctx->dstep_meta.reset(); ctx->dstep_unit.reset(); ctx->dstep_segs.reset(); ctx->dstep_rounds.reset();
     ctx->dstep_partial.reset();
     ctx->spec_ahead_valid = false;
@@ -828,6 +828,7 @@ static int ensure_step_buffers(gnsscorr_ctx *ctx)
     GC_RESERVE(ctx, ctx->dstep_segs, units);
     GC_RESERVE(ctx, ctx->dstep_rounds, units * nseg * 4);        // four rounds (one per wavefront) per workgroup
     GC_RESERVE(ctx, ctx->dstep_partial, units * nseg * 2 * ctx->ntap);
+    GC_RESERVE(ctx, ctx->dloop_lapped, 1);
     int rc = ctx->hostflags.reserve(16, hipHostMallocMapped);
     if (rc) return rc;
     GC_RESERVE(ctx, ctx->dstep_meta, ctx->nch);                   // last: the test above
@@ -855,6 +856,7 @@ extern "C" int gnsscorr_trk_run_loop(gnsscorr_ctx *ctx, int nperiod)
     GC_HIP(hipMemsetAsync(ctx->dcorrQ, 0, sizeof(double) * units * ctx->ntap, ctx->stream));
     GC_HIP(hipMemsetAsync(ctx->slot[0].nsamp, 0, sizeof(int) * units, ctx->stream));
     GC_HIP(hipMemsetAsync(ctx->dstep_meta, 0, sizeof(GcStepMeta) * ctx->nch, ctx->stream));
+    GC_HIP(hipMemsetAsync(ctx->dloop_lapped, 0, sizeof(int), ctx->stream));
     // write position of each channel's ring (ref src/sdrtrk.c:26-28: fendbuffsize*buffcnt), read together with the
     // ingest fence under the lock: the positions cover only samples whose transfer the compute stream is ordered behind
     std::vector<uint64_t> wp(ctx->nch);
@@ -897,7 +899,7 @@ extern "C" int gnsscorr_trk_run_loop(gnsscorr_ctx *ctx, int nperiod)
                 rc = gc_launch_step_tail(ctx->stream, ctx->dchan, ctx->dstate2[ctx->state_cur], ctx->dloop, ctx->dstep_meta, dwp,
                                          ctx->dstep_partial, ctx->dstep_unit, ctx->dstep_segs, ctx->dstep_rounds, ctx->dcorrI,
                                          ctx->dcorrQ, ctx->slot[0].nsamp, ctx->dlooplog, ctx->dloopdone, ctx->dnco_overflow,
-                                         ctx->hostflags.dev, ctx->nch, nperiod, ctx->step_nseg, ctx->ntap, ctx->max_n, kcap, 1);
+                                         ctx->dloop_lapped, ctx->hostflags.dev, ctx->nch, nperiod, ctx->step_nseg, ctx->ntap, ctx->max_n, kcap, 1);
                 if (rc) { cleanup(); return rc; }
             }
             for (int dtype = 1; dtype <= 2; dtype++) {
@@ -916,7 +918,7 @@ extern "C" int gnsscorr_trk_run_loop(gnsscorr_ctx *ctx, int nperiod)
     // close whatever the last correlator launch produced
     rc = gc_launch_step_tail(ctx->stream, ctx->dchan, ctx->dstate2[ctx->state_cur], ctx->dloop, ctx->dstep_meta, dwp, ctx->dstep_partial,
                              ctx->dstep_unit, ctx->dstep_segs, ctx->dstep_rounds, ctx->dcorrI, ctx->dcorrQ, ctx->slot[0].nsamp,
-                             ctx->dlooplog, ctx->dloopdone, ctx->dnco_overflow, ctx->hostflags.dev, ctx->nch, nperiod, ctx->step_nseg,
+                             ctx->dlooplog, ctx->dloopdone, ctx->dnco_overflow, ctx->dloop_lapped, ctx->hostflags.dev, ctx->nch, nperiod, ctx->step_nseg,
                              ctx->ntap, ctx->max_n, 1, 0);
     cleanup();
     if (rc) return rc;
@@ -937,6 +939,16 @@ extern "C" int gnsscorr_trk_fetch_log(gnsscorr_ctx *ctx, gnsscorr_trklog_t *log,
     if (ndone) GC_HIP(hipMemcpyAsync(ndone, ctx->dloopdone, sizeof(int) * ctx->nch, hipMemcpyDeviceToHost, ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
     return nco_check(ctx);
+}
+
+extern "C" int gnsscorr_trk_loop_lapped(gnsscorr_ctx *ctx, int *nlapped)
+{
+    if (!ctx || !nlapped) return gc_fail(GNSSCORR_EINVAL, "trk_loop_lapped: null argument");
+    if (!ctx->last_loop_nper) return gc_fail(GNSSCORR_ESTATE, "trk_loop_lapped: no completed trk_run_loop");
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_HIP(hipMemcpyAsync(nlapped, ctx->dloop_lapped, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));
+    return GNSSCORR_OK;
 }
 
 // Units whose NCO piece tables overflowed (a code step that wraps the code more than ~twice per call, a

@@ -185,6 +185,7 @@ struct gnsscorr_ctx {
     bool loop_sync_hint = false;                   // some channel had its nav bit synchronised when last seen
     int loop_kmax = 1;                             // largest loopms among the channels' loop states (gnsscorr_loop_set)
     GcDevBuf<gnsscorr_trklog_t> dlooplog;          // [nch][nperiod]
+    GcDevBuf<int> dloop_lapped;                    // periods of the last trk_run_loop read after the writer lapped them
     GcDevBuf<int> dloopdone;                       // [nch], then the rings' write positions [nch] (uint64)
     int last_loop_nper = 0;                        // > 0: the last run was a closed-loop one of that many periods
     int last_slot = 0;                             // slot of the last completed trk_run

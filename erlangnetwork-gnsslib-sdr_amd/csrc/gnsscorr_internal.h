@@ -172,7 +172,7 @@ int gc_step_nseg(int dtype, int max_n);          // workgroups (one round each) 
 int gc_launch_step_tail(hipStream_t st, const GcChan *chan, GcTrkState *state, gnsscorr_loop_t *loop, GcStepMeta *meta,
                         const uint64_t *wrpos, const int *partial, GcTrkUnit *unit, GcUnitSegs *segs, GcRound *rounds,
                         double *corrI, double *corrQ, int *nsamp_out, gnsscorr_trklog_t *log, int *ndone, int *nco_overflow,
-                        unsigned *hostflags, int nch, int nper, int nseg, int ntap, int max_n, int kcap, int plan);
+                        int *lapped, unsigned *hostflags, int nch, int nper, int nseg, int ntap, int max_n, int kcap, int plan);
 int gc_launch_step_corr(hipStream_t st, const GcChan *chan, const GcStepMeta *meta, const GcTrkUnit *unit, const GcUnitSegs *segs,
                         const GcRound *rounds, int *partial, int nch, int kcap, int nseg, int dtype, int ntap, int max_n,
                         int smax_max);

@@ -429,8 +429,8 @@ __global__ __launch_bounds__(64 * GC_TAIL_NW) void trk_step_tail_kernel(
     GcStepMeta *__restrict__ meta, const uint64_t *__restrict__ wrpos, const int *__restrict__ partial,
     GcTrkUnit *__restrict__ unit, GcUnitSegs *__restrict__ segs, GcRound *__restrict__ rounds, double *__restrict__ corrI,
     double *__restrict__ corrQ, int *__restrict__ nsamp_out, gnsscorr_trklog_t *__restrict__ log, int *__restrict__ ndone,
-    int *__restrict__ nco_overflow, unsigned *__restrict__ hostflags, int nch, int nper, int nseg, int ntap_stride, int max_n,
-    int kcap, int plan)
+    int *__restrict__ nco_overflow, int *__restrict__ lapped, unsigned *__restrict__ hostflags, int nch, int nper, int nseg,
+    int ntap_stride, int max_n, int kcap, int plan)
 {
     __shared__ __attribute__((aligned(16))) TailShared S;
     const int ch = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -706,6 +706,9 @@ __global__ __launch_bounds__(64 * GC_TAIL_NW) void trk_step_tail_kernel(
                 const bool fastdiv = spc > 1e-300 && spc < 1e300 && yspc < 1e300;
                 for (int e = 0; e < want; e++) {
                     if (!(have_data && bufflocnow > buffloc)) { if (lane == 0) S.starved = 1; break; }
+                    // a period whose first samples the writer has overwritten since (more than a ring behind it): run as the
+                    // reference's sdrtracking() runs it, and counted (gnsscorr_trk_loop_lapped)
+                    if (lane == 0 && wp > c.ringlen && buffloc < wp - c.ringlen) atomicAdd(lapped, 1);
                     // (dlen - remcode) / (codefreq / f_sf), ref src/sdrtrk.c:31-32: correctly rounded through the reciprocal
                     // (gc_div_y) where that is safe, as the batch planner divides
                     const double num = __dsub_rn(dlen, remcode);
@@ -1027,11 +1030,11 @@ int gc_step_nseg(int dtype, int max_n)
 int gc_launch_step_tail(hipStream_t st, const GcChan *chan, GcTrkState *state, gnsscorr_loop_t *loop, GcStepMeta *meta,
                         const uint64_t *wrpos, const int *partial, GcTrkUnit *unit, GcUnitSegs *segs, GcRound *rounds,
                         double *corrI, double *corrQ, int *nsamp_out, gnsscorr_trklog_t *log, int *ndone, int *nco_overflow,
-                        unsigned *hostflags, int nch, int nper, int nseg, int ntap, int max_n, int kcap, int plan)
+                        int *lapped, unsigned *hostflags, int nch, int nper, int nseg, int ntap, int max_n, int kcap, int plan)
 {
     if (kcap < 1 || kcap > GC_STEP_KMAX) return gc_fail(GNSSCORR_EINVAL, "trk_step: %d periods per step (1..%d)", kcap, GC_STEP_KMAX);
     hipLaunchKernelGGL(trk_step_tail_kernel, dim3(nch), dim3(64 * GC_TAIL_NW), 0, st, chan, state, loop, meta, wrpos, partial, unit, segs, rounds,
-                       corrI, corrQ, nsamp_out, log, ndone, nco_overflow, hostflags, nch, nper, nseg, ntap, max_n, kcap, plan);
+                       corrI, corrQ, nsamp_out, log, ndone, nco_overflow, lapped, hostflags, nch, nper, nseg, ntap, max_n, kcap, plan);
     GC_HIP(hipGetLastError());
     return 0;
 }

@@ -264,8 +264,13 @@ int  gnsscorr_frame_replay(gnsscorr_frame_t *st, const gnsscorr_trklog_t *log, i
  * <= buffloc).  Returns when the last launches are queued (it keeps at most a few
  * filter intervals of launches ahead of the device); results by gnsscorr_trk_fetch
  * (II/QQ per period, periods not run are zero with nsamp_out 0) and
- * gnsscorr_trk_fetch_log. */
+ * gnsscorr_trk_fetch_log.  A period that starts more than ringlen samples behind
+ * the write position reads samples the writer has overwritten since: it is run,
+ * as sdrtracking() runs it, and counted (gnsscorr_trk_loop_lapped). */
 int  gnsscorr_trk_run_loop(gnsscorr_ctx *ctx, int nperiod);
+/* *nlapped = periods of the last gnsscorr_trk_run_loop that read overwritten
+ * samples (0: every period read what the ring holds); synchronises */
+int  gnsscorr_trk_loop_lapped(gnsscorr_ctx *ctx, int *nlapped);
 /* log[nch][nperiod] of the last gnsscorr_trk_run_loop; ndone[nch] = periods run */
 int  gnsscorr_trk_fetch_log(gnsscorr_ctx *ctx, gnsscorr_trklog_t *log, int *ndone);
 

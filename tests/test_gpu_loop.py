@@ -166,17 +166,29 @@ def test_closed_loop_stops_where_data_ends(gc, orc, synth, engine):
     assert np.all(ndone2 == 10)
 
 
-def _check_against_oracle(orc, engine, ochs, ring, bufflocs, nrun, ntap, done=0, tol=1e-14):
+def _check_against_oracle(orc, engine, ochs, ring, bufflocs, nrun, ntap, done=0, tol=1e-14, stops=False,
+                          between=None):
     """One trk_run_loop(nrun) against nrun oracle steps per channel: sums, samples, flags and remainders bit for
-    bit, filter states to 1e-12."""
+    bit, filter states to 1e-12.  ring: the oracle's ring, or a list of one per channel.  stops: a channel may stop
+    where its ring's data ends (the oracle's step finds nothing to track); it must stop at the same period, with zero
+    rows after it.  between: called after trk_run_loop returns and before the fetch, while the run's launches may
+    still be queued.  Returns ndone."""
     L = orc.lib()
     engine.trk_run_loop(nrun)
+    if between is not None:
+        between()
     II, QQ, ns = engine.trk_fetch()
     log, ndone = engine.trk_fetch_log()
-    assert np.all(ndone == nrun), ndone
+    if not stops:
+        assert np.all(ndone == nrun), ndone
     for i, o in enumerate(ochs):
+        ring_i = ring[i] if isinstance(ring, list) else ring
         for e in range(nrun):
-            assert L.orc_sdrthread_step(C.byref(o), C.byref(ring), C.byref(bufflocs[i])) == 1
+            if not L.orc_sdrthread_step(C.byref(o), C.byref(ring_i), C.byref(bufflocs[i])):
+                assert stops and ndone[i] == e, (i, done + e, int(ndone[i]))
+                assert np.all(ns[i, e:] == 0) and np.all(log[i, e:]["currnsamp"] == 0), (i, e)
+                assert not np.any(II[i, e:]) and not np.any(QQ[i, e:]), (i, e)
+                break
             where = (i, done + e)
             assert ns[i, e] == o.currnsamp, where
             assert np.array_equal(II[i, e], np.ctypeslib.as_array(o.II)[:ntap]), where
@@ -185,6 +197,9 @@ def _check_against_oracle(orc, engine, ochs, ring, bufflocs, nrun, ntap, done=0,
             assert r["flagloopfilter"] == o.flagloopfilter, where
             assert r["remcode"] == o.remcode and r["remcarr"] == o.remcarr, where
             _adopt(o, r, where, tol)
+        else:
+            assert ndone[i] == nrun, (i, int(ndone[i]))
+    return ndone
 
 
 def test_closed_loop_bench_configuration_32_channels(gc, orc, synth, engine):
