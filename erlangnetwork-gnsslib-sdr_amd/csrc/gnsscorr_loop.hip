@@ -179,9 +179,10 @@ struct LdsCarTable {        // GcCarTable (gnsscorr_nco.h): pieces as (x, d) dou
     gc_lds_car seg;
     int n, overflow;
     bool lastzero;
+    __device__ void reset() { n = 0; overflow = 0; lastzero = false; }
     __device__ void operator()(int k, double x, double d, int)
     {
-        const int e = (int)((gc_d2u(x) >> 52) & 0x7FF) - 1023;
+        const int e = gc_expo(x) - 1023;
         const bool zero = e < 0 || e >= 31;             // gc_carseg_make gives the all-zero piece exactly then
         if (n > 0 && zero && lastzero) return;
         if (n >= GC_NCAR) { overflow = 1; return; }
@@ -207,6 +208,7 @@ struct LdsCodeTable {       // GcCodeTable (gnsscorr_nco.h); inv is filled in by
     int cap, n, overflow;
     int lw, lcnt;           // the last piece: wrap count, positions
     double ly0, lyl;        //                 first and last value
+    __device__ void reset() { n = 0; overflow = 0; }
     __device__ void operator()(int j, double y, double d, int count, int w)
     {
         GC_FP_STRICT
@@ -280,8 +282,8 @@ __device__ __forceinline__ void fast_init_lanes(GcNcoFast &f, double s, bool wit
 {
     GC_FP_STRICT
     const uint64_t us = gc_d2u(s);
-    const int es = (int)((us >> 52) & 0x7FF);
-    const bool ok = es > 60 && es < 0x7FF - GC_NB - 4;
+    const int es = gc_expo(s);
+    const bool ok = gc_fast_has_table(s);
     double d = 0.0, inv = 0.0;
     bool tie = false;
     if (ok && lane < GC_NB) {
@@ -305,7 +307,7 @@ __device__ __forceinline__ void fast_init_lanes(GcNcoFast &f, double s, bool wit
         f.s = s;
         f.inv_s = __ddiv_rn(1.0, fabs(s));
         f.tie = (unsigned)tm & ((1u << GC_NB) - 1u);
-        f.ex0 = ok ? es + 2 : 0x7FFFFFF;
+        f.ex0 = ok ? es + 2 : GC_NO_TABLE;
     }
 }
 // gc_code_plan_init(P, ci, len, smax) around fast_init_lanes
@@ -316,26 +318,7 @@ __device__ __forceinline__ void code_plan_init_lanes(GcCodePlan &P, double ci, i
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const double dlen = (double)len;
-    const double limtop = gc_u2d(gc_d2u(dlen) - 1);
-    const int ex0 = P.f.ex0;
-    const unsigned tie = P.f.tie;
-    const int itop = (int)((gc_d2u(limtop) >> 52) & 0x7FF) - ex0;
-    const bool ok = ex0 != 0x7FFFFFF && ci > 0.0 && itop >= 1 && itop < GC_NB &&
-                    dlen + ci < gc_u2d((uint64_t)(ex0 + itop + 1) << 52) && !((tie >> itop) & 1);
-    int it = -1;
-#pragma unroll
-    for (int i = 0; i < GC_NB; i++)
-        if (((tie >> i) & 1) && i <= itop) it = i;
-    if (lane == 0) {
-        P.dlen = dlen;
-        P.smaxci = (double)smax * ci;
-        P.limtop = limtop;
-        P.itop = itop;
-        P.ok = ok;
-        P.exact = ok && gc_cert_exact(limtop, ci, dlen);
-        P.it = it;
-    }
+    if (lane == 0) gc_code_plan_shape(P, ci, len, smax);
 }
 
 // the general walkers for a period the shaped steps decline (a tie in the top binade, a phase next to zero, ...):
@@ -368,9 +351,9 @@ __device__ __attribute__((noinline)) bool tail_code_checked(const GcCodePlan *PC
     GcCodeClaims c2 = *cl;
     double r;
     bool ok;
-    if (tcls == 0) ok = gc_code_claims_step<IT, 8, false, true>(*PC, SC, remcode, nt, c2, &r);
-    else if (tcls == 1) ok = gc_code_claims_step<IT, GC_CLAIM_TAIL, false, true>(*PC, SC, remcode, nt, c2, &r);
-    else ok = gc_code_claims_step<IT, GC_CLAIM_TAIL2, false, true>(*PC, SC, remcode, nt, c2, &r);
+    if (tcls == 0) ok = gc_code_claims_step<IT, gc_tail_max(0), false, true>(*PC, SC, remcode, nt, c2, &r);
+    else if (tcls == 1) ok = gc_code_claims_step<IT, gc_tail_max(1), false, true>(*PC, SC, remcode, nt, c2, &r);
+    else ok = gc_code_claims_step<IT, gc_tail_max(2), false, true>(*PC, SC, remcode, nt, c2, &r);
     if (ok) *out = r;
     return ok;
 }
@@ -621,8 +604,7 @@ __global__ __launch_bounds__(64 * GC_TAIL_NW) void trk_step_tail_kernel(
                 int nhat;
                 gc_spec_start(S.remcode[0], S.remcarr[0], ci, spc, ps, dlen, pe, &rc, &rk, &nhat);
                 end = hiend ? rc + W : rc - W;
-                const double q = __ddiv_rn(__dsub_rn(dlen, end), spc);           // ref src/sdrtrk.c:31-32
-                n = (q > -2147483648.0 && q < 2147483648.0) ? (int)q : 0;
+                n = gc_period_nsamp(dlen, end, spc);
                 side = end - S.PC.smaxci < 0.0 ? 1 : 0;                          // (ref src/sdrcmn.c:614: one branch for the whole bracket)
                 if (n > 0 && n <= (1 << 24)) ok = gc_code_claims<true>(S.PC, end, n + 2 * c.smax, cc, &dummy);
             }
@@ -635,8 +617,7 @@ __global__ __launch_bounds__(64 * GC_TAIL_NW) void trk_step_tail_kernel(
             const double other = __shfl(end, lane ^ 32, 64);
             if (!hiend) {
                 // (the discovering step allows the widest tail; the chain's instance may be narrower)
-                const int tmax = c.smax + 1 > 8 ? (c.smax + 1 > GC_CLAIM_TAIL ? GC_CLAIM_TAIL2 : GC_CLAIM_TAIL) : 8;
-                cc.tag = (same && n + 2 * c.smax - cc.jsum <= tmax) ? 1 : 0;
+                cc.tag = (same && n + 2 * c.smax - cc.jsum <= gc_tail_max(gc_tail_class(c.smax))) ? 1 : 0;
                 cc.n = n;
                 cc.lo = end;
                 cc.hi = other;
@@ -697,7 +678,7 @@ __global__ __launch_bounds__(64 * GC_TAIL_NW) void trk_step_tail_kernel(
                 GcCodeStepC<IT> SC;
                 const bool inst = ITOP != 0 && S.PC.ok;
                 if (inst) gc_code_stepc_init(SC, S.PC);
-                const int tcls = c.smax + 1 > 8 ? (c.smax + 1 > GC_CLAIM_TAIL ? 2 : 1) : 0;       // tail positions: 8, 15 or 32
+                const int tcls = gc_tail_class(c.smax);
                 double remcode = S.remcode[0];
                 uint64_t buffloc = S.buffloc[0];
                 GcNoEmit ne;
@@ -734,9 +715,9 @@ __global__ __launch_bounds__(64 * GC_TAIL_NW) void trk_step_tail_kernel(
                             const bool inside = __builtin_amdgcn_readfirstlane((inst && cl.tag == 1 && remcode >= cl.lo && remcode <= cl.hi && n == cl.n) ? 1 : 0) != 0;
                             bool ok = inside;
                             if (inside) {
-                                if (tcls == 0) (void)gc_code_claims_step<IT, 8, false>(S.PC, SC, remcode, nt, cl, &r);
-                                else if (tcls == 1) (void)gc_code_claims_step<IT, GC_CLAIM_TAIL, false>(S.PC, SC, remcode, nt, cl, &r);
-                                else (void)gc_code_claims_step<IT, GC_CLAIM_TAIL2, false>(S.PC, SC, remcode, nt, cl, &r);
+                                if (tcls == 0) (void)gc_code_claims_step<IT, gc_tail_max(0), false>(S.PC, SC, remcode, nt, cl, &r);
+                                else if (tcls == 1) (void)gc_code_claims_step<IT, gc_tail_max(1), false>(S.PC, SC, remcode, nt, cl, &r);
+                                else (void)gc_code_claims_step<IT, gc_tail_max(2), false>(S.PC, SC, remcode, nt, cl, &r);
                             } else if (inst && cl.tag == 1) {
                                 double r2;
                                 ok = tail_code_checked<IT>(&S.PC, remcode, nt, tcls, &S.ccl[e], &r2);
@@ -831,8 +812,7 @@ __global__ __launch_bounds__(64 * GC_TAIL_NW) void trk_step_tail_kernel(
             const double remcode = S.remcode[e];
             double r;
             if (!gc_code_period(S.PC, remcode, n + 2 * c.smax, fill, &r, dt)) {
-                dt.n = 0;
-                dt.overflow = 0;
+                dt.reset();
                 r = tail_code_slow(ci, remcode, c.clen, c.smax, n + 2 * c.smax, dt);
             }
             tail_wave_sync();
@@ -846,9 +826,7 @@ __global__ __launch_bounds__(64 * GC_TAIL_NW) void trk_step_tail_kernel(
             const double remcarr = S.remcarr[e];
             double r;
             if (!gc_carrier_period(S.PK, remcarr, n, fill, &r, ct)) {
-                ct.n = 0;
-                ct.overflow = 0;
-                ct.lastzero = false;
+                ct.reset();
                 r = tail_carrier_slow(ps, remcarr, n, ct);
             }
             tail_wave_sync();

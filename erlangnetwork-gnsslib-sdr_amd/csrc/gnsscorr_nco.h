@@ -27,6 +27,7 @@
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
+#include <type_traits>
 
 #if defined(__HIPCC__)
 #define GC_HD __host__ __device__ inline
@@ -62,6 +63,8 @@
 
 GC_HD uint64_t gc_d2u(double x) { uint64_t u; memcpy(&u, &x, 8); return u; }
 GC_HD double gc_u2d(uint64_t u) { double x; memcpy(&x, &u, 8); return x; }
+GC_HD int gc_expo(double x) { return (int)((gc_d2u(x) >> 52) & 0x7FF); }      // biased exponent
+GC_HD uint32_t gc_hi32(double x) { return (uint32_t)(gc_d2u(x) >> 32); }
 
 // Sequence x_0 = x, x_{i+1} = fl(x_i + s).  Returns m in [0, cap] and *d such that
 // x_i = x + i*(*d) EXACTLY (every such value is representable) for i = 0..m.
@@ -81,7 +84,7 @@ GC_HD int64_t gc_nco_run(double x, double s, int64_t cap, double *d)
     if (cap <= 0) return 0;
     if (s == 0.0) return cap;
     const uint64_t ux = gc_d2u(x), us = gc_d2u(s);
-    const int ex = (int)((ux >> 52) & 0x7FF), es = (int)((us >> 52) & 0x7FF);
+    const int ex = gc_expo(x), es = gc_expo(s);
     if (ex == 0 || ex == 0x7FF || es == 0 || es == 0x7FF) return 0;      // zero, subnormal, inf, nan
     // t = s / u = s * 2^(1075 - ex), exact while its exponent stays in range
     const int et = es + 1075 - ex;
@@ -145,9 +148,11 @@ GC_HD double gc_carrier_walk(double x, double ps, int n, Emit &emit)
     return x;
 }
 
+// (reset(): an emitter forgets the pieces of an attempt that was given up, before the next one starts)
 struct GcNoEmit {
     GC_HDM void operator()(int, double, double, int) const {}
     GC_HDM void operator()(int, double, double, int, int) const {}
+    GC_HDM void reset() const {}
 };
 
 // phase remainder: prem = phi*DPI/CDIV; while (prem > DPI) prem -= DPI  (ref :666-668),
@@ -240,7 +245,7 @@ GC_HD GcCarSeg gc_carseg_make(double x, double d)
     s.fx = 0;
     s.dfx = 0;
     const uint64_t ux = gc_d2u(x);
-    const int e = (int)((ux >> 52) & 0x7FF) - 1023;
+    const int e = gc_expo(x) - 1023;
     if (e < 0 || e >= 31) return s;
     const uint64_t A = (ux & 0x000FFFFFFFFFFFFFull) | 0x0010000000000000ull;   // |x| = A 2^(e-52)
     const int sh = e + 7;                                                     // -> A 2^(e-52+59)
@@ -261,6 +266,7 @@ struct GcCarTable {
     int *k0;
     GcCarSeg *seg;
     int cap, n, overflow;
+    GC_HDM void reset() { n = 0; overflow = 0; }
     GC_HDM void operator()(int k, double x, double d, int /*count*/)
     {
         const GcCarSeg s = gc_carseg_make(x, d);
@@ -281,6 +287,7 @@ struct GcCodeSeg {
 struct GcCodeTable {
     GcCodeSeg *seg;
     int cap, n, overflow;
+    GC_HDM void reset() { n = 0; overflow = 0; }
     GC_HDM void operator()(int j, double y, double d, int count, int w)
     {
         GC_FP_STRICT
@@ -356,6 +363,7 @@ GC_HD int gc_carrier_idx_at(const int *k0, const GcCarSeg *seg, int nseg, int k)
 // falls through to one gc_nco_run() piece and the fast pass is tried again: both
 // produce exact values, so mixing them is free of consequences.
 #define GC_NB 20
+#define GC_NO_TABLE 0x7FFFFFF       // GcNcoFast.ex0 of an addend without a table: zero, subnormal, inf, nan or exponents out of range
 struct GcNcoFast {
     double s;
     double inv_s;               // RN(1/|s|)
@@ -365,17 +373,25 @@ struct GcNcoFast {
     double inv[GC_NB];          // 1/|d| (0 when d = 0)
 };
 
+// an addend has a table when its exponent leaves room for GC_NB binades above it (and it is no zero, subnormal, ...)
+GC_HD bool gc_fast_has_table(double s)
+{
+    const int es = gc_expo(s);
+    return es > 60 && es < 0x7FF - GC_NB - 4;
+}
+
 // with_inv = false leaves inv[] zero (the period steps need only inv_s and, for the code, inv[itop])
+// (the closed loop's fast_init_lanes builds the same table one binade per lane)
 GC_HD void gc_fast_init(GcNcoFast &f, double s, bool with_inv = true)
 {
     GC_FP_STRICT
     const uint64_t us = gc_d2u(s);
-    const int es = (int)((us >> 52) & 0x7FF);
+    const int es = gc_expo(s);
     f.s = s;
     f.inv_s = 1.0 / fabs(s);
     f.tie = 0;
-    f.ex0 = 0x7FFFFFF;          // no table: zero, subnormal, inf, nan or exponents out of range
-    const bool ok = es > 60 && es < 0x7FF - GC_NB - 4;
+    f.ex0 = GC_NO_TABLE;
+    const bool ok = gc_fast_has_table(s);
     if (ok) f.ex0 = es + 2;
 #pragma unroll
     for (int i = 0; i < GC_NB; i++) {
@@ -395,15 +411,9 @@ GC_HD void gc_fast_init(GcNcoFast &f, double s, bool with_inv = true)
     }
 }
 
-// one table piece: x in binade ex0 + i, growing.  lim_below: values must stay below it (code: the code
-// length; carrier: +inf).  Returns the run length m <= cap with x + j d exact for j <= m.
-GC_HD int gc_piece_len(double d, double inv, double x, int cap, double lim_below);
-GC_HD int gc_fast_piece(const GcNcoFast &f, int i, double x, int cap, double lim_below)
-{
-    return gc_piece_len(f.d[i], f.inv[i], x, cap, lim_below);
-}
-
-// d, inv: the step RN_u(s) of x's binade and RN(1/|d|)
+// one table piece: x in its binade, growing; d, inv: the step RN_u(s) of that binade and RN(1/|d|).  lim_below:
+// values must stay below it (code: the code length; carrier: +inf).  Returns the run length m <= cap with
+// x + j d exact for j <= m.
 GC_HD int gc_piece_len(double d, double inv, double x, int cap, double lim_below)
 {
     GC_FP_STRICT
@@ -430,26 +440,26 @@ GC_HD double gc_fast_carrier_walk(const GcNcoFast &f, double x, int n, Emit &emi
 {
     GC_FP_STRICT
     const double s = f.s;
-    const bool table = f.ex0 != 0x7FFFFFF;
+    const bool table = f.ex0 != GC_NO_TABLE;
     int k = 0;
     while (k < n) {
         const int kin = k;
         // next to zero (fewer than ~4 steps per binade) every sample is its own piece: the reference's
         // own additions, in a loop of their own
-        while (table && k < n && (x == 0.0 || (int)((gc_d2u(x) >> 52) & 0x7FF) < f.ex0)) {
+        while (table && k < n && (x == 0.0 || gc_expo(x) < f.ex0)) {
             emit(k, x, 0.0, 1);
             x = x + s;
             k += 1;
         }
         if (k < n && x != 0.0 && (gc_d2u(x) >> 63) == (gc_d2u(s) >> 63)) {
-            const int i0 = (int)((gc_d2u(x) >> 52) & 0x7FF) - f.ex0;
+            const int i0 = gc_expo(x) - f.ex0;
 #pragma unroll
             for (int i = 0; i < GC_NB; i++) {
                 if (i < i0) continue;
                 const uint64_t ux = gc_d2u(x);
-                if (!(k < n && (int)((ux >> 52) & 0x7FF) == f.ex0 + i)) break;
+                if (!(k < n && gc_expo(x) == f.ex0 + i)) break;
                 if (!(((f.tie >> i) & 1) && (ux & 1))) {
-                    const int m = gc_fast_piece(f, i, x, n - 1 - k, INFINITY);
+                    const int m = gc_piece_len(f.d[i], f.inv[i], x, n - 1 - k, INFINITY);
                     emit(k, x, f.d[i], m + 1);
                     x = fma((double)m, f.d[i], x);
                     k += m;
@@ -475,25 +485,25 @@ GC_HD double gc_fast_code_walk(const GcNcoFast &f, double c, int len, int nt, Em
 {
     GC_FP_STRICT
     const double ci = f.s, dlen = (double)len;
-    const bool table = f.ex0 != 0x7FFFFFF && ci > 0.0;
+    const bool table = f.ex0 != GC_NO_TABLE && ci > 0.0;
     int j = 0, w = 0;
     while (j < nt) {
         if (c >= dlen) { c = c - dlen; w++; }
         const int jin = j;
-        while (table && j < nt && c < dlen && (c == 0.0 || (int)((gc_d2u(c) >> 52) & 0x7FF) < f.ex0)) {
+        while (table && j < nt && c < dlen && (c == 0.0 || gc_expo(c) < f.ex0)) {
             emit(j, c, 0.0, 1, w);
             c = c + ci;
             j += 1;
         }
         if (table && j < nt && c > 0.0 && c < dlen) {
-            const int i0 = (int)((gc_d2u(c) >> 52) & 0x7FF) - f.ex0;
+            const int i0 = gc_expo(c) - f.ex0;
 #pragma unroll
             for (int i = 0; i < GC_NB; i++) {
                 if (i < i0) continue;
                 const uint64_t uc = gc_d2u(c);
-                if (!(j < nt && c < dlen && (int)((uc >> 52) & 0x7FF) == f.ex0 + i)) break;
+                if (!(j < nt && c < dlen && gc_expo(c) == f.ex0 + i)) break;
                 if (!(((f.tie >> i) & 1) && (uc & 1))) {
-                    const int m = gc_fast_piece(f, i, c, nt - 1 - j, dlen);
+                    const int m = gc_piece_len(f.d[i], f.inv[i], c, nt - 1 - j, dlen);
                     emit(j, c, f.d[i], m + 1, w);
                     c = fma((double)m, f.d[i], c);
                     j += m;
@@ -529,13 +539,13 @@ GC_HD double gc_fast_prem(const GcNcoFast &f, double phi)
     if (!(p < 1.0e300)) return p;
     // table binades start at 2^(ex0 - 1023) = 16 > DPI: inside them every value exceeds DPI, so the loop
     // condition holds for every step of a piece
-    bool more = (int)((gc_d2u(p) >> 52) & 0x7FF) >= f.ex0 && p > 0.0;      // below 16: the plain loop at the end
+    bool more = gc_expo(p) >= f.ex0 && p > 0.0;      // below 16: the plain loop at the end
     while (more) {
         more = false;
 #pragma unroll
         for (int i = GC_NB - 1; i >= 0; i--) {
             const uint64_t up = gc_d2u(p);
-            if ((int)((up >> 52) & 0x7FF) == f.ex0 + i && !(up >> 63) && !(((f.tie >> i) & 1) && (up & 1))) {
+            if (gc_expo(p) == f.ex0 + i && !(up >> 63) && !(((f.tie >> i) & 1) && (up & 1))) {
                 // down to the multiplier 2^52 + 1 of this binade
                 const double lo = gc_u2d((up & 0xFFF0000000000000ull) | 1ull);
                 const double R = p - lo;
@@ -551,7 +561,7 @@ GC_HD double gc_fast_prem(const GcNcoFast &f, double phi)
                 more = true;
             }
         }
-        if ((int)((gc_d2u(p) >> 52) & 0x7FF) >= f.ex0 + GC_NB) return gc_carrier_prem(phi);   // beyond the table
+        if (gc_expo(p) >= f.ex0 + GC_NB) return gc_carrier_prem(phi);   // beyond the table
     }
     while (p > GC_NCO_DPI) p = p - GC_NCO_DPI;
     return p;
@@ -568,6 +578,22 @@ GC_HD double gc_div_y(double x, double b, double y)
     const double q = x * y;
     const double r = fma(-q, b, x);
     return fma(r, y, q);
+}
+
+// samples of the period that starts at code phase remcode: (int)((len - remcode)/spc), spc = chips per sample
+// (ref src/sdrtrk.c:31-32); 0 where the quotient leaves the range of int.  yspc = gc_period_yspc(spc): the
+// division by reciprocal (gc_div_y) where it has one.
+GC_HD int gc_period_nsamp(double dlen, double remcode, double spc, double yspc = 0.0)
+{
+    GC_FP_STRICT
+    const double num = dlen - remcode;
+    const double q = yspc != 0.0 ? gc_div_y(num, spc, yspc) : GC_DDIV(num, spc);
+    return (q > -2147483648.0 && q < 2147483648.0) ? (int)q : 0;
+}
+GC_HD double gc_period_yspc(double spc)
+{
+    const double yspc = GC_DDIV(1.0, spc);
+    return (spc > 1e-300 && spc < 1e300 && yspc < 1e300) ? yspc : 0.0;
 }
 
 // gc_code_start without its division while -len <= coff - smax*ci < len (the neighbours of -1, 0 and 1
@@ -645,7 +671,7 @@ GC_HD double gc_cert_margin(double b, double inv)
 // ulp(top)
 GC_HD bool gc_cert_exact(double x0, double s, double top)
 {
-    const int et = (int)((gc_d2u(top) >> 52) & 0x7FF);
+    const int et = gc_expo(top);
     if (et < 64) return false;
     const double sc = gc_u2d((uint64_t)(2046 - (et - 52)) << 52);           // 1/ulp(top)
     const double a = x0 * sc, b = s * sc;
@@ -693,7 +719,7 @@ GC_HD bool gc_cert_chain(const GcNcoFast &f, double *px, int *pk, int n, int i0,
 
 // Crossings of one growing stretch, computed "per lane": boundary index i in (i0, GC_NB) is the bottom
 // of table binade i, boundary GC_NB is the walk's limit (the code length; carrier: none).  On the host
-// this is a loop, on the device lane i computes K[i] (gnsscorr_trk.hip) -- same function per boundary.
+// this is a loop (GcFillLoop), on the device lane i computes K[i] (GcFillLanes) -- same function per boundary.
 struct GcCertCtx {
     double a0, sabs, inv;   // |x0|, |s|, RN(1/|s|)
     int    n;               // steps available
@@ -712,14 +738,14 @@ GC_HD int gc_cert_lane(const GcCertCtx &c, int i, double lim)
 
 // One growing stretch through the table by certified crossings: x at index k (same sign as s, inside
 // the table, below lim) -> index n or the first sample at/above lim.  gc_cert_setup checks the shape
-// and prepares the per-boundary context; then one gc_cert_lane per boundary (host: a loop, device: one
-// lane each); then gc_cert_chain.  false: not done (caller falls back to the piece walkers).
+// and prepares the per-boundary context; then one gc_cert_lane per boundary (`fill`); then gc_cert_chain.
+// false: not done (caller falls back to the piece walkers).
 GC_HD bool gc_cert_setup(const GcNcoFast &f, double x, int k, int n, double lim, GcCertCtx *c, int *pi0, int *pilim)
 {
     GC_FP_STRICT
-    const int ex = (int)((gc_d2u(x) >> 52) & 0x7FF);
+    const int ex = gc_expo(x);
     const int i0 = ex - f.ex0;
-    if (f.ex0 == 0x7FFFFFF || i0 < 0 || i0 >= GC_NB || !(fabs(x) < lim)) return false;
+    if (f.ex0 == GC_NO_TABLE || i0 < 0 || i0 >= GC_NB || !(fabs(x) < lim)) return false;
     if ((gc_d2u(x) >> 63) != (gc_d2u(f.s) >> 63)) return false;
     c->a0 = fabs(x);
     c->sabs = fabs(f.s);
@@ -731,7 +757,7 @@ GC_HD bool gc_cert_setup(const GcNcoFast &f, double x, int k, int n, double lim,
     if (lim < 1.0e300) {
         // binade of the largest value below the limit
         const double below = gc_u2d(gc_d2u(lim) - 1);
-        ilim = (int)((gc_d2u(below) >> 52) & 0x7FF) - f.ex0;
+        ilim = gc_expo(below) - f.ex0;
         if (ilim < i0 || ilim >= GC_NB) return false;
         // the sample that reaches the limit must still be inside binade ilim (lim + |s| below its top)
         if (!(lim + c->sabs < gc_u2d((uint64_t)(f.ex0 + ilim + 1) << 52))) return false;
@@ -745,15 +771,60 @@ GC_HD bool gc_cert_setup(const GcNcoFast &f, double x, int k, int n, double lim,
     return true;
 }
 
-GC_HD bool gc_cert_stretch(const GcNcoFast &f, double *px, int *pk, int n, double lim, int *K)
+// fill(K, ctx, i0, itop, lim): K[i] = certified crossing of boundary i (i0 < i <= itop: bottom of table
+// binade i; i == GC_NB: lim) relative to ctx.a0 -- gc_cert_lane per boundary; returns false on any
+// GC_CERT_FAIL.  (host: GcFillLoop below; device: GcFillLanes, one lane per boundary + readlane)
+// The crossings handed back are strictly increasing over i0 < i <= itop, and K[GC_NB] above K[itop] (a
+// fill that finds them otherwise returns false).
+struct GcFillLoop {
+    GC_HDM bool operator()(int *K, const GcCertCtx &c, int i0, int itop, double lim) const
+    {
+        int prev = 0;
+        for (int i = i0 + 1; i <= GC_NB; i++) {
+            K[i] = (i <= itop || i == GC_NB) ? gc_cert_lane(c, i, lim) : GC_CERT_FAR;
+            if (K[i] == GC_CERT_FAIL) return false;
+            if (i <= itop || i == GC_NB) {
+                if (K[i] <= prev && !(K[i] == GC_CERT_FAR && (i != GC_NB || !(lim < 1.0e300)))) return false;    // (several may be out of reach)
+                prev = K[i];
+            }
+        }
+        return true;
+    }
+};
+
+#if defined(__HIPCC__)
+// crossings one boundary per lane, handed to every lane by readlane (wave-uniform afterwards)
+struct GcFillLanes {
+    int lane;
+    __device__ bool operator()(int *K, const GcCertCtx &c, int i0, int itop, double lim) const
+    {
+        int Kl = GC_CERT_FAR;
+        const bool mine = lane > i0 && lane <= GC_NB && (lane <= itop || lane == GC_NB);
+        if (mine) Kl = gc_cert_lane(c, lane, lim);
+        // strictly increasing: against the lane below (lane GC_NB against lane itop)
+        const int src = lane == GC_NB ? itop : lane - 1;
+        const int below = __shfl(Kl, src < 0 ? 0 : src, 64);
+        const bool bad = mine && (Kl == GC_CERT_FAIL || (src > i0 && Kl <= below && !(Kl == GC_CERT_FAR && (lane != GC_NB || !(lim < 1.0e300)))) || Kl <= 0);
+        if (__any(bad)) return false;
+#pragma unroll
+        for (int i = 0; i <= GC_NB; i++) K[i] = __builtin_amdgcn_readlane(Kl, i);
+        return true;
+    }
+};
+#endif
+
+template <class Fill>
+GC_HD bool gc_cert_stretch(const GcNcoFast &f, double *px, int *pk, int n, double lim, Fill &fill)
 {
     GcCertCtx c;
     int i0, ilim;
     if (!gc_cert_setup(f, *px, *pk, n, lim, &c, &i0, &ilim)) return false;
-    for (int i = i0 + 1; i <= GC_NB; i++) {     // (device: one lane each, gnsscorr_trk.hip)
-        K[i] = (i <= ilim || i == GC_NB) ? gc_cert_lane(c, i, lim) : GC_CERT_FAR;
-        if (K[i] == GC_CERT_FAIL) return false;
-    }
+    // (a fill takes a limit that is given for one that is reached, as the period steps need it; a stretch may end
+    // below its limit -- the code's last one, after the second wrap, always does -- and then asks without one)
+    const int klim = gc_cert_lane(c, GC_NB, lim);
+    if (klim == GC_CERT_FAIL) return false;
+    int K[GC_NB + 1];
+    if (!fill(K, c, i0, ilim, klim == GC_CERT_FAR ? INFINITY : lim)) return false;
     double y = *px;
     int k = 0;
     if (!gc_cert_chain(f, &y, &k, c.n, i0, K, ilim, K[GC_NB])) return false;
@@ -764,21 +835,22 @@ GC_HD bool gc_cert_stretch(const GcNcoFast &f, double *px, int *pk, int n, doubl
 
 // The planner's code walk (end value only): literal steps next to zero, certified stretches through the
 // table, wraps in between; false when a stretch could not be certified (caller: gc_fast_code_walk).
-GC_HD bool gc_plan_code_walk(const GcNcoFast &f, double c, int len, int nt, int *K, double *cend)
+template <class Fill>
+GC_HD bool gc_plan_code_walk(const GcNcoFast &f, double c, int len, int nt, Fill &fill, double *cend)
 {
     GC_FP_STRICT
     const double ci = f.s, dlen = (double)len;
-    if (f.ex0 == 0x7FFFFFF || !(ci > 0.0)) return false;
+    if (f.ex0 == GC_NO_TABLE || !(ci > 0.0)) return false;
     int j = 0;
     while (j < nt) {
         if (c >= dlen) c = c - dlen;
-        while (j < nt && c < dlen && (c == 0.0 || (int)((gc_d2u(c) >> 52) & 0x7FF) < f.ex0)) {
+        while (j < nt && c < dlen && (c == 0.0 || gc_expo(c) < f.ex0)) {
             c = c + ci;
             j += 1;
         }
         if (j >= nt) break;
         if (c >= dlen) continue;
-        if (!(c > 0.0) || !gc_cert_stretch(f, &c, &j, nt, dlen, K)) return false;
+        if (!(c > 0.0) || !gc_cert_stretch(f, &c, &j, nt, dlen, fill)) return false;
     }
     *cend = c;
     return true;
@@ -792,7 +864,7 @@ GC_HD bool gc_one_binade_walk(double x, double s, int n, double *xn, double *dou
     GC_FP_STRICT
     const uint64_t ux = gc_d2u(x), us = gc_d2u(s);
     if (tie_out) *tie_out = false;
-    const int ex = (int)((ux >> 52) & 0x7FF), es = (int)((us >> 52) & 0x7FF);
+    const int ex = gc_expo(x), es = gc_expo(s);
     if (ex == 0 || ex == 0x7FF || es == 0 || es == 0x7FF || (ux >> 63) != (us >> 63)) return false;
     const int et = es + 1075 - ex;
     if (et >= 1023 + 51) return false;
@@ -813,86 +885,34 @@ GC_HD bool gc_one_binade_walk(double x, double s, int n, double *xn, double *dou
 }
 
 // The planner's carrier walk (value after n additions); false: caller uses gc_fast_carrier_walk.
-GC_HD bool gc_plan_carrier_walk(const GcNcoFast &f, double x, int n, int *K, double *xn)
+template <class Fill>
+GC_HD bool gc_plan_carrier_walk(const GcNcoFast &f, double x, int n, Fill &fill, double *xn)
 {
     GC_FP_STRICT
-    if (f.ex0 == 0x7FFFFFF) return false;
-    if ((int)((gc_d2u(x) >> 52) & 0x7FF) >= f.ex0 + GC_NB) return gc_one_binade_walk(x, f.s, n, xn);
+    if (f.ex0 == GC_NO_TABLE) return false;
+    if (gc_expo(x) >= f.ex0 + GC_NB) return gc_one_binade_walk(x, f.s, n, xn);
     int k = 0;
-    while (k < n && (x == 0.0 || (int)((gc_d2u(x) >> 52) & 0x7FF) < f.ex0)) {
+    while (k < n && (x == 0.0 || gc_expo(x) < f.ex0)) {
         x = x + f.s;
         k += 1;
     }
-    if (k < n && !gc_cert_stretch(f, &x, &k, n, INFINITY, K)) return false;
+    if (k < n && !gc_cert_stretch(f, &x, &k, n, INFINITY, fill)) return false;
     if (k != n) return false;
     *xn = x;
     return true;
 }
 
-#if defined(__HIPCC__)
-// ---------------------------------------------------------------------------
-// device planner: one wavefront per channel, lane i = binade boundary i
-// ---------------------------------------------------------------------------
-// device form of gc_cert_stretch (gnsscorr_nco.h): the crossings one per lane.  Ks: LDS, GC_NB + 2 ints.
-__device__ __forceinline__ bool cert_stretch_dev(const GcNcoFast &f, double *px, int *pk, int n, double lim, int *Ks,
-                                                 int lane)
+// (host callers that still hand in a crossings array of their own: the stretch keeps its own now)
+GC_HD bool gc_plan_code_walk(const GcNcoFast &f, double c, int len, int nt, int *, double *cend)
 {
-    GcCertCtx c;
-    int i0, ilim;
-    if (!gc_cert_setup(f, *px, *pk, n, lim, &c, &i0, &ilim)) return false;        // (wave-uniform)
-    int Kl = GC_CERT_FAR;
-    if (lane > i0 && lane <= GC_NB && (lane <= ilim || lane == GC_NB)) Kl = gc_cert_lane(c, lane, lim);
-    if (__any(Kl == GC_CERT_FAIL)) return false;
-    if (lane <= GC_NB) Ks[lane] = Kl;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                         // (one wavefront: LDS order suffices)
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    double y = *px;
-    int k = 0;
-    const bool ok = gc_cert_chain(f, &y, &k, c.n, i0, Ks, ilim, Ks[GC_NB]);
-    __builtin_amdgcn_wave_barrier();                                               // before Ks is rewritten
-    if (!ok) return false;
-    *px = y;
-    *pk += k;
-    return true;
+    GcFillLoop fill;
+    return gc_plan_code_walk(f, c, len, nt, fill, cend);
 }
-
-// gc_plan_code_walk / gc_plan_carrier_walk with the lanes at work
-__device__ __forceinline__ bool plan_code_dev(const GcNcoFast &f, double c, int len, int nt, int *Ks, int lane, double *cend)
+GC_HD bool gc_plan_carrier_walk(const GcNcoFast &f, double x, int n, int *, double *xn)
 {
-    const double ci = f.s, dlen = (double)len;
-    if (f.ex0 == 0x7FFFFFF || !(ci > 0.0)) return false;
-    int j = 0;
-    while (j < nt) {
-        if (c >= dlen) c = __dsub_rn(c, dlen);
-        while (j < nt && c < dlen && (c == 0.0 || (int)((gc_d2u(c) >> 52) & 0x7FF) < f.ex0)) {
-            c = __dadd_rn(c, ci);
-            j += 1;
-        }
-        if (j >= nt) break;
-        if (c >= dlen) continue;
-        if (!(c > 0.0) || !cert_stretch_dev(f, &c, &j, nt, dlen, Ks, lane)) return false;
-    }
-    *cend = c;
-    return true;
+    GcFillLoop fill;
+    return gc_plan_carrier_walk(f, x, n, fill, xn);
 }
-
-__device__ __forceinline__ bool plan_carrier_dev(const GcNcoFast &f, double x, int n, int *Ks, int lane, double *xn)
-{
-    if (f.ex0 == 0x7FFFFFF) return false;
-    if ((int)((gc_d2u(x) >> 52) & 0x7FF) >= f.ex0 + GC_NB) return gc_one_binade_walk(x, f.s, n, xn);
-    int k = 0;
-    while (k < n && (x == 0.0 || (int)((gc_d2u(x) >> 52) & 0x7FF) < f.ex0)) {
-        x = __dadd_rn(x, f.s);
-        k += 1;
-    }
-    if (k < n && !cert_stretch_dev(f, &x, &k, n, INFINITY, Ks, lane)) return false;
-    if (k != n) return false;
-    *xn = x;
-    return true;
-}
-
-#endif
 
 // ---------------------------------------------------------------------------
 // the planner's period step, specialised to the shape a tracked channel has
@@ -919,21 +939,29 @@ struct GcCodePlan {
     bool   ok;              // the table covers the code (else: general walkers only)
 };
 
-GC_HD void gc_code_plan_init(GcCodePlan &P, double ci, int len, int smax, bool with_inv = true)
+// every field but the table, from the table's ex0 and tie mask (gc_code_plan_init below; the closed loop builds
+// the table one binade per lane and then calls this on one lane)
+GC_HD void gc_code_plan_shape(GcCodePlan &P, double ci, int len, int smax)
 {
     GC_FP_STRICT
-    gc_fast_init(P.f, ci, with_inv);
     P.dlen = (double)len;
     P.smaxci = (double)smax * ci;
     P.limtop = gc_u2d(gc_d2u(P.dlen) - 1);
-    P.itop = (int)((gc_d2u(P.limtop) >> 52) & 0x7FF) - P.f.ex0;
-    P.ok = P.f.ex0 != 0x7FFFFFF && ci > 0.0 && P.itop >= 1 && P.itop < GC_NB &&
+    P.itop = gc_expo(P.limtop) - P.f.ex0;
+    P.ok = P.f.ex0 != GC_NO_TABLE && ci > 0.0 && P.itop >= 1 && P.itop < GC_NB &&
            P.dlen + ci < gc_u2d((uint64_t)(P.f.ex0 + P.itop + 1) << 52) && !((P.f.tie >> P.itop) & 1);
     P.exact = P.ok && gc_cert_exact(P.limtop, ci, P.dlen);
     P.it = -1;
 #pragma unroll
     for (int i = 0; i < GC_NB; i++)
         if (((P.f.tie >> i) & 1) && i <= P.itop) P.it = i;
+}
+
+GC_HD void gc_code_plan_init(GcCodePlan &P, double ci, int len, int smax, bool with_inv = true)
+{
+    GC_FP_STRICT
+    gc_fast_init(P.f, ci, with_inv);
+    gc_code_plan_shape(P, ci, len, smax);
     if (P.ok && !with_inv) {
 #pragma unroll
         for (int i = 0; i < GC_NB; i++)
@@ -941,67 +969,9 @@ GC_HD void gc_code_plan_init(GcCodePlan &P, double ci, int len, int smax, bool w
     }
 }
 
-// fill(K, ctx, i0, itop, lim): K[i] = certified crossing of boundary i (i0 < i <= itop: bottom of table
-// binade i; i == GC_NB: lim) relative to ctx.a0 -- gc_cert_lane per boundary; returns false on any
-// GC_CERT_FAIL.  (host: GcFillLoop below; device: one lane per boundary + readlane)
-// The crossings handed back are strictly increasing over i0 < i <= itop, and K[GC_NB] above K[itop] (a
-// fill that finds them otherwise returns false).
-struct GcFillLoop {
-    GC_HDM bool operator()(int *K, const GcCertCtx &c, int i0, int itop, double lim) const
-    {
-        int prev = 0;
-        for (int i = i0 + 1; i <= GC_NB; i++) {
-            K[i] = (i <= itop || i == GC_NB) ? gc_cert_lane(c, i, lim) : GC_CERT_FAR;
-            if (K[i] == GC_CERT_FAIL) return false;
-            if (i <= itop || i == GC_NB) {
-                if (K[i] <= prev && !(K[i] == GC_CERT_FAR && (i != GC_NB || !(lim < 1.0e300)))) return false;    // (several may be out of reach)
-                prev = K[i];
-            }
-        }
-        return true;
-    }
-};
-
-// The climb's chain for a table whose binade ITOP holds the code length: written for a compile-time ITOP
-// so that nothing but one fma and one addition per binade sits on the dependency path (the loop bounds,
-// the table entries and the tie test are constants or scalar work beside it).
-template <int ITOP, class Emit>
-GC_HD bool gc_code_climb(const GcNcoFast &f, const int *K, int i0, int cn, double ci, double *py, int *pk, int jbase, Emit &emit)
-{
-    GC_FP_STRICT
-    double y = *py;
-    int k = 0;
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i <= ITOP; i++) {
-        const bool active = i >= i0;                // (i0 is 0 or 1)
-        const int Kn = i == ITOP ? K[GC_NB] : K[i + 1];
-        int last = Kn - 1;
-        last = last > cn - 1 ? cn - 1 : last;
-        int m = last - k;
-        ok = ok && (m >= 0 || !active);
-        int kb = k;
-        if ((f.tie >> i) & 1) {                     // (at most one table binade: a scalar branch)
-            const bool odd = active && (gc_d2u(y) & 1) && m > 0;
-            if (odd) emit(jbase + kb, y, 0.0, 1, 1);
-            const double yl = y + ci;
-            y = odd ? yl : y;
-            m -= odd ? 1 : 0;
-            kb += odd ? 1 : 0;
-        }
-        m = active ? m : 0;
-        if (active && m >= 0) emit(jbase + kb, y, f.d[i], m + 1, 1);
-        const double yn = fma((double)m, f.d[i], y) + ci;
-        y = active ? yn : y;
-        k = active ? last + 1 : k;
-    }
-    *py = y;
-    *pk = k;
-    return ok;
-}
-
-// The same with the second wrap inside the period (always, for a tracked channel) and the crossings known
-// to increase: no test is left beside the two operations, except in the one binade (if any: `it`, else -1)
+// The climb's chain for a table whose binade ITOP holds the code length: written for a compile-time ITOP so
+// that nothing but one fma and one addition per binade sits on the dependency path.  The second wrap lies
+// inside the period (always, for a tracked channel) and the crossings are known to increase: no test is left beside the two operations, except in the one binade (if any: `it`, else -1)
 // in which the addend is a tie -- entered on an odd multiplier, its first step is the reference's own
 // addition (it rounds to the even neighbour), the rest are the table's.
 template <int ITOP, class Emit>
@@ -1040,7 +1010,7 @@ GC_HD bool gc_code_period_body(const GcCodePlan &P, double remcode, int nt, Fill
     const double fl = cs < 0.0 ? -1.0 : 0.0;
     if (!(cs >= -dlen && cs < dlen)) return false;
     const double c0 = cs - fl * dlen;
-    if ((int)((gc_d2u(c0) >> 52) & 0x7FF) != f.ex0 + ITOP || !(c0 < dlen)) return false;
+    if (gc_expo(c0) != f.ex0 + ITOP || !(c0 < dlen)) return false;
     const double dtop = f.d[ITOP];
     double y;
     int j;
@@ -1073,7 +1043,7 @@ GC_HD bool gc_code_period_body(const GcCodePlan &P, double remcode, int nt, Fill
     c.n = nt - j;
     c.exact = P.exact;
     c.ex0 = f.ex0;
-    const int i0 = (int)((gc_d2u(y) >> 52) & 0x7FF) - f.ex0;
+    const int i0 = gc_expo(y) - f.ex0;
     if (i0 < 0 || i0 > 1) return false;
     int K[GC_NB + 1];
     if (!fill(K, c, i0, ITOP, dlen)) return false;
@@ -1102,9 +1072,10 @@ GC_HD bool gc_code_period_body(const GcCodePlan &P, double remcode, int nt, Fill
     return true;
 }
 
-// (out of line: inlined six times into the closed-loop kernel the step made that kernel hang -- a
-// compiler-sensitive failure)
-#ifdef GC_CODE_PERIOD_INLINE        // (tools/debug: the r2 build in which the closed-loop kernel stalled)
+// Out of line by default (the planner kernels call the step off their hot path; inlined six times into round 2's
+// closed-loop kernel it made that kernel stall -- a compiler-sensitive failure).  gnsscorr_loop.hip
+// defines GC_CODE_PERIOD_INLINE for speed: inline, the step's table emitter lives in registers, not in scratch.
+#ifdef GC_CODE_PERIOD_INLINE
 #define GC_PERIOD_ATTR GC_HD
 #else
 #define GC_PERIOD_ATTR GC_HD_NOINLINE
@@ -1115,19 +1086,28 @@ GC_PERIOD_ATTR bool gc_code_period_t(const GcCodePlan &P, double remcode, int nt
     return gc_code_period_body<ITOP>(P, remcode, nt, fill, remcode_out, emit);
 }
 
+// The shape classes of the code step: returns f(std::integral_constant<int, ITOP>{}) -- a bool -- for the table
+// binade that holds the code length (GPS / GLONASS codes at 2..64 samples per chip: 7..12); false, and no call,
+// for any other.
+template <class F>
+GC_HD bool gc_with_itop(int itop, F &&f)
+{
+    switch (itop) {
+    case 7:  return f(std::integral_constant<int, 7>{});
+    case 8:  return f(std::integral_constant<int, 8>{});
+    case 9:  return f(std::integral_constant<int, 9>{});
+    case 10: return f(std::integral_constant<int, 10>{});
+    case 11: return f(std::integral_constant<int, 11>{});
+    case 12: return f(std::integral_constant<int, 12>{});
+    default: return false;
+    }
+}
+
 template <class Fill, class Emit>
 GC_HD bool gc_code_period(const GcCodePlan &P, double remcode, int nt, Fill &fill, double *remcode_out, Emit &emit)
 {
     if (!P.ok) return false;
-    switch (P.itop) {           // (GPS / GLONASS codes at 2..64 samples per chip: 7..12)
-    case 7:  return gc_code_period_t<7>(P, remcode, nt, fill, remcode_out, emit);
-    case 8:  return gc_code_period_t<8>(P, remcode, nt, fill, remcode_out, emit);
-    case 9:  return gc_code_period_t<9>(P, remcode, nt, fill, remcode_out, emit);
-    case 10: return gc_code_period_t<10>(P, remcode, nt, fill, remcode_out, emit);
-    case 11: return gc_code_period_t<11>(P, remcode, nt, fill, remcode_out, emit);
-    case 12: return gc_code_period_t<12>(P, remcode, nt, fill, remcode_out, emit);
-    default: return false;
-    }
+    return gc_with_itop(P.itop, [&](auto IT) { return gc_code_period_t<decltype(IT)::value>(P, remcode, nt, fill, remcode_out, emit); });
 }
 
 template <class Fill>
@@ -1157,12 +1137,12 @@ GC_HD bool gc_carrier_period(const GcCarPlan &P, double remcarr, int n, Fill &fi
 {
     GC_FP_STRICT
     const GcNcoFast &f = P.f;
-    if (f.ex0 == 0x7FFFFFF || n < 1) return false;
+    if (f.ex0 == GC_NO_TABLE || n < 1) return false;
     const double s = f.s;
     double x = gc_div_y(remcarr * GC_NCO_CDIV, GC_NCO_DPI, P.ydpi);      // ref :649
     int k = 0;
     bool done = false;
-    if ((int)((gc_d2u(x) >> 52) & 0x7FF) >= f.ex0 + GC_NB) {
+    if (gc_expo(x) >= f.ex0 + GC_NB) {
         const double x0 = x;
         double d1;
         if (!gc_one_binade_walk(x, s, n, &x, &d1)) return false;
@@ -1171,13 +1151,13 @@ GC_HD bool gc_carrier_period(const GcCarPlan &P, double remcarr, int n, Fill &fi
     }
     if (!done) {
         // next to zero: the reference's own additions (a channel fresh out of acquisition starts at phase 0)
-        for (int t = 0; t < 8 && k < n && (x == 0.0 || (int)((gc_d2u(x) >> 52) & 0x7FF) < f.ex0); t++) {
+        for (int t = 0; t < 8 && k < n && (x == 0.0 || gc_expo(x) < f.ex0); t++) {
             emit(k, x, 0.0, 1);
             x = x + s;
             k += 1;
         }
         if (k < n) {
-            const int i0 = (int)((gc_d2u(x) >> 52) & 0x7FF) - f.ex0;
+            const int i0 = gc_expo(x) - f.ex0;
             if (i0 < 0 || i0 >= GC_NB || (gc_d2u(x) >> 63) != (gc_d2u(s) >> 63)) return false;
             GcCertCtx c;
             c.a0 = fabs(x);
@@ -1218,7 +1198,7 @@ GC_HD bool gc_carrier_period(const GcCarPlan &P, double remcarr, int n, Fill &fi
     // phase remainder (ref :666-668)
     double p = x * GC_NCO_DPI * (1.0 / GC_NCO_CDIV);        // (/32: an exact scaling)
     if (!(p < 1.0e300)) { *remcarr_out = p; return true; }
-    if ((int)((gc_d2u(p) >> 52) & 0x7FF) >= P.fprem.ex0 && p > 0.0) p = gc_fast_prem(P.fprem, x);
+    if (gc_expo(p) >= P.fprem.ex0 && p > 0.0) p = gc_fast_prem(P.fprem, x);
     else while (p > GC_NCO_DPI) p = p - GC_NCO_DPI;
     *remcarr_out = p;
     return true;
@@ -1229,6 +1209,52 @@ GC_HD bool gc_carrier_period(const GcCarPlan &P, double remcarr, int n, Fill &fi
 {
     GcNoEmit ne;
     return gc_carrier_period(P, remcarr, n, fill, remcarr_out, ne);
+}
+
+// ---------------------------------------------------------------------------
+// one period, whatever its shape: what a chain takes when its claims step declines
+// ---------------------------------------------------------------------------
+// The period step above; when it declines, the same start value (ref src/sdrcmn.c:613-614 / :649) through
+// certified stretches (STRETCH: they emit nothing, so only for GcNoEmit; and a caller whose lanes hold different
+// periods, where the crossings are a loop per lane and no cheaper than the walker, says false), then through the
+// table walkers.  Every tier yields the reference's values; *tier says which one served (gc_plan_stats counts
+// GC_TIER_PERIOD as "certified", the other two as "walkers").  P: built with its reciprocals (and, for the
+// carrier, with the -DPI table).
+enum { GC_TIER_PERIOD = 3, GC_TIER_STRETCH = 4, GC_TIER_WALKER = 5 };
+
+template <class Fill, class Emit, bool STRETCH = std::is_same<Emit, GcNoEmit>::value>
+GC_HD double gc_code_period_any(const GcCodePlan &P, double remcode, int nt, Fill &fill, Emit &emit, int *tier)
+{
+    GC_FP_STRICT
+    double r;
+    *tier = GC_TIER_PERIOD;
+    if (gc_code_period(P, remcode, nt, fill, &r, emit)) return r;
+    emit.reset();
+    const int len = (int)P.dlen;
+    const double c0 = gc_code_start_fast(remcode, P.smaxci, len);
+    *tier = GC_TIER_STRETCH;
+    if (!(STRETCH && gc_plan_code_walk(P.f, c0, len, nt, fill, &r))) {
+        *tier = GC_TIER_WALKER;
+        r = gc_fast_code_walk(P.f, c0, len, nt, emit);
+    }
+    return r - P.smaxci;                            // ref :620
+}
+
+template <class Fill, class Emit, bool STRETCH = std::is_same<Emit, GcNoEmit>::value>
+GC_HD double gc_carrier_period_any(const GcCarPlan &P, double remcarr, int n, Fill &fill, Emit &emit, int *tier)
+{
+    GC_FP_STRICT
+    double r;
+    *tier = GC_TIER_PERIOD;
+    if (gc_carrier_period(P, remcarr, n, fill, &r, emit)) return r;
+    emit.reset();
+    const double phis = gc_div_y(remcarr * GC_NCO_CDIV, GC_NCO_DPI, P.ydpi);       // ref :649
+    *tier = GC_TIER_STRETCH;
+    if (!(STRETCH && gc_plan_carrier_walk(P.f, phis, n, fill, &r))) {
+        *tier = GC_TIER_WALKER;
+        r = gc_fast_carrier_walk(P.f, phis, n, emit);
+    }
+    return gc_fast_prem(P.fprem, r);                // ref :666-668
 }
 
 // Closed-form start of period e of a batch whose frequencies are held (what the speculation pass works
@@ -1298,6 +1324,10 @@ GC_HD void gc_spec_start(double remcode0, double remcarr0, double ci, double spc
 #define GC_CLAIM_CSEG  13           // carrier: binade segments, at most
 #define GC_CLAIM_PREM  12           // carrier: subtractions of DPI in the remainder loop, at most (12: up to ~11 kHz at 1 ms)
 
+// which instance of the code step holds a channel's tail: positions 8, GC_CLAIM_TAIL, GC_CLAIM_TAIL2 (classes 0, 1, 2)
+GC_HD constexpr int gc_tail_class(int smax) { return smax + 1 > 8 ? (smax + 1 > GC_CLAIM_TAIL ? 2 : 1) : 0; }
+GC_HD constexpr int gc_tail_max(int cls) { return cls == 0 ? 8 : (cls == 1 ? GC_CLAIM_TAIL : GC_CLAIM_TAIL2); }
+
 struct GcCodeClaims {               // GC_CLAIM_ROW ints
     int tag;                        // 1: claims present
     int i0, q, nl, jsum;            // entry binade of the climb, head steps, literal additions, samples before the tail
@@ -1313,9 +1343,6 @@ struct GcCarClaims {                // GC_CLAIM_ROW ints
     int pad[2];
     double lo, hi;                  // bracket form: period starts (remcarr) the claims were proved for
 };
-
-GC_HD int gc_expo(double x) { return (int)((gc_d2u(x) >> 52) & 0x7FF); }
-GC_HD uint32_t gc_hi32(double x) { return (uint32_t)(gc_d2u(x) >> 32); }
 
 // per-channel constants of the code step, as the evaluation wants them: every one a plain value (on the device
 // they are pinned to vector registers, GC_PIN_V: the chain's wavefront has few scalar registers to spare)
@@ -1467,7 +1494,7 @@ GC_HD bool gc_code_claims_step(const GcCodePlan &P, const GcCodeStepC<ITOP> &C, 
         const double y1 = y + (active ? C.pre[i] : 0.0);
         int dm;
         if (DISCOVER) {
-            dm = active ? gc_fast_piece(P.f, i, y1, 1 << 24, i == ITOP ? dlen : INFINITY) : 0;
+            dm = active ? gc_piece_len(P.f.d[i], P.f.inv[i], y1, 1 << 24, i == ITOP ? dlen : INFINITY) : 0;
             cl.dm[i] = dm;
             j += active ? (C.pre[i] != 0.0 ? 1 : 0) + dm + 1 : 0;
         } else {
@@ -1527,15 +1554,7 @@ GC_HD bool gc_code_claims(const GcCodePlan &P, double remcode, int nt, GcCodeCla
 {
     if (DISCOVER) cl.tag = 0;
     if (!P.ok) return false;
-    switch (P.itop) {           // (GPS / GLONASS codes at 2..64 samples per chip: 7..12)
-    case 7:  return gc_code_claims_itop<7, DISCOVER>(P, remcode, nt, cl, remcode_out);
-    case 8:  return gc_code_claims_itop<8, DISCOVER>(P, remcode, nt, cl, remcode_out);
-    case 9:  return gc_code_claims_itop<9, DISCOVER>(P, remcode, nt, cl, remcode_out);
-    case 10: return gc_code_claims_itop<10, DISCOVER>(P, remcode, nt, cl, remcode_out);
-    case 11: return gc_code_claims_itop<11, DISCOVER>(P, remcode, nt, cl, remcode_out);
-    case 12: return gc_code_claims_itop<12, DISCOVER>(P, remcode, nt, cl, remcode_out);
-    default: return false;
-    }
+    return gc_with_itop(P.itop, [&](auto IT) { return gc_code_claims_itop<decltype(IT)::value, DISCOVER>(P, remcode, nt, cl, remcode_out); });
 }
 
 // Carrier step on claims.  A tracked channel's phase (in LUT steps) starts a period inside (0, 32] -- or, for a
@@ -1565,7 +1584,7 @@ GC_HD void gc_car_stepc_init(GcCarStepC &C, const GcCarPlan &P, int nmax)
     C.ex0 = f.ex0;
     C.ilo = 0;
     C.ptie = -1;
-    if (f.ex0 != 0x7FFFFFF) {
+    if (f.ex0 != GC_NO_TABLE) {
         const double xmax = fma((double)nmax, fabs(f.s), GC_NCO_CDIV);
         int imax = gc_expo(xmax) - f.ex0;
         imax = imax < GC_CLAIM_CWIN - 1 ? GC_CLAIM_CWIN - 1 : (imax > GC_NB - 1 ? GC_NB - 1 : imax);
@@ -1601,7 +1620,7 @@ GC_HD bool gc_carrier_claims_step(const GcCarPlan &P, const GcCarStepC &C, doubl
         for (int j = 0; j < GC_CLAIM_CSEG; j++) cl.dm[j] = 0;
         cl.pad[0] = cl.pad[1] = 0;
     }
-    if (C.ex0 == 0x7FFFFFF || n < 1) return false;
+    if (C.ex0 == GC_NO_TABLE || n < 1) return false;
     double x = gc_div_y(remcarr * GC_NCO_CDIV, GC_NCO_DPI, P.ydpi);      // ref src/sdrcmn.c:649
     bool ok = true;
     if (DISCOVER) {
@@ -1706,12 +1725,11 @@ GC_HD bool gc_carrier_claims_step(const GcCarPlan &P, const GcCarStepC &C, doubl
 // per-channel constants stay in registers.  A channel without a tie binade (nearly all) makes no addition of zero.
 
 // Control flow, not selects: a block that the compiler could compute unconditionally and then select (one fp64
-// addition, say) would put the selects back on the dependent path; GC_KEEP_V pins the block's value so that the
+// addition, say) would put the selects back on the dependent path; GC_PIN_V pins the block's value so that the
 // block stays a branch around it.  Branches are not free either (a lone wavefront pays for every scalar test and
 // branch it issues), so there are few of them: k equal additions go in blocks of 2^b by the bits of k -- every
 // addition is the same operation, so the grouping leaves the sequence as it is -- and the tie binade's own
 // addition is decided once per channel, not once per binade.
-#define GC_KEEP_V(x) GC_PIN_V(x)
 
 template <int N>
 struct GcPow2Floor { static constexpr int value = N < 2 ? 1 : 2 * GcPow2Floor<N / 2>::value; };
@@ -1729,7 +1747,7 @@ GC_HD double gc_add_n(double y, double a, int k)
         if (k & b) {
 #pragma unroll
             for (int j = 0; j < b; j++) y = y + a;
-            GC_KEEP_V(y);
+            GC_PIN_V(y);
         }
     }
     return y;
@@ -1777,7 +1795,7 @@ GC_HD double gc_code_value_step(const GcCodeStepC<ITOP> &C, double remcode, int 
         if (it == 0) y = y + ci;                    // (the tie binade's own addition: C.pre[it] = ci)
         y = fma(dmd[0], C.d[0], y);
         y = y + ci;
-        GC_KEEP_V(y);
+        GC_PIN_V(y);
     }
     if (it <= 0) {                                  // no tie binade above binade 0: the climb is one fma and one addition per binade
 #pragma unroll
@@ -1815,15 +1833,15 @@ GC_HD double gc_carrier_value_step(const GcCarPlan &P, const GcCarStepC &C, doub
         if (p0 < PH) {
 #pragma unroll
             for (int p = 0; p < PH; p++)
-                if ((act >> p) & 1u) { x = fma(dmd[p], C.d[p], x); x = x + C.s; GC_KEEP_V(x); }
+                if ((act >> p) & 1u) { x = fma(dmd[p], C.d[p], x); x = x + C.s; GC_PIN_V(x); }
         }
 #pragma unroll
         for (int p = PH; p < GC_CLAIM_CWIN; p++)
-            if ((act >> p) & 1u) { x = fma(dmd[p], C.d[p], x); x = x + C.s; GC_KEEP_V(x); }
+            if ((act >> p) & 1u) { x = fma(dmd[p], C.d[p], x); x = x + C.s; GC_PIN_V(x); }
     } else {                                        // a tie binade in the window: its own addition (C.pre) at every position
 #pragma unroll
         for (int p = 0; p < GC_CLAIM_CWIN; p++)
-            if ((act >> p) & 1u) { x = x + C.pre[p]; x = fma(dmd[p], C.d[p], x); x = x + C.s; GC_KEEP_V(x); }
+            if ((act >> p) & 1u) { x = x + C.pre[p]; x = fma(dmd[p], C.d[p], x); x = x + C.s; GC_PIN_V(x); }
     }
     return gc_prem_value(x, kprem);
 }
@@ -1834,7 +1852,7 @@ GC_HD bool gc_carrier_value_step_one(const GcCarPlan &P, const GcCarStepC &C, do
                                      double *remcarr_out)
 {
     GC_FP_STRICT
-    if (C.ex0 == 0x7FFFFFF || n < 1) return false;
+    if (C.ex0 == GC_NO_TABLE || n < 1) return false;
     double x = gc_div_y(remcarr * GC_NCO_CDIV, GC_NCO_DPI, P.ydpi);      // ref src/sdrcmn.c:649
     if (!gc_one_binade_walk(x, C.s, n, &x)) return false;
     bool held;
@@ -1843,24 +1861,3 @@ GC_HD bool gc_carrier_value_step_one(const GcCarPlan &P, const GcCarStepC &C, do
     *remcarr_out = p;
     return true;
 }
-
-#if defined(__HIPCC__)
-// crossings one boundary per lane, handed to every lane by readlane (wave-uniform afterwards)
-struct GcFillLanes {
-    int lane;
-    __device__ bool operator()(int *K, const GcCertCtx &c, int i0, int itop, double lim) const
-    {
-        int Kl = GC_CERT_FAR;
-        const bool mine = lane > i0 && lane <= GC_NB && (lane <= itop || lane == GC_NB);
-        if (mine) Kl = gc_cert_lane(c, lane, lim);
-        // strictly increasing: against the lane below (lane GC_NB against lane itop)
-        const int src = lane == GC_NB ? itop : lane - 1;
-        const int below = __shfl(Kl, src < 0 ? 0 : src, 64);
-        const bool bad = mine && (Kl == GC_CERT_FAIL || (src > i0 && Kl <= below && !(Kl == GC_CERT_FAR && (lane != GC_NB || !(lim < 1.0e300)))) || Kl <= 0);
-        if (__any(bad)) return false;
-#pragma unroll
-        for (int i = 0; i <= GC_NB; i++) K[i] = __builtin_amdgcn_readlane(Kl, i);
-        return true;
-    }
-};
-#endif

@@ -46,12 +46,6 @@ namespace {
 #define GC_SPEC_WC  9.313225746154785e-10       // 2^-30 chips
 #define GC_SPEC_WK  9.313225746154785e-10       // 2^-30 rad, at least; 2^-36 of the phase beyond that
 
-__device__ __forceinline__ int spec_nsamp(double dlen, double remcode, double spc)      // ref src/sdrtrk.c:31-32
-{
-    const double qn = __ddiv_rn(__dsub_rn(dlen, remcode), spc);
-    return (qn > -2147483648.0 && qn < 2147483648.0) ? (int)qn : 0;
-}
-
 struct SpecChan {               // a channel's constants for the discovery passes
     GcCodePlan PC;
     GcCarPlan PK;
@@ -70,7 +64,7 @@ __device__ __forceinline__ void spec_chan_init(SpecChan &C, const GcChan &c, con
     C.clen = c.clen;
     C.smax = c.smax;
     C.ps = gc_carrier_ps(s.carrfreq, c.ti);
-    C.tmax = c.smax + 1 > 8 ? (c.smax + 1 > GC_CLAIM_TAIL ? GC_CLAIM_TAIL2 : GC_CLAIM_TAIL) : 8;
+    C.tmax = gc_tail_max(gc_tail_class(c.smax));
     C.ok = C.ci > 0.0 && C.ci < C.dlen && C.spc > 1e-300 && C.spc < 1e300;
     if (!C.ok) return;
     gc_code_plan_init(C.PC, C.ci, c.clen, c.smax);
@@ -94,24 +88,19 @@ __global__ __launch_bounds__(64) void trk_specdev_kernel(const GcChan *__restric
         int nhat;
         gc_spec_start(s.remcode, s.remcarr, C.ci, C.spc, C.ps, C.dlen, e, &r0, &g0, &nhat);
         gc_spec_start(s.remcode, s.remcarr, C.ci, C.spc, C.ps, C.dlen, e + 1, &r1, &g1, &nhat);
-        const int n = spec_nsamp(C.dlen, r0, C.spc);
+        const int n = gc_period_nsamp(C.dlen, r0, C.spc);
         if (n > 0 && n <= (1 << 24)) {
             GcFillLoop fill;
             GcNoEmit ne;
             const int nt = n + 2 * C.smax;
             GcCodeClaims cc;
+            int tier;
             double F = r1;
-            if (!gc_code_claims<true>(C.PC, r0, nt, cc, &F) && !gc_code_period(C.PC, r0, nt, fill, &F)) {
-                const double c0 = gc_code_start_fast(r0, C.PC.smaxci, C.clen);
-                F = __dsub_rn(gc_fast_code_walk(C.PC.f, c0, C.clen, nt, ne), C.PC.smaxci);
-            }
+            if (!gc_code_claims<true>(C.PC, r0, nt, cc, &F)) F = gc_code_period_any<GcFillLoop, GcNoEmit, false>(C.PC, r0, nt, fill, ne, &tier);
             dc = F - r1;
             GcCarClaims ck;
             double G = g1;
-            if (!gc_carrier_claims_step<true>(C.PK, C.CK, g0, n, ck, &G) && !gc_carrier_period(C.PK, g0, n, fill, &G)) {
-                const double phis = gc_div_y(__dmul_rn(g0, GC_NCO_CDIV), GC_NCO_DPI, C.PK.ydpi);
-                G = gc_fast_prem(C.PK.fprem, gc_fast_carrier_walk(C.PK.f, phis, n, ne));
-            }
+            if (!gc_carrier_claims_step<true>(C.PK, C.CK, g0, n, ck, &G)) G = gc_carrier_period_any<GcFillLoop, GcNoEmit, false>(C.PK, g0, n, fill, ne, &tier);
             dk = G - g1;
             // (the closed form and the step may sit on different sides of a whole turn)
             dk = dk > 0.5 * GC_NCO_DPI ? dk - GC_NCO_DPI : (dk < -0.5 * GC_NCO_DPI ? dk + GC_NCO_DPI : dk);
@@ -192,7 +181,7 @@ __global__ __launch_bounds__(GC_SPEC_CHUNK) void trk_spec_kernel(const GcChan *_
         for (int att = 0; att < 2 && !bracketed; att++) {
             const double w = att == 0 ? GC_SPEC_WC : GC_SPEC_WC * 0.00390625;
             const double lo = rt - w, hi = rt + w;
-            const int nlo = spec_nsamp(C.dlen, lo, C.spc), nhi = spec_nsamp(C.dlen, hi, C.spc);
+            const int nlo = gc_period_nsamp(C.dlen, lo, C.spc), nhi = gc_period_nsamp(C.dlen, hi, C.spc);
             if (!(nlo == nhi && nlo > 0 && nlo <= (1 << 24))) continue;
             double dummy;
             const bool side = (lo - C.PC.smaxci < 0.0) == (hi - C.PC.smaxci < 0.0);     // (ref src/sdrcmn.c:614: one branch for the whole bracket)
@@ -211,7 +200,7 @@ __global__ __launch_bounds__(GC_SPEC_CHUNK) void trk_spec_kernel(const GcChan *_
             }
         }
         if (!bracketed) {
-            ncode = spec_nsamp(C.dlen, rt, C.spc);
+            ncode = gc_period_nsamp(C.dlen, rt, C.spc);
             cc.tag = 0;
             if (ncode > 0 && ncode <= (1 << 24)) {
                 double dummy;
@@ -270,13 +259,11 @@ __device__ unsigned long long gc_plan_stats[8];
 __host__ __device__ inline int plan2_class(double ti, double codefreq, int clen, int smax)
 {
     const double ci = ti * codefreq;
-    const uint64_t us = gc_d2u(ci);
-    const int es = (int)((us >> 52) & 0x7FF);
-    if (!(ci > 0.0) || es <= 60 || es >= 0x7FF - GC_NB - 4) return -1;
-    const int itop = gc_expo(gc_u2d(gc_d2u((double)clen) - 1)) - (es + 2);
+    if (!(ci > 0.0) || !gc_fast_has_table(ci)) return -1;
+    const int itop = gc_expo(gc_u2d(gc_d2u((double)clen) - 1)) - (gc_expo(ci) + 2);
     if (itop < 7 || itop > 12) return -1;
     if (smax + 1 > GC_CLAIM_TAIL2) return -1;      // (tail longer than the widest instance: the certifying chain)
-    return (itop - 7) * 3 + (smax + 1 > 8 ? (smax + 1 > GC_CLAIM_TAIL ? 2 : 1) : 0);
+    return (itop - 7) * 3 + gc_tail_class(smax);
 }
 
 // Two wavefronts per channel: wavefront 0 chains the code NCO (and with it the samples per period and the
@@ -288,7 +275,6 @@ __device__ __attribute__((noinline)) void trk_plan_body(const GcChan *__restrict
                                                         GcTrkState *__restrict__ state_out,
                                                         GcTrkPlan *__restrict__ plan, int nch, int nepoch)
 {
-    __shared__ int Ks2[2][GC_NB + 2];
     __shared__ int nsh[GC_PLAN_MAXE];
     __shared__ int prog;
     const int ch = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -300,7 +286,6 @@ __device__ __attribute__((noinline)) void trk_plan_body(const GcChan *__restrict
     if (threadIdx.x == 0) prog = 0;
     __syncthreads();
     if (!split && wave == 1) return;
-    int *Ks = Ks2[wave];
     const GcChan c = chan[ch];
     GcTrkState s = state_in[ch];
     const double ci = __dmul_rn(c.ti, s.codefreq);          // ti*crate, ref src/sdrcmn.c:709
@@ -318,17 +303,12 @@ __device__ __attribute__((noinline)) void trk_plan_body(const GcChan *__restrict
     GcCarPlan PK;
     if (do_code) gc_code_plan_init(PC, ci, c.clen, c.smax);
     if (do_car) gc_car_plan_init(PK, ps);
-    const GcNcoFast &fcode = PC.f, &fcar = PK.f, &fprem = PK.fprem;
-    const double yspc = __ddiv_rn(1.0, spc), ydpi = __ddiv_rn(1.0, GC_NCO_DPI);
-    const double smaxci = __dmul_rn((double)c.smax, ci);
-    const bool fastdiv = spc > 1e-300 && spc < 1e300 && yspc < 1e300;
+    const double yspc = gc_period_yspc(spc);
     unsigned tally[6] = {0, 0, 0, 0, 0, 0};
     for (int e = 0; e < nepoch; e++) {
         int n;
         if (do_code) {
-            const double num = __dsub_rn(dlen, s.remcode);                      // ref src/sdrtrk.c:31-32
-            const double q = fastdiv ? gc_div_y(num, spc, yspc) : __ddiv_rn(num, spc);
-            n = (q > -2147483648.0 && q < 2147483648.0) ? (int)q : 0;
+            n = gc_period_nsamp(dlen, s.remcode, spc, yspc);
             if (lane == 0) {
                 out[e].buffloc = s.buffloc;
                 out[e].coff = s.remcode;
@@ -349,30 +329,19 @@ __device__ __attribute__((noinline)) void trk_plan_body(const GcChan *__restrict
         const bool walk = n > 0 && n <= (1 << 24);
         if (do_car) {
             if (lane == 0) out[e].phi0 = s.remcarr;
-            double rp;
-            if (walk && gc_carrier_period(PK, s.remcarr, n, fill, &rp)) {
-                s.remcarr = rp;
-                tally[4]++;
-            } else if (walk) {      // any other shape: the general walkers
-                tally[5]++;
-                const double phis = gc_div_y(__dmul_rn(s.remcarr, GC_NCO_CDIV), GC_NCO_DPI, ydpi);     // ref src/sdrcmn.c:649
-                double xn;
-                if (!plan_carrier_dev(fcar, phis, n, Ks, lane, &xn)) xn = gc_fast_carrier_walk(fcar, phis, n, ne);
-                s.remcarr = gc_fast_prem(fprem, xn);
+            if (walk) {
+                int tier;
+                s.remcarr = gc_carrier_period_any(PK, s.remcarr, n, fill, ne, &tier);
+                if (tier == GC_TIER_PERIOD) tally[4]++;
+                else tally[5]++;
             }
         }
         if (do_code) {
-            double rc;
-            if (walk && code_ok && gc_code_period(PC, s.remcode, n + 2 * c.smax, fill, &rc)) {
-                s.remcode = rc;
-                tally[1]++;
-            } else if (walk && code_ok) {
-                tally[2]++;
-                const double c0 = gc_code_start_fast(s.remcode, smaxci, c.clen);
-                double cend;
-                if (!plan_code_dev(fcode, c0, c.clen, n + 2 * c.smax, Ks, lane, &cend))
-                    cend = gc_fast_code_walk(fcode, c0, c.clen, n + 2 * c.smax, ne);
-                s.remcode = __dsub_rn(cend, smaxci);
+            if (walk && code_ok) {
+                int tier;
+                s.remcode = gc_code_period_any(PC, s.remcode, n + 2 * c.smax, fill, ne, &tier);
+                if (tier == GC_TIER_PERIOD) tally[1]++;
+                else tally[2]++;
             }
             s.buffloc += (uint64_t)(int64_t)n;
         }
@@ -417,7 +386,6 @@ struct Plan4Shared {
     unsigned long long vbuff[GC_P4_BLK];
     int prog;                                       // periods the code chain has finished
     GcCarPlan pkfull;                               // the carrier's tables as the certified step wants them, built once per batch
-    int Ks2[2][GC_NB + 2];
 };
 __shared__ __attribute__((aligned(16))) Plan4Shared g_plan4;
 
@@ -487,32 +455,21 @@ __device__ __attribute__((noinline)) int plan2_code_slow(double ci_, int clen_, 
     gc_code_plan_init(PC, ci, clen, smax);
     GcFillLanes fill{lane};
     GcNoEmit ne;
-    double rc;
-    if (gc_code_period(PC, remcode, n + 2 * smax, fill, &rc)) { *out = rc; return 1; }
-    const double smaxci = __dmul_rn((double)smax, ci);
-    const double c0 = gc_code_start_fast(remcode, smaxci, clen);
-    double cend;
-    if (!plan_code_dev(PC.f, c0, clen, n + 2 * smax, g_plan4.Ks2[0], lane, &cend))
-        cend = gc_fast_code_walk(PC.f, c0, clen, n + 2 * smax, ne);
-    *out = __dsub_rn(cend, smaxci);
-    return 2;
+    int tier;
+    *out = gc_code_period_any(PC, remcode, n + 2 * smax, fill, ne, &tier);
+    return tier == GC_TIER_PERIOD ? 1 : 2;
 }
 
-__device__ __attribute__((noinline)) int plan2_car_slow(double ps_, double remcarr_, int n_, int lane, double *out)
+__device__ __attribute__((noinline)) int plan2_car_slow(double remcarr_, int n_, int lane, double *out)
 {
     const double remcarr = plan2_uni(remcarr_);
     const int n = plan2_uni(n_);
-    (void)ps_;
     const GcCarPlan &PK = g_plan4.pkfull;           // (plan4_car_wave built it for this channel's ps)
     GcFillLanes fill{lane};
     GcNoEmit ne;
-    double rp;
-    if (gc_carrier_period(PK, remcarr, n, fill, &rp)) { *out = rp; return 1; }
-    const double phis = gc_div_y(__dmul_rn(remcarr, GC_NCO_CDIV), GC_NCO_DPI, __ddiv_rn(1.0, GC_NCO_DPI));     // ref src/sdrcmn.c:649
-    double xn;
-    if (!plan_carrier_dev(PK.f, phis, n, g_plan4.Ks2[1], lane, &xn)) xn = gc_fast_carrier_walk(PK.f, phis, n, ne);
-    *out = gc_fast_prem(PK.fprem, xn);
-    return 2;
+    int tier;
+    *out = gc_carrier_period_any(PK, remcarr, n, fill, ne, &tier);
+    return tier == GC_TIER_PERIOD ? 1 : 2;
 }
 
 #ifdef GC_PLAN_PROF     // (tools/debug) per channel and chain: clocks in the loop, in the slow path, waiting for rows, waiting for n; slow periods
@@ -723,7 +680,7 @@ __device__ __attribute__((noinline)) int plan4_car_other(double ps_, int nsamp_,
         double rp;
         if (gc_carrier_claims_step<false, true>(PK, CK, remcarr, n, c2, &rp)) { *out = rp; return 0; }
     }
-    return plan2_car_slow(ps_, remcarr_, n_, lane, out);
+    return plan2_car_slow(remcarr_, n_, lane, out);
 }
 
 // The carrier chain of a channel whose periods the discovery has no claims for (a real front end at 4 MHz IF: the
@@ -738,7 +695,6 @@ __device__ __attribute__((noinline)) void plan4_car_cert_wave(double ps_, const 
     gc_car_plan_init(PK, ps);
     GcFillLanes fill{lane};
     GcNoEmit ne;
-    const double ydpi = __ddiv_rn(1.0, GC_NCO_DPI);
     unsigned tally1 = 0, tally2 = 0;
     GC_GLOBAL GcTrkPlan *out = (GC_GLOBAL GcTrkPlan *)J.out;
     double remcarr = J.s.remcarr;
@@ -753,17 +709,10 @@ __device__ __attribute__((noinline)) void plan4_car_cert_wave(double ps_, const 
             const int n = plan2_uni(g_plan4.nsh[e0 + i]);
             if (lane == 0) g_plan4.vstart[1][i] = remcarr;
             if (n > 0 && n <= (1 << 24)) {
-                double rp;
-                if (gc_carrier_period(PK, remcarr, n, fill, &rp)) {
-                    tally1++;
-                } else {
-                    const double phis = gc_div_y(__dmul_rn(remcarr, GC_NCO_CDIV), GC_NCO_DPI, ydpi);      // ref src/sdrcmn.c:649
-                    double xn;
-                    if (!plan_carrier_dev(PK.f, phis, n, g_plan4.Ks2[1], lane, &xn)) xn = gc_fast_carrier_walk(PK.f, phis, n, ne);
-                    rp = gc_fast_prem(PK.fprem, xn);
-                    tally2++;
-                }
-                remcarr = rp;
+                int tier;
+                remcarr = gc_carrier_period_any(PK, remcarr, n, fill, ne, &tier);
+                tally1 += tier == GC_TIER_PERIOD ? 1 : 0;
+                tally2 += tier == GC_TIER_PERIOD ? 0 : 1;
             }
         }
         if (lane < nb) out[e0 + lane].phi0 = g_plan4.vstart[1][lane];
@@ -893,9 +842,9 @@ __device__ __attribute__((noinline)) void plan4_car_wave(double ps_, int nsamp_,
 template <int ITOP>
 __device__ __forceinline__ void plan4_code_dispatch(int tcls, double ci, double spc, int clen, int smax, const Plan4Job *J, int lane)
 {
-    if (tcls == 0) plan4_code_wave<ITOP, 8>(ci, spc, clen, smax, J, lane);
-    else if (tcls == 1) plan4_code_wave<ITOP, GC_CLAIM_TAIL>(ci, spc, clen, smax, J, lane);
-    else plan4_code_wave<ITOP, GC_CLAIM_TAIL2>(ci, spc, clen, smax, J, lane);
+    if (tcls == 0) plan4_code_wave<ITOP, gc_tail_max(0)>(ci, spc, clen, smax, J, lane);
+    else if (tcls == 1) plan4_code_wave<ITOP, gc_tail_max(1)>(ci, spc, clen, smax, J, lane);
+    else plan4_code_wave<ITOP, gc_tail_max(2)>(ci, spc, clen, smax, J, lane);
 }
 
 __global__ __launch_bounds__(128) void trk_plan4_kernel(const GcChan *__restrict__ chan, const GcTrkState *__restrict__ state_in,
@@ -929,14 +878,7 @@ __global__ __launch_bounds__(128) void trk_plan4_kernel(const GcChan *__restrict
     // the chains are latency bound and share their SIMDs with correlator wavefronts of the batch before: let them issue first
     __builtin_amdgcn_s_setprio(3);
     if (wave == 0) {
-        switch (itop) {
-        case 7:  plan4_code_dispatch<7>(tcls, ci, spc, c.clen, c.smax, &J, lane); break;
-        case 8:  plan4_code_dispatch<8>(tcls, ci, spc, c.clen, c.smax, &J, lane); break;
-        case 9:  plan4_code_dispatch<9>(tcls, ci, spc, c.clen, c.smax, &J, lane); break;
-        case 10: plan4_code_dispatch<10>(tcls, ci, spc, c.clen, c.smax, &J, lane); break;
-        case 11: plan4_code_dispatch<11>(tcls, ci, spc, c.clen, c.smax, &J, lane); break;
-        default: plan4_code_dispatch<12>(tcls, ci, spc, c.clen, c.smax, &J, lane); break;
-        }
+        gc_with_itop(itop, [&](auto IT) { plan4_code_dispatch<decltype(IT)::value>(tcls, ci, spc, c.clen, c.smax, &J, lane); return true; });
     } else {
         plan4_car_wave(ps, c.nsamp, &J, lane);
     }

@@ -76,8 +76,8 @@ void nco_chain_fast(double phi0, double freq, double ti, double f_sf, double cod
     gc_fast_init(fcar, ps);
     gc_fast_init(fcode, ci);
     gc_fast_init(fprem, -GC_NCO_DPI);
-    const double yspc = 1.0 / spc, ydpi = 1.0 / GC_NCO_DPI, smaxci = (double)smax * ci;
-    const int n = (int)gc_div_y((double)len - coff, spc, yspc);
+    const double ydpi = 1.0 / GC_NCO_DPI, smaxci = (double)smax * ci;
+    const int n = gc_period_nsamp((double)len, coff, spc, gc_period_yspc(spc));
     GcNoEmit ne;
     const double phis = gc_div_y(phi0 * GC_NCO_CDIV, GC_NCO_DPI, ydpi);
     *prem = gc_fast_prem(fprem, gc_fast_carrier_walk(fcar, phis, n, ne));
@@ -85,7 +85,8 @@ void nco_chain_fast(double phi0, double freq, double ti, double f_sf, double cod
     *n_out = n;
 }
 
-// the certified-crossing planner path; *used = 1 when the certified path produced the values (else fallback)
+// the certified stretches (the device planner's, crossings by GcFillLoop instead of one lane each); *used: bit 0 /
+// bit 1 set when the stretches produced the carrier's / the code's value (else the table walkers did)
 void nco_chain_cert(double phi0, double freq, double ti, double f_sf, double codefreq, int len, double coff, int smax,
                     int *n_out, double *prem, double *rem, int *used)
 {
@@ -94,18 +95,18 @@ void nco_chain_cert(double phi0, double freq, double ti, double f_sf, double cod
     gc_fast_init(fcar, ps);
     gc_fast_init(fcode, ci);
     gc_fast_init(fprem, -GC_NCO_DPI);
-    const double yspc = 1.0 / spc, ydpi = 1.0 / GC_NCO_DPI, smaxci = (double)smax * ci;
-    const int n = (int)gc_div_y((double)len - coff, spc, yspc);
+    const double ydpi = 1.0 / GC_NCO_DPI, smaxci = (double)smax * ci;
+    const int n = gc_period_nsamp((double)len, coff, spc, gc_period_yspc(spc));
     GcNoEmit ne;
-    int K[GC_NB + 2];
+    GcFillLoop fill;
     const double phis = gc_div_y(phi0 * GC_NCO_CDIV, GC_NCO_DPI, ydpi);
     double xn, cend;
     *used = 0;
-    if (gc_plan_carrier_walk(fcar, phis, n, K, &xn)) *used |= 1;
+    if (gc_plan_carrier_walk(fcar, phis, n, fill, &xn)) *used |= 1;
     else xn = gc_fast_carrier_walk(fcar, phis, n, ne);
     *prem = gc_fast_prem(fprem, xn);
     const double c0 = gc_code_start_fast(coff, smaxci, len);
-    if (gc_plan_code_walk(fcode, c0, len, n + 2 * smax, K, &cend)) *used |= 2;
+    if (gc_plan_code_walk(fcode, c0, len, n + 2 * smax, fill, &cend)) *used |= 2;
     else cend = gc_fast_code_walk(fcode, c0, len, n + 2 * smax, ne);
     *rem = cend - smaxci;
     *n_out = n;
@@ -155,8 +156,9 @@ int nco_period_tables(double ti, double freq, double remcarr, double codefreq, i
 }
 
 // The batch planner's steps on claims (gnsscorr_plan.hip: trk_spec_kernel discovers, trk_plan2_kernel evaluates): state after every
-// period; hits[0]/[1]: periods the code / carrier evaluation served, the rest go to the certified steps
-// ([2]/[3]) and the walkers ([4]/[5]).  shift_*: added to the discovering run's start values.
+// period; hits[0]/[1]: periods the code / carrier evaluation served, the rest go down the planner's ladder
+// (gc_*_period_any): the certified steps ([2]/[3]), else stretches and walkers ([4]/[5]).  shift_*: added to the
+// discovering run's start values.
 void nco_claims_chain(double ti, double f_sf, double freq, double codefreq, int len, int smax, double remcode0, double remcarr0,
                       int nepoch, double shift_code, double shift_car, double *rem_out, double *prem_out, int *n_out, int *hits)
 {
@@ -166,10 +168,8 @@ void nco_claims_chain(double ti, double f_sf, double freq, double codefreq, int 
     GcCarPlan PK;
     gc_code_plan_init(PC, ci, len, smax);
     gc_car_plan_init(PK, ps);
-    GcNcoFast fcode = PC.f, fcar = PK.f;
     GcCarStepC CK;
     gc_car_stepc_init(CK, PK, (int)(f_sf * 1e-3) + 16);
-    const double smaxci = (double)smax * ci, ydpi = 1.0 / GC_NCO_DPI;
     GcNoEmit ne;
     double remcode = remcode0, remcarr = remcarr0;
     for (int i = 0; i < 6; i++) hits[i] = 0;
@@ -187,22 +187,21 @@ void nco_claims_chain(double ti, double f_sf, double freq, double codefreq, int 
                 gc_carrier_claims_step<true>(PK, CK, rk + shift_car, ns, ck, &dummy);
             }
         }
-        const int n = (int)((dlen - remcode) / spc);
+        const int n = gc_period_nsamp(dlen, remcode, spc);
         n_out[e] = n;
         double r;
+        int tier;
         GcFillLoop fill;
         if (gc_carrier_claims_step<false>(PK, CK, remcarr, n, ck, &r)) hits[1]++;
-        else if (gc_carrier_period(PK, remcarr, n, fill, &r)) hits[3]++;
         else {
-            hits[5]++;
-            r = gc_fast_prem(PK.fprem, gc_fast_carrier_walk(fcar, gc_div_y(remcarr * GC_NCO_CDIV, GC_NCO_DPI, ydpi), n, ne));
+            r = gc_carrier_period_any(PK, remcarr, n, fill, ne, &tier);
+            hits[tier == GC_TIER_PERIOD ? 3 : 5]++;
         }
         remcarr = r;
         if (gc_code_claims<false>(PC, remcode, n + 2 * smax, cc, &r)) hits[0]++;
-        else if (gc_code_period(PC, remcode, n + 2 * smax, fill, &r)) hits[2]++;
         else {
-            hits[4]++;
-            r = gc_fast_code_walk(fcode, gc_code_start_fast(remcode, smaxci, len), len, n + 2 * smax, ne) - smaxci;
+            r = gc_code_period_any(PC, remcode, n + 2 * smax, fill, ne, &tier);
+            hits[tier == GC_TIER_PERIOD ? 2 : 4]++;
         }
         remcode = r;
         rem_out[e] = remcode;

@@ -12,7 +12,7 @@ GC_HD bool gc_code_period_prof(long long *T, const GcCodePlan &P, double remcode
     const double fl = cs < 0.0 ? -1.0 : 0.0;
     if (!(cs >= -dlen && cs < dlen)) return false;
     const double c0 = cs - fl * dlen;
-    if ((int)((gc_d2u(c0) >> 52) & 0x7FF) != f.ex0 + ITOP || !(c0 < dlen)) return false;
+    if (gc_expo(c0) != f.ex0 + ITOP || !(c0 < dlen)) return false;
     const double dtop = f.d[ITOP];
     double y;
     int j;
@@ -47,7 +47,7 @@ GC_HD bool gc_code_period_prof(long long *T, const GcCodePlan &P, double remcode
     c.n = nt - j;
     c.exact = P.exact;
     c.ex0 = f.ex0;
-    const int i0 = (int)((gc_d2u(y) >> 52) & 0x7FF) - f.ex0;
+    const int i0 = gc_expo(y) - f.ex0;
     if (i0 < 0 || i0 > 1) return false;
     int K[GC_NB + 1];
     if (!fill(K, c, i0, ITOP, dlen)) return false;

@@ -9,7 +9,6 @@ struct Cnt { int n = 0; __host__ __device__ void operator()(int, double, double,
 
 __global__ __launch_bounds__(64) void chain_kernel(int mode, int nper, double carrfreq, double codefreq, double *out, long long *clk)
 {
-    __shared__ int Ks[GC_NB + 2];
     const int lane = threadIdx.x;
     if (threadIdx.x && mode < 16) return;
     const double ti = 1 / 16.368e6, f_sf = 16.368e6;
@@ -19,7 +18,7 @@ __global__ __launch_bounds__(64) void chain_kernel(int mode, int nper, double ca
     gc_fast_init(fcar, ps);
     gc_fast_init(fcode, ci);
     gc_fast_init(fprem, -GC_NCO_DPI);
-    const double yspc = 1.0 / spc, ydpi = 1.0 / GC_NCO_DPI, smaxci = smax * ci;
+    const double yspc = gc_period_yspc(spc), ydpi = 1.0 / GC_NCO_DPI, smaxci = smax * ci;
     double remcode = 0, remcarr = 0;
     Cnt c1, c2;
     long long T[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -30,7 +29,7 @@ __global__ __launch_bounds__(64) void chain_kernel(int mode, int nper, double ca
     GcFillLanes fill{lane};
     const long long t0 = wall_clock64();
     for (int p = 0; p < nper; p++) {
-        const int n = (int)gc_div_y(len - remcode, spc, yspc);
+        const int n = gc_period_nsamp(len, remcode, spc, yspc);
         if (mode & 1) remcarr = gc_fast_prem(fprem, gc_fast_carrier_walk(fcar, gc_div_y(remcarr * 32.0, GC_NCO_DPI, ydpi), n, c1));
         if (mode & 2) remcode = gc_fast_code_walk(fcode, gc_code_start_fast(remcode, smaxci, len), len, n + 2 * smax, c2) - smaxci;
         if (mode & 4) remcarr = gc_carrier_prem(gc_carrier_walk(gc_carrier_phis(remcarr), ps, n, c1));
@@ -38,18 +37,19 @@ __global__ __launch_bounds__(64) void chain_kernel(int mode, int nper, double ca
             const double phis = gc_div_y(remcarr * 32.0, GC_NCO_DPI, ydpi);
             double xn;
             GcNoEmit ne;
-            if (!plan_carrier_dev(fcar, phis, n, Ks, lane, &xn)) { xn = gc_fast_carrier_walk(fcar, phis, n, ne); c1.n++; }
+            if (!gc_plan_carrier_walk(fcar, phis, n, fill, &xn)) { xn = gc_fast_carrier_walk(fcar, phis, n, ne); c1.n++; }
             remcarr = gc_fast_prem(fprem, xn);
         }
         if (mode & 32) {
             const double c0 = gc_code_start_fast(remcode, smaxci, len);
             double cend;
             GcNoEmit ne;
-            if (!plan_code_dev(fcode, c0, len, n + 2 * smax, Ks, lane, &cend)) { cend = gc_fast_code_walk(fcode, c0, len, n + 2 * smax, ne); c2.n++; }
+            if (!gc_plan_code_walk(fcode, c0, len, n + 2 * smax, fill, &cend)) { cend = gc_fast_code_walk(fcode, c0, len, n + 2 * smax, ne); c2.n++; }
             remcode = cend - smaxci;
         }
-        if (mode & 64) { double rp; if (gc_carrier_period(PK, remcarr, n, fill, &rp)) remcarr = rp; else { GcNoEmit ne; c1.n++; remcarr = gc_fast_prem(fprem, gc_fast_carrier_walk(fcar, gc_div_y(remcarr * 32.0, GC_NCO_DPI, ydpi), n, ne)); } }
-        if (mode & 128) { double rc; if (gc_code_period(PC, remcode, n + 2 * smax, fill, &rc)) remcode = rc; else { GcNoEmit ne; c2.n++; remcode = gc_fast_code_walk(fcode, gc_code_start_fast(remcode, smaxci, len), len, n + 2 * smax, ne) - smaxci; } }
+        // (the planner's ladder; counted: periods the certified step did not serve)
+        if (mode & 64) { GcNoEmit ne; int tier; remcarr = gc_carrier_period_any(PK, remcarr, n, fill, ne, &tier); c1.n += tier != GC_TIER_PERIOD; }
+        if (mode & 128) { GcNoEmit ne; int tier; remcode = gc_code_period_any(PC, remcode, n + 2 * smax, fill, ne, &tier); c2.n += tier != GC_TIER_PERIOD; }
         if (mode & 256) { double rc; GcNoEmit ne; if (gc_code_period_prof<11>(T, PC, remcode, n + 2 * smax, fill, &rc, ne)) remcode = rc; else c2.n++; }
         if (mode & 8) remcode = gc_code_rem(gc_code_walk(gc_code_start(remcode, smax, ci, len), ci, len, n + 2 * smax, c2), smax, ci);
     }
