@@ -135,6 +135,16 @@ class AcqRes(C.Structure):
                 ("iters", C.c_int), ("buffloc", C.c_uint64)]
 
 
+CH_IDLE, CH_SEARCH, CH_TRACK = 0, 1, 2
+ACQSLEEP = 2000                              # ms, ref src/sdr.h:149
+
+
+class RxStat(C.Structure):
+    """gnsscorr_rxstat_t: one channel of the receiver schedule (gnsscorr_rx_status)."""
+    _fields_ = [("state", C.c_int), ("attempts", C.c_int), ("next_try", C.c_uint64), ("acq_wrpos", C.c_uint64),
+                ("acq", AcqRes), ("cnt", C.c_uint64)]
+
+
 # ---- ctypes mirrors of include/sdr_compat.h (ref src/sdr.h:344-511) --------
 OBSINTERPN = 80
 
@@ -209,7 +219,9 @@ EXPORTS_GNSSCORR = [
     "gnsscorr_trk_fetch", "gnsscorr_trk_fetch_sums", "gnsscorr_trk_devptrs", "gnsscorr_acq_run",
     "gnsscorr_acq_fetch", "gnsscorr_trk_start_from_acq", "gnsscorr_acq_power", "gnsscorr_fft16k", "gnsscorr_pspec",
     "gnsscorr_timing_enable", "gnsscorr_timing_read", "gnsscorr_timing_reset", "gnsscorr_default_ctx",
-    "gnsscorr_spec_run", "gnsscorr_spec_fetch", "gnsscorr_trk_loop_lapped"]
+    "gnsscorr_spec_run", "gnsscorr_spec_fetch", "gnsscorr_trk_loop_lapped",
+    "gnsscorr_acq_run_subset", "gnsscorr_loop_start_from_acq", "gnsscorr_rx_start", "gnsscorr_rx_set",
+    "gnsscorr_rx_step", "gnsscorr_rx_status"]
 EXPORTS_SDR = [
     "sdracquisition", "checkacquisition", "sdrtracking", "cumsumcorr", "clearcumsumcorr", "pll", "dll",
     "readinifile", "chk_initvalue", "initacqstruct", "inittrkprmstruct", "inittrkstruct", "initsdrch",
@@ -260,7 +272,13 @@ def lib():
     L.gnsscorr_trk_fetch_log.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.gnsscorr_trk_loop_lapped.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     L.gnsscorr_acq_run.argtypes = [C.c_void_p, C.c_uint64]
+    L.gnsscorr_acq_run_subset.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_int), C.c_int]
     L.gnsscorr_acq_fetch.argtypes = [C.c_void_p, C.POINTER(AcqRes)]
+    L.gnsscorr_loop_start_from_acq.argtypes = [C.c_void_p]
+    L.gnsscorr_rx_start.argtypes = [C.c_void_p, C.c_int]
+    L.gnsscorr_rx_set.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.gnsscorr_rx_step.argtypes = [C.c_void_p, C.c_int]
+    L.gnsscorr_rx_status.argtypes = [C.c_void_p, C.POINTER(RxStat)]
     L.gnsscorr_trk_start_from_acq.argtypes = [C.c_void_p]
     L.gnsscorr_acq_power.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.gnsscorr_fft16k.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
@@ -579,8 +597,14 @@ class Engine:
         return n.value
 
     # -- acquisition
-    def acq_run(self, wrpos=0):
-        _check(self._L.gnsscorr_acq_run(self.h, wrpos))
+    def acq_run(self, wrpos=0, channels=None):
+        """channels: None searches every channel (gnsscorr_acq_run), a sequence of distinct channel indices only
+        those (gnsscorr_acq_run_subset)."""
+        if channels is None:
+            _check(self._L.gnsscorr_acq_run(self.h, wrpos))
+        else:
+            arr = (C.c_int * len(channels))(*channels)
+            _check(self._L.gnsscorr_acq_run_subset(self.h, wrpos, arr, len(channels)))
 
     def acq_fetch(self):
         arr = (AcqRes * len(self.channels))()
@@ -591,11 +615,37 @@ class Engine:
     def trk_start_from_acq(self):
         _check(self._L.gnsscorr_trk_start_from_acq(self.h))
 
+    def loop_start_from_acq(self):
+        """Device hand-over of the last search's acquired channels into the closed loop (tracking and loop state)."""
+        _check(self._L.gnsscorr_loop_start_from_acq(self.h))
+
     def acq_power(self, ch):
         c = self.channels[ch]
         P = np.empty((c.nfreq, c.nsamp), np.float64)
         _check(self._L.gnsscorr_acq_power(self.h, ch, P.ctypes.data))
         return P
+
+    # -- receiver schedule
+    def rx_start(self, retry_ms=0):
+        """Every channel -> SEARCH (gnsscorr_rx_start); retry_ms <= 0: ACQSLEEP."""
+        _check(self._L.gnsscorr_rx_start(self.h, int(retry_ms)))
+
+    def rx_set(self, ch, state):
+        _check(self._L.gnsscorr_rx_set(self.h, ch, state))
+
+    def rx_step(self, max_periods):
+        """One scheduling step at the rings' current write positions; its tracking part reports through trk_fetch /
+        trk_fetch_log like trk_run_loop(max_periods)."""
+        _check(self._L.gnsscorr_rx_step(self.h, max_periods))
+        self._nepoch = max_periods
+
+    def rx_status(self):
+        arr = (RxStat * len(self.channels))()
+        _check(self._L.gnsscorr_rx_status(self.h, arr))
+        return [dict(state=a.state, attempts=a.attempts, next_try=a.next_try, acq_wrpos=a.acq_wrpos, cnt=a.cnt,
+                     acq=dict(acqcodei=a.acq.acqcodei, freqi=a.acq.freqi, acqfreq=a.acq.acqfreq, cn0=a.acq.cn0,
+                              peakr=a.acq.peakr, flagacq=a.acq.flagacq, iters=a.acq.iters, buffloc=a.acq.buffloc))
+                for a in arr]
 
     # -- IF monitor
     def spectrum(self, ftype, buffloc, n, f_sf, nfft=16384, nloop=SPEC_NLOOP, offsets=None, seed=None):

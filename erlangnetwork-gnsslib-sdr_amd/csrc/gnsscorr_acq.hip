@@ -25,6 +25,13 @@
 //            workgroup.  P only leaves the chip when the caller asks for it.
 //   acq_final (per channel): the decision of checkacquisition() after each
 //            iteration, first success wins (ref src/sdracq.c:39-42).
+//
+// Every run works on a channel list (gnsscorr_acq_run_subset; gnsscorr_acq_run is the list 0..nch-1): the
+// per-channel kernels take their channel from a compacted device list, acq_fwd its frequency grid from the
+// list of grids that have a listed channel, so grid sizes follow the list.  Everything a channel owns (code
+// spectrum, rows, arrival counters, result) stays indexed by the channel itself: what a listed channel computes
+// does not depend on who else is listed.
+#include <cstddef>
 #include <cstdlib>
 #include <type_traits>
 #include <vector>
@@ -70,6 +77,9 @@ struct GcAcqWork {
     std::vector<int> grid_chan;         // a representative channel per grid
     GcDevBuf<int> d_grid_chan;          // device copy of grid_chan
     GcDevBuf<uint64_t> d_grid_wrpos;    // ring write position seen by each grid
+    GcDevBuf<int> d_list;               // [nch] channels of the last run, then [ngrid] the grids that have one of them
+    std::vector<int> list, glist;       // host copies of what d_list holds
+    std::vector<char> listed;           // [nch] channel was part of the last run
     bool code_ready = false;
     uint64_t last_wrpos[2] = {0, 0};
     bool ran = false;
@@ -236,16 +246,17 @@ __global__ void acq_nco_kernel(const GcChan *__restrict__ chan, const int *__res
     if (ct.overflow) atomicAdd(overflow, 1);
 }
 
-// acq_fwd: grid (bin, iteration, grid group)
+// acq_fwd: grid (bin, iteration, entry of the list of frequency grids in use)
 __global__ __launch_bounds__(GC_FFT_THREADS) void acq_fwd_kernel(
-    const GcChan *__restrict__ chan, const int *__restrict__ grid_chan, const GcAcqCar *__restrict__ car,
+    const GcChan *__restrict__ chan, const int *__restrict__ grid_chan, const int *__restrict__ glist,
+    const GcAcqCar *__restrict__ car,
     const uint64_t *__restrict__ grid_wrpos, const float2 *__restrict__ tw16k,
     const float2 *__restrict__ tw32p, const float2 *__restrict__ tw64p1, const float2 *__restrict__ tw64p3,
     float2 *__restrict__ X, int maxfreq, int maxintg, int L)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2 *lds = reinterpret_cast<float2 *>(smem);
-    const int bin = blockIdx.x, it = blockIdx.y, g = blockIdx.z, tid = threadIdx.x;
+    const int bin = blockIdx.x, it = blockIdx.y, g = glist[blockIdx.z], tid = threadIdx.x;
     const GcChan &c = chan[grid_chan[g]];
     if (bin >= c.nfreq || it >= c.intg) return;
     const int n = c.nsamp, n2 = 2 * n, dtype = c.dtype;
@@ -371,8 +382,8 @@ template <int NT>
 __global__ __launch_bounds__(NT) void acq_corr_kernel(
     const GcChan *__restrict__ chan, const float2 *__restrict__ tw16k, const float2 *__restrict__ tw32p,
     const float2 *__restrict__ X, const float2 *__restrict__ C, const int *__restrict__ iters,
-    GcAcqRow *rows, double *__restrict__ Pout, int pout_ch, int maxfreq, int maxintg, int nchg,
-    int *arrive, int *done)
+    GcAcqRow *rows, double *__restrict__ Pout, int pout_ch, int maxfreq, int maxintg,
+    const int *__restrict__ list, int nlist, int *arrive, int *done)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2 *lds = reinterpret_cast<float2 *>(smem);
@@ -394,8 +405,9 @@ __global__ __launch_bounds__(NT) void acq_corr_kernel(
     const int bpx = (maxfreq + 7) >> 3;                 // bins per XCD slot
     const int grp = qq / (bpx * G), rem = qq - grp * (bpx * G);
     const int bin = Pout ? qq * 8 + slot : (rem / G) * 8 + slot;
-    const int ch = Pout ? pout_ch : grp * G + rem % G;
-    if (bin >= maxfreq || (!Pout && ch >= nchg)) return;
+    const int li = grp * G + rem % G;                   // entry of the channel list
+    if (bin >= maxfreq || (!Pout && li >= nlist)) return;
+    const int ch = Pout ? pout_ch : list[li];
     const GcChan &c = chan[ch];
     if (bin >= c.nfreq) return;
     const int n = c.nsamp, nit = iters[ch], nsc2 = 2 * c.nsampchip;
@@ -564,7 +576,8 @@ __global__ __launch_bounds__(512) void acq_corr64_kernel(
     const GcChan *__restrict__ chan, const float2 *__restrict__ tw16k, const float2 *__restrict__ tw32p,
     const float2 *__restrict__ tw64p1, const float2 *__restrict__ tw64p3,
     const float2 *__restrict__ X, const float2 *__restrict__ C, const int *__restrict__ iters,
-    GcAcqRow *__restrict__ rows, double *__restrict__ Pout, int pout_ch, int maxfreq, int maxintg, int nchg)
+    GcAcqRow *__restrict__ rows, double *__restrict__ Pout, int pout_ch, int maxfreq, int maxintg,
+    const int *__restrict__ list, int nlist)
 {
     constexpr int NT = 512, L = 2 * GC_L, NP = 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -574,8 +587,9 @@ __global__ __launch_bounds__(512) void acq_corr64_kernel(
     const int tid0 = threadIdx.x;
     const int slot = blockIdx.x & 7, qq = blockIdx.x >> 3;
     const int bin = Pout ? qq * 8 + slot : qq % maxfreq;
-    const int ch = Pout ? pout_ch : (qq / maxfreq) * 8 + slot;
-    if (bin >= maxfreq || (!Pout && ch >= nchg)) return;
+    const int li = (qq / maxfreq) * 8 + slot;           // entry of the channel list
+    if (bin >= maxfreq || (!Pout && li >= nlist)) return;
+    const int ch = Pout ? pout_ch : list[li];
     const GcChan &c = chan[ch];
     if (bin >= c.nfreq) return;
     const int n = c.nsamp, nit = iters[ch], nsc2 = 2 * c.nsampchip;
@@ -724,15 +738,17 @@ __global__ __launch_bounds__(512) void acq_corr64_kernel(
     }
 }
 
-// acq_final: one wavefront per channel; the lanes share the bins of an iteration
+// acq_final: one wavefront per listed channel; the lanes share the bins of an iteration
 __global__ __launch_bounds__(64) void acq_final_kernel(const GcChan *__restrict__ chan, const double *__restrict__ freqs,
                                                        const GcAcqRow *__restrict__ rows,
                                                        const uint64_t *__restrict__ grid_wrpos,
                                                        gnsscorr_acqres_t *__restrict__ res, int *__restrict__ iters_out,
-                                                       int nch, int maxfreq, int maxintg)
+                                                       const int *__restrict__ list, int nlist, int maxfreq,
+                                                       int maxintg)
 {
-    const int ch = blockIdx.x, lane = threadIdx.x;
-    if (ch >= nch) return;
+    const int lane = threadIdx.x;
+    if ((int)blockIdx.x >= nlist) return;
+    const int ch = list[blockIdx.x];
     const GcChan &c = chan[ch];
     const int n = c.nsamp;
     gnsscorr_acqres_t r;
@@ -774,10 +790,10 @@ __global__ __launch_bounds__(64) void acq_final_kernel(const GcChan *__restrict_
     }
 }
 
-__global__ void fill_int_kernel(int *p, const GcChan *__restrict__ chan, int nch)
+__global__ void fill_int_kernel(int *p, const GcChan *__restrict__ chan, const int *__restrict__ list, int nlist)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < nch) p[i] = chan[i].intg;
+    if (i < nlist) p[list[i]] = chan[list[i]].intg;
 }
 
 // stand-alone batch FFT (op-level entry point and tests): grid (batch); natural order in and out
@@ -905,6 +921,9 @@ static int acq_prepare(gnsscorr_ctx *ctx)
     GC_RESERVE(ctx, w->res, nch);
     GC_RESERVE(ctx, w->d_grid_chan, w->ngrid);
     GC_RESERVE(ctx, w->d_grid_wrpos, w->ngrid);
+    GC_RESERVE(ctx, w->d_list, (size_t)nch + w->ngrid);
+    w->list.clear();
+    w->glist.clear();
     GC_HIP(hipMemcpyAsync(w->d_grid_chan, w->grid_chan.data(), sizeof(int) * w->ngrid, hipMemcpyHostToDevice,
                           ctx->stream));
     GC_RESERVE(ctx, w->car, (size_t)w->ngrid * w->maxfreq);
@@ -930,21 +949,42 @@ static int acq_prepare(gnsscorr_ctx *ctx)
     return GNSSCORR_OK;
 }
 
-extern "C" int gnsscorr_acq_run(gnsscorr_ctx *ctx, uint64_t wrpos)
+// One search over the channels chlist[0..n) (distinct; nullptr: all of them).  wp_ring[r]: write position of ring
+// r + 1 the search ends at, 0: the ring's current one.
+int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chlist, int n)
 {
     if (!ctx) return gc_fail(GNSSCORR_EINVAL, "null context");
     if (!ctx->nch) return gc_fail(GNSSCORR_ESTATE, "acq_run: no channels set");
+    const int nch = ctx->nch;
+    if (!chlist) n = nch;
+    if (n < 1 || n > nch) return gc_fail(GNSSCORR_EINVAL, "acq_run: list of %d channels (1..%d)", n, nch);
+    std::vector<int> list(n);
+    std::vector<char> listed(nch, 0);
+    for (int i = 0; i < n; i++) {
+        const int ch = chlist ? chlist[i] : i;
+        if (ch < 0 || ch >= nch || listed[ch])
+            return gc_fail(GNSSCORR_EINVAL, "acq_run: list entry %d: channel %d (0..%d, each once)", i, ch, nch - 1);
+        list[i] = ch;
+        listed[ch] = 1;
+    }
     GC_HIP(hipSetDevice(ctx->device));
     int rc = acq_prepare(ctx);
     if (rc) return rc;
     rc = gc_ingest_fence(ctx);
     if (rc) return rc;
     GcAcqWork *w = ctx->acq;
-    std::vector<uint64_t> gw(w->ngrid);
+    // the grids that have a listed channel, in grid order
+    std::vector<int> glist;
     for (int g = 0; g < w->ngrid; g++) {
+        bool used = false;
+        for (int i = 0; i < n && !used; i++) used = ctx->hchan[list[i]].grid == g;
+        if (used) glist.push_back(g);
+    }
+    std::vector<uint64_t> gw(w->ngrid, 0);
+    for (int g : glist) {
         const GcChan &c = ctx->hchan[w->grid_chan[g]];
         const int ft = ctx->hdesc[w->grid_chan[g]].ftype;
-        const uint64_t wp = wrpos ? wrpos : ctx->ring[ft - 1].wrpos;
+        const uint64_t wp = wp_ring[ft - 1] ? wp_ring[ft - 1] : ctx->ring[ft - 1].wrpos;
         if (wp < (uint64_t)(c.intg + 1) * c.nsamp)
             return gc_fail(GNSSCORR_ESTATE, "acq_run: ring %d holds %llu samples, %llu needed", ft,
                            (unsigned long long)wp, (unsigned long long)((uint64_t)(c.intg + 1) * c.nsamp));
@@ -953,50 +993,78 @@ extern "C" int gnsscorr_acq_run(gnsscorr_ctx *ctx, uint64_t wrpos)
                            ft, (unsigned long long)c.ringlen, c.intg + 1);
         gw[g] = wp;
     }
-    // pageable source: the copy is staged before the call returns
+    // pageable sources: the copies are staged before the call returns.  The lists go up only when they change.
+    const int ng = (int)glist.size();
+    if (list != w->list || glist != w->glist) {
+        GC_HIP(hipMemcpyAsync(w->d_list, list.data(), sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
+        GC_HIP(hipMemcpyAsync(w->d_list + nch, glist.data(), sizeof(int) * ng, hipMemcpyHostToDevice, ctx->stream));
+        w->list.clear();            // (until the copies are staged)
+    }
     GC_HIP(hipMemcpyAsync(w->d_grid_wrpos, gw.data(), sizeof(uint64_t) * w->ngrid, hipMemcpyHostToDevice,
                           ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
+    w->list = list;
+    w->glist = glist;
+    w->ran = false;                 // until every launch below is queued
+    const int *dlist = w->d_list, *dglist = w->d_list + nch;
     const int lds = GC_FFT_LDS + 256;
     {
         GcTimed t(ctx, "acq_fwd");
-        hipLaunchKernelGGL(acq_fwd_kernel, dim3(w->maxfreq, w->maxintg, w->ngrid), dim3(GC_FFT_THREADS), lds + GC_ACQ_CARLDS,
-                           ctx->stream, ctx->dchan, w->d_grid_chan, w->car, w->d_grid_wrpos, w->tw16k, w->tw32p,
+        hipLaunchKernelGGL(acq_fwd_kernel, dim3(w->maxfreq, w->maxintg, ng), dim3(GC_FFT_THREADS), lds + GC_ACQ_CARLDS,
+                           ctx->stream, ctx->dchan, w->d_grid_chan, dglist, w->car, w->d_grid_wrpos, w->tw16k, w->tw32p,
                            w->tw64p1, w->tw64p3, w->X, w->maxfreq, w->maxintg, w->L);
     }
     GC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(fill_int_kernel, dim3((ctx->nch + 63) / 64), dim3(64), 0, ctx->stream, w->iters,
-                       ctx->dchan, ctx->nch);
+    // channels that are not listed: no iterations, a zero result row
+    if (n < nch) {
+        GC_HIP(hipMemsetAsync(w->iters, 0, sizeof(int) * nch, ctx->stream));
+        GC_HIP(hipMemsetAsync(w->res, 0, sizeof(gnsscorr_acqres_t) * nch, ctx->stream));
+    }
+    hipLaunchKernelGGL(fill_int_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, w->iters, ctx->dchan, dlist, n);
     // arrival counters per (channel, iteration) and the channels' "acquired" flags
-    GC_HIP(hipMemsetAsync(w->arrive, 0, sizeof(int) * ((size_t)ctx->nch * w->maxintg + ctx->nch), ctx->stream));
+    GC_HIP(hipMemsetAsync(w->arrive, 0, sizeof(int) * ((size_t)nch * w->maxintg + nch), ctx->stream));
     {
         GcTimed t(ctx, "acq_corr");
         static const int nt = getenv("GNSSCORR_ACQ_NT") ? atoi(getenv("GNSSCORR_ACQ_NT")) : 512;
-        // (bins per XCD slot) x (channels, in groups of GC_ACQ_G) x 8 slots
-        const unsigned acq_grid = 8u * (unsigned)((w->maxfreq + 7) / 8) * (unsigned)(GC_ACQ_G * ((ctx->nch + GC_ACQ_G - 1) / GC_ACQ_G));
+        // (bins per XCD slot) x (listed channels, in groups of GC_ACQ_G) x 8 slots
+        const unsigned acq_grid = 8u * (unsigned)((w->maxfreq + 7) / 8) * (unsigned)(GC_ACQ_G * ((n + GC_ACQ_G - 1) / GC_ACQ_G));
         if (w->L == 2 * GC_L)
-            hipLaunchKernelGGL(acq_corr64_kernel, dim3(8 * ((ctx->nch + 7) / 8) * w->maxfreq), dim3(512), lds + 256,
+            hipLaunchKernelGGL(acq_corr64_kernel, dim3(8 * ((n + 7) / 8) * w->maxfreq), dim3(512), lds + 256,
                                ctx->stream, ctx->dchan, w->tw16k, w->tw32p, w->tw64p1, w->tw64p3, w->X, w->C, w->iters,
-                               w->rows, (double *)nullptr, 0, w->maxfreq, w->maxintg, ctx->nch);
+                               w->rows, (double *)nullptr, 0, w->maxfreq, w->maxintg, dlist, n);
         else if (nt == 1024)
             hipLaunchKernelGGL(acq_corr_kernel<1024>, dim3(acq_grid), dim3(1024), lds + 256,
                                ctx->stream, ctx->dchan, w->tw16k, w->tw32p, w->X, w->C, w->iters, w->rows,
-                               (double *)nullptr, 0, w->maxfreq, w->maxintg, ctx->nch, w->arrive, w->arrive + (size_t)ctx->nch * w->maxintg);
+                               (double *)nullptr, 0, w->maxfreq, w->maxintg, dlist, n, w->arrive, w->arrive + (size_t)nch * w->maxintg);
         else
             hipLaunchKernelGGL(acq_corr_kernel<512>, dim3(acq_grid), dim3(512), lds + 256,
                                ctx->stream, ctx->dchan, w->tw16k, w->tw32p, w->X, w->C, w->iters, w->rows,
-                               (double *)nullptr, 0, w->maxfreq, w->maxintg, ctx->nch, w->arrive, w->arrive + (size_t)ctx->nch * w->maxintg);
+                               (double *)nullptr, 0, w->maxfreq, w->maxintg, dlist, n, w->arrive, w->arrive + (size_t)nch * w->maxintg);
     }
     GC_HIP(hipGetLastError());
     {
         GcTimed t(ctx, "acq_final");
-        hipLaunchKernelGGL(acq_final_kernel, dim3(ctx->nch), dim3(64), 0, ctx->stream, ctx->dchan,
-                           ctx->dfreqs, w->rows, w->d_grid_wrpos, w->res, w->iters, ctx->nch, w->maxfreq,
+        hipLaunchKernelGGL(acq_final_kernel, dim3(n), dim3(64), 0, ctx->stream, ctx->dchan,
+                           ctx->dfreqs, w->rows, w->d_grid_wrpos, w->res, w->iters, dlist, n, w->maxfreq,
                            w->maxintg);
     }
     GC_HIP(hipGetLastError());
+    w->listed = listed;
     w->ran = true;
     return GNSSCORR_OK;
+}
+
+extern "C" int gnsscorr_acq_run(gnsscorr_ctx *ctx, uint64_t wrpos)
+{
+    const uint64_t wp[2] = {wrpos, wrpos};
+    return gc_acq_run_list(ctx, wp, nullptr, 0);
+}
+
+extern "C" int gnsscorr_acq_run_subset(gnsscorr_ctx *ctx, uint64_t wrpos, const int *chlist, int n)
+{
+    if (!chlist) return gc_fail(GNSSCORR_EINVAL, "acq_run_subset: null channel list");
+    const uint64_t wp[2] = {wrpos, wrpos};
+    return gc_acq_run_list(ctx, wp, chlist, n);
 }
 
 extern "C" int gnsscorr_acq_fetch(gnsscorr_ctx *ctx, gnsscorr_acqres_t *res)
@@ -1039,10 +1107,58 @@ extern "C" int gnsscorr_trk_start_from_acq(gnsscorr_ctx *ctx)
     return GNSSCORR_OK;
 }
 
+// The same hand-over into the closed loop: one workgroup per listed channel; an acquired one gets the tracking state
+// above and the loop state sdrthread() starts tracking with -- the channel's constants kept (filter coefficients,
+// ne / nl, loopms, rate, prn, the sdrch_t constants), acqfreq from the search, every running field as inittrkstruct()
+// / initnavstruct() leave it (ref src/sdrinit.c:432-480,485-560: zero) and cnt = 0.  That is gnsscorr_loop_t from
+// flagsync up to prn and from biti to the end.
+__global__ __launch_bounds__(64) void acq_to_loop_kernel(const GcChan *__restrict__ chan, const gnsscorr_acqres_t *__restrict__ res,
+                                                         GcTrkState *__restrict__ state, gnsscorr_loop_t *__restrict__ loop,
+                                                         const int *__restrict__ list, int nlist)
+{
+    if ((int)blockIdx.x >= nlist) return;
+    const int ch = list[blockIdx.x], tid = threadIdx.x;
+    const gnsscorr_acqres_t r = res[ch];
+    if (!r.flagacq) return;
+    static_assert(offsetof(gnsscorr_loop_t, flagsync) % 4 == 0 && offsetof(gnsscorr_loop_t, prn) % 4 == 0 &&
+                  offsetof(gnsscorr_loop_t, biti) == offsetof(gnsscorr_loop_t, prn) + 4 && sizeof(gnsscorr_loop_t) % 4 == 0,
+                  "loop state layout");
+    constexpr int a0 = offsetof(gnsscorr_loop_t, flagsync) / 4, a1 = offsetof(gnsscorr_loop_t, prn) / 4;
+    constexpr int b0 = offsetof(gnsscorr_loop_t, biti) / 4, b1 = sizeof(gnsscorr_loop_t) / 4;
+    int *w = reinterpret_cast<int *>(loop + ch);
+    for (int k = a0 + tid; k < a1; k += 64) w[k] = 0;
+    for (int k = b0 + tid; k < b1; k += 64) w[k] = 0;
+    if (tid == 0) {
+        loop[ch].acqfreq = r.acqfreq;
+        GcTrkState s;
+        s.carrfreq = r.acqfreq;
+        s.codefreq = chan[ch].crate;
+        s.remcode = 0.0;
+        s.remcarr = 0.0;
+        s.buffloc = r.buffloc;
+        state[ch] = s;
+    }
+}
+
+int gc_acq_handover(gnsscorr_ctx *ctx, bool quiesce)
+{
+    if (!ctx || !ctx->acq || !ctx->acq->ran) return gc_fail(GNSSCORR_ESTATE, "loop_start_from_acq: no acq_run yet");
+    GC_HIP(hipSetDevice(ctx->device));
+    if (quiesce) { int rc = gc_quiesce(ctx); if (rc) return rc; }
+    const int n = (int)ctx->acq->list.size();
+    hipLaunchKernelGGL(acq_to_loop_kernel, dim3(n), dim3(64), 0, ctx->stream, ctx->dchan, ctx->acq->res,
+                       ctx->dstate2[ctx->state_cur], ctx->dloop, ctx->acq->d_list, n);
+    GC_HIP(hipGetLastError());
+    return GNSSCORR_OK;
+}
+
+extern "C" int gnsscorr_loop_start_from_acq(gnsscorr_ctx *ctx) { return gc_acq_handover(ctx, true); }
+
 extern "C" int gnsscorr_acq_power(gnsscorr_ctx *ctx, int ch, double *power)
 {
     if (!ctx || !ctx->acq || !ctx->acq->ran) return gc_fail(GNSSCORR_ESTATE, "acq_power: no acq_run yet");
     if (ch < 0 || ch >= ctx->nch || !power) return gc_fail(GNSSCORR_EINVAL, "acq_power: channel %d", ch);
+    if (!ctx->acq->listed[ch]) return gc_fail(GNSSCORR_ESTATE, "acq_power: channel %d was not part of the last search", ch);
     GC_HIP(hipSetDevice(ctx->device));
     GcAcqWork *w = ctx->acq;
     const GcChan &c = ctx->hchan[ch];
@@ -1053,11 +1169,11 @@ extern "C" int gnsscorr_acq_power(gnsscorr_ctx *ctx, int ch, double *power)
     if (w->L == 2 * GC_L)
         hipLaunchKernelGGL(acq_corr64_kernel, dim3(8 * ((c.nfreq + 7) / 8)), dim3(512), GC_FFT_LDS + 512,
                            ctx->stream, ctx->dchan, w->tw16k, w->tw32p, w->tw64p1, w->tw64p3, w->X, w->C, w->iters,
-                           w->rows, w->P, ch, w->maxfreq, w->maxintg, 1);
+                           w->rows, w->P, ch, w->maxfreq, w->maxintg, (const int *)nullptr, 0);
     else
         hipLaunchKernelGGL(acq_corr_kernel<512>, dim3(8 * ((c.nfreq + 7) / 8)), dim3(512), GC_FFT_LDS + 512,
                            ctx->stream, ctx->dchan, w->tw16k, w->tw32p, w->X, w->C, w->iters, w->rows, w->P, ch,
-                           w->maxfreq, w->maxintg, 1, (int *)nullptr, (int *)nullptr);
+                           w->maxfreq, w->maxintg, (const int *)nullptr, 0, (int *)nullptr, (int *)nullptr);
     GC_HIP(hipGetLastError());
     GC_HIP(hipMemcpyAsync(power, w->P, sizeof(double) * elems, hipMemcpyDeviceToHost, ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));

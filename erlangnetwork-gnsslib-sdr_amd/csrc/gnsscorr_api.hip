@@ -114,6 +114,8 @@ static void drop_channel_buffers(gnsscorr_ctx *ctx)
     ctx->step_nseg = 0;
     ctx->last_loop_nper = 0;
     ctx->state_cur = 0;
+    ctx->loop_isset.clear();
+    ctx->rx = GcRx();
 }
 
 extern "C" void gnsscorr_destroy(gnsscorr_ctx *ctx)
@@ -458,6 +460,7 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
     drop_channel_buffers(ctx);
 
     ctx->nch = nch;
+    ctx->loop_isset.assign(nch, 0);
     ctx->hdesc.assign(ch, ch + nch);
     ctx->hcode.resize(nch);
     ctx->hfreq.resize(nch);
@@ -796,6 +799,7 @@ extern "C" int gnsscorr_loop_set(gnsscorr_ctx *ctx, int ch0, int nch, const gnss
     GC_HIP(hipMemcpyAsync(ctx->dloop + ch0, lp, sizeof(gnsscorr_loop_t) * nch, hipMemcpyHostToDevice, ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < nch; i++) {
+        ctx->loop_isset[ch0 + i] = 1;
         if (lp[i].loopms > ctx->loop_kmax) ctx->loop_kmax = lp[i].loopms < GC_STEP_KMAX ? lp[i].loopms : GC_STEP_KMAX;
         if (lp[i].flagsync) ctx->loop_sync_hint = true;
     }
@@ -836,7 +840,11 @@ static int ensure_step_buffers(gnsscorr_ctx *ctx)
     return GNSSCORR_OK;
 }
 
-extern "C" int gnsscorr_trk_run_loop(gnsscorr_ctx *ctx, int nperiod)
+extern "C" int gnsscorr_trk_run_loop(gnsscorr_ctx *ctx, int nperiod) { return gc_trk_run_loop(ctx, nperiod, nullptr); }
+
+// wp_ch: nullptr, or the write position each channel is tracked up to ([nch]; 0 starves the channel at once: it plans
+// no period and keeps its state), which the caller read under the context's lock
+int gc_trk_run_loop(gnsscorr_ctx *ctx, int nperiod, const uint64_t *wp_ch)
 {
     if (!ctx || nperiod <= 0) return gc_fail(GNSSCORR_EINVAL, "trk_run_loop: nperiod %d", nperiod);
     if (!ctx->nch) return gc_fail(GNSSCORR_ESTATE, "trk_run_loop: no channels set");
@@ -862,7 +870,7 @@ extern "C" int gnsscorr_trk_run_loop(gnsscorr_ctx *ctx, int nperiod)
     std::vector<uint64_t> wp(ctx->nch);
     {
         std::lock_guard<std::mutex> lk(ctx->mtx);
-        for (int i = 0; i < ctx->nch; i++) wp[i] = ctx->ring[ctx->hdesc[i].ftype - 1].wrpos;
+        for (int i = 0; i < ctx->nch; i++) wp[i] = wp_ch ? wp_ch[i] : ctx->ring[ctx->hdesc[i].ftype - 1].wrpos;
         rc = gc_ingest_fence(ctx);
         if (rc) return rc;
     }

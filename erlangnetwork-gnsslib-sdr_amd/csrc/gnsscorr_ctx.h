@@ -114,6 +114,13 @@ struct GcPlanSlot {
     bool fin_pending = false;      // ev_fin has been recorded
 };
 
+// The receiver schedule (gnsscorr_rx.hip): sdrthread()'s per-channel state, kept by the host
+struct GcRx {
+    bool on = false;
+    int retry_ms = 0;                              // the reference's ACQSLEEP, counted on each channel's sample clock
+    std::vector<gnsscorr_rxstat_t> st;             // [nch] (cnt is filled in by gnsscorr_rx_status)
+};
+
 struct gnsscorr_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -183,6 +190,8 @@ struct gnsscorr_ctx {
     int step_nseg = 0;
     GcPinBuf<unsigned> hostflags;                  // mapped: [0] channels whose run is over, [1] some channel has its nav bit synchronised
     bool loop_sync_hint = false;                   // some channel had its nav bit synchronised when last seen
+    std::vector<char> loop_isset;                  // [nch] the channel's loop constants have been set (gnsscorr_loop_set)
+    GcRx rx;
     int loop_kmax = 1;                             // largest loopms among the channels' loop states (gnsscorr_loop_set)
     GcDevBuf<gnsscorr_trklog_t> dlooplog;          // [nch][nperiod]
     GcDevBuf<int> dloop_lapped;                    // periods of the last trk_run_loop read after the writer lapped them
@@ -236,3 +245,8 @@ int gc_quiesce(gnsscorr_ctx *ctx, bool ingest = false);
 // the acquisition's forward twiddle tables (made on first use): exp(-2 pi i t/16384), exp(-2 pi i t/32768), t < 16384
 int gc_acq_twiddles(gnsscorr_ctx *ctx, const float2 **tw16k, const float2 **tw32k);
 int gc_ingest_fence(gnsscorr_ctx *ctx);      // orders the compute stream behind the last ring transfer
+// gnsscorr_acq.hip: one search over a channel list; the device hand-over of its acquired channels into the closed loop
+int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chlist, int n);
+int gc_acq_handover(gnsscorr_ctx *ctx, bool quiesce);
+// gnsscorr_api.hip: gnsscorr_trk_run_loop with per-channel write positions
+int gc_trk_run_loop(gnsscorr_ctx *ctx, int nperiod, const uint64_t *wp_ch);

@@ -1,0 +1,118 @@
+// gnsscorr_rx.hip -- the receiver schedule: sdrthread()'s per-channel state machine (ref src/sdrmain.c:247-316) on the
+// batched engine.  A channel searches (sdracquisition(), retried after a pause) until it is acquired, then tracks one
+// code period after the other.  The states live on the host, which needs them to size the launches; the work they
+// select runs on the device: the due channels' search as one list (gnsscorr_acq.hip), the hand-over of the acquired
+// ones into the closed loop (acq_to_loop_kernel), and the closed loop itself, in which a channel that is not tracking
+// is handed a write position of 0 and so plans nothing (trk_step_tail_kernel, ref src/sdrtrk.c:26-30).
+//
+// The reference sleeps ACQSLEEP = 2000 ms of wall time after a failed search (ref src/sdracq.c:57-60).  Here the pause
+// is counted on the sample clock -- retry_ms * 1e-3 * f_sf samples of the channel's ring from the write position of
+// the failed search -- so that the schedule depends on the input alone.
+#include <vector>
+
+#include "gnsscorr_ctx.h"
+
+#define GC_ACQSLEEP 2000        // ms, ref src/sdr.h (ACQSLEEP)
+
+static uint64_t rx_first_try(const GcChan &c) { return (uint64_t)(c.intg + 1) * (uint64_t)c.nsamp; }   // ref src/sdracq.c:24-26
+
+extern "C" int gnsscorr_rx_start(gnsscorr_ctx *ctx, int retry_ms)
+{
+    if (!ctx) return gc_fail(GNSSCORR_EINVAL, "null context");
+    if (!ctx->nch) return gc_fail(GNSSCORR_ESTATE, "rx_start: no channels set");
+    for (int i = 0; i < ctx->nch; i++)
+        if (!ctx->loop_isset[i])
+            return gc_fail(GNSSCORR_ESTATE, "rx_start: channel %d has no loop constants (gnsscorr_loop_set)", i);
+    GcRx &rx = ctx->rx;
+    rx.retry_ms = retry_ms > 0 ? retry_ms : GC_ACQSLEEP;
+    gnsscorr_rxstat_t z;
+    memset(&z, 0, sizeof(z));
+    rx.st.assign(ctx->nch, z);
+    for (int i = 0; i < ctx->nch; i++) {
+        rx.st[i].state = GNSSCORR_CH_SEARCH;
+        rx.st[i].next_try = rx_first_try(ctx->hchan[i]);
+    }
+    rx.on = true;
+    return GNSSCORR_OK;
+}
+
+extern "C" int gnsscorr_rx_set(gnsscorr_ctx *ctx, int ch, int state)
+{
+    if (!ctx || !ctx->rx.on) return gc_fail(GNSSCORR_ESTATE, "rx_set: no gnsscorr_rx_start yet");
+    if (ch < 0 || ch >= ctx->nch) return gc_fail(GNSSCORR_EINVAL, "rx_set: channel %d of %d", ch, ctx->nch);
+    gnsscorr_rxstat_t &s = ctx->rx.st[ch];
+    if (state == GNSSCORR_CH_IDLE) {
+        s.state = GNSSCORR_CH_IDLE;
+    } else if (state == GNSSCORR_CH_SEARCH) {
+        std::lock_guard<std::mutex> lk(ctx->mtx);
+        s.state = GNSSCORR_CH_SEARCH;
+        s.next_try = ctx->ring[ctx->hdesc[ch].ftype - 1].wrpos;
+    } else {
+        return gc_fail(GNSSCORR_EINVAL, "rx_set: state %d (a channel starts tracking through acquisition only)", state);
+    }
+    return GNSSCORR_OK;
+}
+
+extern "C" int gnsscorr_rx_step(gnsscorr_ctx *ctx, int max_periods)
+{
+    if (!ctx || !ctx->rx.on) return gc_fail(GNSSCORR_ESTATE, "rx_step: no gnsscorr_rx_start yet");
+    if (max_periods <= 0) return gc_fail(GNSSCORR_EINVAL, "rx_step: max_periods %d", max_periods);
+    GC_HIP(hipSetDevice(ctx->device));
+    GcRx &rx = ctx->rx;
+    const int nch = ctx->nch;
+    uint64_t wpr[2];
+    {
+        std::lock_guard<std::mutex> lk(ctx->mtx);
+        wpr[0] = ctx->ring[0].wrpos;
+        wpr[1] = ctx->ring[1].wrpos;
+    }
+    // 1. the channels whose search is due, as one list
+    std::vector<int> due;
+    for (int i = 0; i < nch; i++) {
+        const uint64_t wp = wpr[ctx->hdesc[i].ftype - 1];
+        if (rx.st[i].state == GNSSCORR_CH_SEARCH && wp >= rx.st[i].next_try && wp >= rx_first_try(ctx->hchan[i])) due.push_back(i);
+    }
+    if (!due.empty()) {
+        int rc = gc_acq_run_list(ctx, wpr, due.data(), (int)due.size());
+        if (rc) return rc;
+        // the closed loop owns the tracking state; a look-ahead plan of the batched interface would too
+        if (ctx->ahead_valid || ctx->slot[0].fin_pending || ctx->slot[1].fin_pending) { rc = gc_quiesce(ctx); if (rc) return rc; }
+        rc = gc_acq_handover(ctx, false);
+        if (rc) return rc;
+        // 2. the outcome: the schedule needs the acquired flags
+        std::vector<gnsscorr_acqres_t> res(nch);
+        rc = gnsscorr_acq_fetch(ctx, res.data());
+        if (rc) return rc;
+        for (int i : due) {
+            gnsscorr_rxstat_t &s = rx.st[i];
+            const uint64_t wp = wpr[ctx->hdesc[i].ftype - 1];
+            s.attempts++;
+            s.acq = res[i];
+            s.acq_wrpos = wp;
+            if (res[i].flagacq) s.state = GNSSCORR_CH_TRACK;
+            else s.next_try = wp + (uint64_t)((double)rx.retry_ms * 1e-3 * ctx->hdesc[i].f_sf);
+        }
+    }
+    // 3. the closed loop for the tracking channels, those acquired above included
+    std::vector<uint64_t> wp(nch);
+    for (int i = 0; i < nch; i++) wp[i] = rx.st[i].state == GNSSCORR_CH_TRACK ? wpr[ctx->hdesc[i].ftype - 1] : 0;
+    return gc_trk_run_loop(ctx, max_periods, wp.data());
+}
+
+extern "C" int gnsscorr_rx_status(gnsscorr_ctx *ctx, gnsscorr_rxstat_t *st)
+{
+    if (!ctx || !ctx->rx.on) return gc_fail(GNSSCORR_ESTATE, "rx_status: no gnsscorr_rx_start yet");
+    if (!st) return gc_fail(GNSSCORR_EINVAL, "rx_status: null status array");
+    GC_HIP(hipSetDevice(ctx->device));
+    const int nch = ctx->nch;
+    // sdrthread's cnt of every channel: one column of the device's loop states, behind whatever the stream still runs
+    std::vector<uint64_t> cnt(nch);
+    GC_HIP(hipMemcpy2DAsync(cnt.data(), sizeof(uint64_t), (const char *)ctx->dloop.p + offsetof(gnsscorr_loop_t, cnt),
+                            sizeof(gnsscorr_loop_t), sizeof(uint64_t), nch, hipMemcpyDeviceToHost, ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < nch; i++) {
+        st[i] = ctx->rx.st[i];
+        st[i].cnt = cnt[i];
+    }
+    return GNSSCORR_OK;
+}

@@ -289,16 +289,68 @@ typedef struct {
 
 /* wrpos == 0: use each ring's current write position.  Asynchronous. */
 int  gnsscorr_acq_run(gnsscorr_ctx *ctx, uint64_t wrpos);
+/* The same search for the n distinct channels chlist[0..n) only: the per-channel kernels run over that list (their
+ * grids follow n), the shared forward transforms only for the frequency grids that have a listed channel.  A listed
+ * channel's result is bit for bit what gnsscorr_acq_run at the same write position gives it; the other channels'
+ * rows of the result array are zero (flagacq = 0, iters = 0), so gnsscorr_trk_start_from_acq touches none of them.
+ * gnsscorr_acq_run is the list of all channels. */
+int  gnsscorr_acq_run_subset(gnsscorr_ctx *ctx, uint64_t wrpos, const int *chlist, int n);
 int  gnsscorr_acq_fetch(gnsscorr_ctx *ctx, gnsscorr_acqres_t *res);
 /* Device-side hand-over of the last gnsscorr_acq_run to tracking: every acquired
  * channel gets the state sdracquisition() leaves behind (ref src/sdracq.c:51-55:
  * carrfreq = acqfreq, codefreq = crate, remcode = remcarr = 0, buffloc = the
  * returned sample index); channels not acquired keep theirs.  Asynchronous. */
 int  gnsscorr_trk_start_from_acq(gnsscorr_ctx *ctx);
+/* The same hand-over into the closed loop, on the device: every channel the last search listed and acquired gets that
+ * tracking state and the loop state sdrthread() starts tracking with -- acqfreq from the search, every running field
+ * as inittrkstruct() / initnavstruct() leave it (ref src/sdrinit.c:432-480,485-560) with cnt = 0, the constants set by
+ * gnsscorr_loop_set kept (filter coefficients, ne / nl, loopms, rate, prn, f_if ... ctime).  Other channels keep
+ * their tracking and loop state.  Asynchronous. */
+int  gnsscorr_loop_start_from_acq(gnsscorr_ctx *ctx);
 /* The reference's `power` array for one channel: nfreq*nsamp doubles,
  * accumulated over res.iters iterations (re-runs the search for that channel
- * with the iteration count of the last gnsscorr_acq_run). */
+ * with the iteration count of the last gnsscorr_acq_run).  A channel the last
+ * search did not list: GNSSCORR_ESTATE. */
 int  gnsscorr_acq_power(gnsscorr_ctx *ctx, int ch, double *power);
+
+/* ---- receiver schedule: acquire, hand over and track each channel by state ----
+ * sdrthread()'s state machine (ref src/sdrmain.c:247-316) for every channel of the context: a channel calls
+ * sdracquisition() until flagacq, pausing ACQSLEEP after each failure (ref src/sdracq.c:57-60), and from then on tracks
+ * one code period per call.  Opt-in: without gnsscorr_rx_start every other entry point behaves as if this section did
+ * not exist.
+ * The reference's pause is 2000 ms of wall time (sleepms).  Here it is restated on the sample clock: a failed search
+ * at write position wp is retried once the channel's ring has reached wp + retry_ms * 1e-3 * f_sf samples, so the
+ * schedule depends on the input alone, not on how fast it is fed. */
+#define GNSSCORR_CH_IDLE   0   /* parked: never searched, never tracked            */
+#define GNSSCORR_CH_SEARCH 1   /* sdrthread before flagacq                         */
+#define GNSSCORR_CH_TRACK  2   /* sdrthread after flagacq                          */
+typedef struct {
+    int      state, attempts;       /* GNSSCORR_CH_*; searches run so far                          */
+    uint64_t next_try;              /* SEARCH: due once the ring's write position reaches this     */
+    uint64_t acq_wrpos;             /* write position the last search ended at                     */
+    gnsscorr_acqres_t acq;          /* result of the last search (of the acquiring one once TRACK) */
+    uint64_t cnt;                   /* ref sdrthread's cnt: periods tracked since the hand-over    */
+} gnsscorr_rxstat_t;
+
+/* Every channel -> SEARCH, first due at (intg + 1) * nsamp samples, the first moment sdracquisition()'s look-back
+ * fits (ref src/sdracq.c:24-26).  retry_ms <= 0: ACQSLEEP (2000).  Needs the channels set and gnsscorr_loop_set done
+ * for every one of them (the constants the hand-over keeps); otherwise GNSSCORR_ESTATE. */
+int  gnsscorr_rx_start(gnsscorr_ctx *ctx, int retry_ms);
+/* Park a channel (GNSSCORR_CH_IDLE: its tracking and loop state freeze) or re-arm it (GNSSCORR_CH_SEARCH: due at its
+ * ring's current write position).  GNSSCORR_CH_TRACK is reached through acquisition only: GNSSCORR_EINVAL. */
+int  gnsscorr_rx_set(gnsscorr_ctx *ctx, int ch, int state);
+/* One scheduling step at the rings' current write positions wp, ordered on the context's stream:
+ *   1. every SEARCH channel with wp >= next_try is searched, all of them in one gnsscorr_acq_run_subset over the window
+ *      that ends at wp (the reference's buffloc = fendbuffsize*buffcnt - (intg+1)*nsamp);
+ *   2. acquired -> gnsscorr_loop_start_from_acq's hand-over, state TRACK; failed -> next_try = wp + the pause;
+ *   3. gnsscorr_trk_run_loop(max_periods) for the TRACK channels, those acquired in 1 included (they start at the
+ *      returned buffloc and catch up with wp like any other).  IDLE and SEARCH channels plan no period: ndone = 0,
+ *      zero log and II/QQ rows, tracking and loop state untouched.
+ * A step without a due channel synchronises no more than gnsscorr_trk_run_loop; one with due channels reads their
+ * acquired flags back.  gnsscorr_trk_fetch, gnsscorr_trk_fetch_log and gnsscorr_trk_loop_lapped report part 3. */
+int  gnsscorr_rx_step(gnsscorr_ctx *ctx, int max_periods);
+/* st[nch]; synchronises the stream (cnt comes from the device's loop state) */
+int  gnsscorr_rx_status(gnsscorr_ctx *ctx, gnsscorr_rxstat_t *st);
 
 /* ---- op-level device entry points (used by the per-call symbols and tests) --
  * 16384-point complex FFT batches on device memory, unnormalised, sign -1
