@@ -290,6 +290,9 @@ def lib():
     L.gnsscorr_spec_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                       C.c_size_t, C.c_void_p, C.c_size_t]
     L.gnsscorr_debug_poison.argtypes = [C.c_void_p, C.c_int]      # (tests; not part of include/gnsscorr.h)
+    if hasattr(L, "gnsscorr_debug_cmb_stats"):                    # (tests; bound when present, like the symbols below)
+        L.gnsscorr_debug_cmb_stats.argtypes = [C.c_void_p]
+        L.gnsscorr_debug_cmb_stats.restype = None
     # reference-named symbols (bound when present; tests/test_abi.py checks that all are)
     def _sig(name, restype, argtypes):
         try:
@@ -315,6 +318,8 @@ def lib():
     _sig("readinifile_at", _KEEP, [C.POINTER(SdrIni), C.c_char_p])
     _sig("rcvinit_file", _KEEP, [C.POINTER(SdrIni)])
     _sig("file_pushtomembuf", None, [])
+    _sig("file_getbuff", None, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p])
+    _sig("rcvgetbuff", _KEEP, [C.POINTER(SdrIni), C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p])
     _sig("chk_initvalue", _KEEP, [C.POINTER(SdrIni)])
     _sig("cpxpspec", None, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p])
     _sig("cpxfft", None, [C.c_void_p, C.c_void_p, C.c_int])
@@ -343,6 +348,13 @@ def sdrini():
 
 def sdrstat():
     return SdrStat.in_dll(lib(), "sdrstat")
+
+
+def cmb_stats():
+    """(tests) sdrtracking()'s combiner so far: (launch chains, requests served, requests of the largest chain)."""
+    out = (C.c_ulonglong * 3)()
+    lib().gnsscorr_debug_cmb_stats(out)
+    return tuple(out)
 
 
 def gencode(prn, ctype):

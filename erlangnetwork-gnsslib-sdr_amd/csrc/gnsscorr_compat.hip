@@ -185,6 +185,7 @@ struct TrkReq {
     char err[200];
 };
 
+#define GC_CMB_MAXCODES 256
 struct CodeSlot { GcDevBuf<int8_t> dcode; unsigned long sum = ~0ul; int clen = 0, nedge = 0, pm1 = 0; };
 
 struct TrkCombiner {
@@ -193,6 +194,7 @@ struct TrkCombiner {
     std::vector<TrkReq *> queue;
     bool leader = false;
     std::map<sdrch_t *, CodeSlot> codes;
+    std::mutex codes_mtx;           // the table itself: a launch chain holds it from its first group to its last
     // device / pinned staging for `cap` requests.  One pinned block goes down per launch chain (the requests' GcChan
     // and GcTrkPlan records, side by side); the results come back without a copy: trk_finish writes the sums into
     // pinned host memory (hres), and the piece-table overflow counter lives there too (hover).
@@ -226,6 +228,8 @@ struct CmbProf {
     }
 };
 CmbProf g_cprof;
+// launch chains so far, requests they served, requests of the largest one (gnsscorr_debug_cmb_stats; under ctx->mtx)
+unsigned long long g_cmb_stats[3] = {0, 0, 0};
 
 int cmb_reserve(gnsscorr_ctx *ctx, int k, int nseg)
 {
@@ -255,11 +259,8 @@ int cmb_reserve(gnsscorr_ctx *ctx, int k, int nseg)
 // the channel's code block on the device (uploaded when the code of this sdrch_t is first seen or changes)
 int cmb_code(gnsscorr_ctx *ctx, sdrch_t *sdr, unsigned long sum, CodeSlot **out)
 {
-    // (keyed by the caller's sdrch_t: a receiver has at most MAXSAT of them; a caller that keeps handing in new structs
-    // gets the table emptied instead of growing without bound -- the stream is idle here, every call ends synchronised)
-    if (g_cmb.codes.size() > 256 && !g_cmb.codes.count(sdr)) {
-        g_cmb.codes.clear();
-    }
+    // (keyed by the caller's sdrch_t; cmb_run bounds the table between batches, never while a group holds pointers
+    // into it)
     CodeSlot &cs = g_cmb.codes[sdr];
     if (!cs.dcode || cs.sum != sum || cs.clen != sdr->clen) {
         GC_RESERVE(ctx, cs.dcode, GC_CODEBLOCK);
@@ -334,6 +335,8 @@ int cmb_run_group(gnsscorr_ctx *ctx, std::vector<TrkReq *> &grp)
         memcpy(grp[i]->cI, q.hres + (size_t)i * ntap, sizeof(double) * ntap);
         memcpy(grp[i]->cQ, q.hres + (size_t)(q.cap + i) * ntap, sizeof(double) * ntap);
     }
+    g_cmb_stats[0]++; g_cmb_stats[1] += (unsigned long long)k;
+    if ((unsigned long long)k > g_cmb_stats[2]) g_cmb_stats[2] = (unsigned long long)k;
     if (g_cprof.on) {
         const double tp4 = CmbProf::now();
         g_cprof.batches++; g_cprof.reqs += (unsigned long long)k;
@@ -354,6 +357,13 @@ void cmb_run(std::vector<TrkReq *> &batch)
     std::lock_guard<std::mutex> lk(ctx->mtx);
     if (hipSetDevice(ctx->device) != hipSuccess) { fail_all(batch, "hipSetDevice"); return; }
     if (gc_ingest_fence(ctx)) { fail_all(batch, gnsscorr_last_error()); return; }      // behind the grabber's last block
+    // A receiver has at most MAXSAT channel structs; a caller that keeps handing in new ones gets the code table
+    // emptied instead of growing without bound.  Here and only here: no group of this batch has taken a block's address
+    // yet, and the stream is idle (every launch chain ends synchronised).
+    // So the table holds at most GC_CMB_MAXCODES entries plus one batch's new ones; a caller with more live structs
+    // than that has every block uploaded again after each clear.  Correct, and slow only for such a caller.
+    std::lock_guard<std::mutex> lkc(g_cmb.codes_mtx);
+    if (g_cmb.codes.size() > GC_CMB_MAXCODES) g_cmb.codes.clear();
     // groups of equal dtype and tap count (one [TRACK] section per receiver: normally a single group)
     std::vector<bool> taken(batch.size(), false);
     for (size_t i = 0; i < batch.size(); i++) {
@@ -401,6 +411,27 @@ void cmb_submit(TrkReq *req)
 }
 
 }  // namespace
+
+// (tests; not part of include/gnsscorr.h) how far sdrtracking()'s callers were combined: launch chains, requests, the
+// largest chain's requests
+extern "C" void gnsscorr_debug_cmb_stats(unsigned long long out[3])
+{
+    gnsscorr_ctx *ctx = gnsscorr_default_ctx();
+    if (!ctx) { out[0] = out[1] = out[2] = 0; return; }
+    std::lock_guard<std::mutex> lk(ctx->mtx);
+    memcpy(out, g_cmb_stats, sizeof(g_cmb_stats));
+}
+
+// freesdrch(): the struct's code block goes with it (not during a launch chain: codes_mtx)
+extern "C" void gc_compat_forget_codes(sdrch_t *sdr)
+{
+    std::lock_guard<std::mutex> lk(g_cmb.codes_mtx);
+    auto it = g_cmb.codes.find(sdr);
+    if (it == g_cmb.codes.end()) return;
+    gnsscorr_ctx *ctx = gnsscorr_default_ctx();         // (exists: it allocated the block)
+    if (ctx) hipSetDevice(ctx->device);
+    g_cmb.codes.erase(it);
+}
 
 extern "C" {
 

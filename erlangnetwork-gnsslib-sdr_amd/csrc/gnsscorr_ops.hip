@@ -186,6 +186,9 @@ __global__ __launch_bounds__(1024) void vstat_kernel(const double *__restrict__ 
             if (smax[w] > mx || (smax[w] == mx && sidx[w] < mi)) { mx = smax[w]; mi = sidx[w]; }
             sum += ssum[w]; cnt += scnt[w];
         }
+        // a NaN in element 0 is the seed no comparison replaces (max < data[i] is false): it comes back, index 0.
+        // NaNs elsewhere lose every comparison above, as in the reference
+        if (d[0] != d[0]) { mx = d[0]; mi = 0; }
         out[0] = mx; out[1] = sum; out[2] = (double)cnt; iout[0] = mi;
     }
 }
@@ -495,35 +498,102 @@ int checkacquisition(double *P, sdrch_t *sdr)
 // context and keeps the channel's replica spectrum and work buffers resident
 // between attempts (a failed acquisition is retried every ACQSLEEP ms forever,
 // ref src/sdracq.c:57-59).
-static std::map<sdrch_t *, gnsscorr_ctx *> g_acqctx;
+//
+// The struct's address alone does not name a channel: the reference keeps its channels in one global array and runs
+// initsdrch() on it again at every receiver start, and rcvinit re-creates the rings.  The engine therefore remembers
+// what it was built from -- the channel's constants, code and Doppler grid, and the ring memory it borrows -- and is
+// destroyed and rebuilt when any of that no longer matches.
+// (gc_compat_forget, gc_compat_forget_codes and gnsscorr_debug_cmb_stats are exported but internal: no header names them.)
+//
+// The channel as gnsscorr_set_channels() wants it, stated once: the scalars in a zeroed gnsscorr_chan_t (so that two of
+// them compare with memcmp, padding included) whose three pointers are null, and copies of what they point to.
+struct AcqDesc {
+    gnsscorr_chan_t d;
+    std::vector<short> code;
+    std::vector<double> freq;
+    std::vector<int> corrp;         // (acquisition does not read the taps; they are part of what set_channels is given)
+    explicit AcqDesc(const sdrch_t *s)
+    {
+        memset(&d, 0, sizeof(d));
+        d.prn = s->prn; d.ctype = s->ctype; d.dtype = s->dtype; d.ftype = s->ftype;
+        d.clen = s->clen; d.nsamp = s->nsamp; d.nsampchip = s->nsampchip;
+        d.f_sf = s->f_sf; d.f_if = s->f_if; d.foffset = s->foffset;
+        d.crate = s->crate; d.ctime = s->ctime; d.ti = s->ti;
+        d.intg = s->acq.intg; d.nfreq = s->acq.nfreq; d.nfft = s->acq.nfft; d.corrn = s->trk.corrn;
+        if (s->code && s->clen > 0) code.assign(s->code, s->code + s->clen);
+        if (s->acq.freq && s->acq.nfreq > 0) freq.assign(s->acq.freq, s->acq.freq + s->acq.nfreq);
+        if (s->trk.corrp && s->trk.corrn > 0) corrp.assign(s->trk.corrp, s->trk.corrp + s->trk.corrn);
+    }
+    bool operator==(const AcqDesc &o) const
+    {
+        return !memcmp(&d, &o.d, sizeof(d)) && code == o.code && freq == o.freq && corrp == o.corrp;
+    }
+    gnsscorr_chan_t filled() const      // with the pointers set to this object's copies
+    {
+        gnsscorr_chan_t f = d;
+        f.code = code.data();
+        f.freq = freq.data();
+        f.corrp = corrp.data();
+        return f;
+    }
+};
+// The ring's identity is (device pointer, length): the engine holds nothing else of it -- no write position (every
+// gnsscorr_acq_run is given one), no copy of samples.  A ring that a second rcvinit frees and gets back at the same
+// address with the same length therefore needs no new engine; any other address or length does.
+struct AcqSlot {
+    gnsscorr_ctx *eng;
+    AcqDesc desc;
+    const int8_t *ringmem;
+    uint64_t ringlen;
+};
+static std::map<sdrch_t *, AcqSlot> g_acqctx;
 static std::mutex g_acqctx_mtx;
 
 static gnsscorr_ctx *acq_engine(sdrch_t *sdr, gnsscorr_ctx *def)
 {
     std::lock_guard<std::mutex> lk(g_acqctx_mtx);
-    auto it = g_acqctx.find(sdr);
-    if (it != g_acqctx.end()) return it->second;
     const GcRing &r = def->ring[sdr->ftype == FTYPE2 ? 1 : 0];
-    if (!r.mem || r.dtype != sdr->dtype) {
+    const bool ring_ok = r.mem && r.dtype == sdr->dtype;
+    AcqDesc desc(sdr);
+    auto it = g_acqctx.find(sdr);
+    if (it != g_acqctx.end()) {
+        const AcqSlot &s = it->second;
+        if (ring_ok && s.ringmem == r.mem && s.ringlen == r.ringlen && s.desc == desc) return s.eng;
+        gnsscorr_destroy(s.eng);                    // (a borrowed ring is not the engine's to free)
+        g_acqctx.erase(it);
+    }
+    if (!ring_ok) {
         gc_fail(GNSSCORR_ESTATE, "IF ring %d is not mirrored on the GPU", sdr->ftype);
+        return nullptr;
+    }
+    if (desc.code.empty() || desc.freq.empty()) {
+        gc_fail(GNSSCORR_EINVAL, "sdracquisition: the channel struct is not initialised");
         return nullptr;
     }
     gnsscorr_ctx *c = nullptr;
     if (gnsscorr_create(&c, def->device, nullptr)) return nullptr;
-    gnsscorr_chan_t d;
-    memset(&d, 0, sizeof(d));
-    d.prn = sdr->prn; d.ctype = sdr->ctype; d.dtype = sdr->dtype; d.ftype = sdr->ftype;
-    d.clen = sdr->clen; d.nsamp = sdr->nsamp; d.nsampchip = sdr->nsampchip;
-    d.f_sf = sdr->f_sf; d.f_if = sdr->f_if; d.foffset = sdr->foffset;
-    d.crate = sdr->crate; d.ctime = sdr->ctime; d.ti = sdr->ti;
-    d.code = sdr->code; d.intg = sdr->acq.intg; d.nfreq = sdr->acq.nfreq; d.freq = sdr->acq.freq;
-    d.nfft = sdr->acq.nfft; d.corrn = sdr->trk.corrn; d.corrp = sdr->trk.corrp;
+    const gnsscorr_chan_t d = desc.filled();
     if (gnsscorr_ring_create(c, sdr->ftype, sdr->dtype, r.ringlen, r.mem) || gnsscorr_set_channels(c, 1, &d)) {
         gnsscorr_destroy(c);
         return nullptr;
     }
-    g_acqctx[sdr] = c;
+    g_acqctx.emplace(sdr, AcqSlot{c, std::move(desc), r.mem, r.ringlen});
     return c;
+}
+
+// freesdrch(): the struct's private engine goes with it (the combiner's code block: gnsscorr_compat.hip)
+void gc_compat_forget_codes(sdrch_t *sdr);
+extern "C" void gc_compat_forget(sdrch_t *sdr)
+{
+    {
+        std::lock_guard<std::mutex> lk(g_acqctx_mtx);
+        auto it = g_acqctx.find(sdr);
+        if (it != g_acqctx.end()) {
+            gnsscorr_destroy(it->second.eng);
+            g_acqctx.erase(it);
+        }
+    }
+    gc_compat_forget_codes(sdr);
 }
 
 // ref src/sdracq.c:14-62

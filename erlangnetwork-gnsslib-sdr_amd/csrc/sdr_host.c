@@ -443,9 +443,12 @@ int initsdrch(int chno, int sys, int prn, int ctype, int dtype, int ftype, doubl
     return 0;
 }
 
-/* ref src/sdrinit.c:663-686 */
+/* ref src/sdrinit.c:663-686; what the per-call symbols keep on the device for this struct (its private acquisition
+ * engine, its code block) is dropped too: the address may come back as another channel */
+void gc_compat_forget(sdrch_t *sdr);
 void freesdrch(sdrch_t *sdr)
 {
+    gc_compat_forget(sdr);
     free(sdr->code);
     free(sdr->trk.II); free(sdr->trk.QQ); free(sdr->trk.oldI); free(sdr->trk.oldQ);
     free(sdr->trk.sumI); free(sdr->trk.sumQ); free(sdr->trk.oldsumI); free(sdr->trk.oldsumQ);

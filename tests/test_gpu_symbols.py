@@ -352,3 +352,286 @@ def test_sdrtracking_call_rate_from_32_pthreads(gc, orc, synth, tmp_path):
             O.orc_clearcumsumcorr(C.byref(o))
             b += o.currnsamp
         assert got[i] == [acc, o.carrfreq, o.codefreq], (i, got[i], acc, o.carrfreq, o.codefreq)
+
+
+# ---- the op-level symbols at the shapes the front ends produce, and at their edges ---------------------------------
+DPI = 2.0 * 3.1415926535897932
+
+
+from test_nco_host import nco          # noqa: E402,F401  (csrc/gnsscorr_nco.h on the host, for piece counts)
+
+
+def _carrier_pieces(nco, phi0, freq, n):
+    idx, prem = np.zeros(n, np.int32), C.c_double()
+    return nco.nco_carrier(phi0, freq, TI, n, 256, idx.ctypes.data, C.byref(prem))
+
+
+def _code_pieces(nco, length, coff, smax, ci, n):
+    chip, rem = np.zeros(n + 2 * smax, np.int32), C.c_double()
+    return nco.nco_code(length, coff, smax, ci, n, 256, chip.ctypes.data, C.byref(rem))
+
+
+MIXCARR_EDGES = (
+    [(2, n, 1234.5, 0.4, None) for n in (1, 2, 255, 256, 257, 65537)] +
+    [(1, n, 4.092e6 + 1700.0, 1.9, None) for n in (1, 257, 65537)] +
+    [(1, 16369, 0.0, 1.3, None), (2, 16369, 0.0, 0.0, None),                  # the step is zero
+     (1, 16369, -4.092e6 + 300.0, 0.2, None),                                 # negative frequency on real samples
+     (2, 16369, 2200.0, 0.0, -128), (1, 16369, 4.0932e6, 0.7, -128)] +        # full-scale samples
+    # a start phase on a LUT boundary (index 5 | 6 of 32) and one ulp to either side of it
+    [(2, 4099, 700.0, p, None) for p in (6 * DPI / 32, np.nextafter(6 * DPI / 32, 0.0), np.nextafter(6 * DPI / 32, 9.0))] +
+    [(1, 4099, -700.0, p, None) for p in (6 * DPI / 32, np.nextafter(6 * DPI / 32, 0.0), np.nextafter(6 * DPI / 32, 9.0))])
+
+
+@pytest.mark.parametrize("dtype,n,freq,phi0,fill", MIXCARR_EDGES)
+def test_mixcarr_edges(gc, orc, dtype, n, freq, phi0, fill):
+    L, O = gc.lib(), orc.lib()
+    rng = np.random.default_rng(n)
+    data = rng.integers(-128, 128, size=n * dtype, dtype=np.int8) if fill is None else np.full(n * dtype, fill, np.int8)
+    I, Q, oI, oQ = (np.full(n, 77, np.int16) for _ in range(4))
+    r = L.mixcarr(data.ctypes.data, dtype, TI, n, freq, float(phi0), I.ctypes.data, Q.ctypes.data)
+    ro = O.orc_mixcarr_seq(data.ctypes.data, dtype, TI, n, freq, float(phi0), oI.ctypes.data, oQ.ctypes.data)
+    assert np.array_equal(I, oI) and np.array_equal(Q, oQ) and r == ro
+
+
+def test_mixcarr_more_binades_than_a_code_period(gc, orc, nco):      # noqa: F811
+    """2 000 000 samples at 4.1 MHz from phase 0: the running phase crosses seven binades more than in a 1-ms call, each
+    a piece of its own in the carrier table.  No mixcarr() call was found that overflows GC_OPSEG = 256 pieces, so the
+    overflow path is tested through rescode() below.  That rests on an argument, not on a measurement: a piece ends
+    where the phase changes binade (about three per binade, plus the one literal step a rounding tie can force),
+    phases below 1 and from 2^31 on share one all-zero piece, so 31 binades on either side of zero bound the count
+    near 190.  The sweep below (36 phase / frequency pairs, 300 000 samples) only shows that ordinary calls stay
+    under 80.  op_tables()' error text still names "carrier binades per call" for the callers that share it."""
+    L, O = gc.lib(), orc.lib()
+    n, freq = 2000000, 4.1e6
+    common, here = _carrier_pieces(nco, 0.0, freq, 16368), _carrier_pieces(nco, 0.0, freq, n)
+    assert 0 < common < here <= 256, (common, here)
+    worst = max(_carrier_pieces(nco, p, f, 300000) for p in (0.0, -12345.678, 2.0e5, -3.0e6, 1e-9, -1e-9)
+                for f in (4.1e6, -4.1e6, 8.0e6, 137.77, 0.001, 8.184e6 / 3))
+    assert 0 < worst < 80, worst
+    data = np.random.default_rng(3).integers(-128, 128, size=n, dtype=np.int8)
+    I, Q, oI, oQ = (np.zeros(n, np.int16) for _ in range(4))
+    r = L.mixcarr(data.ctypes.data, 1, TI, n, freq, 0.0, I.ctypes.data, Q.ctypes.data)
+    ro = O.orc_mixcarr_seq(data.ctypes.data, 1, TI, n, freq, 0.0, oI.ctypes.data, oQ.ctypes.data)
+    assert np.array_equal(I, oI) and np.array_equal(Q, oQ) and r == ro
+
+
+RESCODE_EDGES = [
+    # ctype, coff, smax, chip-rate offset, n
+    (20, 100.25, 6, 0.0, 16368), (20, 510.9999999, 3, 1.1, 16368), (20, 0.0, 0, -0.7, 32736),        # len 511
+    (1, 7.5, 0, 0.3, 16368), (1, 7.5, 64, 0.3, 16368), (20, 7.5, 64, 0.3, 16368),                    # smax 0 and 64
+    (1, -3.7, 6, 0.0, 16368), (1, -2049.2, 6, 1.0, 4000), (20, -0.25, 64, 0.0, 100),                 # coff negative
+    (1, 2 * 1023 + 17.3, 6, 0.0, 16368), (20, 5 * 511 + 0.5, 3, 2.0, 16368),                         # beyond 2 len
+    (1, 1023 - 1e-9, 6, 0.0, 16368), (1, 1023 - 1e-9, 0, 0.0, 5), (20, 511 - 1e-9, 0, 0.0, 3),       # the lazy wrap
+    (1, 0.0, 0, 0.0, 1), (1, 1022.99, 0, 0.0, 1), (20, 510.99, 0, 0.0, 1)]                           # n + 2 smax = 1
+
+
+@pytest.mark.parametrize("ctype,coff,smax,dc,n", RESCODE_EDGES)
+def test_rescode_edges(gc, orc, ctype, coff, smax, dc, n):
+    L, O = gc.lib(), orc.lib()
+    code, crate = orc.gencode(3, ctype)
+    a, b = np.full(n + 2 * smax, 77, np.int16), np.full(n + 2 * smax, 78, np.int16)
+    ci = TI * (crate + dc)
+    r = L.rescode(code.ctypes.data, len(code), coff, smax, ci, n, a.ctypes.data)
+    ro = O.orc_rescode_seq(code.ctypes.data, len(code), coff, smax, ci, n, b.ctypes.data)
+    assert np.array_equal(a, b) and r == ro
+
+
+def _printed(capfd):
+    """What the library's printf has written since the last call (its stdio buffer flushed first)."""
+    C.CDLL(None).fflush(None)
+    return capfd.readouterr().out
+
+
+def test_rescode_refused_steps_and_table_overflow(gc, orc, nco, capfd):      # noqa: F811
+    """Chip steps outside (0, len) and a call that spans more code periods than GC_OPSEG pieces hold print an error and
+    leave rcode untouched; the longest call that fits equals the oracle.  The sizes come from the NCO header on the
+    host (one piece per code period at this step)."""
+    L, O = gc.lib(), orc.lib()
+    code, _ = orc.gencode(3, 20)
+    for ci in (0.0, -0.03, 511.0, 600.5):
+        a = np.full(1000, 77, np.int16)
+        _printed(capfd)
+        L.rescode(code.ctypes.data, 511, 1.5, 0, ci, 1000, a.ctypes.data)
+        assert np.all(a == 77), ci
+        assert "error: rescode: chip step" in _printed(capfd), ci
+    ci, lo, hi = 0.5, 1000, 400000
+    assert _code_pieces(nco, 511, 0.0, 0, ci, lo) > 0 and _code_pieces(nco, 511, 0.0, 0, ci, hi) == -1
+    while hi - lo > 1:                  # smallest n that overflows
+        mid = (lo + hi) // 2
+        lo, hi = (lo, mid) if _code_pieces(nco, 511, 0.0, 0, ci, mid) == -1 else (mid, hi)
+    assert 0 < _code_pieces(nco, 511, 0.0, 0, ci, lo) <= 256, lo
+    a, b = np.full(hi, 77, np.int16), np.zeros(hi, np.int16)
+    _printed(capfd)
+    L.rescode(code.ctypes.data, 511, 0.0, 0, ci, hi, a.ctypes.data)
+    assert np.all(a == 77)
+    assert "error: rescode: the call needs more than 256 NCO pieces" in _printed(capfd)
+    r = L.rescode(code.ctypes.data, 511, 0.0, 0, ci, lo, a.ctypes.data)
+    assert "error" not in _printed(capfd)
+    ro = O.orc_rescode_seq(code.ctypes.data, 511, 0.0, 0, ci, lo, b.ctypes.data)
+    assert np.array_equal(a[:lo], b[:lo]) and a[lo] == 77 and r == ro
+
+
+@pytest.mark.parametrize("n", [1, 2, 255, 257, 1025, 16366, 52000])
+def test_cpxfft_cpxpspec_edge_lengths(gc, orc, n):
+    """One and two points, one lane short of / past a 256-lane workgroup, one past DFT_TILE, GN3S v2's 2 * 8183 (prime
+    factor 167) and the 26 Msps IQ front end's 52 000: the bars of test_cpxfft_cpxpspec_any_length."""
+    test_cpxfft_cpxpspec_any_length(gc, orc, n)
+
+
+# (f_sf, f_if, dtype, n, m): RTL-SDR, GN3S v2, real samples at a 4 MHz IF (the longest carrier walk), 26 Msps IQ
+PCORR_SHAPES = {"rtlsdr_2048": (2.048e6, 0.0, 2, 2048, 4096), "gn3sv2_8183": (8.1838e6, 38.4e3, 1, 8183, 16366),
+                "real_if4M_20000": (20e6, 4.0e6, 1, 20000, 40000), "iq_26000": (26e6, 0.0, 2, 26000, 52000),
+                "gn3sv2_8183_iq": (8.1838e6, 0.0, 2, 8183, 16366)}
+
+
+@pytest.mark.parametrize("shape", list(PCORR_SHAPES))
+def test_pcorrelator_front_end_shapes(gc, orc, shape):
+    """pcorrelator() at m = 2 * nsamp of each front end, the grid's outer bins (negative frequencies at zero IF) and one
+    inner bin, P preloaded (it accumulates).  dft_direct_kernel sums in fp64: what remains is the float rounding of
+    its outputs, so the bar is the reference length's."""
+    L, O = gc.lib(), orc.lib()
+    f_sf, f_if, dtype, n, m = PCORR_SHAPES[shape]
+    o = orc.make_chan(6, dtype=dtype, f_sf=f_sf, f_if=f_if)
+    assert (o.nsamp, o.nfft) == (n, m)
+    xc = orc.codespectrum(o)
+    data = np.random.default_rng(n).integers(-60, 61, size=2 * n * dtype, dtype=np.int8)
+    freq = np.array([f_if - 7000.0, f_if + 200.0, f_if + 7000.0])
+    P = np.full(3 * n, 0.25)
+    P[::7] = 3.0
+    Po = P.copy()
+    L.pcorrelator(data.ctypes.data, dtype, o.ti, n, freq.ctypes.data, 3, o.crate, m, xc.ctypes.data, P.ctypes.data)
+    O.orc_pcorrelator(data.ctypes.data, dtype, o.ti, n, freq.ctypes.data, 3, o.crate, m, xc.ctypes.data, Po.ctypes.data)
+    print(f"\n{shape}: n {n} m {m} rel err {rel_err(P, Po):.3g}")
+    assert rel_err(P, Po) < 1e-4
+
+
+@pytest.mark.parametrize("m,n,flagsum", [(32736, 16368, 1), (4096, 1000, 1), (4096, 1000, 0), (16366, 5000, 1), (52000, 1, 1),
+                                         (40000, 20000, 1)])
+def test_cpxconv_flagsum_and_short_outputs(gc, orc, m, n, flagsum):
+    """cpxconv() accumulating into conv (flagsum 1) and with n < m/2 outputs; elements past n stay as they were."""
+    L, O = gc.lib(), orc.lib()
+    rng = np.random.default_rng(m + n)
+    a = (rng.standard_normal(m) + 1j * rng.standard_normal(m)).astype(np.complex64)
+    b = (rng.standard_normal(m) + 1j * rng.standard_normal(m)).astype(np.complex64)
+    a2 = a.copy()
+    conv = rng.uniform(0.5, 2.0, n + 3) * 1e-3
+    convo = conv.copy()
+    L.cpxconv(None, None, a.ctypes.data, b.ctypes.data, m, n, flagsum, conv.ctypes.data)
+    O.orc_cpxconv(a2.ctypes.data, b.ctypes.data, m, n, flagsum, convo.ctypes.data)
+    assert rel_err(conv[:n], convo[:n]) < 1e-4
+    assert np.array_equal(conv[n:], convo[n:])
+    assert np.abs(a - a2).max() / np.abs(a2).max() < 1e-5
+
+
+def _same(a, b):
+    return (np.isnan(a) and np.isnan(b)) or a == b
+
+
+VSTAT_WINDOWS = lambda n: [(-1, -1), (n, n + 4), (0, 0), (n - 3, 2), (2, n - 3), (1, 0), (1, n - 1), (0, n - 1), (n - 1, n - 1),  # noqa: E731
+                           (n - 1, 0), (3, 1)]
+
+
+@pytest.mark.parametrize("n", [1, 2, 64, 1024, 1025, 16368])
+@pytest.mark.parametrize("kind", ["random", "max_last", "equal_maxima", "nan_first", "nan_elsewhere", "all_equal"])
+def test_maxvd_meanvd_edges(gc, orc, n, kind):
+    """maxvd() / meanvd() against the reference's loops: exclusion windows that are empty, wrap, or cover everything
+    but element 0 (which always seeds the maximum); the maximum in the last element; equal maxima (lowest index); a
+    NaN in element 0 (returned, index 0) and elsewhere (never wins)."""
+    L, O = gc.lib(), orc.lib()
+    d = np.random.default_rng(n).uniform(0, 1, n)
+    if kind == "max_last":
+        d[n - 1] = 2.0
+    elif kind == "equal_maxima":
+        d[[n // 3, n // 2, n - 1]] = 1.5
+    elif kind == "nan_first":
+        d[0] = np.nan
+    elif kind == "nan_elsewhere":
+        d[[n // 2, n - 1]] = np.nan
+        if n > 1:
+            d[0] = 0.5
+    elif kind == "all_equal":
+        d[:] = 0.75
+    for exs, exe in VSTAT_WINDOWS(n):
+        i1, i2 = C.c_int(-5), C.c_int(-5)
+        got, want = L.maxvd(d.ctypes.data, n, exs, exe, C.byref(i1)), O.orc_maxvd(d.ctypes.data, n, exs, exe, C.byref(i2))
+        assert _same(got, want) and i1.value == i2.value, (exs, exe, got, want, i1.value, i2.value)
+        with np.errstate(all="ignore"):
+            got, want = L.meanvd(d.ctypes.data, n, exs, exe), O.orc_meanvd(d.ctypes.data, n, exs, exe)
+        assert (np.isnan(got) and np.isnan(want)) or got == pytest.approx(want, rel=1e-12), (exs, exe, got, want)
+
+
+@pytest.mark.parametrize("f_sf,nsampchip", [(2.048e6, 2), (8.1838e6, 7), (16.368e6, 16)])
+@pytest.mark.parametrize("where", ["low", "high", "first", "last", "nan_first", "nan_elsewhere"])
+def test_checkacquisition_window_edges(gc, orc, f_sf, nsampchip, where):
+    """The peak at codei < 2 * nsampchip and at codei >= n - 2 * nsampchip (the exclusion window wraps), in the first
+    and in the last element; a NaN in element 0 of P (not acquired, indices 0, NaN ratios -- not an index out of the
+    array) and elsewhere (ignored)."""
+    L, O = gc.lib(), orc.lib()
+    ini = gc.sdrini()
+    ini.trkcorrn, ini.trkcorrd, ini.trkcorrp = 2, 3, 3
+    sdr = gc.SdrCh()
+    assert L.initsdrch(1, gc.SYS_GPS, 5, gc.CTYPE_L1CA, 2, 1, 1575.42e6, f_sf, 0.0, C.byref(sdr)) == 0
+    n, nf = sdr.nsamp, sdr.acq.nfreq
+    assert sdr.nsampchip == nsampchip
+    P = np.random.default_rng(n).uniform(0.5, 1.0, nf * n)
+    row = 40 if where != "last" else nf - 1
+    codei = {"low": nsampchip, "high": n - nsampchip - 1, "first": 0, "last": n - 1}.get(where, n // 2)
+    P[row * n + codei] = 30.0
+    P[row * n + (codei + n // 3) % n] = 6.0                                # the runner-up, outside the window
+    P[row * n + (codei + 2 * nsampchip) % n] = 20.0                        # the window's last element: not the runner-up
+    P[row * n + (codei - 2 * nsampchip) % n] = 20.0
+    if where == "nan_first":
+        P[0] = np.nan
+    if where == "nan_elsewhere":
+        P[[5, row * n + 7, nf * n - 1]] = np.nan
+    got = L.checkacquisition(P.ctypes.data, C.byref(sdr))
+    res = orc.AcqRes()
+    freq = np.ctypeslib.as_array(sdr.acq.freq, shape=(nf,)).copy()
+    with np.errstate(all="ignore"):
+        want = O.orc_checkacquisition(P.ctypes.data, n, nf, nsampchip, sdr.ctime, freq.ctypes.data, C.byref(res))
+    assert got == want
+    assert (sdr.acq.acqcodei, sdr.acq.freqi, sdr.acq.acqfreq) == (res.acqcodei, res.freqi, res.acqfreq)
+    if where == "nan_first":
+        assert got == 0 and (res.acqcodei, res.freqi) == (0, 0) and np.isnan(sdr.acq.peakr) and np.isnan(res.peakr)
+        assert np.isnan(sdr.acq.cn0) and np.isnan(res.cn0)
+    elif where == "nan_elsewhere" or where in ("low", "high", "last"):
+        if where == "nan_elsewhere":
+            assert np.isnan(res.cn0) and np.isnan(sdr.acq.cn0)          # (the row's mean holds a NaN)
+        else:
+            assert sdr.acq.cn0 == pytest.approx(res.cn0, rel=1e-12)
+        assert got == 1 and res.acqcodei == codei and sdr.acq.peakr == pytest.approx(res.peakr, rel=1e-12)
+    else:
+        # the peak in element 0 seeds the runner-up search too: ratio 1, not acquired
+        assert got == 0 and sdr.acq.peakr == res.peakr == 1.0 and sdr.acq.cn0 == pytest.approx(res.cn0, rel=1e-12)
+    L.freesdrch(C.byref(sdr))
+
+
+def test_correlator_direct_symbol_edges(gc, orc):
+    """correlator() itself: one sample, one short of and one past a 1024-sample round, one and sixteen tap pairs, a
+    511-chip code, and the sample type switched between successive calls (the scratch ring's length in samples is
+    derived from a byte buffer that only grows)."""
+    L = gc.lib()
+    rng = np.random.default_rng(9)
+    ca, g1 = orc.gencode(4, 1), orc.gencode(0, 20)
+    calls = [(2, 16368, ca, [3]), (1, 20000, ca, [3, 6]), (2, 1, ca, [1]), (1, 1, g1, [2]), (1, 1023, ca, [3]),
+             (2, 1025, g1, [3]), (1, 1025, ca, list(range(2, 34, 2))), (2, 1023, g1, list(range(1, 17))),
+             (1, 20000, ca, [8, 16]), (2, 16368, g1, [4, 8, 12]), (1, 16368, g1, [4]), (2, 2047, ca, [3])]
+    for k, (dtype, n, (code, crate), s) in enumerate(calls):
+        data = rng.integers(-128, 128, size=n * dtype, dtype=np.int8)
+        freq, phi0, coff = 1000.0 + 333.3 * k, 0.1 * k, 17.25 * k
+        sp = np.array(s, np.int32)
+        nt = 1 + 2 * len(s)
+        II, QQ = np.zeros(nt), np.zeros(nt)
+        remc, remp = C.c_double(), C.c_double()
+        L.correlator(data.ctypes.data, dtype, TI, n, freq, phi0, crate + 0.5, coff, sp.ctypes.data, len(s), II.ctypes.data,
+                     QQ.ctypes.data, C.byref(remc), C.byref(remp), code.ctypes.data, len(code))
+        oI, oQ, oc, op = orc.correlator(data, dtype, TI, n, freq, phi0, crate + 0.5, coff, s, code)
+        assert np.array_equal(II, oI) and np.array_equal(QQ, oQ), (k, dtype, n, II, oI)
+        assert (remc.value, remp.value) == (oc, op), k
+    # a call over more code periods than the tracking tables hold is refused: an error, the outputs as they were
+    data = rng.integers(-128, 128, size=40000, dtype=np.int8)
+    II, QQ = np.full(3, 7.5), np.full(3, -7.5)
+    sp = np.array([3], np.int32)
+    L.correlator(data.ctypes.data, 1, TI, 40000, 1000.0, 0.0, ca[1], 0.0, sp.ctypes.data, 1, II.ctypes.data, QQ.ctypes.data,
+                 C.byref(remc), C.byref(remp), ca[0].ctypes.data, 1023)
+    assert np.all(II == 7.5) and np.all(QQ == -7.5)
