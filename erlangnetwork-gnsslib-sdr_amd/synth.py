@@ -11,7 +11,8 @@ def make_if(codes, nsamp, f_sf=16.368e6, f_if=0.0, dtype=2, sats=None, seed=SEED
             f_cf=1575.42e6, chunk=1 << 22):
     """codes: {prn: (chips int array, chip rate)}.  sats: list of dicts
     (prn, doppler Hz, code phase chips, cn0 dB-Hz, carrier phase rad; optional t_on, seconds: the satellite
-    contributes nothing before it, and its code and carrier phase run from t = 0 as if it had always been there).
+    contributes nothing before it, and its code and carrier phase run from t = 0 as if it had always been there;
+    optional t_off, seconds: nothing from it on).
     Returns int8 array of shape (nsamp, 2) for dtype 2 or (nsamp,) for dtype 1."""
     rng = np.random.default_rng(seed)
     if sats is None:
@@ -38,6 +39,8 @@ def make_if(codes, nsamp, f_sf=16.368e6, f_if=0.0, dtype=2, sats=None, seed=SEED
                 c = c * bit[((t * 50.0).astype(np.int64)) % len(bit)]
             if s.get("t_on") is not None:
                 c = c * (t >= s["t_on"])
+            if s.get("t_off") is not None:
+                c = c * (t < s["t_off"])
             ph = 2 * np.pi * (f_if + fd) * t + s.get("phase", 0.0)
             if dtype == 2:
                 # the reference's mixer multiplies the samples by exp(+i phi) (ref
