@@ -120,6 +120,17 @@ def frame_replay(state, log_rows, cnt0=0):
         raise RuntimeError("gnsscorr_frame_replay: error %d" % rc)
 
 
+class SbasFrameState(C.Structure):
+    """gnsscorr_sbasframe_t: frame synchronisation of SBAS L1 on the decided symbols (ref src/sdrnav.c:40-82)."""
+    _fields_ = ([("fbits", C.c_int * 1512)] +
+                [(n, C.c_int) for n in ("polarity", "flagsyncf", "flagtow", "flagdec", "flagpol", "id", "week", "pad")] +
+                [("firstsf", C.c_uint64), ("firstsfcnt", C.c_uint64), ("firstsftow", C.c_double), ("tow_gpst", C.c_double),
+                 ("tow", C.c_double), ("msg", C.c_ubyte * 32)])
+
+
+V27POLYA, V27POLYB = 0x6d, 0x4f              # libfec's fec.h (ref src/sdrinit.c:502)
+
+
 class SpecParams(C.Structure):
     """gnsscorr_spec_t: one IF-monitor configuration (include/gnsscorr.h)."""
     _fields_ = [("ftype", C.c_int), ("nfft", C.c_int), ("nloop", C.c_int), ("n", C.c_int), ("f_sf", C.c_double)]
@@ -221,7 +232,7 @@ EXPORTS_GNSSCORR = [
     "gnsscorr_timing_enable", "gnsscorr_timing_read", "gnsscorr_timing_reset", "gnsscorr_default_ctx",
     "gnsscorr_spec_run", "gnsscorr_spec_fetch", "gnsscorr_trk_loop_lapped",
     "gnsscorr_acq_run_subset", "gnsscorr_loop_start_from_acq", "gnsscorr_rx_start", "gnsscorr_rx_set",
-    "gnsscorr_rx_step", "gnsscorr_rx_status"]
+    "gnsscorr_rx_step", "gnsscorr_rx_status", "gnsscorr_fec_run", "gnsscorr_sbasframe_replay"]
 EXPORTS_SDR = [
     "sdracquisition", "checkacquisition", "sdrtracking", "cumsumcorr", "clearcumsumcorr", "pll", "dll",
     "readinifile", "chk_initvalue", "initacqstruct", "inittrkprmstruct", "inittrkstruct", "initsdrch",
@@ -289,6 +300,10 @@ def lib():
     L.gnsscorr_spec_run.argtypes = [C.c_void_p, C.POINTER(SpecParams), C.c_int, C.c_void_p, C.c_void_p]
     L.gnsscorr_spec_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                       C.c_size_t, C.c_void_p, C.c_size_t]
+    L.gnsscorr_fec_run.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p, C.c_int]
+    L.gnsscorr_sbasframe_replay.argtypes = [C.c_void_p, C.POINTER(SbasFrameState), C.c_void_p, C.c_int, C.c_uint64,
+                                            C.c_void_p, C.c_int]
+    L.gnsscorr_debug_fec_parts.argtypes = [C.c_void_p, C.c_int]   # (tools; not part of include/gnsscorr.h)
     L.gnsscorr_debug_poison.argtypes = [C.c_void_p, C.c_int]      # (tests; not part of include/gnsscorr.h)
     if hasattr(L, "gnsscorr_debug_cmb_stats"):                    # (tests; bound when present, like the symbols below)
         L.gnsscorr_debug_cmb_stats.argtypes = [C.c_void_p]
@@ -685,6 +700,38 @@ class Engine:
         if single:
             return freq, pspec[0], s[0], hist[0]
         return freq, pspec, s, hist
+
+    # -- FEC / SBAS frame synchronisation
+    def fec_run(self, sym, pos0, npos, stride=1, win=1512, ndec=750, polyA=V27POLYA, polyB=V27POLYB, rowbytes=None):
+        """gnsscorr_fec_run on sym[nch][nsym] (or [nsym]) of +-1 / 0: uint8 rows [nch][npos][rowbytes], the ndec decoded
+        bits of the window that ends at symbol pos0 + p*stride packed MSB first (np.unpackbits gives them back)."""
+        a = np.ascontiguousarray(np.atleast_2d(sym), dtype=np.int8)
+        nch, nsym = a.shape
+        rowbytes = (ndec + 7) // 8 if rowbytes is None else rowbytes
+        out = np.zeros((nch, max(npos, 0), max(rowbytes, 0)), np.uint8)
+        buf = out if out.size else np.zeros(1, np.uint8)
+        _check(self._L.gnsscorr_fec_run(self.h, a.ctypes.data, nch, nsym, pos0, npos, stride, win, ndec, polyA, polyB,
+                                        buf.ctypes.data, rowbytes))
+        return out
+
+    def sbasframe_replay(self, state, log_rows, cnt0=0, aid_tow=None, aid_week=0):
+        """The symbols of one channel's log rows (numpy array of TrkLog) through the SBAS frame synchronisation: Viterbi
+        decodes on this engine's device, the walk on the host; `state` (SbasFrameState) is updated."""
+        log_rows = np.ascontiguousarray(log_rows)
+        n = int(log_rows.shape[0])
+        aid = None
+        if aid_tow is not None:
+            aid = np.ascontiguousarray(aid_tow, dtype=np.float64)
+            if aid.shape != (n,):
+                raise ValueError("aid_tow: one value per log row")
+        rc = self._L.gnsscorr_sbasframe_replay(self.h, C.byref(state), log_rows.ctypes.data, n, int(cnt0),
+                                               aid.ctypes.data if aid is not None else None, int(aid_week))
+        if rc:
+            raise GnsscorrError("gnsscorr_sbasframe_replay: error %d (%s)" % (rc, lib().gnsscorr_last_error().decode()))
+
+    def debug_fec_parts(self, parts):
+        """(tools) 3: the decoder; 1 / 2: the forward pass / the chainback of fec_viterbi27 alone (rows are no decodes)."""
+        _check(self._L.gnsscorr_debug_fec_parts(self.h, parts))
 
     # -- timing
     def timing(self, on=True):

@@ -209,6 +209,11 @@ struct gnsscorr_ctx {
     // IF monitor (spectrum / histogram) scratch
     GcSpecWork *spec = nullptr;
 
+    // FEC (gnsscorr_fec.hip): staging of gnsscorr_fec_run's symbol streams and packed rows
+    GcDevBuf<signed char> dfec_sym;                // [nch][nsym]
+    GcDevBuf<unsigned char> dfec_out;              // [nch][npos][rowbytes]
+    int fec_parts = 3;                             // (tools) 3: the decoder; 1 / 2: forward pass / chainback alone
+
     // timing
     int timing = 0;                                // 0: off, 1: every kernel, 2: only the two correlator kernels (trk_corr, acq_corr)
     std::map<std::string, GcTimer> timers;

@@ -647,6 +647,144 @@ int gnsscorr_frame_replay(gnsscorr_frame_t *st, const gnsscorr_trklog_t *rows, i
     return GNSSCORR_OK;
 }
 
+/* ------------------------------------------------------------------------- */
+/* frame synchronisation of SBAS L1 on the decided symbols: ref src/sdrnav.c:40-82 for CTYPE_L1SBAS */
+/* ------------------------------------------------------------------------- */
+#define SBAS_WIN   1512                 /* NAVFLEN_SBAS + NAVADDFLEN_SBAS symbols (ref src/sdr.h:166-167) */
+#define SBAS_NDEC  750                  /* decoded bits per window: three messages */
+#define SBAS_ROW   96                   /* bytes of a packed row */
+#define SBAS_UPDATE 1000                /* ref src/sdrinit.c:530: flen / 3 * rate periods */
+#define SBAS_POLYA 0x6d                 /* libfec's V27POLYA, V27POLYB (ref src/sdrinit.c:502) */
+#define SBAS_POLYB 0x4f
+
+/* fbitsdec[n] < 0 of a packed row */
+static int sbas_rowbit(const unsigned char *row, int n) { return (row[n >> 3] >> (7 - (n & 7))) & 1; }
+
+/* CRC-24Q (polynomial 0x1864CFB, no initial value, no reflection) of bits [0, n) of the message; leading zero bits
+ * leave it unchanged, so this is the reference's CRC of the 226 bits right-aligned in 29 bytes (ref src/sdrnav.c:352-356) */
+static unsigned sbas_crc24q(const unsigned char *bits, int n)
+{
+    unsigned crc = 0;
+    for (int i = 0; i < n; i++) {
+        crc ^= (unsigned)bits[i] << 23;
+        crc = (crc & 0x800000u) ? ((crc << 1) ^ 0x1864CFBu) : (crc << 1);
+        crc &= 0xFFFFFFu;
+    }
+    return crc;
+}
+
+/* the first message of a row under polarity: bits[250] (1 = the reference's -1 after polarity), and its CRC verdict */
+static int sbas_message(const unsigned char *row, int polarity, unsigned char *bits)
+{
+    unsigned sent = 0;
+    for (int i = 0; i < 250; i++) bits[i] = (unsigned char)(sbas_rowbit(row, i) ^ (polarity < 0));
+    for (int i = 226; i < 250; i++) sent = (sent << 1) | bits[i];
+    return sbas_crc24q(bits, 226) == sent;
+}
+
+static unsigned sbas_getbitu(const unsigned char *bits, int pos, int len)
+{
+    unsigned v = 0;
+    for (int i = 0; i < len; i++) v = (v << 1) | bits[pos + i];
+    return v;
+}
+
+int gnsscorr_sbasframe_replay(gnsscorr_ctx *ctx, gnsscorr_sbasframe_t *st, const gnsscorr_trklog_t *rows, int nper,
+                              uint64_t cnt0, const double *aid_tow, int aid_week)
+{
+    /* ref src/sdrinit.c:498-500, elements 0..15 as they stand: 0x53, 0x9A with a one as -1 */
+    static const int prebits[16] = {1, -1, 1, -1, 1, 1, -1, -1, -1, 1, 1, -1, -1, 1, -1, 1};
+    if (!ctx || !st || !rows || nper < 0) return GNSSCORR_EINVAL;
+    int n = 0;
+    for (int p = 0; p < nper; p++) n += rows[p].navbit != 0;
+    if (!n) return GNSSCORR_OK;
+    /* the symbol stream: the carried history, then this piece's symbols as the log has them (the walk flips those
+     * behind the symbol that raises flagpol); per symbol the period it was decided in */
+    signed char *sym = (signed char *)malloc((size_t)SBAS_WIN + n);
+    int *per = (int *)malloc(sizeof(int) * (size_t)n);
+    unsigned char *dec = (unsigned char *)malloc((size_t)SBAS_ROW * n);
+    if (!sym || !per || !dec) {
+        free(sym); free(per); free(dec);
+        return GNSSCORR_EINVAL;
+    }
+    for (int i = 0; i < SBAS_WIN; i++) sym[i] = (signed char)st->fbits[i];
+    for (int p = 0, k = 0; p < nper; p++)
+        if (rows[p].navbit) {
+            sym[SBAS_WIN + k] = (signed char)(st->flagpol ? -rows[p].navbit : rows[p].navbit);
+            per[k++] = p;
+        }
+    int lo = 0, hi = 0, rc = GNSSCORR_OK;       /* rows [lo, hi) of dec are decodes of the stream as it stands */
+    for (int k = 0; k < n && !rc; k++) {
+        const int p = per[k];
+        const uint64_t cnt = cnt0 + (uint64_t)p;
+        const int search = !st->flagtow;
+        if (!search && (int)(cnt - st->firstsfcnt) % SBAS_UPDATE != 0) continue;
+        if (k < lo || k >= hi) {
+            /* predecodefec(): while the frame is searched every symbol wants its decode, so all that are left go in
+             * one launch; a tracked frame wants one a second */
+            lo = k;
+            hi = search ? n : k + 1;
+            rc = gnsscorr_fec_run(ctx, sym, 1, SBAS_WIN + n, SBAS_WIN + lo, hi - lo, 1, SBAS_WIN, SBAS_NDEC, SBAS_POLYA,
+                                  SBAS_POLYB, dec + (size_t)SBAS_ROW * lo, SBAS_ROW);
+            if (rc) break;
+        }
+        const unsigned char *row = dec + (size_t)SBAS_ROW * k;
+        unsigned char bits[250];
+        if (search) {                           /* findpreamble(): ref src/sdrnav.c:384-389,398-408 */
+            int corr = 0;
+            for (int i = 0; i < 8; i++) {
+                corr += (sbas_rowbit(row, i) ? -1 : 1) * prebits[i];
+                corr += (sbas_rowbit(row, 250 + i) ? -1 : 1) * prebits[8 + i];
+            }
+            st->flagsyncf = 0;
+            if (corr == 16 || corr == -16) {
+                st->polarity = corr > 0 ? 1 : -1;
+                if (sbas_message(row, st->polarity, bits)) {
+                    st->flagsyncf = 1;
+                } else if (st->polarity == 1 && !st->flagpol) {
+                    st->flagpol = 1;            /* checkbit() flips every symbol from the next one on */
+                    for (int j = k + 1; j < n; j++) sym[SBAS_WIN + j] = (signed char)-sym[SBAS_WIN + j];
+                    hi = k + 1;
+                }
+            }
+            if (st->flagsyncf) {
+                st->firstsf = rows[p].buffloc;
+                st->firstsfcnt = cnt;
+                st->flagtow = 1;
+            }
+        }
+        if (st->flagtow && (int)(cnt - st->firstsfcnt) % SBAS_UPDATE == 0) {
+            /* decode_l1sbas(): ref src/sdrnav_sbs.c:100-140 (a failing CRC is reported there, not acted on) */
+            sbas_message(row, st->polarity, bits);
+            memset(st->msg, 0, sizeof(st->msg));
+            for (int i = 0; i < 250; i++) st->msg[i >> 3] |= (unsigned char)(bits[i] << (7 - (i & 7)));
+            st->id = (int)sbas_getbitu(bits, 8, 6);
+            if (st->id == 12) {
+                st->tow = sbas_getbitu(bits, 107, 20) + 1.0;
+                st->week = (int)sbas_getbitu(bits, 127, 10) + 1024;
+            } else {
+                st->tow += 1.0;
+            }
+            if (aid_tow && aid_week != 0) {
+                st->tow = aid_tow[p];
+                st->week = aid_week;
+            }
+            if (st->week != 0) st->tow_gpst = st->tow;
+            if (st->tow_gpst == 0) {            /* no time yet: start over (ref src/sdrnav.c:69-72) */
+                st->flagsyncf = 0;
+                st->flagtow = 0;
+            } else if (cnt == st->firstsfcnt) {
+                st->flagdec = 1;
+                st->firstsftow = st->tow_gpst;
+            }
+        }
+    }
+    if (!rc)
+        for (int i = 0; i < SBAS_WIN; i++) st->fbits[i] = sym[n + i];
+    free(sym); free(per); free(dec);
+    return rc;
+}
+
 /* 2nd order PLL assisted by a 1st order FLL */
 void pll(sdrch_t *sdr, sdrtrkprm_t *prm, double dt)
 {

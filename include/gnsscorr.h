@@ -259,6 +259,54 @@ typedef struct {
 /* log[nper]: one channel's rows; cnt0: sdrthread's cnt at log[0].  Returns 0, or GNSSCORR_EINVAL. */
 int  gnsscorr_frame_replay(gnsscorr_frame_t *st, const gnsscorr_trklog_t *log, int nper, uint64_t cnt0);
 
+/* ---- FEC: sliding-window Viterbi decoder (K = 7, rate 1/2) on the device ------
+ * predecodefec() for CTYPE_L1SBAS (ref src/sdrnav.c:302-318): init_viterbi27(.., 0), update_blk over win/2 symbol
+ * pairs, chainback(.., ndec, end state 0), for npos windows of every channel in one launch (one wavefront per window).
+ * sym[nch][nsym] holds each channel's decided symbols (+1, -1, or 0 for history not filled yet); window p of a channel
+ * is the win symbols that end at symbol pos0 + p*stride, symbols in front of the stream counting as 0.  +1 is received
+ * as 0, anything else as 255 (ref :305-306).  polyA, polyB: the generator masks over the register (the last seven
+ * input bits, newest in bit 0), first and second symbol of a pair: libfec's V27POLYA, V27POLYB = 0x6d, 0x4f (ref
+ * src/sdrinit.c:502,539).  The decoder is defined in DESIGN.md 3.5; it walks back from state 0 whatever the metrics
+ * say, so the last six steps are read as a tail.
+ * out[nch][npos][rowbytes]: the ndec decoded bits of each window, packed MSB first (a set bit is fbitsdec = -1, ref
+ * :311-312), the rest of the row zero; rowbytes >= (ndec + 7)/8 (96 for the reference's 750 bits).
+ * win even and <= 1512, ndec <= win/2 - 6, no negative count, the last window inside the stream: otherwise
+ * GNSSCORR_EINVAL.  Runs on the context's stream and synchronises it; timer name "fec_viterbi27". */
+int  gnsscorr_fec_run(gnsscorr_ctx *ctx, const signed char *sym, int nch, int nsym, int pos0, int npos, int stride,
+                      int win, int ndec, int polyA, int polyB, unsigned char *out, int rowbytes);
+
+/* Frame synchronisation of SBAS L1 on the batched symbols: what sdrnavigation() does behind checkbit() for
+ * CTYPE_L1SBAS (ref src/sdrnav.c:40-82) -- the last 1512 decided symbols, predecodefec() on every symbol until the frame
+ * is found and every 1000 periods from then on (ref src/sdrinit.c:530), the two-preamble search on the decoded bits (ref
+ * src/sdrnav.c:384-389) with its CRC-24Q check (ref :351-359), and of decode_l1sbas() the CRC verdict's message, its type
+ * and the time of message type 12 (ref src/sdrnav_sbs.c:69-73,100-140) -- replayed over the `navbit` column of a
+ * closed-loop log.  It yields what setobsdata() needs from the frame decoder: flagsyncf, polarity, firstsfcnt,
+ * firstsftow.  The Viterbi decodes run on the device (gnsscorr_fec_run, all candidate positions of the call in one
+ * launch); the walk over the decoded rows is host code.
+ * flagpol: a matched preamble of polarity +1 whose CRC fails sets it (ref src/sdrnav.c:404-406), and in the reference it
+ * then flips every symbol checkbit() decides (ref :266-271).  The log's symbols were decided with the device's flagpol
+ * as it was when the run began, so the replay keeps its own: once it is on, the log's later symbols are multiplied by
+ * -1 (and the rows behind that symbol decoded again).  It is never written to the device and never goes off.
+ * The NovAtel message, the TCP output and the correction / ephemeris contents are not part of this library. */
+typedef struct {
+    int    fbits[1512];                     /* ref sdrnav_t.fbits (flen 1500 + addflen 12), newest last; 0: not filled */
+    int    polarity, flagsyncf, flagtow, flagdec, flagpol;  /* ref sdrnav_t                                        */
+    int    id;                              /* ref sdrsbas_t.id: message type decoded last                         */
+    int    week;                            /* ref sdrsbas_t.week (= sdreph_t.week_gpst once it is not 0)          */
+    int    pad;
+    uint64_t firstsf, firstsfcnt;           /* ref sdrnav_t: sample / period counter of the symbol that found it   */
+    double firstsftow, tow_gpst;            /* ref sdrnav_t.firstsftow, sdreph_t.tow_gpst                          */
+    double tow;                             /* ref sdrsbas_t.tow: type 12's time, else + 1.0 per message            */
+    unsigned char msg[32];                  /* ref sdrsbas_t.msg: the 250 bits of the message decoded last         */
+} gnsscorr_sbasframe_t;
+/* log[nper]: one channel's rows; cnt0: sdrthread's cnt at log[0].  aid_tow[nper] / aid_week: the reference borrows
+ * time from the last-but-one channel once that has a week (ref src/sdrnav_sbs.c:123-127): that channel's tow[0] per
+ * period of this log (e.g. from gnsscorr_obs_replay) and its week; NULL / 0: no aid.  While week stays 0, tow_gpst
+ * stays 0 and the frame flags reset after every decode, as ref src/sdrnav.c:69-72 does.
+ * Returns 0, GNSSCORR_EINVAL, or gnsscorr_fec_run's error (there is no CPU path). */
+int  gnsscorr_sbasframe_replay(gnsscorr_ctx *ctx, gnsscorr_sbasframe_t *st, const gnsscorr_trklog_t *log, int nper,
+                               uint64_t cnt0, const double *aid_tow, int aid_week);
+
 /* Track `nperiod` code periods of every channel closed loop.  A channel stops early
  * where sdrtracking() would find no data yet (ref src/sdrtrk.c:26-30: bufflocnow
  * <= buffloc).  Returns when the last launches are queued (it keeps at most a few
@@ -397,7 +445,7 @@ int  gnsscorr_spec_fetch(gnsscorr_ctx *ctx, double *s, size_t s_cap,
 /* per-kernel launch timing: enable, run, then read the accumulated HIP-event
  * time of the named kernel ("trk_corr", "trk_plan", "trk_spec", "trk_expand",
  * "trk_finish", "acq_fwd", "acq_corr", "acq_code", "acq_final", "spec_psd",
- * "spec_sum", "spec_hist").
+ * "spec_sum", "spec_hist", "fec_viterbi27").
  * on = 1: every kernel; on = 2: only the two correlator kernels ("trk_corr",
  * "acq_corr"), leaving the planner and finish streams free of events; 0: off */
 int  gnsscorr_timing_enable(gnsscorr_ctx *ctx, int on);
