@@ -117,6 +117,21 @@ __global__ void tw_init_kernel(float2 *tw16k, float2 *tw32k, float2 *tw32p)
     tw32p[t] = make_float2((float)c, (float)s);
 }
 
+// four adjacent float2 (a butterfly's pass-order positions p..p+3) as two 16-byte accesses
+__device__ __forceinline__ void st4(float2 *dst, float2 x0, float2 x1, float2 x2, float2 x3)
+{
+    float4 *d = reinterpret_cast<float4 *>(dst);
+    d[0] = make_float4(x0.x, x0.y, x1.x, x1.y);
+    d[1] = make_float4(x2.x, x2.y, x3.x, x3.y);
+}
+__device__ __forceinline__ void ld4(const float2 *src, float2 (&v)[4])
+{
+    const float4 *d = reinterpret_cast<const float4 *>(src);
+    const float4 a = d[0], b = d[1];
+    v[0] = make_float2(a.x, a.y); v[1] = make_float2(a.z, a.w);
+    v[2] = make_float2(b.x, b.y); v[3] = make_float2(b.z, b.w);
+}
+
 // Forward 32768-point transform of a sequence given by a per-sample functor, decimated in time:
 // Ee = FFT16k(x[2j]), Oo = FFT16k(x[2j+1]), X[f] = Ee[f] + w^f Oo[f], X[f + 16384] = Ee[f] - w^f Oo[f]
 // (w = exp(-2 pi i/32768), f < 16384).  out[0][p] / out[1][p] = X[f(p)] / X[f(p) + 16384], p in pass
@@ -128,26 +143,17 @@ __device__ __forceinline__ void fwd32k_store(F sample, float2 *lds, const float2
                                              int tid)
 {
     gcfft::dif<-1>([&](int j) { return sample(2 * j); },
-                   [out](int p, float2 x0, float2 x1, float2 x2, float2 x3) {
-                       float4 *d = reinterpret_cast<float4 *>(out + p);
-                       d[0] = make_float4(x0.x, x0.y, x1.x, x1.y);
-                       d[1] = make_float4(x2.x, x2.y, x3.x, x3.y);
-                   },
+                   [out](int p, float2 x0, float2 x1, float2 x2, float2 x3) { st4(out + p, x0, x1, x2, x3); },
                    lds, tw16k, tid);
     __syncthreads();
     gcfft::dif<-1>([&](int j) { return sample(2 * j + 1); },
                    [out, tw32p](int p, float2 x0, float2 x1, float2 x2, float2 x3) {
-                       float4 *lo = reinterpret_cast<float4 *>(out + p);
-                       float4 *hi = reinterpret_cast<float4 *>(out + GC_LH + p);
-                       const float4 ea = lo[0], eb = lo[1];
-                       const float4 ta = *reinterpret_cast<const float4 *>(tw32p + p);
-                       const float4 tb = *reinterpret_cast<const float4 *>(tw32p + p + 2);
-                       const float2 o0 = cmul(x0, make_float2(ta.x, ta.y)), o1 = cmul(x1, make_float2(ta.z, ta.w));
-                       const float2 o2 = cmul(x2, make_float2(tb.x, tb.y)), o3 = cmul(x3, make_float2(tb.z, tb.w));
-                       lo[0] = make_float4(ea.x + o0.x, ea.y + o0.y, ea.z + o1.x, ea.w + o1.y);
-                       lo[1] = make_float4(eb.x + o2.x, eb.y + o2.y, eb.z + o3.x, eb.w + o3.y);
-                       hi[0] = make_float4(ea.x - o0.x, ea.y - o0.y, ea.z - o1.x, ea.w - o1.y);
-                       hi[1] = make_float4(eb.x - o2.x, eb.y - o2.y, eb.z - o3.x, eb.w - o3.y);
+                       float2 e[4], t[4];
+                       ld4(out + p, e);
+                       ld4(tw32p + p, t);
+                       const float2 o[4] = {cmul(x0, t[0]), cmul(x1, t[1]), cmul(x2, t[2]), cmul(x3, t[3])};
+                       st4(out + p, cadd(e[0], o[0]), cadd(e[1], o[1]), cadd(e[2], o[2]), cadd(e[3], o[3]));
+                       st4(out + GC_LH + p, csub(e[0], o[0]), csub(e[1], o[1]), csub(e[2], o[2]), csub(e[3], o[3]));
                    },
                    lds, tw16k, tid);
 }
@@ -164,31 +170,20 @@ __device__ __forceinline__ void fwd64k_store(F sample, float2 *lds, const float2
                                              const float2 *__restrict__ tw32p, const float2 *__restrict__ tw64p1,
                                              const float2 *__restrict__ tw64p3, float2 *__restrict__ out, int tid)
 {
-    auto put = [](float2 *dst, float2 x0, float2 x1, float2 x2, float2 x3) {
-        float4 *d = reinterpret_cast<float4 *>(dst);
-        d[0] = make_float4(x0.x, x0.y, x1.x, x1.y);
-        d[1] = make_float4(x2.x, x2.y, x3.x, x3.y);
-    };
-    auto get = [](const float2 *src, float2 (&v)[4]) {
-        const float4 *d = reinterpret_cast<const float4 *>(src);
-        const float4 a = d[0], b = d[1];
-        v[0] = make_float2(a.x, a.y); v[1] = make_float2(a.z, a.w);
-        v[2] = make_float2(b.x, b.y); v[3] = make_float2(b.z, b.w);
-    };
     // r = 0: E_0 -> out[0]
     gcfft::dif<-1>([&](int j) { return sample(4 * j); },
-                   [&](int p, float2 x0, float2 x1, float2 x2, float2 x3) { put(out + p, x0, x1, x2, x3); },
+                   [&](int p, float2 x0, float2 x1, float2 x2, float2 x3) { st4(out + p, x0, x1, x2, x3); },
                    lds, tw16k, tid);
     __syncthreads();
     // r = 2: P+ -> out[0], P- -> out[1]
     gcfft::dif<-1>([&](int j) { return sample(4 * j + 2); },
                    [&](int p, float2 x0, float2 x1, float2 x2, float2 x3) {
                        float2 e[4], t[4];
-                       get(out + p, e);
-                       get(tw32p + p, t);
+                       ld4(out + p, e);
+                       ld4(tw32p + p, t);
                        const float2 a[4] = {cmul(x0, t[0]), cmul(x1, t[1]), cmul(x2, t[2]), cmul(x3, t[3])};
-                       put(out + p, cadd(e[0], a[0]), cadd(e[1], a[1]), cadd(e[2], a[2]), cadd(e[3], a[3]));
-                       put(out + GC_LH + p, csub(e[0], a[0]), csub(e[1], a[1]), csub(e[2], a[2]), csub(e[3], a[3]));
+                       st4(out + p, cadd(e[0], a[0]), cadd(e[1], a[1]), cadd(e[2], a[2]), cadd(e[3], a[3]));
+                       st4(out + GC_LH + p, csub(e[0], a[0]), csub(e[1], a[1]), csub(e[2], a[2]), csub(e[3], a[3]));
                    },
                    lds, tw16k, tid);
     __syncthreads();
@@ -196,8 +191,8 @@ __device__ __forceinline__ void fwd64k_store(F sample, float2 *lds, const float2
     gcfft::dif<-1>([&](int j) { return sample(4 * j + 1); },
                    [&](int p, float2 x0, float2 x1, float2 x2, float2 x3) {
                        float2 t[4];
-                       get(tw64p1 + p, t);
-                       put(out + 2 * GC_LH + p, cmul(x0, t[0]), cmul(x1, t[1]), cmul(x2, t[2]), cmul(x3, t[3]));
+                       ld4(tw64p1 + p, t);
+                       st4(out + 2 * GC_LH + p, cmul(x0, t[0]), cmul(x1, t[1]), cmul(x2, t[2]), cmul(x3, t[3]));
                    },
                    lds, tw16k, tid);
     __syncthreads();
@@ -205,10 +200,10 @@ __device__ __forceinline__ void fwd64k_store(F sample, float2 *lds, const float2
     gcfft::dif<-1>([&](int j) { return sample(4 * j + 3); },
                    [&](int p, float2 x0, float2 x1, float2 x2, float2 x3) {
                        float2 t[4], a1[4], pp[4], pm[4];
-                       get(tw64p3 + p, t);
-                       get(out + 2 * GC_LH + p, a1);
-                       get(out + p, pp);
-                       get(out + GC_LH + p, pm);
+                       ld4(tw64p3 + p, t);
+                       ld4(out + 2 * GC_LH + p, a1);
+                       ld4(out + p, pp);
+                       ld4(out + GC_LH + p, pm);
                        const float2 a3[4] = {cmul(x0, t[0]), cmul(x1, t[1]), cmul(x2, t[2]), cmul(x3, t[3])};
                        float2 X0[4], X1[4], X2[4], X3[4];
 #pragma unroll
@@ -220,10 +215,10 @@ __device__ __forceinline__ void fwd64k_store(F sample, float2 *lds, const float2
                            X1[i] = csub(pm[i], iqm);
                            X3[i] = cadd(pm[i], iqm);
                        }
-                       put(out + p, X0[0], X0[1], X0[2], X0[3]);
-                       put(out + GC_LH + p, X1[0], X1[1], X1[2], X1[3]);
-                       put(out + 2 * GC_LH + p, X2[0], X2[1], X2[2], X2[3]);
-                       put(out + 3 * GC_LH + p, X3[0], X3[1], X3[2], X3[3]);
+                       st4(out + p, X0[0], X0[1], X0[2], X0[3]);
+                       st4(out + GC_LH + p, X1[0], X1[1], X1[2], X1[3]);
+                       st4(out + 2 * GC_LH + p, X2[0], X2[1], X2[2], X2[3]);
+                       st4(out + 3 * GC_LH + p, X3[0], X3[1], X3[2], X3[3]);
                    },
                    lds, tw16k, tid);
 }
@@ -366,8 +361,182 @@ __device__ __forceinline__ void wg_sum_max(double &s, double &m, double *sd, int
     for (int w = 1; w < NT / 64; w++) { s += sd[w]; m = fmax(m, sd[16 + w]); }
 }
 
-struct RawXC { float4 la, lb, ha, hb, cla, clb, cha, chb; };     // X[f], X[f+L/2], C[f], C[f+L/2] at 4 positions
-struct RawXCT { RawXC r; float4 ta, tb; };                        // + their 32768-point twiddles
+// Row statistics for checkacquisition() (ref src/sdracq.c:71-95) of the power row a workgroup of NT lanes holds in
+// registers, lane `tid` owning lag lag_of(tid, s) in P[s] (lags >= n are not part of the row): the maximum and its
+// lag (first index on ties), and, outside the window of +-nsc2 samples (2 chips, wrapping) around it, the sum and
+// the maximum -- for which element 0 always is a candidate: it seeds maxvd().  Two workgroup reductions (wg_argmax,
+// then wg_sum_max); every lane returns the row.
+template <int NT, int NP, class LagOf>
+__device__ __forceinline__ GcAcqRow acq_row_stats(const double (&P)[NP], LagOf lag_of, int n, int nsc2, double *sd,
+                                                  int *si, int tid)
+{
+    MaxIdx m; m.v = -1.0; m.k = 0x7fffffff;
+#pragma unroll
+    for (int s = 0; s < NP; s++) {
+        const int k = lag_of(tid, s);
+        if (k < n) { MaxIdx t; t.v = P[s]; t.k = k; m = better(m, t); }
+    }
+    m = wg_argmax<NT>(m, sd, si, tid);
+    int exs = m.k - nsc2; if (exs < 0) exs += n;
+    int exe = m.k + nsc2; if (exe >= n) exe -= n;
+    double so = 0.0, mo = -1.0;
+#pragma unroll
+    for (int s = 0; s < NP; s++) {
+        const int k = lag_of(tid, s);
+        if (k < n) {
+            const bool outside = (exs <= exe) ? (k < exs || k > exe) : (k < exs && k > exe);
+            if (outside) so += P[s];
+            if (outside || k == 0) mo = fmax(mo, P[s]);    // element 0 seeds maxvd()
+        }
+    }
+    wg_sum_max<NT>(so, mo, sd, tid);
+    GcAcqRow r;
+    r.rowmax = m.v; r.sum_out = so; r.max_out = mo; r.argmax = m.k; r.pad = 0;
+    return r;
+}
+
+// The decision of one iteration, taken by a wavefront from the rows of the channel's nfreq bins: the best row is the
+// one with the largest rowmax, lowest bin on ties (every lane returns it); the channel is acquired when that row's
+// peak ratio passes ACQTH (ref src/sdr.h:148, src/sdracq.c:39-42).
+__device__ __forceinline__ int acq_best_row(const GcAcqRow *row, int nfreq, int lane)
+{
+    double bv = -1.0;
+    int bi = 0x7fffffff;
+    for (int b = lane; b < nfreq; b += 64) {
+        const double v = row[b].rowmax;
+        if (v > bv) { bv = v; bi = b; }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double ov = __shfl_xor(bv, d);
+        const int oi = __shfl_xor(bi, d);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    return bi;
+}
+
+__device__ __forceinline__ bool acq_passes(const GcAcqRow &w) { return w.rowmax / w.max_out > 3.0; }
+
+// X[f + 16384 q], C[f + 16384 q] (q < Q) at the four pass-order positions of a butterfly, as loaded; with the
+// positions' twiddles behind them
+template <int Q> struct RawXC { float4 x[Q][2], c[Q][2]; };
+template <int Q> struct RawXCT { RawXC<Q> r; float4 ta, tb; };
+template <int Q> __device__ __forceinline__ const RawXC<Q> &acq_raw(const RawXC<Q> &r) { return r; }
+template <int Q> __device__ __forceinline__ const RawXC<Q> &acq_raw(const RawXCT<Q> &t) { return t.r; }
+
+template <int Q>
+__device__ __forceinline__ RawXC<Q> acq_load(const float2 *Xb, const float2 *Cc, int p)
+{
+    RawXC<Q> r;
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+        r.x[q][0] = *reinterpret_cast<const float4 *>(Xb + q * GC_LH + p);
+        r.x[q][1] = *reinterpret_cast<const float4 *>(Xb + q * GC_LH + p + 2);
+        r.c[q][0] = *reinterpret_cast<const float4 *>(Cc + q * GC_LH + p);
+        r.c[q][1] = *reinterpret_cast<const float4 *>(Cc + q * GC_LH + p + 2);
+    }
+    return r;
+}
+template <int Q>
+__device__ __forceinline__ RawXCT<Q> acq_load_tw(const float2 *Xb, const float2 *Cc, const float2 *twp, int p)
+{
+    RawXCT<Q> t;
+    t.r = acq_load<Q>(Xb, Cc, p);
+    t.ta = *reinterpret_cast<const float4 *>(twp + p);
+    t.tb = *reinterpret_cast<const float4 *>(twp + p + 2);
+    return t;
+}
+// Y[f + 16384 q] = X conj(C) at position k (0..3) of the butterfly, and that position's twiddle
+template <int Q>
+__device__ __forceinline__ float2 acq_y(const RawXC<Q> &r, int q, int k)
+{
+    const float4 xv = r.x[q][k >> 1], cv = r.c[q][k >> 1];
+    return (k & 1) ? cmulc(make_float2(xv.z, xv.w), make_float2(cv.z, cv.w))
+                   : cmulc(make_float2(xv.x, xv.y), make_float2(cv.x, cv.y));
+}
+template <int Q>
+__device__ __forceinline__ float2 acq_w(const RawXCT<Q> &t, int k)
+{
+    const float4 v = k < 2 ? t.ta : t.tb;
+    return (k & 1) ? make_float2(v.z, v.w) : make_float2(v.x, v.y);
+}
+
+// dit() sink: |y|^2/L^2 of the lags a transform ends in (of a lane's outputs o + 1024 q those with q < 8: lags below
+// nsamp) onto the fp64 accumulators P[OFF + 8 h + q] (ref src/sdrcmn.c:244-246 with the m-point scaling folded)
+template <int OFF, int NP>
+__device__ __forceinline__ auto acq_add_power(double (&P)[NP], float invL2)
+{
+    return [&P, invL2](int h, int, float2 (&a)[16]) {
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const float pw = fmaf(a[q].x, a[q].x, a[q].y * a[q].y) * invL2;
+            P[OFF + 8 * h + q] += (double)pw;
+        }
+    };
+}
+
+// the bin's power row, from the registers to Pout[bin][lag]
+template <int NP, class LagOf>
+__device__ __forceinline__ void acq_write_power(double *__restrict__ Pout, const double (&P)[NP], LagOf lag_of,
+                                                int tid, int bin, int n)
+{
+#pragma unroll
+    for (int s = 0; s < NP; s++) {
+        const int k = lag_of(tid, s);
+        if (k < n) Pout[(size_t)bin * n + k] = P[s];
+    }
+}
+
+// dynamic LDS of the correlation kernels: the FFT image, then the reductions' scratch (32 doubles sd, 16 ints si),
+// in the 256-byte units of the other FFT kernels' sizes
+#define GC_ACQ_SD       GC_FFT_LDS
+#define GC_ACQ_SI       (GC_ACQ_SD + 32 * (int)sizeof(double))
+#define GC_ACQ_CORR_LDS ((GC_ACQ_SI + 16 * (int)sizeof(int) + 255) & ~255)
+
+#define GC_ACQ_G 4              // channels that share an XCD's forward spectra (acq_corr_kernel)
+
+// Block order of acq_corr_kernel.  Blocks b and b + 8 tend to share an XCD (speed only).  Search: XCD `slot` takes
+// the bins slot, slot + 8, ... of GC_ACQ_G channels at a time: the ~9 spectra X[iteration][bin] it needs per
+// iteration (2.3 MB) and the G code spectra (1 MB) fit its 4 MB L2, so a spectrum leaves the Infinity Cache (which
+// holds all of them, 186 MB) once per G channels (and both lag parities) instead of once per channel and parity;
+// chip-wide the G channels' bins all run side by side and reach the end of each iteration together, which is what
+// lets a channel stop at the iteration that acquires it.  Pout (one channel's power array): block = bin.
+// A block whose bin or list entry does not exist (bin >= nbins, li >= nlist) has nothing to do.
+struct AcqBlock { int bin, li; };       // Doppler bin, entry of the channel list
+
+__device__ __forceinline__ AcqBlock acq_corr_block(int b, int nbins, bool pout)
+{
+    constexpr int G = GC_ACQ_G;
+    const int slot = b & 7, qq = b >> 3;
+    const int bpx = (nbins + 7) >> 3;                   // bins per XCD slot
+    const int grp = qq / (bpx * G), rem = qq - grp * (bpx * G);
+    AcqBlock r;
+    r.bin = pout ? qq * 8 + slot : (rem / G) * 8 + slot;
+    r.li = grp * G + rem % G;
+    return r;
+}
+// its grid: 8 slots x bins per slot (x the listed channels in whole groups of G)
+unsigned acq_corr_blocks(int nbins, int nlist, bool pout)
+{
+    const unsigned per_channel = 8u * (unsigned)((nbins + 7) / 8);
+    return pout ? per_channel : per_channel * (unsigned)(GC_ACQ_G * ((nlist + GC_ACQ_G - 1) / GC_ACQ_G));
+}
+
+// Block order of acq_corr64_kernel.  Search: slot = list entry within a round of 8, the rounds' bins consecutive.
+// Pout: block = bin.
+__device__ __forceinline__ AcqBlock acq_corr64_block(int b, int nbins, bool pout)
+{
+    const int slot = b & 7, qq = b >> 3;
+    AcqBlock r;
+    r.bin = pout ? qq * 8 + slot : qq % nbins;
+    r.li = (qq / nbins) * 8 + slot;
+    return r;
+}
+// its grid: (rounds of 8 list entries) x bins x 8 slots
+unsigned acq_corr64_blocks(int nbins, int nlist, bool pout)
+{
+    return pout ? 8u * (unsigned)((nbins + 7) / 8) : 8u * (unsigned)((nlist + 7) / 8) * (unsigned)nbins;
+}
 
 // acq_corr: one workgroup of NT lanes per (bin, channel).
 // y = IFFT_L(Y), Y = X conj(C) (ref src/sdrcmn.c:236-246; the reference's extra minus sign vanishes
@@ -377,7 +546,6 @@ struct RawXCT { RawXC r; float4 ta, tb; };                        // + their 327
 // Lags k < nsamp <= 16384 are wanted, i.e. j < 8192: of a lane's outputs j = o + 1024 q those with
 // q < 8.  Nothing has to wait for the other transform, so the only long-lived registers are the
 // power accumulators.
-#define GC_ACQ_G 4              // channels that share an XCD's forward spectra (acq_corr_kernel)
 template <int NT>
 __global__ __launch_bounds__(NT) void acq_corr_kernel(
     const GcChan *__restrict__ chan, const float2 *__restrict__ tw16k, const float2 *__restrict__ tw32p,
@@ -387,27 +555,13 @@ __global__ __launch_bounds__(NT) void acq_corr_kernel(
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2 *lds = reinterpret_cast<float2 *>(smem);
-    double *sd = reinterpret_cast<double *>(smem + GC_FFT_LDS);       // 32 doubles
-    int *si = reinterpret_cast<int *>(smem + GC_FFT_LDS + 256);       // 16 ints
-    // Workgroup order: the Doppler bins of one channel are consecutive blocks, so they run side by side (71
-    // bins on 256 CUs: three to four channels at a time) and reach the end of each iteration together --
-    // what lets the channel stop at the iteration that acquires it (below).  The channel's code spectrum
-    // (256 KB) is then held by every XCD's L2, the forward spectra stream from the Infinity Cache, which
-    // holds all of them (186 MB).  (Pout: one channel's power array, blocks = its bins.)
+    double *sd = reinterpret_cast<double *>(smem + GC_ACQ_SD);
+    int *si = reinterpret_cast<int *>(smem + GC_ACQ_SI);
     const int tid0 = threadIdx.x;
-    const int slot = blockIdx.x & 7, qq = blockIdx.x >> 3;
-    // Search: blocks b and b + 8 tend to share an XCD (speed only).  XCD `slot` takes the bins slot, slot + 8, ... of
-    // GC_ACQ_G channels at a time: the ~9 spectra X[iteration][bin] it needs per iteration (2.3 MB) and the G code
-    // spectra (1 MB) fit its 4 MB L2, so a spectrum leaves the Infinity Cache once per G channels (and both lag
-    // parities) instead of once per channel and parity; chip-wide the G channels' bins all run side by side, which is
-    // what lets a channel stop at the iteration that acquires it.
-    constexpr int G = GC_ACQ_G;
-    const int bpx = (maxfreq + 7) >> 3;                 // bins per XCD slot
-    const int grp = qq / (bpx * G), rem = qq - grp * (bpx * G);
-    const int bin = Pout ? qq * 8 + slot : (rem / G) * 8 + slot;
-    const int li = grp * G + rem % G;                   // entry of the channel list
-    if (bin >= maxfreq || (!Pout && li >= nlist)) return;
-    const int ch = Pout ? pout_ch : list[li];
+    const AcqBlock blk = acq_corr_block(blockIdx.x, maxfreq, Pout != nullptr);
+    const int bin = blk.bin;
+    if (bin >= maxfreq || (!Pout && blk.li >= nlist)) return;
+    const int ch = Pout ? pout_ch : list[blk.li];
     const GcChan &c = chan[ch];
     if (bin >= c.nfreq) return;
     const int n = c.nsamp, nit = iters[ch], nsc2 = 2 * c.nsampchip;
@@ -429,101 +583,34 @@ __global__ __launch_bounds__(NT) void acq_corr_kernel(
         int tid = tid0;
         asm volatile("" : "+v"(tid));
         const float2 *Xb = X + (((size_t)c.grid * maxintg + it) * maxfreq + bin) * GC_L;
-        auto load8 = [Xb, Cc](int p) {
-            RawXC r;
-            r.la = *reinterpret_cast<const float4 *>(Xb + p);
-            r.lb = *reinterpret_cast<const float4 *>(Xb + p + 2);
-            r.ha = *reinterpret_cast<const float4 *>(Xb + GC_LH + p);
-            r.hb = *reinterpret_cast<const float4 *>(Xb + GC_LH + p + 2);
-            r.cla = *reinterpret_cast<const float4 *>(Cc + p);
-            r.clb = *reinterpret_cast<const float4 *>(Cc + p + 2);
-            r.cha = *reinterpret_cast<const float4 *>(Cc + GC_LH + p);
-            r.chb = *reinterpret_cast<const float4 *>(Cc + GC_LH + p + 2);
-            return r;
-        };
-        // Y[f] = X[f] conj(C[f]) at the four positions of a butterfly, low and high half of the spectrum
-#define GC_YLO(r, k) cmulc(make_float2((k) < 2 ? ((k) & 1 ? (r).la.z : (r).la.x) : ((k) & 1 ? (r).lb.z : (r).lb.x), \
-                                       (k) < 2 ? ((k) & 1 ? (r).la.w : (r).la.y) : ((k) & 1 ? (r).lb.w : (r).lb.y)), \
-                           make_float2((k) < 2 ? ((k) & 1 ? (r).cla.z : (r).cla.x) : ((k) & 1 ? (r).clb.z : (r).clb.x), \
-                                       (k) < 2 ? ((k) & 1 ? (r).cla.w : (r).cla.y) : ((k) & 1 ? (r).clb.w : (r).clb.y)))
-#define GC_YHI(r, k) cmulc(make_float2((k) < 2 ? ((k) & 1 ? (r).ha.z : (r).ha.x) : ((k) & 1 ? (r).hb.z : (r).hb.x), \
-                                       (k) < 2 ? ((k) & 1 ? (r).ha.w : (r).ha.y) : ((k) & 1 ? (r).hb.w : (r).hb.y)), \
-                           make_float2((k) < 2 ? ((k) & 1 ? (r).cha.z : (r).cha.x) : ((k) & 1 ? (r).chb.z : (r).chb.x), \
-                                       (k) < 2 ? ((k) & 1 ? (r).cha.w : (r).cha.y) : ((k) & 1 ? (r).chb.w : (r).chb.y)))
         // even lags
-        gcfft::dit<+1, NT, CHUNK>(load8,
-                       [&](const RawXC &r, float2 &x0, float2 &x1, float2 &x2, float2 &x3) {
-                           x0 = cadd(GC_YLO(r, 0), GC_YHI(r, 0));
-                           x1 = cadd(GC_YLO(r, 1), GC_YHI(r, 1));
-                           x2 = cadd(GC_YLO(r, 2), GC_YHI(r, 2));
-                           x3 = cadd(GC_YLO(r, 3), GC_YHI(r, 3));
+        gcfft::dit<+1, NT, CHUNK>([Xb, Cc](int p) { return acq_load<2>(Xb, Cc, p); },
+                       [](const RawXC<2> &r, float2 &x0, float2 &x1, float2 &x2, float2 &x3) {
+                           x0 = cadd(acq_y(r, 0, 0), acq_y(r, 1, 0));
+                           x1 = cadd(acq_y(r, 0, 1), acq_y(r, 1, 1));
+                           x2 = cadd(acq_y(r, 0, 2), acq_y(r, 1, 2));
+                           x3 = cadd(acq_y(r, 0, 3), acq_y(r, 1, 3));
                        },
-                       [&](int h, int, float2 (&a)[16]) {
-#pragma unroll
-                           for (int q = 0; q < 8; q++) {
-                               const float pw = fmaf(a[q].x, a[q].x, a[q].y * a[q].y) * invL2;
-                               P[8 * h + q] += (double)pw;      // (ref :244-246 with the m-point scaling folded)
-                           }
-                       },
-                       lds, tw16k, tid);
+                       acq_add_power<0>(P, invL2), lds, tw16k, tid);
         __syncthreads();
         asm volatile("" : "+v"(tid));            // (as above: the second transform recomputes its addresses)
         // odd lags; exp(+2 pi i f/L) = conj of the forward twiddle
-        gcfft::dit<+1, NT, CHUNK>([&](int p) {
-                           RawXCT t;
-                           t.r = load8(p);
-                           t.ta = *reinterpret_cast<const float4 *>(tw32p + p);
-                           t.tb = *reinterpret_cast<const float4 *>(tw32p + p + 2);
-                           return t;
+        gcfft::dit<+1, NT, CHUNK>([Xb, Cc, tw32p](int p) { return acq_load_tw<2>(Xb, Cc, tw32p, p); },
+                       [](const RawXCT<2> &t, float2 &x0, float2 &x1, float2 &x2, float2 &x3) {
+                           x0 = cmulc(csub(acq_y(t.r, 0, 0), acq_y(t.r, 1, 0)), acq_w(t, 0));
+                           x1 = cmulc(csub(acq_y(t.r, 0, 1), acq_y(t.r, 1, 1)), acq_w(t, 1));
+                           x2 = cmulc(csub(acq_y(t.r, 0, 2), acq_y(t.r, 1, 2)), acq_w(t, 2));
+                           x3 = cmulc(csub(acq_y(t.r, 0, 3), acq_y(t.r, 1, 3)), acq_w(t, 3));
                        },
-                       [&](const RawXCT &t, float2 &x0, float2 &x1, float2 &x2, float2 &x3) {
-                           x0 = cmulc(csub(GC_YLO(t.r, 0), GC_YHI(t.r, 0)), make_float2(t.ta.x, t.ta.y));
-                           x1 = cmulc(csub(GC_YLO(t.r, 1), GC_YHI(t.r, 1)), make_float2(t.ta.z, t.ta.w));
-                           x2 = cmulc(csub(GC_YLO(t.r, 2), GC_YHI(t.r, 2)), make_float2(t.tb.x, t.tb.y));
-                           x3 = cmulc(csub(GC_YLO(t.r, 3), GC_YHI(t.r, 3)), make_float2(t.tb.z, t.tb.w));
-                       },
-                       [&](int h, int, float2 (&a)[16]) {
-#pragma unroll
-                           for (int q = 0; q < 8; q++) {
-                               const float pw = fmaf(a[q].x, a[q].x, a[q].y * a[q].y) * invL2;
-                               P[NPH + 8 * h + q] += (double)pw;
-                           }
-                       },
-                       lds, tw16k, tid);
-#undef GC_YLO
-#undef GC_YHI
+                       acq_add_power<NPH>(P, invL2), lds, tw16k, tid);
 
-        // row statistics for checkacquisition()
-        MaxIdx m; m.v = -1.0; m.k = 0x7fffffff;
-#pragma unroll
-        for (int s = 0; s < NP; s++) {
-            const int k = lag_of(tid, s);
-            if (k < n) { MaxIdx t; t.v = P[s]; t.k = k; m = better(m, t); }
-        }
-        m = wg_argmax<NT>(m, sd, si, tid);
-        int exs = m.k - nsc2; if (exs < 0) exs += n;
-        int exe = m.k + nsc2; if (exe >= n) exe -= n;
-        double so = 0.0, mo = -1.0;
-#pragma unroll
-        for (int s = 0; s < NP; s++) {
-            const int k = lag_of(tid, s);
-            if (k < n) {
-                const bool outside = (exs <= exe) ? (k < exs || k > exe) : (k < exs && k > exe);
-                if (outside) so += P[s];
-                if (outside || k == 0) mo = fmax(mo, P[s]);    // element 0 seeds maxvd()
-            }
-        }
-        wg_sum_max<NT>(so, mo, sd, tid);
-        if (tid == 0) {
-            GcAcqRow r;
-            r.rowmax = m.v; r.sum_out = so; r.max_out = mo; r.argmax = m.k; r.pad = 0;
-            rows[((size_t)ch * maxintg + it) * maxfreq + bin] = r;
-        }
+        const GcAcqRow r = acq_row_stats<NT>(P, lag_of, n, nsc2, sd, si, tid);
+        if (tid == 0) rows[((size_t)ch * maxintg + it) * maxfreq + bin] = r;
         // The reference stops a channel at the first iteration whose peak ratio passes the threshold
         // (ref src/sdracq.c:39-42); so does this: the workgroup that finishes an iteration of its channel
-        // last takes the decision acq_final will take from the same rows, and the channel's workgroups
-        // leave at the next iteration boundary they reach after it.  (Iterations past the acquiring one
-        // are never looked at: what they would have written is not missed.)
+        // last takes acq_final's decision from the same rows (acq_best_row, acq_passes), and the channel's
+        // workgroups leave at the next iteration boundary they reach after it.  (Iterations past the
+        // acquiring one are never looked at: what they would have written is not missed.)
         if (arrive && tid < 64) {
             int last = 0;
             if (tid == 0) {
@@ -534,20 +621,8 @@ __global__ __launch_bounds__(NT) void acq_corr_kernel(
             if (last) {
                 __threadfence();
                 const GcAcqRow *row = rows + ((size_t)ch * maxintg + it) * maxfreq;
-                double bv = -1.0;
-                int bi = 0x7fffffff;
-                for (int b = tid; b < c.nfreq; b += 64) {
-                    const double v = row[b].rowmax;
-                    if (v > bv) { bv = v; bi = b; }
-                }
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) {
-                    const double ov = __shfl_xor(bv, d);
-                    const int oi = __shfl_xor(bi, d);
-                    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-                }
-                const GcAcqRow w = row[bi];
-                if (tid == 0 && w.rowmax / w.max_out > 3.0)                 // ACQTH, as acq_final
+                const GcAcqRow w = row[acq_best_row(row, c.nfreq, tid)];
+                if (tid == 0 && acq_passes(w))
                     __hip_atomic_store(&done[ch], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
             }
             if (tid == 0) si[15] = __hip_atomic_load(&done[ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -555,13 +630,7 @@ __global__ __launch_bounds__(NT) void acq_corr_kernel(
         __syncthreads();      // LDS image and reduction scratch are reused next iteration
         if (arrive && si[15]) break;
     }
-    if (Pout) {
-#pragma unroll
-        for (int s = 0; s < NP; s++) {
-            const int k = lag_of(tid0, s);
-            if (k < n) Pout[(size_t)bin * n + k] = P[s];
-        }
-    }
+    if (Pout) acq_write_power(Pout, P, lag_of, tid0, bin, n);
 }
 
 // acq_corr for the 65536-point transform: one workgroup of 512 lanes per (bin, channel).  The inverse
@@ -570,8 +639,6 @@ __global__ __launch_bounds__(NT) void acq_corr_kernel(
 // -- so that, as in the 32768-point kernel, every 16384-point transform ends in final lags and the
 // only long-lived registers are the power accumulators: lane `tid` owns lags 4 (tid + 512 h + 1024 q) + s,
 // h < 2, q < 8, s < 4 (lags below nsamp <= 32768), register index 16 s + 8 h + q.
-struct RawXC4 { float4 x[4][2], c[4][2]; };
-
 __global__ __launch_bounds__(512) void acq_corr64_kernel(
     const GcChan *__restrict__ chan, const float2 *__restrict__ tw16k, const float2 *__restrict__ tw32p,
     const float2 *__restrict__ tw64p1, const float2 *__restrict__ tw64p3,
@@ -582,14 +649,13 @@ __global__ __launch_bounds__(512) void acq_corr64_kernel(
     constexpr int NT = 512, L = 2 * GC_L, NP = 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2 *lds = reinterpret_cast<float2 *>(smem);
-    double *sd = reinterpret_cast<double *>(smem + GC_FFT_LDS);       // 32 doubles
-    int *si = reinterpret_cast<int *>(smem + GC_FFT_LDS + 256);       // 16 ints
+    double *sd = reinterpret_cast<double *>(smem + GC_ACQ_SD);
+    int *si = reinterpret_cast<int *>(smem + GC_ACQ_SI);
     const int tid0 = threadIdx.x;
-    const int slot = blockIdx.x & 7, qq = blockIdx.x >> 3;
-    const int bin = Pout ? qq * 8 + slot : qq % maxfreq;
-    const int li = (qq / maxfreq) * 8 + slot;           // entry of the channel list
-    if (bin >= maxfreq || (!Pout && li >= nlist)) return;
-    const int ch = Pout ? pout_ch : list[li];
+    const AcqBlock blk = acq_corr64_block(blockIdx.x, maxfreq, Pout != nullptr);
+    const int bin = blk.bin;
+    if (bin >= maxfreq || (!Pout && blk.li >= nlist)) return;
+    const int ch = Pout ? pout_ch : list[blk.li];
     const GcChan &c = chan[ch];
     if (bin >= c.nfreq) return;
     const int n = c.nsamp, nit = iters[ch], nsc2 = 2 * c.nsampchip;
@@ -603,139 +669,67 @@ __global__ __launch_bounds__(512) void acq_corr64_kernel(
         int tid = tid0;
         asm volatile("" : "+v"(tid));
         const float2 *Xb = X + (((size_t)c.grid * maxintg + it) * maxfreq + bin) * (size_t)L;
-        auto load = [Xb, Cc](int p) {
-            RawXC4 r;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                r.x[q][0] = *reinterpret_cast<const float4 *>(Xb + q * GC_LH + p);
-                r.x[q][1] = *reinterpret_cast<const float4 *>(Xb + q * GC_LH + p + 2);
-                r.c[q][0] = *reinterpret_cast<const float4 *>(Cc + q * GC_LH + p);
-                r.c[q][1] = *reinterpret_cast<const float4 *>(Cc + q * GC_LH + p + 2);
-            }
-            return r;
-        };
-        // Y_q at position k (0..3) of the butterfly
-        auto Y = [](const RawXC4 &r, int q, int k) {
-            const float4 xv = r.x[q][k >> 1], cv = r.c[q][k >> 1];
-            return (k & 1) ? cmulc(make_float2(xv.z, xv.w), make_float2(cv.z, cv.w))
-                           : cmulc(make_float2(xv.x, xv.y), make_float2(cv.x, cv.y));
-        };
-        auto residue = [&](auto s_tag) {
+        // Lags 4 j + S.  The twiddle w^(-f S) = conj(twp[p]) (S > 0) has to be applied per input: dit() hands `make`
+        // only the raw operands, so the twiddled residues fetch their factors with the operands.
+        auto residue = [&](auto s_tag, const float2 *__restrict__ twp) {
             constexpr int S = decltype(s_tag)::value;
-            gcfft::dit<+1, NT, 1>(
-                [&](int p) { return load(p); },
-                [&](const RawXC4 &r, float2 &x0, float2 &x1, float2 &x2, float2 &x3) {
-                    float2 z[4];
-                    // (the pass position of this butterfly: recomputed from the lane, dit() fetched it at 4*(tid + NT*i))
+            auto make = [](const auto &t, float2 &x0, float2 &x1, float2 &x2, float2 &x3) {
+                float2 z[4];
 #pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        const float2 y0 = Y(r, 0, k), y1 = Y(r, 1, k), y2 = Y(r, 2, k), y3 = Y(r, 3, k);
+                for (int k = 0; k < 4; k++) {
+                    const RawXC<4> &r = acq_raw(t);
+                    const float2 y0 = acq_y(r, 0, k), y1 = acq_y(r, 1, k), y2 = acq_y(r, 2, k), y3 = acq_y(r, 3, k);
+                    if constexpr (S == 0) {
+                        z[k] = cadd(cadd(y0, y2), cadd(y1, y3));
+                    } else {
                         float2 v;
-                        if (S == 0) v = cadd(cadd(y0, y2), cadd(y1, y3));
-                        else if (S == 2) v = csub(cadd(y0, y2), cadd(y1, y3));
+                        if (S == 2) v = csub(cadd(y0, y2), cadd(y1, y3));
                         else {
                             const float2 d = csub(y1, y3), id = make_float2(-d.y, d.x);      // i (y1 - y3)
                             v = S == 1 ? cadd(csub(y0, y2), id) : csub(csub(y0, y2), id);
                         }
-                        z[k] = v;
+                        z[k] = cmulc(v, acq_w(t, k));      // exp(+2 pi i f S/65536) = conj of the forward twiddle
                     }
-                    x0 = z[0]; x1 = z[1]; x2 = z[2]; x3 = z[3];
-                },
-                [&](int h, int, float2 (&a)[16]) {
-#pragma unroll
-                    for (int q = 0; q < 8; q++) {
-                        const float pw = fmaf(a[q].x, a[q].x, a[q].y * a[q].y) * invL2;
-                        P[16 * S + 8 * h + q] += (double)pw;
-                    }
-                },
-                lds, tw16k, tid);
+                }
+                x0 = z[0]; x1 = z[1]; x2 = z[2]; x3 = z[3];
+            };
+            if constexpr (S == 0)
+                gcfft::dit<+1, NT, 1>([Xb, Cc](int p) { return acq_load<4>(Xb, Cc, p); }, make,
+                                      acq_add_power<0>(P, invL2), lds, tw16k, tid);
+            else
+                gcfft::dit<+1, NT, 1>([Xb, Cc, twp](int p) { return acq_load_tw<4>(Xb, Cc, twp, p); }, make,
+                                      acq_add_power<16 * S>(P, invL2), lds, tw16k, tid);
         };
-        (void)residue;
-        // The twiddle w^(-f s) has to be applied per input: dit() hands `make` only the raw operands, so the
-        // twiddled variants fetch their factors with the operands.
-        struct RawT { RawXC4 r; float4 ta, tb; };
-        auto residue_tw = [&](auto s_tag, const float2 *__restrict__ twp) {
-            constexpr int S = decltype(s_tag)::value;
-            gcfft::dit<+1, NT, 1>(
-                [&](int p) {
-                    RawT t;
-                    t.r = load(p);
-                    t.ta = *reinterpret_cast<const float4 *>(twp + p);
-                    t.tb = *reinterpret_cast<const float4 *>(twp + p + 2);
-                    return t;
-                },
-                [&](const RawT &t, float2 &x0, float2 &x1, float2 &x2, float2 &x3) {
-                    float2 z[4];
-#pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        const float2 y0 = Y(t.r, 0, k), y1 = Y(t.r, 1, k), y2 = Y(t.r, 2, k), y3 = Y(t.r, 3, k);
-                        float2 v;
-                        if (S == 2) v = csub(cadd(y0, y2), cadd(y1, y3));
-                        else {
-                            const float2 d = csub(y1, y3), id = make_float2(-d.y, d.x);
-                            v = S == 1 ? cadd(csub(y0, y2), id) : csub(csub(y0, y2), id);
-                        }
-                        const float2 w = k == 0 ? make_float2(t.ta.x, t.ta.y) : k == 1 ? make_float2(t.ta.z, t.ta.w)
-                                       : k == 2 ? make_float2(t.tb.x, t.tb.y) : make_float2(t.tb.z, t.tb.w);
-                        z[k] = cmulc(v, w);          // exp(+2 pi i f s/65536) = conj of the forward twiddle
-                    }
-                    x0 = z[0]; x1 = z[1]; x2 = z[2]; x3 = z[3];
-                },
-                [&](int h, int, float2 (&a)[16]) {
-#pragma unroll
-                    for (int q = 0; q < 8; q++) {
-                        const float pw = fmaf(a[q].x, a[q].x, a[q].y * a[q].y) * invL2;
-                        P[16 * S + 8 * h + q] += (double)pw;
-                    }
-                },
-                lds, tw16k, tid);
-        };
-        residue(std::integral_constant<int, 0>{});
+        residue(std::integral_constant<int, 0>{}, nullptr);
         __syncthreads();
         asm volatile("" : "+v"(tid));
-        residue_tw(std::integral_constant<int, 1>{}, tw64p1);
+        residue(std::integral_constant<int, 1>{}, tw64p1);
         __syncthreads();
         asm volatile("" : "+v"(tid));
-        residue_tw(std::integral_constant<int, 2>{}, tw32p);
+        residue(std::integral_constant<int, 2>{}, tw32p);
         __syncthreads();
         asm volatile("" : "+v"(tid));
-        residue_tw(std::integral_constant<int, 3>{}, tw64p3);
+        residue(std::integral_constant<int, 3>{}, tw64p3);
 
-        // row statistics for checkacquisition()
-        MaxIdx m; m.v = -1.0; m.k = 0x7fffffff;
-#pragma unroll
-        for (int s = 0; s < NP; s++) {
-            const int k = lag_of(tid, s);
-            if (k < n) { MaxIdx t; t.v = P[s]; t.k = k; m = better(m, t); }
-        }
-        m = wg_argmax<NT>(m, sd, si, tid);
-        int exs = m.k - nsc2; if (exs < 0) exs += n;
-        int exe = m.k + nsc2; if (exe >= n) exe -= n;
-        double so = 0.0, mo = -1.0;
-#pragma unroll
-        for (int s = 0; s < NP; s++) {
-            const int k = lag_of(tid, s);
-            if (k < n) {
-                const bool outside = (exs <= exe) ? (k < exs || k > exe) : (k < exs && k > exe);
-                if (outside) so += P[s];
-                if (outside || k == 0) mo = fmax(mo, P[s]);    // element 0 seeds maxvd()
-            }
-        }
-        wg_sum_max<NT>(so, mo, sd, tid);
-        if (tid == 0) {
-            GcAcqRow r;
-            r.rowmax = m.v; r.sum_out = so; r.max_out = mo; r.argmax = m.k; r.pad = 0;
-            rows[((size_t)ch * maxintg + it) * maxfreq + bin] = r;
-        }
+        const GcAcqRow r = acq_row_stats<NT>(P, lag_of, n, nsc2, sd, si, tid);
+        if (tid == 0) rows[((size_t)ch * maxintg + it) * maxfreq + bin] = r;
         __syncthreads();
     }
-    if (Pout) {
-#pragma unroll
-        for (int s = 0; s < NP; s++) {
-            const int k = lag_of(tid0, s);
-            if (k < n) Pout[(size_t)bin * n + k] = P[s];
-        }
-    }
+    if (Pout) acq_write_power(Pout, P, lag_of, tid0, bin, n);
+}
+
+// The tracking state an acquired channel starts with, where sdracquisition() leaves it (ref src/sdracq.c:51-55:
+// trk.carrfreq = acq.acqfreq, trk.codefreq = crate, code and carrier remainders zero, tracking from the returned
+// buffloc)
+__device__ __forceinline__ GcTrkState acq_start_state(const gnsscorr_acqres_t &r, const GcChan &c)
+{
+    GcTrkState s;
+    s.carrfreq = r.acqfreq;
+    s.codefreq = c.crate;
+    s.remcode = 0.0;
+    s.remcarr = 0.0;
+    s.buffloc = r.buffloc;
+    return s;
 }
 
 // acq_final: one wavefront per listed channel; the lanes share the bins of an iteration
@@ -757,20 +751,7 @@ __global__ __launch_bounds__(64) void acq_final_kernel(const GcChan *__restrict_
     int it = 0;
     for (; it < c.intg; it++) {
         const GcAcqRow *row = rows + ((size_t)ch * maxintg + it) * maxfreq;
-        // best row: largest rowmax, lowest flat index (= lowest bin) on ties
-        double bv = -1.0;
-        int bi = 0x7fffffff;
-        for (int b = lane; b < c.nfreq; b += 64) {
-            const double v = row[b].rowmax;
-            if (v > bv) { bv = v; bi = b; }
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const double ov = __shfl_xor(bv, d);
-            const int oi = __shfl_xor(bi, d);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
-        const int fi = bi;
+        const int fi = acq_best_row(row, c.nfreq, lane);
         const GcAcqRow w = row[fi];
         const int ne = 4 * c.nsampchip + 1;                     // samples inside the excluded window
         const double meanP = w.sum_out / (double)(n - ne);
@@ -779,7 +760,7 @@ __global__ __launch_bounds__(64) void acq_final_kernel(const GcChan *__restrict_
         r.acqcodei = w.argmax;
         r.freqi = fi;
         r.acqfreq = freqs[c.freq_off + fi];
-        if (r.peakr > 3.0) { r.flagacq = 1; break; }            // ACQTH, ref src/sdr.h:148
+        if (acq_passes(w)) { r.flagacq = 1; break; }
     }
     r.iters = r.flagacq ? it + 1 : c.intg;
     // ref src/sdracq.c:51-53 / :62
@@ -874,9 +855,9 @@ static int acq_tables(gnsscorr_ctx *ctx)
         const int lds = GC_FFT_LDS + 256;
         GC_HIP(hipFuncSetAttribute((const void *)acq_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds + GC_ACQ_CARLDS));
         GC_HIP(hipFuncSetAttribute((const void *)acq_code_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        GC_HIP(hipFuncSetAttribute((const void *)acq_corr_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + 256));
-        GC_HIP(hipFuncSetAttribute((const void *)acq_corr_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + 256));
-        GC_HIP(hipFuncSetAttribute((const void *)acq_corr64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds + 256));
+        GC_HIP(hipFuncSetAttribute((const void *)acq_corr_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, GC_ACQ_CORR_LDS));
+        GC_HIP(hipFuncSetAttribute((const void *)acq_corr_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, GC_ACQ_CORR_LDS));
+        GC_HIP(hipFuncSetAttribute((const void *)acq_corr64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GC_ACQ_CORR_LDS));
         GC_HIP(hipFuncSetAttribute((const void *)fft16k_kernel<-1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         GC_HIP(hipFuncSetAttribute((const void *)fft16k_kernel<+1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         GC_HIP(hipFuncSetAttribute((const void *)pspec_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -947,6 +928,31 @@ static int acq_prepare(gnsscorr_ctx *ctx)
         return gc_fail(GNSSCORR_EINVAL, "acquisition: %d Doppler bins need more carrier NCO pieces than the tables hold", over);
     }
     return GNSSCORR_OK;
+}
+
+// acq_corr over the list dlist[0..n) with early stop (Pout null), or the power array of channel pout_ch into Pout
+// (no early stop; always the 512-lane kernel).  GNSSCORR_ACQ_NT=1024: the 1024-lane variant of the 32768-point search.
+static void launch_acq_corr(gnsscorr_ctx *ctx, GcAcqWork *w, double *Pout, int pout_ch, const int *dlist, int n)
+{
+    static const int nt = getenv("GNSSCORR_ACQ_NT") ? atoi(getenv("GNSSCORR_ACQ_NT")) : 512;
+    const bool pout = Pout != nullptr;
+    const int nbins = pout ? ctx->hchan[pout_ch].nfreq : w->maxfreq;
+    int *arrive = pout ? nullptr : (int *)w->arrive;         // [ch][iter] arrival counters, then [ch] "acquired" flags
+    int *done = pout ? nullptr : w->arrive + (size_t)ctx->nch * w->maxintg;
+    auto corr32 = [&](auto nt_tag) {
+        constexpr int NT = decltype(nt_tag)::value;
+        hipLaunchKernelGGL(acq_corr_kernel<NT>, dim3(acq_corr_blocks(nbins, n, pout)), dim3(NT), GC_ACQ_CORR_LDS,
+                           ctx->stream, ctx->dchan, w->tw16k, w->tw32p, w->X, w->C, w->iters, w->rows, Pout, pout_ch,
+                           w->maxfreq, w->maxintg, dlist, n, arrive, done);
+    };
+    if (w->L == 2 * GC_L)
+        hipLaunchKernelGGL(acq_corr64_kernel, dim3(acq_corr64_blocks(nbins, n, pout)), dim3(512), GC_ACQ_CORR_LDS,
+                           ctx->stream, ctx->dchan, w->tw16k, w->tw32p, w->tw64p1, w->tw64p3, w->X, w->C, w->iters,
+                           w->rows, Pout, pout_ch, w->maxfreq, w->maxintg, dlist, n);
+    else if (nt == 1024 && !pout)
+        corr32(std::integral_constant<int, 1024>{});
+    else
+        corr32(std::integral_constant<int, 512>{});
 }
 
 // One search over the channels chlist[0..n) (distinct; nullptr: all of them).  wp_ring[r]: write position of ring
@@ -1025,21 +1031,7 @@ int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chl
     GC_HIP(hipMemsetAsync(w->arrive, 0, sizeof(int) * ((size_t)nch * w->maxintg + nch), ctx->stream));
     {
         GcTimed t(ctx, "acq_corr");
-        static const int nt = getenv("GNSSCORR_ACQ_NT") ? atoi(getenv("GNSSCORR_ACQ_NT")) : 512;
-        // (bins per XCD slot) x (listed channels, in groups of GC_ACQ_G) x 8 slots
-        const unsigned acq_grid = 8u * (unsigned)((w->maxfreq + 7) / 8) * (unsigned)(GC_ACQ_G * ((n + GC_ACQ_G - 1) / GC_ACQ_G));
-        if (w->L == 2 * GC_L)
-            hipLaunchKernelGGL(acq_corr64_kernel, dim3(8 * ((n + 7) / 8) * w->maxfreq), dim3(512), lds + 256,
-                               ctx->stream, ctx->dchan, w->tw16k, w->tw32p, w->tw64p1, w->tw64p3, w->X, w->C, w->iters,
-                               w->rows, (double *)nullptr, 0, w->maxfreq, w->maxintg, dlist, n);
-        else if (nt == 1024)
-            hipLaunchKernelGGL(acq_corr_kernel<1024>, dim3(acq_grid), dim3(1024), lds + 256,
-                               ctx->stream, ctx->dchan, w->tw16k, w->tw32p, w->X, w->C, w->iters, w->rows,
-                               (double *)nullptr, 0, w->maxfreq, w->maxintg, dlist, n, w->arrive, w->arrive + (size_t)nch * w->maxintg);
-        else
-            hipLaunchKernelGGL(acq_corr_kernel<512>, dim3(acq_grid), dim3(512), lds + 256,
-                               ctx->stream, ctx->dchan, w->tw16k, w->tw32p, w->X, w->C, w->iters, w->rows,
-                               (double *)nullptr, 0, w->maxfreq, w->maxintg, dlist, n, w->arrive, w->arrive + (size_t)nch * w->maxintg);
+        launch_acq_corr(ctx, w, nullptr, 0, dlist, n);
     }
     GC_HIP(hipGetLastError());
     {
@@ -1078,21 +1070,13 @@ extern "C" int gnsscorr_acq_fetch(gnsscorr_ctx *ctx, gnsscorr_acqres_t *res)
     return GNSSCORR_OK;
 }
 
-// Acquired channels start tracking where sdracquisition() leaves them (ref src/sdracq.c:51-55:
-// trk.carrfreq = acq.acqfreq, trk.codefreq = crate, code and carrier remainders zero, tracking from the
-// returned buffloc); channels that were not acquired keep their state.
+// Acquired channels start tracking from acq_start_state(); channels that were not acquired keep their state.
 __global__ void acq_to_trk_kernel(const GcChan *__restrict__ chan, const gnsscorr_acqres_t *__restrict__ res,
                                   GcTrkState *__restrict__ state, int nch)
 {
     const int ch = blockIdx.x * blockDim.x + threadIdx.x;
     if (ch >= nch || !res[ch].flagacq) return;
-    GcTrkState s;
-    s.carrfreq = res[ch].acqfreq;
-    s.codefreq = chan[ch].crate;
-    s.remcode = 0.0;
-    s.remcarr = 0.0;
-    s.buffloc = res[ch].buffloc;
-    state[ch] = s;
+    state[ch] = acq_start_state(res[ch], chan[ch]);
 }
 
 extern "C" int gnsscorr_trk_start_from_acq(gnsscorr_ctx *ctx)
@@ -1130,13 +1114,7 @@ __global__ __launch_bounds__(64) void acq_to_loop_kernel(const GcChan *__restric
     for (int k = b0 + tid; k < b1; k += 64) w[k] = 0;
     if (tid == 0) {
         loop[ch].acqfreq = r.acqfreq;
-        GcTrkState s;
-        s.carrfreq = r.acqfreq;
-        s.codefreq = chan[ch].crate;
-        s.remcode = 0.0;
-        s.remcarr = 0.0;
-        s.buffloc = r.buffloc;
-        state[ch] = s;
+        state[ch] = acq_start_state(r, chan[ch]);
     }
 }
 
@@ -1166,14 +1144,7 @@ extern "C" int gnsscorr_acq_power(gnsscorr_ctx *ctx, int ch, double *power)
     GC_RESERVE(ctx, w->P, elems);
     // iteration count of the last run is still in w->iters[ch]; rows of this channel are rewritten
     // with identical values
-    if (w->L == 2 * GC_L)
-        hipLaunchKernelGGL(acq_corr64_kernel, dim3(8 * ((c.nfreq + 7) / 8)), dim3(512), GC_FFT_LDS + 512,
-                           ctx->stream, ctx->dchan, w->tw16k, w->tw32p, w->tw64p1, w->tw64p3, w->X, w->C, w->iters,
-                           w->rows, w->P, ch, w->maxfreq, w->maxintg, (const int *)nullptr, 0);
-    else
-        hipLaunchKernelGGL(acq_corr_kernel<512>, dim3(8 * ((c.nfreq + 7) / 8)), dim3(512), GC_FFT_LDS + 512,
-                           ctx->stream, ctx->dchan, w->tw16k, w->tw32p, w->X, w->C, w->iters, w->rows, w->P, ch,
-                           w->maxfreq, w->maxintg, (const int *)nullptr, 0, (int *)nullptr, (int *)nullptr);
+    launch_acq_corr(ctx, w, w->P, ch, nullptr, 0);
     GC_HIP(hipGetLastError());
     GC_HIP(hipMemcpyAsync(power, w->P, sizeof(double) * elems, hipMemcpyDeviceToHost, ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
