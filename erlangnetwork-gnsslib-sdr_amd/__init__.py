@@ -156,6 +156,25 @@ class RxStat(C.Structure):
                 ("acq", AcqRes), ("cnt", C.c_uint64)]
 
 
+class LockPrm(C.Structure):
+    """gnsscorr_lockprm_t: the lock monitor's parameters (kbits 0: off)."""
+    _fields_ = [("sync_periods", C.c_int), ("kbits", C.c_int), ("nbad", C.c_int), ("pad", C.c_int), ("mu_min", C.c_double)]
+
+
+class LockState(C.Structure):
+    """gnsscorr_lock_t: the lock detector's state of one channel."""
+    _fields_ = ([(n, C.c_double) for n in ("sI", "sQ", "w", "npsum", "mu_last")] + [("lost_cnt", C.c_uint64)] +
+                [(n, C.c_int) for n in ("open", "n", "k", "nbad", "lost", "reason", "windows", "pad")])
+
+
+def mu_from_cn0(cn0_dbhz, rate, ctime):
+    """The mean narrow-band / wide-band power ratio of a nav bit of `rate` periods of `ctime` seconds at that C/N0:
+    (1 + rate*x) / (1 + x) with x = 10^(cn0/10) * ctime, the inverse of C/N0 = (mu - 1) / ((rate - mu) * ctime).  For
+    callers who think of the monitor's mu_min in dB-Hz; the tracker biases the measured mu low."""
+    x = 10.0 ** (cn0_dbhz / 10.0) * ctime
+    return (1.0 + rate * x) / (1.0 + x)
+
+
 # ---- ctypes mirrors of include/sdr_compat.h (ref src/sdr.h:344-511) --------
 OBSINTERPN = 80
 
@@ -232,7 +251,8 @@ EXPORTS_GNSSCORR = [
     "gnsscorr_timing_enable", "gnsscorr_timing_read", "gnsscorr_timing_reset", "gnsscorr_default_ctx",
     "gnsscorr_spec_run", "gnsscorr_spec_fetch", "gnsscorr_trk_loop_lapped",
     "gnsscorr_acq_run_subset", "gnsscorr_loop_start_from_acq", "gnsscorr_rx_start", "gnsscorr_rx_set",
-    "gnsscorr_rx_step", "gnsscorr_rx_status", "gnsscorr_fec_run", "gnsscorr_sbasframe_replay"]
+    "gnsscorr_rx_step", "gnsscorr_rx_status", "gnsscorr_fec_run", "gnsscorr_sbasframe_replay",
+    "gnsscorr_lock_run", "gnsscorr_rx_lock_set", "gnsscorr_rx_lock_status"]
 EXPORTS_SDR = [
     "sdracquisition", "checkacquisition", "sdrtracking", "cumsumcorr", "clearcumsumcorr", "pll", "dll",
     "readinifile", "chk_initvalue", "initacqstruct", "inittrkprmstruct", "inittrkstruct", "initsdrch",
@@ -303,6 +323,9 @@ def lib():
     L.gnsscorr_fec_run.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p, C.c_int]
     L.gnsscorr_sbasframe_replay.argtypes = [C.c_void_p, C.POINTER(SbasFrameState), C.c_void_p, C.c_int, C.c_uint64,
                                             C.c_void_p, C.c_int]
+    L.gnsscorr_lock_run.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int, C.c_int]
+    L.gnsscorr_rx_lock_set.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(LockPrm)]
+    L.gnsscorr_rx_lock_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.gnsscorr_debug_fec_parts.argtypes = [C.c_void_p, C.c_int]   # (tools; not part of include/gnsscorr.h)
     L.gnsscorr_debug_poison.argtypes = [C.c_void_p, C.c_int]      # (tests; not part of include/gnsscorr.h)
     if hasattr(L, "gnsscorr_debug_cmb_stats"):                    # (tests; bound when present, like the symbols below)
@@ -673,6 +696,42 @@ class Engine:
                      acq=dict(acqcodei=a.acq.acqcodei, freqi=a.acq.freqi, acqfreq=a.acq.acqfreq, cn0=a.acq.cn0,
                               peakr=a.acq.peakr, flagacq=a.acq.flagacq, iters=a.acq.iters, buffloc=a.acq.buffloc))
                 for a in arr]
+
+    # -- lock monitor
+    def rx_lock_set(self, prm=None, ch0=0, nch=None):
+        """The lock monitor's parameters for channels ch0 .. ch0+nch-1 (default: all from ch0 on): a LockPrm, a dict of
+        its fields, or None to switch it off."""
+        nch = len(self.channels) - ch0 if nch is None else nch
+        if isinstance(prm, dict):
+            prm = LockPrm(**prm)
+        _check(self._L.gnsscorr_rx_lock_set(self.h, ch0, nch, C.byref(prm) if prm is not None else None))
+
+    def rx_lock_status(self):
+        """(states, losses): numpy arrays [nch] of LockState and of int32 (gnsscorr_rx_lock_status)."""
+        nch = len(self.channels)
+        st = np.zeros(nch, dtype=np.dtype(LockState))
+        losses = np.zeros(nch, np.int32)
+        _check(self._L.gnsscorr_rx_lock_status(self.h, st.ctypes.data, losses.ctypes.data))
+        return st, losses
+
+    def lock_run(self, prm, rate, st, I, Q, log, ndone, cnt0):
+        """gnsscorr_lock_run: prm [nch] of LockPrm, rate [nch], st [nch] of LockState (updated in place), I / Q
+        [nch][nper], log [nch][nper] of TrkLog, ndone [nch], cnt0 [nch].  Returns st."""
+        I = np.ascontiguousarray(I, dtype=np.float64)
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        nch, nper = I.shape
+        prm = np.ascontiguousarray(prm, dtype=np.dtype(LockPrm))
+        rate = np.ascontiguousarray(rate, dtype=np.int32)
+        log = np.ascontiguousarray(log, dtype=np.dtype(TrkLog))
+        ndone = np.ascontiguousarray(ndone, dtype=np.int32)
+        cnt0 = np.ascontiguousarray(cnt0, dtype=np.uint64)
+        if not (Q.shape == log.shape == (nch, nper) and prm.shape == rate.shape == ndone.shape == cnt0.shape == st.shape == (nch,)):
+            raise ValueError("lock_run: array shapes")
+        if st.dtype != np.dtype(LockState) or not st.flags.c_contiguous:
+            raise ValueError("lock_run: st must be a contiguous array of LockState")
+        _check(self._L.gnsscorr_lock_run(self.h, prm.ctypes.data, rate.ctypes.data, st.ctypes.data, I.ctypes.data, Q.ctypes.data,
+                                         log.ctypes.data, ndone.ctypes.data, cnt0.ctypes.data, nch, nper))
+        return st
 
     # -- IF monitor
     def spectrum(self, ftype, buffloc, n, f_sf, nfft=16384, nloop=SPEC_NLOOP, offsets=None, seed=None):

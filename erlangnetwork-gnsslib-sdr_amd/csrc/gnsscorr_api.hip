@@ -44,7 +44,7 @@ static void destroy_handles(gnsscorr_ctx *ctx)
     for (GcPlanSlot &s : ctx->slot)
         for (hipEvent_t e : {s.ev_plan, s.ev_used, s.ev_corr, s.ev_fin})
             if (e) hipEventDestroy(e);
-    for (hipEvent_t e : {ctx->ev_spec, ctx->ev_chain, ctx->ev_pin[0], ctx->ev_pin[1], ctx->ev_in})
+    for (hipEvent_t e : {ctx->ev_spec, ctx->ev_chain, ctx->ev_pin[0], ctx->ev_pin[1], ctx->ev_in, ctx->ev_lock})
         if (e) hipEventDestroy(e);
     for (hipStream_t s : {ctx->stream_plan, ctx->stream_finish, ctx->stream_discover, ctx->stream_in})
         if (s) hipStreamDestroy(s);
@@ -116,6 +116,7 @@ static void drop_channel_buffers(gnsscorr_ctx *ctx)
     ctx->state_cur = 0;
     ctx->loop_isset.clear();
     ctx->rx = GcRx();
+    ctx->lock_pending = false;
 }
 
 extern "C" void gnsscorr_destroy(gnsscorr_ctx *ctx)

@@ -119,6 +119,15 @@ struct GcRx {
     bool on = false;
     int retry_ms = 0;                              // the reference's ACQSLEEP, counted on each channel's sample clock
     std::vector<gnsscorr_rxstat_t> st;             // [nch] (cnt is filled in by gnsscorr_rx_status)
+    // the lock monitor (gnsscorr_lock.hip), off until gnsscorr_rx_lock_set
+    std::vector<gnsscorr_lockprm_t> lockprm;       // [nch]; kbits 0: the channel's monitor is off
+    std::vector<int> losses;                       // [nch] times the channel was sent back to SEARCH
+    int lock_on = 0;                               // channels whose monitor is on
+    std::vector<int> lock_listed;                  // the channels of the launch whose words are still to be read
+    GcDevBuf<gnsscorr_lockprm_t> dlockprm;         // [nch]
+    GcDevBuf<gnsscorr_lock_t> dlock;               // [nch] the detector's state
+    GcPinBuf<int> lock_list;                       // mapped: [nch] the channels of a launch (host writes, kernel reads)
+    GcPinBuf<unsigned> lock_lost;                  // mapped: [nch] 1: the launch declared the channel lost (kernel writes)
 };
 
 struct gnsscorr_ctx {
@@ -192,6 +201,8 @@ struct gnsscorr_ctx {
     bool loop_sync_hint = false;                   // some channel had its nav bit synchronised when last seen
     std::vector<char> loop_isset;                  // [nch] the channel's loop constants have been set (gnsscorr_loop_set)
     GcRx rx;
+    hipEvent_t ev_lock = nullptr;                  // end of the last lock monitor launch (made on first use)
+    bool lock_pending = false;                     // ev_lock is recorded and rx.lock_lost not read yet
     int loop_kmax = 1;                             // largest loopms among the channels' loop states (gnsscorr_loop_set)
     GcDevBuf<gnsscorr_trklog_t> dlooplog;          // [nch][nperiod]
     GcDevBuf<int> dloop_lapped;                    // periods of the last trk_run_loop read after the writer lapped them
@@ -213,6 +224,9 @@ struct gnsscorr_ctx {
     GcDevBuf<signed char> dfec_sym;                // [nch][nsym]
     GcDevBuf<unsigned char> dfec_out;              // [nch][npos][rowbytes]
     int fec_parts = 3;                             // (tools) 3: the decoder; 1 / 2: forward pass / chainback alone
+
+    // lock monitor (gnsscorr_lock.hip): staging of gnsscorr_lock_run's host arrays
+    GcDevBuf<unsigned char> dlock_stage;
 
     // timing
     int timing = 0;                                // 0: off, 1: every kernel, 2: only the two correlator kernels (trk_corr, acq_corr)
@@ -255,3 +269,6 @@ int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chl
 int gc_acq_handover(gnsscorr_ctx *ctx, bool quiesce);
 // gnsscorr_api.hip: gnsscorr_trk_run_loop with per-channel write positions
 int gc_trk_run_loop(gnsscorr_ctx *ctx, int nperiod, const uint64_t *wp_ch);
+// gnsscorr_lock.hip: the lock monitor over the periods the last gc_trk_run_loop tracked, for the TRACK channels that have
+// it on; queues the launch and its event on the context's stream and does not wait
+int gc_rx_lock_launch(gnsscorr_ctx *ctx, int nperiod);

@@ -3,7 +3,9 @@
 // code period after the other.  The states live on the host, which needs them to size the launches; the work they
 // select runs on the device: the due channels' search as one list (gnsscorr_acq.hip), the hand-over of the acquired
 // ones into the closed loop (acq_to_loop_kernel), and the closed loop itself, in which a channel that is not tracking
-// is handed a write position of 0 and so plans nothing (trk_step_tail_kernel, ref src/sdrtrk.c:26-30).
+// is handed a write position of 0 and so plans nothing (trk_step_tail_kernel, ref src/sdrtrk.c:26-30).  The way back,
+// TRACK -> SEARCH, which the reference lacks, is the lock monitor's (gnsscorr_lock.hip): it runs behind the closed loop
+// of a step, and the next step reads its verdicts.
 //
 // The reference sleeps ACQSLEEP = 2000 ms of wall time after a failed search (ref src/sdracq.c:57-60).  Here the pause
 // is counted on the sample clock -- retry_ms * 1e-3 * f_sf samples of the channel's ring from the write position of
@@ -28,6 +30,14 @@ extern "C" int gnsscorr_rx_start(gnsscorr_ctx *ctx, int retry_ms)
     gnsscorr_rxstat_t z;
     memset(&z, 0, sizeof(z));
     rx.st.assign(ctx->nch, z);
+    // the lock monitor is off for all; a launch of an earlier schedule is waited for and its verdicts dropped
+    if (ctx->lock_pending) GC_HIP(hipEventSynchronize(ctx->ev_lock));
+    ctx->lock_pending = false;
+    const gnsscorr_lockprm_t off = {0, 0, 0, 0, 0.0};
+    rx.lockprm.assign(ctx->nch, off);
+    rx.losses.assign(ctx->nch, 0);
+    rx.lock_on = 0;
+    rx.lock_listed.clear();
     for (int i = 0; i < ctx->nch; i++) {
         rx.st[i].state = GNSSCORR_CH_SEARCH;
         rx.st[i].next_try = rx_first_try(ctx->hchan[i]);
@@ -66,6 +76,19 @@ extern "C" int gnsscorr_rx_step(gnsscorr_ctx *ctx, int max_periods)
         wpr[0] = ctx->ring[0].wrpos;
         wpr[1] = ctx->ring[1].wrpos;
     }
+    // 0. the verdicts of the monitor launch behind the previous step's closed loop: a TRACK channel it declared lost is
+    //    due at this step's write position.  Words of channels that are no longer TRACK (parked or re-armed since) are
+    //    ignored.
+    if (ctx->lock_pending) {
+        GC_HIP(hipEventSynchronize(ctx->ev_lock));
+        ctx->lock_pending = false;
+        for (int i : rx.lock_listed) {
+            if (!rx.lock_lost[i] || rx.st[i].state != GNSSCORR_CH_TRACK) continue;
+            rx.st[i].state = GNSSCORR_CH_SEARCH;
+            rx.st[i].next_try = wpr[ctx->hdesc[i].ftype - 1];
+            rx.losses[i]++;
+        }
+    }
     // 1. the channels whose search is due, as one list
     std::vector<int> due;
     for (int i = 0; i < nch; i++) {
@@ -96,7 +119,10 @@ extern "C" int gnsscorr_rx_step(gnsscorr_ctx *ctx, int max_periods)
     // 3. the closed loop for the tracking channels, those acquired above included
     std::vector<uint64_t> wp(nch);
     for (int i = 0; i < nch; i++) wp[i] = rx.st[i].state == GNSSCORR_CH_TRACK ? wpr[ctx->hdesc[i].ftype - 1] : 0;
-    return gc_trk_run_loop(ctx, max_periods, wp.data());
+    int rc = gc_trk_run_loop(ctx, max_periods, wp.data());
+    if (rc || !rx.lock_on) return rc;
+    // 4. the lock monitor over the periods just tracked, behind the loop's last tail; nothing waits for it here
+    return gc_rx_lock_launch(ctx, max_periods);
 }
 
 extern "C" int gnsscorr_rx_status(gnsscorr_ctx *ctx, gnsscorr_rxstat_t *st)

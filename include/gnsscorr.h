@@ -400,6 +400,43 @@ int  gnsscorr_rx_step(gnsscorr_ctx *ctx, int max_periods);
 /* st[nch]; synchronises the stream (cnt comes from the device's loop state) */
 int  gnsscorr_rx_status(gnsscorr_ctx *ctx, gnsscorr_rxstat_t *st);
 
+/* ---- lock monitor: detect loss of lock on the device, send the channel back to SEARCH ----
+ * The reference never clears flagacq: a channel whose satellite sets, or that was acquired on noise, tracks noise for
+ * the rest of the run.  The monitor is the missing TRACK -> SEARCH edge of the schedule above.  Opt-in per channel;
+ * with it off for every channel gnsscorr_rx_step issues the launches and synchronisations it issues without it.
+ * The detector (DESIGN.md 3.2b states it line by line) reads, per tracked period, the prompt sums (tap 0 of
+ * gnsscorr_trk_fetch's II / QQ) and the log row's flagsync and navbit:
+ *   reason 1  the nav bit is not synchronised in the period with cnt + 1 >= sync_periods (sync_periods 0: no such rule);
+ *   reason 2  from bit synchronisation on, per whole nav bit (rate periods between two decided bits) the narrow-band /
+ *             wide-band power ratio np = ((sum I)^2 + (sum Q)^2) / sum (I^2 + Q^2), which is rate for a clean signal
+ *             and about 1 for noise; mu = the mean of kbits consecutive np; nbad consecutive windows with
+ *             mu < mu_min.  The usual C/N0 estimate is (mu - 1) / ((rate - mu) * ctime); the tracker biases mu low.
+ * A lost state is sticky until the hand-over of the next acquisition restarts cnt at 0, which resets the state. */
+typedef struct { int sync_periods, kbits, nbad, pad; double mu_min; } gnsscorr_lockprm_t;
+typedef struct { double sI, sQ, w, npsum, mu_last; uint64_t lost_cnt;
+                 int open, n, k, nbad, lost, reason, windows, pad; } gnsscorr_lock_t;
+/* Op-level: the monitor's kernel over host arrays.  prm[nch], rate[nch] (periods per nav bit, 2..20), st[nch] in-out,
+ * I / Q [nch][nper], log[nch][nper] (only flagsync and navbit are read), ndone[nch] (rows of each channel that count,
+ * 0..nper), cnt0[nch] (sdrthread's cnt of row 0).  kbits 1..4096, nbad >= 1, sync_periods >= 0, 0 < mu_min <= rate:
+ * otherwise GNSSCORR_EINVAL naming the field, st untouched.  Runs on the context's stream and synchronises it; timer
+ * name "rx_lock". */
+int  gnsscorr_lock_run(gnsscorr_ctx *ctx, const gnsscorr_lockprm_t *prm, const int *rate, gnsscorr_lock_t *st,
+                       const double *I, const double *Q, const gnsscorr_trklog_t *log, const int *ndone,
+                       const uint64_t *cnt0, int nch, int nper);
+/* The monitor's parameters for channels ch0 .. ch0+nch-1 of the schedule (one prm for all of them); prm == NULL or
+ * kbits == 0 switches it off for them.  Their detector state is zeroed.  gnsscorr_rx_start leaves the monitor off for
+ * all.  Values as above, against each channel's gnsscorr_loop_t.rate; without gnsscorr_rx_start GNSSCORR_ESTATE.
+ * With the monitor on, gnsscorr_rx_step
+ *   0. reads the verdicts of the previous step's launch (it waits for that launch): a TRACK channel declared lost goes
+ *      to SEARCH, due at this step's write position, and is searched in this very step if its look-back fits;
+ *   4. behind the closed loop, queues the monitor over the periods this step tracked for the TRACK channels that have
+ *      it on, without waiting for it.
+ * A loss found in step k therefore takes effect at the start of step k + 1; a failed re-search pauses like any other. */
+int  gnsscorr_rx_lock_set(gnsscorr_ctx *ctx, int ch0, int nch, const gnsscorr_lockprm_t *prm);
+/* st[nch]: the detector states on the device, behind whatever the stream still runs; losses[nch]: how often the schedule
+ * has sent each channel back to SEARCH.  Either may be NULL.  Synchronises. */
+int  gnsscorr_rx_lock_status(gnsscorr_ctx *ctx, gnsscorr_lock_t *st, int *losses);
+
 /* ---- op-level device entry points (used by the per-call symbols and tests) --
  * 16384-point complex FFT batches on device memory, unnormalised, sign -1
  * forward / +1 backward; in/out are device pointers to float2[batch][16384] */
@@ -445,7 +482,7 @@ int  gnsscorr_spec_fetch(gnsscorr_ctx *ctx, double *s, size_t s_cap,
 /* per-kernel launch timing: enable, run, then read the accumulated HIP-event
  * time of the named kernel ("trk_corr", "trk_plan", "trk_spec", "trk_expand",
  * "trk_finish", "acq_fwd", "acq_corr", "acq_code", "acq_final", "spec_psd",
- * "spec_sum", "spec_hist", "fec_viterbi27").
+ * "spec_sum", "spec_hist", "fec_viterbi27", "rx_lock").
  * on = 1: every kernel; on = 2: only the two correlator kernels ("trk_corr",
  * "acq_corr"), leaving the planner and finish streams free of events; 0: off */
 int  gnsscorr_timing_enable(gnsscorr_ctx *ctx, int on);
