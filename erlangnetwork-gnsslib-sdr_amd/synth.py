@@ -1,7 +1,8 @@
 """Deterministic synthetic IF generator: int8 samples at f_sf,
 real (DTYPE=1) or interleaved I,Q (DTYPE=2), a handful of C/A (or GLONASS)
-signals with Doppler, code phase, 50 bps data and AWGN.  Host-side utility for
-tests and bench.py; not part of the correlation path."""
+signals with Doppler, code phase, 50 bps data (or symbols tied to the code
+epoch: SBAS L1) and AWGN.  Host-side utility for tests and bench.py; not part
+of the correlation path."""
 import numpy as np
 
 SEED = 20240601
@@ -12,7 +13,9 @@ def make_if(codes, nsamp, f_sf=16.368e6, f_if=0.0, dtype=2, sats=None, seed=SEED
     """codes: {prn: (chips int array, chip rate)}.  sats: list of dicts
     (prn, doppler Hz, code phase chips, cn0 dB-Hz, carrier phase rad; optional t_on, seconds: the satellite
     contributes nothing before it, and its code and carrier phase run from t = 0 as if it had always been there;
-    optional t_off, seconds: nothing from it on).
+    optional t_off, seconds: nothing from it on; optional symbol_periods: `bits` are symbols of that many code periods
+    tied to the code, symbol floor((codephase + rate*t) / (clen*symbol_periods)) of the absolute code phase, so that every
+    symbol edge is a code epoch -- SBAS L1: 2; without it `bits` change at 50 per second of t, wherever the code stands).
     Returns int8 array of shape (nsamp, 2) for dtype 2 or (nsamp,) for dtype 1."""
     rng = np.random.default_rng(seed)
     if sats is None:
@@ -36,7 +39,11 @@ def make_if(codes, nsamp, f_sf=16.368e6, f_if=0.0, dtype=2, sats=None, seed=SEED
             c = chips[cph.astype(np.int64)].astype(np.float64)
             bit = s.get("bits")
             if bit is not None:
-                c = c * bit[((t * 50.0).astype(np.int64)) % len(bit)]
+                sp = s.get("symbol_periods")
+                if sp is None:
+                    c = c * bit[((t * 50.0).astype(np.int64)) % len(bit)]
+                else:
+                    c = c * bit[np.floor((s["codephase"] + rate * t) / (clen * sp)).astype(np.int64) % len(bit)]
             if s.get("t_on") is not None:
                 c = c * (t >= s["t_on"])
             if s.get("t_off") is not None:

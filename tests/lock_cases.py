@@ -23,6 +23,7 @@ INTG = 10
 FIRST_TRY = (INTG + 1) * NSAMP
 RETRY_SAMPLES = int(RETRY_MS * 1e-3 * F_SF)
 RATE = 20
+CTYPE_L1CA, CTYPE_SBAS = 1, 27
 T_OFF_12, T_ON_12, T_OFF_30 = 3.0, 5.0, 1.0
 TAPS = dict(corrn=2, corrd=3, corrp=3)       # the receiver's default taps
 PRM = dict(sync_periods=2600, kbits=10, nbad=2, mu_min=5.0)
@@ -72,20 +73,22 @@ def schedule_step(ch, wp, lost_word, search):
     return False
 
 
-def oracle_schedule(gc, orc, sig, prn, prm):
+def oracle_schedule(gc, orc, sig, prn, prm, ctype=CTYPE_L1CA, rate=RATE, taps=TAPS, wrpos=None, keep_rows=False):
     """The scenario of one channel on the oracle alone, free-running: orc_sdracquisition whenever the schedule rule makes
     a search due, orc_sdrthread_step for up to MAX_PERIODS periods per step while TRACK, the restated detector over each
-    step's periods.  Returns dict(steps=[per step: state, attempts, losses, searched, peakr, flagacq, ndone, cnt, lost_word],
-    events=[(kind, step, cnt, value)], sync=[cnt at which each run synchronised], runs=number of hand-overs,
-    lost_t=[stream time in seconds of each losing period])."""
+    step's periods.  ctype, rate: the channel's code type and the periods of its nav bit (L1 C/A: 20, SBAS: 2); wrpos: the
+    write position at each step (default: step_wrpos()).  Returns dict(steps=[per step: state, attempts, losses, searched,
+    peakr, flagacq, ndone, cnt, lost_word], events=[(kind, step, cnt, value)], sync=[cnt at which each run synchronised],
+    runs=number of hand-overs, lost_t=[stream time in seconds of each losing period], handover=[buffloc of each
+    hand-over]); with keep_rows also rows=[per step: dict(run, cnt0, navbit, buffloc)], run counting the hand-overs."""
     L = orc.lib()
     n = sig.shape[0]
     ring = orc.make_ring(sig, n, 0)
-    mk = lambda: orc.make_chan(prn, dtype=2, f_sf=F_SF, f_if=0.0, **TAPS)
+    mk = lambda: orc.make_chan(prn, ctype=ctype, dtype=2, f_sf=F_SF, f_if=0.0, **taps)
     box = dict(o=mk(), buffloc=C.c_uint64(0))
     ch = dict(state=1, next_try=FIRST_TRY, attempts=0, losses=0)
     st = lr.zero_state()
-    out = dict(steps=[], events=[], sync=[], runs=0, lost_t=[])
+    out = dict(steps=[], events=[], sync=[], runs=0, lost_t=[], handover=[], rows=[])
     lost_word = 0
 
     def search(wp):
@@ -96,9 +99,10 @@ def oracle_schedule(gc, orc, sig, prn, prm):
         if o.flagacq:
             out["runs"] += 1
             out["sync"].append(None)
+            out["handover"].append(b)
         return bool(o.flagacq)
 
-    for k, wp in enumerate(step_wrpos()):
+    for k, wp in enumerate(step_wrpos() if wrpos is None else wrpos):
         box["peakr"] = None
         searched = schedule_step(ch, wp, lost_word, search)
         o = box["o"]
@@ -117,10 +121,14 @@ def oracle_schedule(gc, orc, sig, prn, prm):
                 if o.flagsync and out["sync"][-1] is None:
                     out["sync"][-1] = int(o.cnt) - 1
         ev = []
-        lr.run(st, prm, RATE, rows["I"], rows["Q"], rows["fs"], rows["nb"], len(rows["I"]), cnt0, events=ev)
+        lr.run(st, prm, rate, rows["I"], rows["Q"], rows["fs"], rows["nb"], len(rows["I"]), cnt0, events=ev)
         lost_word = int(any(e[0] == "lost" for e in ev))
         out["events"] += [(e[0], k, e[1], e[2]) for e in ev]
         out["lost_t"] += [rows["b"][e[1] - cnt0] / F_SF for e in ev if e[0] == "lost"]
+        if keep_rows:
+            nd = len(rows["I"])
+            out["rows"].append(dict(run=out["runs"], cnt0=cnt0, navbit=np.array(rows["nb"], np.int32),
+                                    buffloc=np.array(rows["b"][:nd], np.uint64)))
         out["steps"].append(dict(state=ch["state"], attempts=ch["attempts"], losses=ch["losses"], searched=searched,
                                  peakr=box["peakr"], flagacq=int(o.flagacq), ndone=len(rows["I"]), cnt=int(o.cnt),
                                  lost_word=lost_word, next_try=ch["next_try"]))

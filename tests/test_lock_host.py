@@ -9,8 +9,11 @@ import subprocess
 import numpy as np
 import pytest
 
+import fec_restate as fr
 import lock_cases as lc
 import lock_restate as lr
+import lock_sbas_cases as ls
+import sbas_if_cases as sic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ["gnsscorr_lock_run", "gnsscorr_rx_lock_set", "gnsscorr_rx_lock_status"]
@@ -210,3 +213,111 @@ def test_loss_of_lock_scenario_is_decided_by_the_oracle(gc, orc, synth):
     h = H[9]
     assert [f for _, f in searches(h)] == [0] * 6 and states(h) == [1] * 32 and lost(h) == []
     assert all(s["peakr"] < 2.0 for s in h["steps"] if s["searched"])
+
+
+# ---- rate 2: SBAS channels inside the schedule, on the oracle alone ---------------------------------------------------
+def _windows(h, handover):
+    """[(start s, end s, mu)] of the monitor's windows of one oracle_schedule history, on the stream's clock: a window that
+    closes in the row with cnt c holds the KBITS symbols of the rows c - 2*KBITS + 1 .. c of the run that began at sample
+    `handover`."""
+    out = []
+    for e in h["events"]:
+        if e[0] == "mu":
+            end = (handover + (e[2] + 1) * ls.NSAMP) / ls.F_SF
+            out.append((end - 2 * ls.KBITS * 1e-3, end, e[3]))
+    return out
+
+
+def _replay(rows, run):
+    """SbasReplay over the decided symbols of one hand-over's rows (oracle_schedule with keep_rows)."""
+    sym, cnts, locs = [], [], []
+    for r in rows:
+        if r["run"] == run:
+            k = np.flatnonzero(r["navbit"])
+            sym += list(r["navbit"][k])
+            cnts += list(r["cnt0"] + k)
+            locs += list(r["buffloc"][k])
+    return sic.replayed(sym, cnts, locs), np.array(cnts)
+
+
+def test_rate2_thresholds_and_scenario_on_the_oracle(gc, orc, synth):
+    """tests/lock_sbas_cases.py on the oracle alone, free-running.
+
+    Thresholds.  With the detector watching only (nbad out of reach) the window means of KBITS = 50 symbols are measured:
+    the smallest of a channel locked on the right edge (PRN 120 while it is on, PRN 133 after its second hand-over) and
+    the largest of everything else (PRN 120's noise after T_OFF, PRN 133 on the wrong edge).  They are the numbers the
+    case file and DESIGN.md 3.2b state, MU_MIN is their midpoint, and each keeps a quarter of the detector's whole
+    range at rate 2 (1 to 2) from it: a window length that separates the two only barely fails here.
+
+    Decisions.  PRN 120 finds the right edge as its hand-over predicts, is never lost while on, holds its frame at the
+    predicted cnt and is lost by the power rule within NBAD + 1 windows of T_OFF; reason 1 never applies to an SBAS
+    channel (it synchronises on the first two like signs behind cnt 2000, signal or not).  PRN 133 finds the wrong
+    edge, looks like noise to the monitor, is lost by the power rule two windows later and searched again; its second
+    hand-over starts one code period off the first one's parity, finds the right edge and stays -- too late for a frame
+    in this recording.  PRN 12 (L1 C/A, the thresholds of tests/lock_cases.py) is never lost."""
+    sig = ls.signal(gc, synth)
+    assert sig.shape == (ls.NCHUNK * ls.CHUNK, 2) and ls.NCHUNK == 28 and ls.RATES == [2, 2, 20]
+    W = [ls.oracle_schedule(gc, orc, sig, i, ls.PRM_WATCH) for i in (0, 1)]
+    H = [ls.oracle_schedule(gc, orc, sig, i, keep_rows=True) for i in (0, 1, 2)]
+    lost = lambda h: [(e[1], e[2], e[3]) for e in h["events"] if e[0] == "lost"]
+    states = lambda h: [s["state"] for s in h["steps"]]
+    searches = lambda h: [(k, s["flagacq"]) for k, s in enumerate(h["steps"]) if s["searched"]]
+    limit = (ls.NBAD + 1) * ls.KBITS * 2 * 1e-3                          # seconds
+
+    # ---- the thresholds
+    assert W[0]["runs"] == W[1]["runs"] == 1 and lost(W[0]) == lost(W[1]) == []
+    w0 = _windows(W[0], W[0]["handover"][0])
+    on = [m for a, b, m in w0 if b <= ls.T_OFF]
+    off = [m for a, b, m in w0 if a >= ls.T_OFF]
+    assert len(on) == 40 and len(off) == 6 and len(w0) == 47            # one window straddles T_OFF
+    assert H[1]["runs"] == 2 and ls.predict(1, H[1]["handover"][1])[2]
+    relocked = [e[3] for e in H[1]["events"] if e[0] == "mu" and e[1] >= 10]      # (windows of the second run)
+    wrong = [m for _, _, m in _windows(W[1], W[1]["handover"][0])]
+    assert len(relocked) >= 20 and len(wrong) == 47
+    lo, hi = min(on + relocked), max(off + wrong)
+    print("rate 2, kbits %d: locked %.4f .. %.4f, noise %.4f .. %.4f, wrong edge %.4f .. %.4f" %
+          (ls.KBITS, lo, max(on + relocked), min(off), max(off), min(wrong), max(wrong)))
+    assert math.floor(lo * 100) / 100 == ls.MU_LOCKED_MIN and math.ceil(hi * 100) / 100 == ls.MU_OTHER_MAX
+    assert ls.MU_MIN == 0.5 * (ls.MU_LOCKED_MIN + ls.MU_OTHER_MAX) and ls.PRM_SBAS["mu_min"] == ls.MU_MIN
+    quarter = 0.25 * (ls.MU_LOCKED_MIN - ls.MU_OTHER_MAX)
+    assert lo - ls.MU_MIN >= quarter and ls.MU_MIN - hi >= quarter       # (a quarter of the gap: true of any midpoint ...)
+    assert lo - ls.MU_MIN >= 0.25 and ls.MU_MIN - hi >= 0.25             # ... and of the range 1 .. 2: true of a wide gap only
+
+    # windows of 10 symbols, what the L1 C/A scenario uses, do not keep that distance on the same signal
+    W10 = [ls.oracle_schedule(gc, orc, sig, i, dict(ls.PRM_WATCH, kbits=10)) for i in (0, 1)]
+    w10 = [(a + 0.08, b, m) for a, b, m in _windows(W10[0], W10[0]["handover"][0])]        # (a window is 0.02 s long here)
+    lo10 = min(m for a, b, m in w10 if b <= ls.T_OFF)
+    hi10 = max([m for a, b, m in w10 if a >= ls.T_OFF] + [m for _, _, m in _windows(W10[1], 0)])
+    print("rate 2, kbits 10: locked from %.4f, everything else up to %.4f" % (lo10, hi10))
+    assert 1.9 < lo10 < lo and hi < hi10 < 1.6 and lo10 - hi10 < 0.5
+
+    # ---- PRN 120: right edge, frame, loss after T_OFF
+    h = H[0]
+    row, synci, right, found = ls.predict(0, h["handover"][0])
+    assert (row, synci, right, found) == (2002, 0, True, 5052)
+    assert h["sync"] == [row] and h["runs"] == 1 and searches(h) == [(0, 1), (26, 0)]
+    assert lost(h) == [(25, 6202, 2)] and len(h["lost_t"]) == 1 and ls.T_OFF < h["lost_t"][0] <= ls.T_OFF + limit
+    assert states(h) == [2] * 26 + [1] * 2 and row + 1 < ls.PRM_SBAS["sync_periods"]
+    rep, cnts = _replay(h["rows"], 1)
+    assert np.all(np.diff(cnts) == 2) and cnts[0] == row
+    assert (rep.flagdec, rep.firstsfcnt, rep.firstsftow, rep.week) == (1, found, ls.TOW, ls.WEEK)
+    # 1000 periods behind the frame the next message is decoded: message 1 (type 2), one second later
+    assert found + 1000 <= cnts[-1] < found + 2000 and (rep.id, rep.tow) == (2, ls.TOW + 1)
+    assert rep.msg == bytes(np.packbits(np.array(sic.messages()[1] + [0] * 6, np.uint8))) and rep.polarity in (1, -1)
+
+    # ---- PRN 133: wrong edge, lost as noise, searched again
+    h = H[1]
+    first, second = ls.predict(1, h["handover"][0]), ls.predict(1, h["handover"][1])
+    assert first == (2002, 0, False, None) and second == (2003, 1, True, None)
+    assert ls.code_period(1, h["handover"][0]) % 2 == 0 and ls.code_period(1, h["handover"][1]) % 2 == 0
+    assert h["sync"] == [2002, 2003] and searches(h) == [(0, 1), (10, 1)]
+    mus = [(e[1], e[2], e[3]) for e in h["events"] if e[0] == "mu"]
+    assert [m[:2] for m in mus[:2]] == [(9, 2102), (9, 2202)] and all(m[2] < ls.MU_OTHER_MAX for m in mus[:2])
+    assert lost(h) == [(9, 2202, 2)] and states(h) == [2] * 28 and [s["losses"] for s in h["steps"]] == [0] * 10 + [1] * 18
+    assert all(m[2] > ls.MU_LOCKED_MIN for m in mus[2:])
+    rep, cnts = _replay(h["rows"], 2)
+    assert cnts[0] == 2003 and rep.flagtow == 0 and rep.fields() == fr.SbasReplay().fields()
+
+    # ---- PRN 12 beside them
+    h = H[2]
+    assert searches(h) == [(0, 1)] and lost(h) == [] and states(h) == [2] * 28 and h["sync"] == [2039]
