@@ -1125,7 +1125,7 @@ int gc_acq_handover(gnsscorr_ctx *ctx, bool quiesce)
     if (quiesce) { int rc = gc_quiesce(ctx); if (rc) return rc; }
     const int n = (int)ctx->acq->list.size();
     hipLaunchKernelGGL(acq_to_loop_kernel, dim3(n), dim3(64), 0, ctx->stream, ctx->dchan, ctx->acq->res,
-                       ctx->dstate2[ctx->state_cur], ctx->dloop, ctx->acq->d_list, n);
+                       ctx->dstate2[ctx->state_cur], ctx->loop.dloop, ctx->acq->d_list, n);
     GC_HIP(hipGetLastError());
     return GNSSCORR_OK;
 }

@@ -1,7 +1,7 @@
 // gnsscorr_api.hip -- C-ABI layer of libgnsscorr.so: context, IF ring in HBM,
 // channel tables, batched tracking entry points, per-kernel timing.
-// (Acquisition entry points live in gnsscorr_acq.hip, the reference-named
-// per-call symbols in gnsscorr_compat.hip.)
+// (Acquisition entry points live in gnsscorr_acq.hip, the closed loop's in
+// gnsscorr_loop.hip, the reference-named per-call symbols in gnsscorr_compat.hip.)
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -46,6 +46,8 @@ static void destroy_handles(gnsscorr_ctx *ctx)
             if (e) hipEventDestroy(e);
     for (hipEvent_t e : {ctx->ev_spec, ctx->ev_chain, ctx->ev_pin[0], ctx->ev_pin[1], ctx->ev_in, ctx->ev_lock})
         if (e) hipEventDestroy(e);
+    for (hipEvent_t e : ctx->ev_burst)
+        if (e) hipEventDestroy(e);
     for (hipStream_t s : {ctx->stream_plan, ctx->stream_finish, ctx->stream_discover, ctx->stream_in})
         if (s) hipStreamDestroy(s);
     if (ctx->own_stream) hipStreamDestroy(ctx->stream);
@@ -74,6 +76,8 @@ extern "C" int gnsscorr_create(gnsscorr_ctx **out, int device, void *stream)
                            &ctx->slot[0].ev_fin, &ctx->slot[1].ev_plan, &ctx->slot[1].ev_used, &ctx->slot[1].ev_corr,
                            &ctx->slot[1].ev_fin})
         if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+    for (hipEvent_t &ev : ctx->ev_burst)
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
     if (e != hipSuccess) {
         destroy_handles(ctx);
         delete ctx;
@@ -106,15 +110,10 @@ static void drop_channel_buffers(gnsscorr_ctx *ctx)
     ctx->dchan.reset(); ctx->dcodes.reset(); ctx->dfreqs.reset(); ctx->detab.reset();
     ctx->dcorrI.reset(); ctx->dcorrQ.reset(); ctx->dsumI.reset(); ctx->dsumQ.reset(); ctx->dfinish.reset();
     ctx->dnco_overflow.reset(); ctx->dring_viol.reset();
-    ctx->dloop.reset(); ctx->dloopdone.reset(); ctx->dloop_lapped.reset(); ctx->dlooplog.reset();
-    ctx->dstep_meta.reset(); ctx->dstep_unit.reset(); ctx->dstep_segs.reset(); ctx->dstep_rounds.reset();
-    ctx->dstep_partial.reset();
     ctx->spec_ahead_valid = false;
     ctx->trk_units = 0;
-    ctx->step_nseg = 0;
-    ctx->last_loop_nper = 0;
     ctx->state_cur = 0;
-    ctx->loop_isset.clear();
+    ctx->loop = GcLoop();
     ctx->rx = GcRx();
     ctx->lock_pending = false;
 }
@@ -198,8 +197,6 @@ extern "C" int gnsscorr_ring_create(gnsscorr_ctx *ctx, int ftype, int dtype, uin
     return GNSSCORR_OK;
 }
 
-int gc_ingest_fence(gnsscorr_ctx *ctx);
-
 // ---- ingest ----------------------------------------------------------------------------------------------
 #define GC_PIN_BYTES (8u << 20)         // per staging buffer
 
@@ -233,6 +230,14 @@ int gc_ingest_fence(gnsscorr_ctx *ctx)
 {
     if (ctx->in_pending) GC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_in, 0));
     return GNSSCORR_OK;
+}
+
+int gc_ring_positions(gnsscorr_ctx *ctx, uint64_t wp_ring[2])
+{
+    std::lock_guard<std::mutex> lk(ctx->mtx);
+    wp_ring[0] = ctx->ring[0].wrpos;
+    wp_ring[1] = ctx->ring[1].wrpos;
+    return gc_ingest_fence(ctx);
 }
 
 // ring bytes [pos, pos + bytes) <- device or pinned source, split at the end of the ring
@@ -461,7 +466,7 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
     drop_channel_buffers(ctx);
 
     ctx->nch = nch;
-    ctx->loop_isset.assign(nch, 0);
+    ctx->loop.isset.assign(nch, 0);
     ctx->hdesc.assign(ch, ch + nch);
     ctx->hcode.resize(nch);
     ctx->hfreq.resize(nch);
@@ -472,6 +477,7 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
     ctx->ntap = 1 + 2 * ch[0].corrn;
     ctx->smax_max = 0;
     ctx->max_n = 0;
+    for (bool &h : ctx->have_dtype) h = false;
     int ngrid = 0;
     for (int i = 0; i < nch; i++) {
         gnsscorr_chan_t &d = ctx->hdesc[i];
@@ -483,6 +489,7 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
         d.corrp = ctx->hcorrp[i].data();
         GcChan &g = ctx->hchan[i];
         gc_build_codeblock(d.code, d.clen, codes.data() + (size_t)i * GC_CODEBLOCK, &g.nedge, &g.pm1);
+        ctx->have_dtype[d.dtype] = true;
         g.dtype = d.dtype; g.clen = d.clen; g.nsamp = d.nsamp; g.nsampchip = d.nsampchip;
         g.ntap = 1 + 2 * d.corrn;
         g.smax = d.corrp[d.corrn - 1];
@@ -512,10 +519,11 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
         GC_RESERVE(ctx, ctx->dstate2[i], nch);
         GC_HIP(hipMemsetAsync(ctx->dstate2[i], 0, sizeof(GcTrkState) * nch, ctx->stream));
     }
-    GC_RESERVE(ctx, ctx->dloop, nch);
-    GC_HIP(hipMemsetAsync(ctx->dloop, 0, sizeof(gnsscorr_loop_t) * nch, ctx->stream));
-    GC_RESERVE(ctx, ctx->dloopdone, 3 * (size_t)nch + 2);        // int [nch], then uint64 [nch] + 8 bytes
-    GC_HIP(hipMemsetAsync(ctx->dloopdone, 0, sizeof(int) * nch + sizeof(uint64_t) * nch + 8, ctx->stream));
+    GC_RESERVE(ctx, ctx->loop.dloop, nch);
+    GC_HIP(hipMemsetAsync(ctx->loop.dloop, 0, sizeof(gnsscorr_loop_t) * nch, ctx->stream));
+    GC_RESERVE(ctx, ctx->loop.ddone, nch);
+    GC_HIP(hipMemsetAsync(ctx->loop.ddone, 0, sizeof(int) * nch, ctx->stream));
+    GC_RESERVE(ctx, ctx->loop.dwrpos, nch);                      // (uploaded by every run before its first tail)
     GC_HIP(hipMemcpyAsync(ctx->dcodes, codes.data(), codes.size(), hipMemcpyHostToDevice, ctx->stream));
     GC_HIP(hipMemcpyAsync(ctx->dfreqs, freqs.data(), sizeof(double) * freqs.size(), hipMemcpyHostToDevice,
                           ctx->stream));
@@ -529,8 +537,6 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
 }
 
 extern "C" int gnsscorr_num_channels(gnsscorr_ctx *ctx) { return ctx ? ctx->nch : 0; }
-
-static int nco_check(gnsscorr_ctx *ctx);
 
 // ---------------------------------------------------------------------------
 // tracking
@@ -563,7 +569,7 @@ extern "C" int gnsscorr_trk_get_state(gnsscorr_ctx *ctx, int ch0, int nch, gnssc
     return GNSSCORR_OK;
 }
 
-static int ensure_trk_buffers(gnsscorr_ctx *ctx, int nepoch)
+int gc_ensure_trk_buffers(gnsscorr_ctx *ctx, int nepoch)
 {
     const size_t units = (size_t)ctx->nch * nepoch;
     if (units <= ctx->trk_units) return GNSSCORR_OK;
@@ -644,18 +650,11 @@ extern "C" int gnsscorr_trk_run(gnsscorr_ctx *ctx, int nepoch)
     if (!ctx || nepoch <= 0) return gc_fail(GNSSCORR_EINVAL, "trk_run: nepoch %d", nepoch);
     if (!ctx->nch) return gc_fail(GNSSCORR_ESTATE, "trk_run: no channels set");
     GC_HIP(hipSetDevice(ctx->device));
-    int rc = ensure_trk_buffers(ctx, nepoch);
+    int rc = gc_ensure_trk_buffers(ctx, nepoch);
     if (rc) return rc;
-    // the rings' write positions and the ingest fence together, under the lock (a grabber thread may be pushing): the
-    // positions handed to the ring check cover only samples whose transfer the compute stream is ordered behind
-    uint64_t wr0, wr1;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mtx);
-        wr0 = ctx->ring[0].wrpos;
-        wr1 = ctx->ring[1].wrpos;
-        rc = gc_ingest_fence(ctx);
-        if (rc) return rc;
-    }
+    uint64_t wr[2];             // what the ring check below may take as written
+    rc = gc_ring_positions(ctx, wr);
+    if (rc) return rc;
     // ---- planner: use the look-ahead plan if it matches, else plan now ----
     // plan = the sequential NCO chain per channel (discovery pass + chain), on the planner stream into the
     // slot's plan buffer; ev_plan marks it ready
@@ -729,11 +728,9 @@ extern "C" int gnsscorr_trk_run(gnsscorr_ctx *ctx, int nepoch)
     }
     // the planned periods against what the rings hold now
     // (the write positions travel as kernel arguments: no copy, no host synchronisation per batch)
-    rc = gc_launch_trk_ringcheck(ctx->stream, ctx->dchan, cur.plan, (const int8_t *)ctx->ring[0].mem, wr0, wr1, ctx->nch,
+    rc = gc_launch_trk_ringcheck(ctx->stream, ctx->dchan, cur.plan, (const int8_t *)ctx->ring[0].mem, wr[0], wr[1], ctx->nch,
                                  nepoch, ctx->dring_viol);
     if (rc) return rc;
-    bool have[3] = {false, false, false};
-    for (int i = 0; i < ctx->nch; i++) have[ctx->hchan[i].dtype] = true;
     {
         // start samples of the periods' chip edges, for the correlator's look-up phase
         GcTimed t(ctx, "trk_edges");
@@ -741,7 +738,7 @@ extern "C" int gnsscorr_trk_run(gnsscorr_ctx *ctx, int nepoch)
         if (rc) return rc;
     }
     for (int dtype = 1; dtype <= 2; dtype++) {
-        if (!have[dtype]) continue;
+        if (!ctx->have_dtype[dtype]) continue;
         GcTimed t(ctx, "trk_corr");
         rc = gc_launch_trk_corr(ctx->stream, ctx->dchan, cur.unit, cur.segs, cur.rounds, cur.partial,
                                 ctx->nch, nepoch, ctx->nseg, ctx->ntap, dtype, ctx->ntap, ctx->max_n, ctx->smax_max, ctx->detab);
@@ -776,193 +773,13 @@ extern "C" int gnsscorr_trk_run(gnsscorr_ctx *ctx, int nepoch)
     }
     ctx->last_slot = slot;
     ctx->last_nepoch = nepoch;
-    ctx->last_loop_nper = 0;
-    return GNSSCORR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// tracking, closed loop
-// ---------------------------------------------------------------------------
-extern "C" int gnsscorr_loop_set(gnsscorr_ctx *ctx, int ch0, int nch, const gnsscorr_loop_t *lp)
-{
-    if (!ctx || !lp || ch0 < 0 || nch <= 0 || ch0 + nch > ctx->nch)
-        return gc_fail(GNSSCORR_EINVAL, "loop_set: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
-    for (int i = 0; i < nch; i++) {
-        const gnsscorr_loop_t &l = lp[i];
-        const int ntap = ctx->hchan[ch0 + i].ntap;
-        if (l.ne < 0 || l.ne >= ntap || l.nl < 0 || l.nl >= ntap)
-            return gc_fail(GNSSCORR_EINVAL, "loop_set: channel %d: early/late tap index %d/%d of %d taps", ch0 + i, l.ne, l.nl, ntap);
-        if (l.loopms < 1 || l.rate < 1 || l.rate > 20)
-            return gc_fail(GNSSCORR_EINVAL, "loop_set: channel %d: loopms %d, rate %d (rate 1..20)", ch0 + i, l.loopms, l.rate);
-    }
-    GC_HIP(hipSetDevice(ctx->device));
-    { int rc = gc_quiesce(ctx); if (rc) return rc; }
-    GC_HIP(hipMemcpyAsync(ctx->dloop + ch0, lp, sizeof(gnsscorr_loop_t) * nch, hipMemcpyHostToDevice, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < nch; i++) {
-        ctx->loop_isset[ch0 + i] = 1;
-        if (lp[i].loopms > ctx->loop_kmax) ctx->loop_kmax = lp[i].loopms < GC_STEP_KMAX ? lp[i].loopms : GC_STEP_KMAX;
-        if (lp[i].flagsync) ctx->loop_sync_hint = true;
-    }
-    return GNSSCORR_OK;
-}
-
-extern "C" int gnsscorr_loop_get(gnsscorr_ctx *ctx, int ch0, int nch, gnsscorr_loop_t *lp)
-{
-    if (!ctx || !lp || ch0 < 0 || nch <= 0 || ch0 + nch > ctx->nch)
-        return gc_fail(GNSSCORR_EINVAL, "loop_get: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
-    GC_HIP(hipSetDevice(ctx->device));
-    { int rc = gc_quiesce(ctx); if (rc) return rc; }
-    GC_HIP(hipMemcpyAsync(lp, ctx->dloop + ch0, sizeof(gnsscorr_loop_t) * nch, hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    return GNSSCORR_OK;
-}
-
-// the step buffers: one filter interval (GC_STEP_KMAX periods at most) per channel
-static int ensure_step_buffers(gnsscorr_ctx *ctx)
-{
-    if (ctx->dstep_meta) return GNSSCORR_OK;
-    int nseg = 1;
-    for (int i = 0; i < ctx->nch; i++) {
-        const int s = gc_step_nseg(ctx->hchan[i].dtype, ctx->max_n);
-        if (s > nseg) nseg = s;
-    }
-    if (nseg > 64) return gc_fail(GNSSCORR_EINVAL, "trk_run_loop: period of %d samples too long (%d rounds, 64 at most)", ctx->max_n, nseg);
-    const size_t units = (size_t)ctx->nch * GC_STEP_KMAX;
-    GC_RESERVE(ctx, ctx->dstep_unit, units);
-    GC_RESERVE(ctx, ctx->dstep_segs, units);
-    GC_RESERVE(ctx, ctx->dstep_rounds, units * nseg * 4);        // four rounds (one per wavefront) per workgroup
-    GC_RESERVE(ctx, ctx->dstep_partial, units * nseg * 2 * ctx->ntap);
-    GC_RESERVE(ctx, ctx->dloop_lapped, 1);
-    int rc = ctx->hostflags.reserve(16, hipHostMallocMapped);
-    if (rc) return rc;
-    GC_RESERVE(ctx, ctx->dstep_meta, ctx->nch);                   // last: the test above
-    ctx->step_nseg = nseg;
-    return GNSSCORR_OK;
-}
-
-extern "C" int gnsscorr_trk_run_loop(gnsscorr_ctx *ctx, int nperiod) { return gc_trk_run_loop(ctx, nperiod, nullptr); }
-
-// wp_ch: nullptr, or the write position each channel is tracked up to ([nch]; 0 starves the channel at once: it plans
-// no period and keeps its state), which the caller read under the context's lock
-int gc_trk_run_loop(gnsscorr_ctx *ctx, int nperiod, const uint64_t *wp_ch)
-{
-    if (!ctx || nperiod <= 0) return gc_fail(GNSSCORR_EINVAL, "trk_run_loop: nperiod %d", nperiod);
-    if (!ctx->nch) return gc_fail(GNSSCORR_ESTATE, "trk_run_loop: no channels set");
-    GC_HIP(hipSetDevice(ctx->device));
-    int rc = ensure_trk_buffers(ctx, nperiod);
-    if (rc) return rc;
-    rc = ensure_step_buffers(ctx);
-    if (rc) return rc;
-    // the look-ahead planner of the batched interface works on the same state: stop it, drop its plan
-    if (ctx->ahead_valid || ctx->slot[0].fin_pending || ctx->slot[1].fin_pending) { rc = gc_quiesce(ctx); if (rc) return rc; }
-    ctx->ahead_valid = false;
-    ctx->state_touched = true;
-    const size_t units = (size_t)ctx->nch * nperiod;
-    GC_RESERVE(ctx, ctx->dlooplog, units);
-    GC_HIP(hipMemsetAsync(ctx->dlooplog, 0, sizeof(gnsscorr_trklog_t) * units, ctx->stream));
-    GC_HIP(hipMemsetAsync(ctx->dcorrI, 0, sizeof(double) * units * ctx->ntap, ctx->stream));
-    GC_HIP(hipMemsetAsync(ctx->dcorrQ, 0, sizeof(double) * units * ctx->ntap, ctx->stream));
-    GC_HIP(hipMemsetAsync(ctx->slot[0].nsamp, 0, sizeof(int) * units, ctx->stream));
-    GC_HIP(hipMemsetAsync(ctx->dstep_meta, 0, sizeof(GcStepMeta) * ctx->nch, ctx->stream));
-    GC_HIP(hipMemsetAsync(ctx->dloop_lapped, 0, sizeof(int), ctx->stream));
-    // write position of each channel's ring (ref src/sdrtrk.c:26-28: fendbuffsize*buffcnt), read together with the
-    // ingest fence under the lock: the positions cover only samples whose transfer the compute stream is ordered behind
-    std::vector<uint64_t> wp(ctx->nch);
-    {
-        std::lock_guard<std::mutex> lk(ctx->mtx);
-        for (int i = 0; i < ctx->nch; i++) wp[i] = wp_ch ? wp_ch[i] : ctx->ring[ctx->hdesc[i].ftype - 1].wrpos;
-        rc = gc_ingest_fence(ctx);
-        if (rc) return rc;
-    }
-    uint64_t *dwp = reinterpret_cast<uint64_t *>(ctx->dloopdone + ctx->nch + (ctx->nch & 1));
-    GC_HIP(hipMemcpyAsync(dwp, wp.data(), sizeof(uint64_t) * ctx->nch, hipMemcpyHostToDevice, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));          // (wp is a local; the flags below are host memory)
-    ctx->hostflags[0] = 0;
-    ctx->hostflags[1] = ctx->loop_sync_hint ? 1u : 0u;     // (some channel is known to be synchronised: steps of loopms periods from the start)
-    bool have[3] = {false, false, false};
-    for (int i = 0; i < ctx->nch; i++) have[ctx->hchan[i].dtype] = true;
-    // One step = tail (close the previous interval, plan the next) + correlator.  Every step advances every channel
-    // that still has work by at least one period, so nperiod steps always suffice; channels whose nav bit is
-    // synchronised advance by up to loopms periods per step.  The host keeps a bounded number of steps ahead of the
-    // device and stops as soon as the device says every channel is done (a pinned word the tail kernel updates).
-    const int kmax = ctx->loop_kmax < 1 ? 1 : ctx->loop_kmax;
-    const int BURST = 4, AHEAD = 3;
-    hipEvent_t ev[AHEAD] = {nullptr, nullptr, nullptr};
-    for (int i = 0; i < AHEAD; i++) GC_HIP(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-    auto cleanup = [&]() { for (int i = 0; i < AHEAD; i++) if (ev[i]) hipEventDestroy(ev[i]); };
-    int steps = 0, burst = 0;
-    bool done = false;
-    while (!done && steps <= nperiod) {
-        if (burst >= AHEAD) {                           // at most AHEAD bursts in flight
-            hipError_t e = hipEventSynchronize(ev[burst % AHEAD]);
-            if (e != hipSuccess) { cleanup(); return gc_fail_hip(e, "hipEventSynchronize", __FILE__, __LINE__); }
-            if (ctx->hostflags[0] >= (unsigned)ctx->nch) break;
-        }
-        for (int b = 0; b < BURST && steps <= nperiod; b++, steps++) {
-            // periods per step: 1 while no channel is synchronised (a performance hint only: the tail never plans more
-            // than kcap periods, and any kcap >= 1 is correct)
-            const int kcap = ctx->hostflags[1] ? kmax : 1;
-            {
-                GcTimed t(ctx, "trk_step_tail");
-                rc = gc_launch_step_tail(ctx->stream, ctx->dchan, ctx->dstate2[ctx->state_cur], ctx->dloop, ctx->dstep_meta, dwp,
-                                         ctx->dstep_partial, ctx->dstep_unit, ctx->dstep_segs, ctx->dstep_rounds, ctx->dcorrI,
-                                         ctx->dcorrQ, ctx->slot[0].nsamp, ctx->dlooplog, ctx->dloopdone, ctx->dnco_overflow,
-                                         ctx->dloop_lapped, ctx->hostflags.dev, ctx->nch, nperiod, ctx->step_nseg, ctx->ntap, ctx->max_n, kcap, 1);
-                if (rc) { cleanup(); return rc; }
-            }
-            for (int dtype = 1; dtype <= 2; dtype++) {
-                if (!have[dtype]) continue;
-                GcTimed t(ctx, "trk_step_corr");
-                rc = gc_launch_step_corr(ctx->stream, ctx->dchan, ctx->dstep_meta, ctx->dstep_unit, ctx->dstep_segs, ctx->dstep_rounds,
-                                         ctx->dstep_partial, ctx->nch, kcap, ctx->step_nseg, dtype, ctx->ntap, ctx->max_n,
-                                         ctx->smax_max);
-                if (rc) { cleanup(); return rc; }
-            }
-        }
-        hipError_t e = hipEventRecord(ev[burst % AHEAD], ctx->stream);
-        if (e != hipSuccess) { cleanup(); return gc_fail_hip(e, "hipEventRecord", __FILE__, __LINE__); }
-        burst++;
-    }
-    // close whatever the last correlator launch produced
-    rc = gc_launch_step_tail(ctx->stream, ctx->dchan, ctx->dstate2[ctx->state_cur], ctx->dloop, ctx->dstep_meta, dwp, ctx->dstep_partial,
-                             ctx->dstep_unit, ctx->dstep_segs, ctx->dstep_rounds, ctx->dcorrI, ctx->dcorrQ, ctx->slot[0].nsamp,
-                             ctx->dlooplog, ctx->dloopdone, ctx->dnco_overflow, ctx->dloop_lapped, ctx->hostflags.dev, ctx->nch, nperiod, ctx->step_nseg,
-                             ctx->ntap, ctx->max_n, 1, 0);
-    cleanup();
-    if (rc) return rc;
-    if (ctx->hostflags[1]) ctx->loop_sync_hint = true;
-    ctx->last_slot = 0;
-    ctx->slot[0].fin_pending = ctx->slot[1].fin_pending = false;
-    ctx->last_nepoch = nperiod;
-    ctx->last_loop_nper = nperiod;
-    return GNSSCORR_OK;
-}
-
-extern "C" int gnsscorr_trk_fetch_log(gnsscorr_ctx *ctx, gnsscorr_trklog_t *log, int *ndone)
-{
-    if (!ctx || !ctx->last_loop_nper) return gc_fail(GNSSCORR_ESTATE, "trk_fetch_log: no completed trk_run_loop");
-    GC_HIP(hipSetDevice(ctx->device));
-    const size_t units = (size_t)ctx->nch * ctx->last_loop_nper;
-    if (log) GC_HIP(hipMemcpyAsync(log, ctx->dlooplog, sizeof(gnsscorr_trklog_t) * units, hipMemcpyDeviceToHost, ctx->stream));
-    if (ndone) GC_HIP(hipMemcpyAsync(ndone, ctx->dloopdone, sizeof(int) * ctx->nch, hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    return nco_check(ctx);
-}
-
-extern "C" int gnsscorr_trk_loop_lapped(gnsscorr_ctx *ctx, int *nlapped)
-{
-    if (!ctx || !nlapped) return gc_fail(GNSSCORR_EINVAL, "trk_loop_lapped: null argument");
-    if (!ctx->last_loop_nper) return gc_fail(GNSSCORR_ESTATE, "trk_loop_lapped: no completed trk_run_loop");
-    GC_HIP(hipSetDevice(ctx->device));
-    GC_HIP(hipMemcpyAsync(nlapped, ctx->dloop_lapped, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->loop.last_nper = 0;
     return GNSSCORR_OK;
 }
 
 // Units whose NCO piece tables overflowed (a code step that wraps the code more than ~twice per call, a
 // carrier that visits more than GC_NCAR binades) were not correlated: say so instead of handing out zeros.
-static int nco_check(gnsscorr_ctx *ctx)
+int gc_nco_check(gnsscorr_ctx *ctx)
 {
     int n = 0, v = 0;
     GC_HIP(hipMemcpy(&v, ctx->dring_viol, sizeof(int), hipMemcpyDeviceToHost));
@@ -993,13 +810,13 @@ extern "C" int gnsscorr_trk_fetch(gnsscorr_ctx *ctx, double *trkII, double *trkQ
     if (nsamp_out)
         GC_HIP(hipMemcpyAsync(nsamp_out, ctx->slot[ctx->last_slot].nsamp, sizeof(int) * units, hipMemcpyDeviceToHost, ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
-    return nco_check(ctx);
+    return gc_nco_check(ctx);
 }
 
 extern "C" int gnsscorr_trk_fetch_sums(gnsscorr_ctx *ctx, double *sumI, double *sumQ)
 {
     if (!ctx || !ctx->last_nepoch) return gc_fail(GNSSCORR_ESTATE, "trk_fetch_sums: no completed trk_run");
-    if (ctx->last_loop_nper) return gc_fail(GNSSCORR_ESTATE, "trk_fetch_sums: the last run was closed loop (its sums are in gnsscorr_loop_get)");
+    if (ctx->loop.last_nper) return gc_fail(GNSSCORR_ESTATE, "trk_fetch_sums: the last run was closed loop (its sums are in gnsscorr_loop_get)");
     GC_HIP(hipSetDevice(ctx->device));
     { int rc = outputs_ready(ctx); if (rc) return rc; }
     const size_t n = (size_t)ctx->nch * ctx->ntap;

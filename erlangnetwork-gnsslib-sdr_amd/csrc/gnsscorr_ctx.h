@@ -114,6 +114,29 @@ struct GcPlanSlot {
     bool fin_pending = false;      // ev_fin has been recorded
 };
 
+#define GC_LOOP_AHEAD 3         // launch bursts gc_trk_run_loop keeps in flight
+// The closed loop (gnsscorr_loop.hip): what gnsscorr_trk_run_loop owns, per channel set.  The step buffers hold one filter
+// interval per channel (GC_STEP_KMAX periods at most): unit constants, NCO tables, rounds, partial sums
+struct GcLoop {
+    GcDevBuf<gnsscorr_loop_t> dloop;               // [nch] the channels' loop states
+    std::vector<char> isset;                       // [nch] the channel's loop constants have been set (gnsscorr_loop_set)
+    GcDevBuf<GcStepMeta> dstep_meta;               // [nch]
+    GcDevBuf<GcTrkUnit> dstep_unit;                // [nch][GC_STEP_KMAX]
+    GcDevBuf<GcUnitSegs> dstep_segs;
+    GcDevBuf<GcRound> dstep_rounds;                // [nch][GC_STEP_KMAX][step_nseg][4]
+    GcDevBuf<int> dstep_partial;                   // [nch][GC_STEP_KMAX][step_nseg][2*ntap]
+    int step_nseg = 0;
+    GcPinBuf<unsigned> hostflags;                  // mapped: [0] channels whose run is over, [1] some channel has its nav bit synchronised
+    int kmax = 1;                                  // largest loopms among the channels' loop states (gnsscorr_loop_set)
+    bool sync_hint = false;                        // some channel had its nav bit synchronised when last seen
+    GcDevBuf<gnsscorr_trklog_t> dlog;              // [nch][nperiod] one row per period
+    GcDevBuf<int> dlapped;                         // periods of the last run read after the writer lapped them
+    GcDevBuf<int> ddone;                           // [nch] periods the last run finished
+    GcDevBuf<uint64_t> dwrpos;                     // [nch] the write position each channel is tracked up to
+    int run_nper = 0;                              // periods of the run being issued (the tail's bound)
+    int last_nper = 0;                             // > 0: the last run was a closed-loop one of that many periods
+};
+
 // The receiver schedule (gnsscorr_rx.hip): sdrthread()'s per-channel state, kept by the host
 struct GcRx {
     bool on = false;
@@ -160,6 +183,7 @@ struct gnsscorr_ctx {
     GcDevBuf<int8_t> dcodes;
     GcDevBuf<double> dfreqs;
     int ntap = 0, smax_max = 0, max_n = 0;
+    bool have_dtype[3] = {false, false, false};    // [dtype] some channel reads a ring of that dtype
 
     // tracking.  The planner (a short sequential NCO chain per channel) runs one batch ahead on
     // its own stream: plan entries and the chained state are double buffered, so batch k+1 is
@@ -188,26 +212,11 @@ struct gnsscorr_ctx {
     bool state_touched = true;                     // set_state since the last run: do not look ahead
     GcDevBuf<int> dnco_overflow;                   // units whose NCO tables overflowed since the last fetch
     GcDevBuf<int> dring_viol;                      // planned periods outside what the ring holds, since the last fetch
-    // closed loop (gnsscorr_trk_run_loop): per channel loop state, one log row per period; the step buffers hold one
-    // filter interval per channel (GC_STEP_KMAX periods at most): unit constants, NCO tables, rounds, partial sums
-    GcDevBuf<gnsscorr_loop_t> dloop;               // [nch]
-    GcDevBuf<GcStepMeta> dstep_meta;               // [nch]
-    GcDevBuf<GcTrkUnit> dstep_unit;                // [nch][GC_STEP_KMAX]
-    GcDevBuf<GcUnitSegs> dstep_segs;
-    GcDevBuf<GcRound> dstep_rounds;                // [nch][GC_STEP_KMAX][step_nseg][4]
-    GcDevBuf<int> dstep_partial;                   // [nch][GC_STEP_KMAX][step_nseg][2*ntap]
-    int step_nseg = 0;
-    GcPinBuf<unsigned> hostflags;                  // mapped: [0] channels whose run is over, [1] some channel has its nav bit synchronised
-    bool loop_sync_hint = false;                   // some channel had its nav bit synchronised when last seen
-    std::vector<char> loop_isset;                  // [nch] the channel's loop constants have been set (gnsscorr_loop_set)
+    GcLoop loop;
+    hipEvent_t ev_burst[GC_LOOP_AHEAD] = {};       // gc_trk_run_loop: the ends of the launch bursts in flight
     GcRx rx;
     hipEvent_t ev_lock = nullptr;                  // end of the last lock monitor launch (made on first use)
     bool lock_pending = false;                     // ev_lock is recorded and rx.lock_lost not read yet
-    int loop_kmax = 1;                             // largest loopms among the channels' loop states (gnsscorr_loop_set)
-    GcDevBuf<gnsscorr_trklog_t> dlooplog;          // [nch][nperiod]
-    GcDevBuf<int> dloop_lapped;                    // periods of the last trk_run_loop read after the writer lapped them
-    GcDevBuf<int> dloopdone;                       // [nch], then the rings' write positions [nch] (uint64)
-    int last_loop_nper = 0;                        // > 0: the last run was a closed-loop one of that many periods
     int last_slot = 0;                             // slot of the last completed trk_run
     GcDevBuf<double> dcorrI, dcorrQ, dsumI, dsumQ;
     GcDevBuf<unsigned long long> dfinish;          // batch-sum scratch of trk_finish
@@ -264,10 +273,19 @@ int gc_quiesce(gnsscorr_ctx *ctx, bool ingest = false);
 // the acquisition's forward twiddle tables (made on first use): exp(-2 pi i t/16384), exp(-2 pi i t/32768), t < 16384
 int gc_acq_twiddles(gnsscorr_ctx *ctx, const float2 **tw16k, const float2 **tw32k);
 int gc_ingest_fence(gnsscorr_ctx *ctx);      // orders the compute stream behind the last ring transfer
+// both rings' write positions and the ingest fence together, under the lock (a grabber thread may be pushing): the
+// positions cover only samples whose transfer the compute stream is ordered behind
+int gc_ring_positions(gnsscorr_ctx *ctx, uint64_t wp_ring[2]);
+// the closed loop takes the tracking state: quiesces if the batched interface has a look-ahead plan or a finish pending;
+// either way no plan is valid afterwards and state_touched is set (the batched tracker plans afresh)
+int gc_loop_take_state(gnsscorr_ctx *ctx);
+// gnsscorr_api.hip: the batched tracker's buffers for nepoch periods per channel; the overflow / ring counters of a fetch
+int gc_ensure_trk_buffers(gnsscorr_ctx *ctx, int nepoch);
+int gc_nco_check(gnsscorr_ctx *ctx);
 // gnsscorr_acq.hip: one search over a channel list; the device hand-over of its acquired channels into the closed loop
 int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chlist, int n);
 int gc_acq_handover(gnsscorr_ctx *ctx, bool quiesce);
-// gnsscorr_api.hip: gnsscorr_trk_run_loop with per-channel write positions
+// gnsscorr_loop.hip: gnsscorr_trk_run_loop with per-channel write positions
 int gc_trk_run_loop(gnsscorr_ctx *ctx, int nperiod, const uint64_t *wp_ch);
 // gnsscorr_lock.hip: the lock monitor over the periods the last gc_trk_run_loop tracked, for the TRACK channels that have
 // it on; queues the launch and its event on the context's stream and does not wait

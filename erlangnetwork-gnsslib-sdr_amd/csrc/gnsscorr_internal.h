@@ -167,12 +167,3 @@ struct GcStepMeta {             // per channel, device resident
     int early;                  // (diagnostic) a filter update fell inside an interval: must stay 0
     int pad;
 };
-int gc_step_nseg(int dtype, int max_n);          // workgroups (one round each) per period
-// closes the intervals the previous correlator launch produced and plans the next ones (plan = 0: closes only)
-int gc_launch_step_tail(hipStream_t st, const GcChan *chan, GcTrkState *state, gnsscorr_loop_t *loop, GcStepMeta *meta,
-                        const uint64_t *wrpos, const int *partial, GcTrkUnit *unit, GcUnitSegs *segs, GcRound *rounds,
-                        double *corrI, double *corrQ, int *nsamp_out, gnsscorr_trklog_t *log, int *ndone, int *nco_overflow,
-                        int *lapped, unsigned *hostflags, int nch, int nper, int nseg, int ntap, int max_n, int kcap, int plan);
-int gc_launch_step_corr(hipStream_t st, const GcChan *chan, const GcStepMeta *meta, const GcTrkUnit *unit, const GcUnitSegs *segs,
-                        const GcRound *rounds, int *partial, int nch, int kcap, int nseg, int dtype, int ntap, int max_n,
-                        int smax_max);

@@ -273,7 +273,7 @@ extern "C" int gnsscorr_rx_lock_set(gnsscorr_ctx *ctx, int ch0, int nch, const g
         p.pad = 0;
         // the channels' nav bit lengths: one column of the device's loop states
         std::vector<int> rate(nch);
-        GC_HIP(hipMemcpy2DAsync(rate.data(), sizeof(int), (const char *)(ctx->dloop.p + ch0) + offsetof(gnsscorr_loop_t, rate),
+        GC_HIP(hipMemcpy2DAsync(rate.data(), sizeof(int), (const char *)(ctx->loop.dloop.p + ch0) + offsetof(gnsscorr_loop_t, rate),
                                 sizeof(gnsscorr_loop_t), sizeof(int), nch, hipMemcpyDeviceToHost, ctx->stream));
         GC_HIP(hipStreamSynchronize(ctx->stream));
         for (int i = 0; i < nch; i++) {
@@ -328,10 +328,10 @@ int gc_rx_lock_launch(gnsscorr_ctx *ctx, int nperiod)
         // trk.II is the correlator's QQ (ref src/sdrtrk.c:42): gnsscorr_trk_fetch's II rows are dcorrQ
         hipLaunchKernelGGL(rx_lock_kernel, dim3((n + GC_LOCK_WAVES - 1) / GC_LOCK_WAVES), dim3(GC_LOCK_WAVES * 64), 0, ctx->stream,
                            (const int *)rx.lock_list.dev, n, (const gnsscorr_lockprm_t *)rx.dlockprm.p,
-                           (const char *)ctx->dloop.p + offsetof(gnsscorr_loop_t, rate), sizeof(gnsscorr_loop_t), rx.dlock.p,
+                           (const char *)ctx->loop.dloop.p + offsetof(gnsscorr_loop_t, rate), sizeof(gnsscorr_loop_t), rx.dlock.p,
                            (const double *)ctx->dcorrQ.p, (const double *)ctx->dcorrI.p, (size_t)nperiod * ctx->ntap, (size_t)ctx->ntap,
-                           (const gnsscorr_trklog_t *)ctx->dlooplog.p, nperiod, (const int *)ctx->dloopdone.p,
-                           (const char *)ctx->dloop.p + offsetof(gnsscorr_loop_t, cnt), sizeof(gnsscorr_loop_t), 1,
+                           (const gnsscorr_trklog_t *)ctx->loop.dlog.p, nperiod, (const int *)ctx->loop.ddone.p,
+                           (const char *)ctx->loop.dloop.p + offsetof(gnsscorr_loop_t, cnt), sizeof(gnsscorr_loop_t), 1,
                            rx.lock_lost.dev);
     }
     GC_HIP(hipGetLastError());

@@ -26,6 +26,7 @@
 #define GC_CODE_PERIOD_INLINE
 #include "gnsscorr_internal.h"
 #include "gnsscorr_ps.h"
+#include "gnsscorr_ctx.h"       // the host driver below the kernels
 
 #ifdef GC_TAIL_PROF     // (tools/debug: shader-clock stamps of channel 0's tail wavefront, summed over the launches)
 __device__ unsigned long long gc_tail_prof[16];
@@ -977,14 +978,18 @@ void trk_step_corr_kernel(const GcChan *__restrict__ chan, const GcStepMeta *__r
                               ntap_stride, max_n, 4, seg, 0, smem, tid, nullptr);
 }
 
+// one launch per dtype present among the channels
 template <int DTYPE>
-int launch_step_corr(hipStream_t st, const GcChan *chan, const GcStepMeta *meta, const GcTrkUnit *unit, const GcUnitSegs *segs,
-                     const GcRound *rounds, int *partial, int nch, int kcap, int nseg, int ntap, int max_n)
+int launch_step_corr(gnsscorr_ctx *ctx, int kcap)
 {
+    if (ctx->smax_max > 64) return gc_fail(GNSSCORR_EINVAL, "trk_step: tap offset %d samples (<= 64 supported)", ctx->smax_max);
     constexpr int NIT = DTYPE == 1 ? 1 : 2;
-    const unsigned grid = (unsigned)(nch * nseg * kcap);
-#define GC_SC(N) do { hipLaunchKernelGGL((trk_step_corr_kernel<DTYPE, N, NIT>), dim3(grid), dim3(256), 0, st, chan, meta, unit, segs, \
-                                         rounds, partial, nch, kcap, nseg, ntap, max_n); \
+    const GcLoop &lp = ctx->loop;
+    const int nch = ctx->nch, ntap = ctx->ntap;
+    const unsigned grid = (unsigned)(nch * lp.step_nseg * kcap);
+#define GC_SC(N) do { hipLaunchKernelGGL((trk_step_corr_kernel<DTYPE, N, NIT>), dim3(grid), dim3(256), 0, ctx->stream, ctx->dchan.p, \
+                                         lp.dstep_meta.p, lp.dstep_unit.p, lp.dstep_segs.p, lp.dstep_rounds.p, lp.dstep_partial.p, nch, \
+                                         kcap, lp.step_nseg, ntap, ctx->max_n); \
                       GC_HIP(hipGetLastError()); return 0; } while (0)
     if (ntap <= 3) GC_SC(3);
     if (ntap <= 5) GC_SC(5);
@@ -995,35 +1000,203 @@ int launch_step_corr(hipStream_t st, const GcChan *chan, const GcStepMeta *meta,
 #undef GC_SC
 }
 
-}  // namespace
-
 // workgroups per period in step mode: four rounds (one per wavefront) each
-int gc_step_nseg(int dtype, int max_n)
+int step_nseg(int dtype, int max_n)
 {
     const int nit = trk_ps_nit(dtype, 2);
     const int groups = (15 + max_n * dtype + 15) / 16 + 1;
     return (groups + 256 * nit - 1) / (256 * nit);
 }
 
-int gc_launch_step_tail(hipStream_t st, const GcChan *chan, GcTrkState *state, gnsscorr_loop_t *loop, GcStepMeta *meta,
-                        const uint64_t *wrpos, const int *partial, GcTrkUnit *unit, GcUnitSegs *segs, GcRound *rounds,
-                        double *corrI, double *corrQ, int *nsamp_out, gnsscorr_trklog_t *log, int *ndone, int *nco_overflow,
-                        int *lapped, unsigned *hostflags, int nch, int nper, int nseg, int ntap, int max_n, int kcap, int plan)
+// closes the intervals the previous correlator launch produced and plans the next ones (plan = 0: closes only)
+int launch_step_tail(gnsscorr_ctx *ctx, int kcap, int plan)
 {
     if (kcap < 1 || kcap > GC_STEP_KMAX) return gc_fail(GNSSCORR_EINVAL, "trk_step: %d periods per step (1..%d)", kcap, GC_STEP_KMAX);
-    hipLaunchKernelGGL(trk_step_tail_kernel, dim3(nch), dim3(64 * GC_TAIL_NW), 0, st, chan, state, loop, meta, wrpos, partial, unit, segs, rounds,
-                       corrI, corrQ, nsamp_out, log, ndone, nco_overflow, lapped, hostflags, nch, nper, nseg, ntap, max_n, kcap, plan);
+    GcLoop &lp = ctx->loop;
+    hipLaunchKernelGGL(trk_step_tail_kernel, dim3(ctx->nch), dim3(64 * GC_TAIL_NW), 0, ctx->stream, ctx->dchan.p,
+                       ctx->dstate2[ctx->state_cur].p, lp.dloop.p, lp.dstep_meta.p, lp.dwrpos.p, lp.dstep_partial.p, lp.dstep_unit.p,
+                       lp.dstep_segs.p, lp.dstep_rounds.p, ctx->dcorrI.p, ctx->dcorrQ.p, ctx->slot[0].nsamp.p, lp.dlog.p, lp.ddone.p,
+                       ctx->dnco_overflow.p, lp.dlapped.p, lp.hostflags.dev, ctx->nch, lp.run_nper, lp.step_nseg, ctx->ntap, ctx->max_n,
+                       kcap, plan);
     GC_HIP(hipGetLastError());
     return 0;
 }
 
-// one launch per dtype present among the channels
-int gc_launch_step_corr(hipStream_t st, const GcChan *chan, const GcStepMeta *meta, const GcTrkUnit *unit, const GcUnitSegs *segs,
-                        const GcRound *rounds, int *partial, int nch, int kcap, int nseg, int dtype, int ntap, int max_n,
-                        int smax_max)
+// One step of the run of loop.run_nper periods: the tail, then the correlator.  plan = 0: the tail that closes the run,
+// alone and untimed.
+int loop_step(gnsscorr_ctx *ctx, int kcap, int plan)
 {
-    if (smax_max > 64) return gc_fail(GNSSCORR_EINVAL, "trk_step: tap offset %d samples (<= 64 supported)", smax_max);
-    if (dtype == 2) return launch_step_corr<2>(st, chan, meta, unit, segs, rounds, partial, nch, kcap, nseg, ntap, max_n);
-    if (dtype == 1) return launch_step_corr<1>(st, chan, meta, unit, segs, rounds, partial, nch, kcap, nseg, ntap, max_n);
-    return gc_fail(GNSSCORR_EINVAL, "trk_step: dtype %d not 1 or 2", dtype);
+    if (!plan) return launch_step_tail(ctx, kcap, 0);
+    {
+        GcTimed t(ctx, "trk_step_tail");
+        int rc = launch_step_tail(ctx, kcap, 1);
+        if (rc) return rc;
+    }
+    for (int dtype = 1; dtype <= 2; dtype++) {
+        if (!ctx->have_dtype[dtype]) continue;
+        GcTimed t(ctx, "trk_step_corr");
+        int rc = dtype == 2 ? launch_step_corr<2>(ctx, kcap) : launch_step_corr<1>(ctx, kcap);
+        if (rc) return rc;
+    }
+    return GNSSCORR_OK;
+}
+
+}  // namespace
+
+// ---- the host driver --------------------------------------------------------------------------------------
+extern "C" int gnsscorr_loop_set(gnsscorr_ctx *ctx, int ch0, int nch, const gnsscorr_loop_t *lp)
+{
+    if (!ctx || !lp || ch0 < 0 || nch <= 0 || ch0 + nch > ctx->nch)
+        return gc_fail(GNSSCORR_EINVAL, "loop_set: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    for (int i = 0; i < nch; i++) {
+        const gnsscorr_loop_t &l = lp[i];
+        const int ntap = ctx->hchan[ch0 + i].ntap;
+        if (l.ne < 0 || l.ne >= ntap || l.nl < 0 || l.nl >= ntap)
+            return gc_fail(GNSSCORR_EINVAL, "loop_set: channel %d: early/late tap index %d/%d of %d taps", ch0 + i, l.ne, l.nl, ntap);
+        if (l.loopms < 1 || l.rate < 1 || l.rate > 20)
+            return gc_fail(GNSSCORR_EINVAL, "loop_set: channel %d: loopms %d, rate %d (rate 1..20)", ch0 + i, l.loopms, l.rate);
+    }
+    GC_HIP(hipSetDevice(ctx->device));
+    { int rc = gc_quiesce(ctx); if (rc) return rc; }
+    GcLoop &L = ctx->loop;
+    GC_HIP(hipMemcpyAsync(L.dloop + ch0, lp, sizeof(gnsscorr_loop_t) * nch, hipMemcpyHostToDevice, ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < nch; i++) {
+        L.isset[ch0 + i] = 1;
+        if (lp[i].loopms > L.kmax) L.kmax = lp[i].loopms < GC_STEP_KMAX ? lp[i].loopms : GC_STEP_KMAX;
+        if (lp[i].flagsync) L.sync_hint = true;
+    }
+    return GNSSCORR_OK;
+}
+
+extern "C" int gnsscorr_loop_get(gnsscorr_ctx *ctx, int ch0, int nch, gnsscorr_loop_t *lp)
+{
+    if (!ctx || !lp || ch0 < 0 || nch <= 0 || ch0 + nch > ctx->nch)
+        return gc_fail(GNSSCORR_EINVAL, "loop_get: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    GC_HIP(hipSetDevice(ctx->device));
+    { int rc = gc_quiesce(ctx); if (rc) return rc; }
+    GC_HIP(hipMemcpyAsync(lp, ctx->loop.dloop + ch0, sizeof(gnsscorr_loop_t) * nch, hipMemcpyDeviceToHost, ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));
+    return GNSSCORR_OK;
+}
+
+// the step buffers: one filter interval (GC_STEP_KMAX periods at most) per channel
+static int ensure_step_buffers(gnsscorr_ctx *ctx)
+{
+    GcLoop &L = ctx->loop;
+    if (L.dstep_meta) return GNSSCORR_OK;
+    int nseg = 1;
+    for (int i = 0; i < ctx->nch; i++) {
+        const int s = step_nseg(ctx->hchan[i].dtype, ctx->max_n);
+        if (s > nseg) nseg = s;
+    }
+    if (nseg > 64) return gc_fail(GNSSCORR_EINVAL, "trk_run_loop: period of %d samples too long (%d rounds, 64 at most)", ctx->max_n, nseg);
+    const size_t units = (size_t)ctx->nch * GC_STEP_KMAX;
+    GC_RESERVE(ctx, L.dstep_unit, units);
+    GC_RESERVE(ctx, L.dstep_segs, units);
+    GC_RESERVE(ctx, L.dstep_rounds, units * nseg * 4);        // four rounds (one per wavefront) per workgroup
+    GC_RESERVE(ctx, L.dstep_partial, units * nseg * 2 * ctx->ntap);
+    GC_RESERVE(ctx, L.dlapped, 1);
+    int rc = L.hostflags.reserve(16, hipHostMallocMapped);
+    if (rc) return rc;
+    GC_RESERVE(ctx, L.dstep_meta, ctx->nch);                   // last: the test above
+    L.step_nseg = nseg;
+    return GNSSCORR_OK;
+}
+
+int gc_loop_take_state(gnsscorr_ctx *ctx)
+{
+    // the look-ahead planner of the batched interface works on the same state: stop it, drop its plan (gc_quiesce
+    // clears ahead_valid and sets state_touched; without a plan ahead_valid is false already)
+    if (ctx->ahead_valid || ctx->slot[0].fin_pending || ctx->slot[1].fin_pending) return gc_quiesce(ctx);
+    ctx->state_touched = true;
+    return GNSSCORR_OK;
+}
+
+extern "C" int gnsscorr_trk_run_loop(gnsscorr_ctx *ctx, int nperiod) { return gc_trk_run_loop(ctx, nperiod, nullptr); }
+
+// wp_ch: nullptr, or the write position each channel is tracked up to ([nch]; 0 starves the channel at once: it plans
+// no period and keeps its state), which the caller read under the context's lock
+int gc_trk_run_loop(gnsscorr_ctx *ctx, int nperiod, const uint64_t *wp_ch)
+{
+    if (!ctx || nperiod <= 0) return gc_fail(GNSSCORR_EINVAL, "trk_run_loop: nperiod %d", nperiod);
+    if (!ctx->nch) return gc_fail(GNSSCORR_ESTATE, "trk_run_loop: no channels set");
+    GC_HIP(hipSetDevice(ctx->device));
+    int rc = gc_ensure_trk_buffers(ctx, nperiod);
+    if (rc) return rc;
+    rc = ensure_step_buffers(ctx);
+    if (rc) return rc;
+    rc = gc_loop_take_state(ctx);
+    if (rc) return rc;
+    GcLoop &L = ctx->loop;
+    L.run_nper = nperiod;
+    const size_t units = (size_t)ctx->nch * nperiod;
+    GC_RESERVE(ctx, L.dlog, units);
+    GC_HIP(hipMemsetAsync(L.dlog, 0, sizeof(gnsscorr_trklog_t) * units, ctx->stream));
+    GC_HIP(hipMemsetAsync(ctx->dcorrI, 0, sizeof(double) * units * ctx->ntap, ctx->stream));
+    GC_HIP(hipMemsetAsync(ctx->dcorrQ, 0, sizeof(double) * units * ctx->ntap, ctx->stream));
+    GC_HIP(hipMemsetAsync(ctx->slot[0].nsamp, 0, sizeof(int) * units, ctx->stream));
+    GC_HIP(hipMemsetAsync(L.dstep_meta, 0, sizeof(GcStepMeta) * ctx->nch, ctx->stream));
+    GC_HIP(hipMemsetAsync(L.dlapped, 0, sizeof(int), ctx->stream));
+    // write position of each channel's ring (ref src/sdrtrk.c:26-28: fendbuffsize*buffcnt)
+    uint64_t wpr[2];
+    rc = gc_ring_positions(ctx, wpr);
+    if (rc) return rc;
+    std::vector<uint64_t> wp(ctx->nch);
+    for (int i = 0; i < ctx->nch; i++) wp[i] = wp_ch ? wp_ch[i] : wpr[ctx->hdesc[i].ftype - 1];
+    GC_HIP(hipMemcpyAsync(L.dwrpos, wp.data(), sizeof(uint64_t) * ctx->nch, hipMemcpyHostToDevice, ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));          // (wp is a local; the flags below are host memory)
+    L.hostflags[0] = 0;
+    L.hostflags[1] = L.sync_hint ? 1u : 0u;     // (some channel is known to be synchronised: steps of loopms periods from the start)
+    // Every step advances every channel that still has work by at least one period, so nperiod steps always suffice;
+    // channels whose nav bit is synchronised advance by up to loopms periods per step.  The host keeps a bounded number
+    // of steps ahead of the device and stops as soon as the device says every channel is done (a pinned word the tail
+    // kernel updates).
+    const int kmax = L.kmax < 1 ? 1 : L.kmax;
+    const int BURST = 4, AHEAD = GC_LOOP_AHEAD;
+    int steps = 0, burst = 0;
+    while (steps <= nperiod) {
+        if (burst >= AHEAD) {                           // at most AHEAD bursts in flight
+            GC_HIP(hipEventSynchronize(ctx->ev_burst[burst % AHEAD]));
+            if (L.hostflags[0] >= (unsigned)ctx->nch) break;
+        }
+        for (int b = 0; b < BURST && steps <= nperiod; b++, steps++) {
+            // periods per step: 1 while no channel is synchronised (a performance hint only: the tail never plans more
+            // than kcap periods, and any kcap >= 1 is correct)
+            rc = loop_step(ctx, L.hostflags[1] ? kmax : 1, 1);
+            if (rc) return rc;
+        }
+        GC_HIP(hipEventRecord(ctx->ev_burst[burst % AHEAD], ctx->stream));
+        burst++;
+    }
+    // close whatever the last correlator launch produced
+    rc = loop_step(ctx, 1, 0);
+    if (rc) return rc;
+    if (L.hostflags[1]) L.sync_hint = true;
+    ctx->last_slot = 0;
+    ctx->slot[0].fin_pending = ctx->slot[1].fin_pending = false;
+    ctx->last_nepoch = nperiod;
+    L.last_nper = nperiod;
+    return GNSSCORR_OK;
+}
+
+extern "C" int gnsscorr_trk_fetch_log(gnsscorr_ctx *ctx, gnsscorr_trklog_t *log, int *ndone)
+{
+    if (!ctx || !ctx->loop.last_nper) return gc_fail(GNSSCORR_ESTATE, "trk_fetch_log: no completed trk_run_loop");
+    GC_HIP(hipSetDevice(ctx->device));
+    const size_t units = (size_t)ctx->nch * ctx->loop.last_nper;
+    if (log) GC_HIP(hipMemcpyAsync(log, ctx->loop.dlog, sizeof(gnsscorr_trklog_t) * units, hipMemcpyDeviceToHost, ctx->stream));
+    if (ndone) GC_HIP(hipMemcpyAsync(ndone, ctx->loop.ddone, sizeof(int) * ctx->nch, hipMemcpyDeviceToHost, ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));
+    return gc_nco_check(ctx);
+}
+
+extern "C" int gnsscorr_trk_loop_lapped(gnsscorr_ctx *ctx, int *nlapped)
+{
+    if (!ctx || !nlapped) return gc_fail(GNSSCORR_EINVAL, "trk_loop_lapped: null argument");
+    if (!ctx->loop.last_nper) return gc_fail(GNSSCORR_ESTATE, "trk_loop_lapped: no completed trk_run_loop");
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_HIP(hipMemcpyAsync(nlapped, ctx->loop.dlapped, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));
+    return GNSSCORR_OK;
 }

@@ -23,7 +23,7 @@ extern "C" int gnsscorr_rx_start(gnsscorr_ctx *ctx, int retry_ms)
     if (!ctx) return gc_fail(GNSSCORR_EINVAL, "null context");
     if (!ctx->nch) return gc_fail(GNSSCORR_ESTATE, "rx_start: no channels set");
     for (int i = 0; i < ctx->nch; i++)
-        if (!ctx->loop_isset[i])
+        if (!ctx->loop.isset[i])
             return gc_fail(GNSSCORR_ESTATE, "rx_start: channel %d has no loop constants (gnsscorr_loop_set)", i);
     GcRx &rx = ctx->rx;
     rx.retry_ms = retry_ms > 0 ? retry_ms : GC_ACQSLEEP;
@@ -98,8 +98,8 @@ extern "C" int gnsscorr_rx_step(gnsscorr_ctx *ctx, int max_periods)
     if (!due.empty()) {
         int rc = gc_acq_run_list(ctx, wpr, due.data(), (int)due.size());
         if (rc) return rc;
-        // the closed loop owns the tracking state; a look-ahead plan of the batched interface would too
-        if (ctx->ahead_valid || ctx->slot[0].fin_pending || ctx->slot[1].fin_pending) { rc = gc_quiesce(ctx); if (rc) return rc; }
+        rc = gc_loop_take_state(ctx);
+        if (rc) return rc;
         rc = gc_acq_handover(ctx, false);
         if (rc) return rc;
         // 2. the outcome: the schedule needs the acquired flags
@@ -133,7 +133,7 @@ extern "C" int gnsscorr_rx_status(gnsscorr_ctx *ctx, gnsscorr_rxstat_t *st)
     const int nch = ctx->nch;
     // sdrthread's cnt of every channel: one column of the device's loop states, behind whatever the stream still runs
     std::vector<uint64_t> cnt(nch);
-    GC_HIP(hipMemcpy2DAsync(cnt.data(), sizeof(uint64_t), (const char *)ctx->dloop.p + offsetof(gnsscorr_loop_t, cnt),
+    GC_HIP(hipMemcpy2DAsync(cnt.data(), sizeof(uint64_t), (const char *)ctx->loop.dloop.p + offsetof(gnsscorr_loop_t, cnt),
                             sizeof(gnsscorr_loop_t), sizeof(uint64_t), nch, hipMemcpyDeviceToHost, ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < nch; i++) {
