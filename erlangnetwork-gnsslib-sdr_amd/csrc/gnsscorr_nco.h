@@ -1861,3 +1861,172 @@ GC_HD bool gc_carrier_value_step_one(const GcCarPlan &P, const GcCarStepC &C, do
     *remcarr_out = p;
     return true;
 }
+
+// ---------------------------------------------------------------------------
+// chain-ready carrier records (the batch planner's carrier chain, gnsscorr_plan.hip)
+// ---------------------------------------------------------------------------
+// What stands in front of the carrier chain's step does not depend on the running phase: the claims row's counts as
+// doubles, the window positions, whether the period's sample count is the claimed one.  One lane per period turns
+// (row, n) into a record once the code chain has the block's sample counts; the sequential chain then reads plain
+// operands.  For a one-binade period (tag 2) the record also carries what gc_one_binade_walk derives from the
+// phase's binade alone -- the step d = RN_u(s), whether s is a tie there, the binade's largest magnitude -- for the
+// binade both ends of the bracket lie in; the chain's step compares its own phase's sign and exponent with the
+// record's and keeps every other condition of the walk (gc_carrier_rec_step_one).
+#define GC_REC_TAG(c)    ((c) & 3)          // the row's tag (0: none, 1: window, 2: one binade, 3: claims without a bracket)
+#define GC_REC_NMATCH    (1 << 2)           // the period's sample count is the one the row was proved for
+#define GC_REC_WALK      (1 << 3)           // 0 < n <= 2^24: there is a period to step
+#define GC_REC_P0(c)     (((c) >> 4) & 15)
+#define GC_REC_PLAST(c)  (((c) >> 8) & 15)
+#define GC_REC_KPREM(c)  (((c) >> 12) & 15)
+#define GC_REC_TIE       (1 << 16)          // one binade: s is a tie on the binade's grid (an odd phase leaves the step)
+#define GC_REC_ONE       (1 << 17)          // one binade: d, top, nd and key are valid
+#define GC_REC_ROW1      (1 << 18)          // the row's own tag was 1 (what the chain's miss tally counts, whatever the record's tag)
+struct GcCarRec {
+    double lo, hi;                  // bracket (remcarr), ends included
+    double dmd[GC_CLAIM_CWIN];      // window: (double)dm[p]; one binade: d, top, (double)n
+    int ctl;                        // GC_REC_*
+    int key;                        // one binade: sign and biased exponent of the phase (bits 63..52 of x)
+};
+
+// What gc_one_binade_walk derives from the phase's biased exponent ex and the addend alone; false: no such step
+GC_HD bool gc_one_binade_consts(int ex, double s, double *d, bool *tie, double *top)
+{
+    GC_FP_STRICT
+    const uint64_t us = gc_d2u(s);
+    const int es = gc_expo(s);
+    *tie = false;
+    if (ex == 0 || ex == 0x7FF || es == 0 || es == 0x7FF) return false;
+    const int et = es + 1075 - ex;
+    if (et >= 1023 + 51) return false;
+    double b = 0.0;
+    if (et >= 1023 - 1) {
+        const double t = gc_u2d((us & 0x800FFFFFFFFFFFFFull) | ((uint64_t)et << 52));
+        b = rint(t);
+        *tie = fabs(t - b) == 0.5;
+    }
+    *d = ldexp(b, ex - 1075);
+    *top = gc_u2d(((uint64_t)ex << 52) | 0x000FFFFFFFFFFFFFull);
+    return true;
+}
+
+// (row, n) -> record.  ilo, s, ex0: the channel's GcCarStepC; ydpi: GcCarPlan
+GC_HD void gc_car_rec_make(GcCarRec &R, const GcCarClaims &row, int n, int ilo, int ex0, double s, double ydpi)
+{
+    GC_FP_STRICT
+    int tag = row.tag & 3;
+    const int p0 = row.i0 - ilo, plast = p0 + row.nseg - 1;
+    // (a window row the discovery wrote has its positions inside the window and its count of subtractions in range;
+    // one that has not goes where rows without a bracket go, and still counts as a window row that missed: GC_REC_ROW1)
+    if (tag == 1 && !(p0 >= 0 && plast >= p0 && plast < GC_CLAIM_CWIN)) tag = 3;
+    if ((tag == 1 || tag == 2) && !(row.kprem >= 0 && row.kprem <= GC_CLAIM_PREM)) tag = 3;
+    int ctl = tag | ((row.tag & 3) == 1 ? GC_REC_ROW1 : 0);
+    ctl |= n == row.nl ? GC_REC_NMATCH : 0;
+    ctl |= (n > 0 && n <= (1 << 24)) ? GC_REC_WALK : 0;
+    R.lo = row.lo;
+    R.hi = row.hi;
+    R.key = 0;
+    for (int p = 0; p < GC_CLAIM_CWIN; p++) R.dmd[p] = 0.0;
+    if (tag == 1) {
+        ctl |= (p0 << 4) | (plast << 8) | (row.kprem << 12);
+        for (int p = 0; p < GC_CLAIM_CWIN; p++) R.dmd[p] = (double)row.dm[p];
+    } else if (tag == 2) {
+        ctl |= row.kprem << 12;
+        const double xlo = gc_div_y(row.lo * GC_NCO_CDIV, GC_NCO_DPI, ydpi);      // ref src/sdrcmn.c:649
+        const double xhi = gc_div_y(row.hi * GC_NCO_CDIV, GC_NCO_DPI, ydpi);
+        const int klo = (int)(gc_d2u(xlo) >> 52), khi = (int)(gc_d2u(xhi) >> 52);
+        double d, top;
+        bool tie;
+        if (ex0 != GC_NO_TABLE && klo == khi && (klo >> 11) == (int)(gc_d2u(s) >> 63) &&
+            gc_one_binade_consts(klo & 0x7FF, s, &d, &tie, &top)) {
+            ctl |= GC_REC_ONE | (tie ? GC_REC_TIE : 0);
+            R.key = klo;
+            R.dmd[0] = d;
+            R.dmd[1] = top;
+            R.dmd[2] = (double)n;
+        }
+    }
+    R.ctl = ctl;
+}
+
+// Carrier, one-binade shape on a record: gc_carrier_value_step_one for a phase whose sign and exponent are the
+// record's (the walk's d, tie and top are functions of those), every other condition of the walk and of the
+// remainder kept.  false: *remcarr_out not written, the caller takes gc_carrier_value_step_one or the certified step.
+GC_HD bool gc_carrier_rec_step_one(double ydpi, double remcarr, int key, bool tie, double d, double top, double nd, int kprem,
+                                   double *remcarr_out)
+{
+    GC_FP_STRICT
+    const double x = gc_div_y(remcarr * GC_NCO_CDIV, GC_NCO_DPI, ydpi);      // ref src/sdrcmn.c:649
+    const uint64_t ux = gc_d2u(x);
+    if ((int)(ux >> 52) != key) return false;
+    if (tie && (ux & 1)) return false;
+    const double y = fma(nd, d, x);
+    if (!(fabs(y) <= top)) return false;
+    bool held;
+    const double p = gc_prem_checked(y, kprem, &held);
+    if (!held) return false;
+    *remcarr_out = p;
+    return true;
+}
+
+// ---------------------------------------------------------------------------
+// the code chain as a scan (the batch planner's code chain, gnsscorr_plan.hip)
+// ---------------------------------------------------------------------------
+// rescode starts a period at c0 = RN(RN(remcode - smax ci) + len) (ref src/sdrcmn.c:613-617, the cs < 0 side), a
+// multiple of u = ulp of the binade below the code length, and uses remcode for nothing else: the period's end
+// r1 and the next period's c0 are functions of c0.  For fixed claims every operation behind c0 adds a constant and
+// rounds to a grid finer than u, or to u itself (only next to the code length, where the addend is no tie: P.ok), so a
+// shift of c0 by m u shifts r1 and the next c0 by m u exactly.  A scan row holds what the step from the bracket's
+// lower end gives -- Yhat = c0 / u, r1, K = (next c0 - c0) / u -- and is valid when the upper end gives the same K,
+// all four heads lie on the cs < 0 side in the code length's binade, and the inner differences of the two ends
+// have one exponent (then their roundings are to one grid).  Then for a period whose exact start lies in the bracket
+// and whose c0 / u is Y:   next remcode = r1 + (Y - Yhat) u   and   next Y = Y + K,   both exact.
+struct GcCodeScanRow {              // 32 bytes
+    long long Yhat, K;              // units of u
+    double r1;
+    int valid, pad;
+};
+
+// c0 of a period that starts at remcode; *neg: the reference took the cs < 0 side; *ecs: exponent of the inner difference
+GC_HD double gc_code_scan_head(double remcode, double smaxci, double dlen, bool *neg, int *ecs)
+{
+    GC_FP_STRICT
+    const double cs = remcode - smaxci;
+    *neg = cs < 0.0;
+    *ecs = gc_expo(cs);
+    return cs + dlen;
+}
+
+// u and 1/u for a code of dlen chips (powers of two)
+GC_HD double gc_code_scan_u(double dlen) { return gc_u2d((uint64_t)(gc_expo(gc_u2d(gc_d2u(dlen) - 1)) - 52) << 52); }
+GC_HD double gc_code_scan_invu(double dlen) { return gc_u2d((uint64_t)(2046 - (gc_expo(gc_u2d(gc_d2u(dlen) - 1)) - 52)) << 52); }
+
+// lo, hi: the bracket; r1lo, r1hi: what the period's step returns from them (same claims, same sample count)
+GC_HD void gc_code_scan_row(GcCodeScanRow &R, const GcCodePlan &P, double lo, double hi, double r1lo, double r1hi)
+{
+    GC_FP_STRICT
+    R.Yhat = R.K = 0;
+    R.r1 = r1lo;
+    R.valid = R.pad = 0;
+    if (!P.ok || P.it >= P.itop) return;            // (a tie on the grid u: the result would depend on the parity of c0 / u)
+    const int etop = gc_expo(P.limtop);
+    bool n0, n1, n2, n3;
+    int e0, e1, e2, e3;
+    const double y0 = gc_code_scan_head(lo, P.smaxci, P.dlen, &n0, &e0), y1 = gc_code_scan_head(hi, P.smaxci, P.dlen, &n1, &e1);
+    const double z0 = gc_code_scan_head(r1lo, P.smaxci, P.dlen, &n2, &e2), z1 = gc_code_scan_head(r1hi, P.smaxci, P.dlen, &n3, &e3);
+    if (!(n0 && n1 && n2 && n3) || e0 != e1 || e2 != e3) return;
+    if (gc_expo(y0) != etop || gc_expo(y1) != etop || gc_expo(z0) != etop || gc_expo(z1) != etop) return;
+    if (!(y0 < P.dlen && y1 < P.dlen && z0 < P.dlen && z1 < P.dlen)) return;
+    const double invu = gc_code_scan_invu(P.dlen);
+    const double k0 = (z0 - y0) * invu, k1 = (z1 - y1) * invu;      // (differences inside one binade, scaled by a power of two: exact)
+    if (!(k0 == k1) || !(fabs(k0) < 4503599627370496.0) || floor(k0) != k0) return;
+    R.Yhat = (long long)(y0 * invu);
+    R.K = (long long)k0;
+    R.valid = 1;
+}
+
+// the period after a row's (r1, Yhat): its start, for a period whose c0 / u is Y
+GC_HD double gc_code_scan_next(double r1, long long Yhat, long long Y, double u)
+{
+    GC_FP_STRICT
+    return r1 + (double)(Y - Yhat) * u;
+}

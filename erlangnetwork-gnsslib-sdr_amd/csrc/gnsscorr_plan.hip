@@ -118,7 +118,7 @@ __global__ __launch_bounds__(64) void trk_specdev_kernel(const GcChan *__restric
 __global__ __launch_bounds__(GC_SPEC_CHUNK) void trk_spec_kernel(const GcChan *__restrict__ chan, const GcTrkState *__restrict__ state_in,
                                                                   const double *__restrict__ devc, const double *__restrict__ devk,
                                                                   int *__restrict__ claims_code, int *__restrict__ claims_car,
-                                                                  int nch, int nepoch, int e_off)
+                                                                  GcCodeScanRow *__restrict__ scan, int nch, int nepoch, int e_off)
 {
     // e_off: periods between the state handed in and the batch's first period (0: the batch starts at that
     // state; nepoch: the state is the start of the batch BEFORE this one, whose chain is still running -- the
@@ -167,6 +167,10 @@ __global__ __launch_bounds__(GC_SPEC_CHUNK) void trk_spec_kernel(const GcChan *_
     ck.tag = 0;
     cc.n = cc.pad = 0;
     cc.lo = cc.hi = ck.lo = ck.hi = 0.0;
+    GcCodeScanRow srow;             // the code chain's scan row (gnsscorr_nco.h): only for a bracketed period
+    srow.Yhat = srow.K = 0;
+    srow.r1 = 0.0;
+    srow.valid = srow.pad = 0;
     if (C.ok) {
         double r0, g0;
         int nhat;
@@ -183,10 +187,10 @@ __global__ __launch_bounds__(GC_SPEC_CHUNK) void trk_spec_kernel(const GcChan *_
             const double lo = rt - w, hi = rt + w;
             const int nlo = gc_period_nsamp(C.dlen, lo, C.spc), nhi = gc_period_nsamp(C.dlen, hi, C.spc);
             if (!(nlo == nhi && nlo > 0 && nlo <= (1 << 24))) continue;
-            double dummy;
+            double flo = 0.0, fhi = 0.0;
             const bool side = (lo - C.PC.smaxci < 0.0) == (hi - C.PC.smaxci < 0.0);     // (ref src/sdrcmn.c:614: one branch for the whole bracket)
-            const bool oklo = gc_code_claims<true>(C.PC, lo, nlo + 2 * C.smax, cc, &dummy);
-            const bool okhi = oklo && gc_code_claims<false>(C.PC, hi, nlo + 2 * C.smax, cc, &dummy);
+            const bool oklo = gc_code_claims<true>(C.PC, lo, nlo + 2 * C.smax, cc, &flo);
+            const bool okhi = oklo && gc_code_claims<false>(C.PC, hi, nlo + 2 * C.smax, cc, &fhi);
             // (the discovering step allows the widest tail; the chain's instance for this channel may be narrower, and
             // in its value form nothing would notice a tail it cannot hold)
             const bool tailfits = nlo + 2 * C.smax - cc.jsum <= C.tmax;
@@ -197,6 +201,7 @@ __global__ __launch_bounds__(GC_SPEC_CHUNK) void trk_spec_kernel(const GcChan *_
                 cc.n = nlo;
                 cc.lo = lo;
                 cc.hi = hi;
+                gc_code_scan_row(srow, C.PC, lo, hi, flo, fhi);
             }
         }
         if (!bracketed) {
@@ -247,11 +252,18 @@ __global__ __launch_bounds__(GC_SPEC_CHUNK) void trk_spec_kernel(const GcChan *_
         rc[q] = pc4[q];
         rk[q] = pk4[q];
     }
+    scan[row] = srow;
 }
 
 // which path served the periods of the batches planned so far: [0] code on claims, [1] code certified,
 // [2] code walkers, [3..5] the same for the carrier (tools/debug, tests)
 __device__ unsigned long long gc_plan_stats[8];
+// per channel (the first GC_PLAN_REC_CH): periods the batch chain's carrier wavefront served by its records' own steps --
+// [2 ch] the window value step, [2 ch + 1] the one-binade record step (tests; gnsscorr_debug_plan_rec)
+#define GC_PLAN_REC_CH 64
+__device__ unsigned long long gc_plan_rec[2 * GC_PLAN_REC_CH];
+// per channel (the first GC_PLAN_REC_CH): periods the code wavefront served by the scan (verify mode: would have served)
+__device__ unsigned long long gc_plan_scan[GC_PLAN_REC_CH];
 
 // Which instance of the batch chain serves a channel: the table binade that holds the code length (the shape
 // of the code step: 2..64 samples per chip give 7..12) and whether the tail fits 8, 15 or 32 positions.  -1: none
@@ -379,11 +391,12 @@ __global__ __launch_bounds__(128) void trk_plan_kernel(const GcChan *__restrict_
 // compute unit's four SIMDs then carried 5300 clocks of fp64 work per period: 0.82 us.)
 // GNSSCORR_PLAN_VERIFY=1 (tests): the chain evaluates WITH the checks; a bracketed start whose step fails them is
 // counted in gc_plan_stats[6] (and redone by the certified path) -- the proof above says the count stays zero.
-#define GC_P4_BLK 64            // periods whose plan entries are written at a time
+#define GC_P4_BLK 64            // periods whose carrier records are staged and whose plan entries are written at a time
 struct Plan4Shared {
     int nsh[GC_PLAN_MAXE];                          // samples per period, code chain -> carrier chain
     double vstart[2][GC_P4_BLK];                    // the block's period starts (remcode | remcarr), for the plan entries
     unsigned long long vbuff[GC_P4_BLK];
+    GcCarRec rec[GC_P4_BLK];                        // the block's carrier records (gnsscorr_nco.h), staged by the carrier wavefront's lanes
     int prog;                                       // periods the code chain has finished
     GcCarPlan pkfull;                               // the carrier's tables as the certified step wants them, built once per batch
 };
@@ -425,7 +438,8 @@ __device__ __forceinline__ GcCodeClaims plan4_code_row(const GC_CONST gc_v4i *r)
     c.hi = gc_u2d(((uint64_t)(unsigned)v5.w << 32) | (unsigned)v5.z);
     return c;
 }
-__device__ __forceinline__ GcCarClaims plan4_car_row(const GC_CONST gc_v4i *r)
+template <class RowPtr>
+__device__ __forceinline__ GcCarClaims plan4_car_row(RowPtr r)
 {
     const gc_v4i v0 = r[0], v1 = r[1], v2 = r[2], v3 = r[3], v5 = r[5];
     GcCarClaims c;
@@ -478,16 +492,19 @@ __device__ unsigned long long gc_plan_prof[64 * 16];
 #define GC_PP_T0(v) const unsigned long long v = __builtin_readcyclecounter()
 #define GC_PP_ADD(k, v) pp_[k] += __builtin_readcyclecounter() - (v)
 #define GC_PP_INC(k) pp_[k] += 1
+#define GC_PP_ADDN(k, n) pp_[k] += (n)
 #define GC_PP_OUT(which) do { if (lane == 0 && blockIdx.x < 64) for (int k_ = 0; k_ < 7; k_++) atomicAdd(&gc_plan_prof[blockIdx.x * 16 + (which) * 8 + k_], pp_[k_]); } while (0)
 #else
 #define GC_PP_DECL do { } while (0)
 #define GC_PP_T0(v) do { } while (0)
 #define GC_PP_ADD(k, v) do { } while (0)
 #define GC_PP_INC(k) do { } while (0)
+#define GC_PP_ADDN(k, n) do { } while (0)
 #define GC_PP_OUT(which) do { } while (0)
 #endif
 struct Plan4Job {               // what both wavefronts know about the batch
     const int4 *claims_code, *claims_car;           // the channel's rows
+    const GcCodeScanRow *scan;                      // ... and its scan rows
     GcTrkPlan *out;
     GcTrkState *state_out;
     GcTrkState s;
@@ -500,6 +517,7 @@ __device__ __forceinline__ Plan4Job plan4_job(const Plan4Job *J_)
     Plan4Job J = *plan2_uni(J_);
     J.claims_code = plan2_uni(J.claims_code);
     J.claims_car = plan2_uni(J.claims_car);
+    J.scan = plan2_uni(J.scan);
     J.out = plan2_uni(J.out);
     J.state_out = plan2_uni(J.state_out);
     J.nepoch = plan2_uni(J.nepoch);
@@ -559,7 +577,75 @@ __device__ __forceinline__ int plan4_scopy(int x)
 }
 __device__ __forceinline__ bool plan4_bcopy(bool x) { return __builtin_amdgcn_readfirstlane(x ? 1 : 0) != 0; }
 
-// The code NCO's chain (one instance per shape of the code step: its constants sit in registers for the batch)
+// ---- the code chain as a scan (gnsscorr_nco.h: "the code chain as a scan") ----
+// inclusive prefix sum over the wavefront's lanes
+__device__ __forceinline__ long long plan4_wscan(long long v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const long long t = __shfl_up(v, d, 64);
+        v += lane >= d ? t : 0;
+    }
+    return v;
+}
+__device__ __forceinline__ double plan4_lane_d(double x, int l) { return plan2_uni(__shfl(x, l, 64)); }
+__device__ __forceinline__ long long plan4_lane_ll(long long x, int l)
+{
+    const long long v = __shfl(x, l, 64);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ int plan4_lane_i(int x, int l) { return plan2_uni(__shfl(x, l, 64)); }
+
+struct Plan4ScanK {             // the channel's constants of the scan
+    double smaxci, dlen, spc, yspc, u, invu;
+    bool fastdiv;
+};
+struct Plan4ScanLane {          // a lane's period of the block: its rows ...
+    long long Yhat, K;
+    double r1, lo, hi;
+    int valid, tag, rown;
+    // ... and what a round of the scan proposes for it
+    double rem, nxt;            // its start; the start of the period behind it
+    long long bl;               // its position in the ring
+    int n;
+    bool inside;                // start inside the bracket with the bracket's sample count (row valid or not)
+};
+
+// One round: periods start .. nb - 1 of the block from the exact state (rem0, buff0) of period `start`.  Lane l
+// proposes period l; returns f, the first period the scan does not serve (nb: none) -- the proposals of periods
+// start .. f (f included: its START is still exact) hold.
+__device__ __forceinline__ int plan4_scan_round(Plan4ScanLane &L, const Plan4ScanK &K, int start, int nb, int lane, double rem0, unsigned long long buff0)
+{
+    bool neg;
+    int ecs;
+    const long long Y0 = (long long)(gc_code_scan_head(rem0, K.smaxci, K.dlen, &neg, &ecs) * K.invu);
+    const bool act = lane >= start && lane < nb;
+    const bool rowok = act && L.tag == 1 && L.valid != 0;
+    const long long k = rowok ? L.K : 0;
+    const long long Y = Y0 + plan4_wscan(k, lane) - k;
+    L.nxt = gc_code_scan_next(L.r1, L.Yhat, Y, K.u);
+    const double prev = __shfl_up(L.nxt, 1, 64);
+    L.rem = lane == start ? rem0 : prev;
+    const double num = __dsub_rn(K.dlen, L.rem);                            // ref src/sdrtrk.c:31-32
+    double qn = gc_div_y(num, K.spc, K.yspc);
+    if (__builtin_expect(!K.fastdiv, 0)) qn = __ddiv_rn(num, K.spc);
+    L.n = (qn > -2147483648.0 && qn < 2147483648.0) ? (int)qn : 0;
+    L.inside = L.tag == 1 && L.rem >= L.lo && L.rem <= L.hi && L.n == L.rown;
+    const bool ok = rowok && L.inside && L.n > 0 && L.n <= (1 << 24);
+    const unsigned long long bad = __ballot(act && !ok);
+    const int f = bad ? (int)__builtin_ctzll(bad) : nb;
+    const long long nn = act ? (long long)L.n : 0;
+    L.bl = (long long)buff0 + plan4_wscan(nn, lane) - nn;
+    return plan2_uni(f);
+}
+
+// The code NCO's chain (one instance per shape of the code step: its constants sit in registers for the batch).
+// Per block the scan serves every run of periods whose exact start lies in its bracket (lanes write their periods'
+// entries); the period that ends a run takes the step with its checks, as before; a block whose runs are empty twice
+// running takes the sequential loop, the chain of the states before.  Verify mode: the sequential loop with its
+// checks for every period, then the scan's proposals held against what it produced (gc_plan_stats[6]).
 template <int ITOP, int TMAX>
 __device__ __attribute__((noinline)) void plan4_code_wave(double ci_, double spc_, int clen_, int smax_, const Plan4Job *J_, int lane)
 {
@@ -574,20 +660,95 @@ __device__ __attribute__((noinline)) void plan4_code_wave(double ci_, double spc
     const double yspc = __ddiv_rn(1.0, spc);
     const bool fastdiv = spc > 1e-300 && spc < 1e300 && yspc < 1e300;
     unsigned tally0 = 0, tally1 = 0, tally2 = 0, miss = 0, mism = 0;    // (scalars: an array indexed by a variable lives in memory)
+    unsigned scanned = 0;
     GC_GLOBAL GcTrkPlan *out = (GC_GLOBAL GcTrkPlan *)J.out;
     double remcode = J.s.remcode;
     unsigned long long buffloc = J.s.buffloc;
+    Plan4ScanK SK;
+    SK.smaxci = PC.smaxci;
+    SK.dlen = dlen;
+    SK.spc = spc;
+    SK.yspc = yspc;
+    SK.u = gc_code_scan_u(dlen);
+    SK.invu = gc_code_scan_invu(dlen);
+    SK.fastdiv = fastdiv;
+    const bool scan_on = J.scan != nullptr && PC.ok;
     GC_PP_DECL;
     GC_PP_T0(ptot_);
     for (int b = 0; b < J.nblk; b++) {
         const int nb = plan4_nb(J, b), e0 = b * GC_P4_BLK;
         const GC_CONST gc_v4i *rows = (const GC_CONST gc_v4i *)J.claims_code + (size_t)e0 * (GC_CLAIM_ROW / 4);
+        Plan4ScanLane L = {};
+        int ifrom = 0;                  // first period of the block left to the sequential loop
+        if (scan_on) {
+            const int el = e0 + (lane < nb ? lane : nb - 1);
+            const GC_GLOBAL gc_v4i *sr = (const GC_GLOBAL gc_v4i *)J.scan + (size_t)el * 2;
+            const GC_GLOBAL gc_v4i *cr = (const GC_GLOBAL gc_v4i *)J.claims_code + (size_t)el * (GC_CLAIM_ROW / 4);
+            const gc_v4i s0 = sr[0], s1 = sr[1], c0 = cr[0], c4 = cr[4], c5 = cr[5];
+            L.Yhat = (long long)(((unsigned long long)(unsigned)s0.y << 32) | (unsigned)s0.x);
+            L.K = (long long)(((unsigned long long)(unsigned)s0.w << 32) | (unsigned)s0.z);
+            L.r1 = gc_u2d(((uint64_t)(unsigned)s1.y << 32) | (unsigned)s1.x);
+            L.valid = s1.z;
+            L.tag = c0.x;
+            L.rown = c4.z;
+            L.lo = gc_u2d(((uint64_t)(unsigned)c5.y << 32) | (unsigned)c5.x);
+            L.hi = gc_u2d(((uint64_t)(unsigned)c5.w << 32) | (unsigned)c5.z);
+        }
+        if (scan_on && !J.verify) {
+            int start = 0, empty = 0;
+            while (start < nb) {
+                const int f = plan4_scan_round(L, SK, start, nb, lane, remcode, buffloc);
+                if (lane >= start && lane < f) {
+                    g_plan4.vstart[0][lane] = L.rem;
+                    g_plan4.vbuff[lane] = (unsigned long long)L.bl;
+                    g_plan4.nsh[e0 + lane] = L.n;
+                }
+                tally0 += (unsigned)(f - start);
+                scanned += (unsigned)(f - start);
+                if (f >= nb) {              // the run reaches the block's end: the state behind its last period
+                    remcode = plan4_lane_d(L.nxt, nb - 1);
+                    buffloc = (unsigned long long)plan4_lane_ll(L.bl + (long long)L.n, nb - 1);
+                    start = nb;
+                    break;
+                }
+                remcode = plan4_lane_d(L.rem, f);
+                buffloc = (unsigned long long)plan4_lane_ll(L.bl, f);
+                empty = f == start ? empty + 1 : 0;
+                if (empty >= 2) {           // no run twice running: the rest of the block by the sequential loop
+                    start = f;
+                    break;
+                }
+                // period f: the step with its checks, then the certified step, then the walkers
+                const int n = plan4_lane_i(L.n, f);
+                const bool inside_u = plan4_lane_i(L.inside ? 1 : 0, f) != 0, claims_u = plan4_lane_i(L.tag, f) == 1;
+                if (lane == 0) {
+                    g_plan4.vstart[0][f] = remcode;
+                    g_plan4.vbuff[f] = buffloc;
+                    g_plan4.nsh[e0 + f] = n;
+                }
+                if (n > 0 && n <= (1 << 24)) {
+                    double rs;
+                    const int how = plan4_code_other<ITOP, TMAX>(ci, clen, smax, remcode, n, lane,
+                                                                 reinterpret_cast<const GcCodeClaims *>(J.claims_code) + e0 + f, &rs);
+                    GC_PP_INC(4);
+                    tally0 += how == 0 ? 1 : 0;
+                    tally1 += how == 1 ? 1 : 0;
+                    tally2 += how == 2 ? 1 : 0;
+                    mism += (inside_u && how != 0) ? 1 : 0;
+                    miss += (!inside_u && claims_u) ? 1 : 0;
+                    remcode = rs;
+                }
+                buffloc += (unsigned long long)(long long)n;
+                start = f + 1;
+            }
+            ifrom = start;
+        }
         // One set of scalar registers holds the row: a period first turns what it needs of it into vector values and
         // scalar copies (the chain pays ~4 clocks for every instruction it issues, whatever the instruction: no copy
         // of the whole row from "next" to "this"), then asks for the next row into the same registers, and evaluates
         // while that is in flight.
-        GcCodeClaims row = plan4_code_row(rows);
-        for (int i = 0; i < nb; i++) {
+        GcCodeClaims row = plan4_code_row(rows + (ifrom < nb ? ifrom : 0) * (GC_CLAIM_ROW / 4));
+        for (int i = ifrom; i < nb; i++) {
             __builtin_amdgcn_s_waitcnt(0xC07F);        // lgkmcnt(0): the row has landed
             const double num = __dsub_rn(dlen, remcode);                            // ref src/sdrtrk.c:31-32
             double qn = gc_div_y(num, spc, yspc);
@@ -637,6 +798,26 @@ __device__ __attribute__((noinline)) void plan4_code_wave(double ci_, double spc
             }
             buffloc += (unsigned long long)(long long)n;
         }
+        if (scan_on && J.verify) {
+            // what the scan would have done with this block, from the exact states the checked chain left in LDS
+            int start = 0;
+            while (start < nb) {
+                const double rem0 = plan2_uni(g_plan4.vstart[0][start]);
+                const unsigned long long b0 = (unsigned long long)plan4_lane_ll((long long)g_plan4.vbuff[start], 0);
+                const int f = plan4_scan_round(L, SK, start, nb, lane, rem0, b0);
+                const int last = f < nb ? f : nb - 1;       // (period f's start is a proposal too)
+                const int li = lane < nb ? lane : 0;
+                const bool differs = lane >= start && lane <= last &&
+                                     (gc_d2u(L.rem) != gc_d2u(g_plan4.vstart[0][li]) || (unsigned long long)L.bl != g_plan4.vbuff[li] ||
+                                      L.n != g_plan4.nsh[e0 + li]);
+                mism += (unsigned)__popcll(__ballot(differs));
+                scanned += (unsigned)(f - start);
+                // (a run that reaches the block's end proposes the state behind it)
+                if (f >= nb) mism += gc_d2u(plan4_lane_d(L.nxt, nb - 1)) != gc_d2u(remcode) ? 1 : 0;
+                start = f + 1;
+            }
+        }
+        if (lane == 0) plan4_publish(e0 + nb);
         // the block's plan entries, one lane per period (the carrier chain adds phi0)
         if (lane < nb) {
             GC_GLOBAL GcTrkPlan *o = out + e0 + lane;
@@ -656,6 +837,7 @@ __device__ __attribute__((noinline)) void plan4_code_wave(double ci_, double spc
         so->codefreq = J.s.codefreq;
         so->remcode = remcode;
         so->buffloc = buffloc;
+        if (scanned && blockIdx.x < GC_PLAN_REC_CH) atomicAdd(&gc_plan_scan[blockIdx.x], (unsigned long long)scanned);
         if (tally0) atomicAdd(&gc_plan_stats[0], (unsigned long long)tally0);
         if (tally1) atomicAdd(&gc_plan_stats[1], (unsigned long long)tally1);
         if (tally2) atomicAdd(&gc_plan_stats[2], (unsigned long long)tally2);
@@ -724,7 +906,122 @@ __device__ __attribute__((noinline)) void plan4_car_cert_wave(double ps_, const 
     }
 }
 
-// The carrier NCO's chain, behind the code's
+// A one-binade period (tag 2) whose record has no step, or whose phase is not in the record's binade: the reference
+// form, which derives the binade's step from the phase itself.  Verify mode comes here for every such period and
+// (only then) holds the record's step against it.
+// returns bit 0: stepped (*out written), bit 1 (verify): the record's step disagrees
+__device__ __attribute__((noinline)) int plan4_car_one(double s_, int ex0_, double remcarr_, int n_, int ctl_, int key_, double d_, double top_,
+                                                       double nd_, int verify_, double *out)
+{
+    const int verify = plan2_uni(verify_);
+    const double s = plan2_uni(s_), remcarr = plan2_uni(remcarr_), d = plan2_uni(d_), top = plan2_uni(top_), nd = plan2_uni(nd_);
+    const int ex0 = plan2_uni(ex0_), n = plan2_uni(n_), ctl = plan2_uni(ctl_), key = plan2_uni(key_);
+    GcCarPlan P;                                    // (the step reads ydpi, s and ex0, nothing else)
+    P.ydpi = 1.0 / GC_NCO_DPI;
+    GcCarStepC C;
+    C.s = s;
+    C.ex0 = ex0;
+    double r = remcarr, r2 = remcarr;
+    const bool done = gc_carrier_value_step_one(P, C, remcarr, n, GC_REC_KPREM(ctl), &r);
+    int bad = 0;
+    if (verify && (ctl & GC_REC_ONE)) {
+        const bool done2 = gc_carrier_rec_step_one(P.ydpi, remcarr, key, (ctl & GC_REC_TIE) != 0, d, top, nd, GC_REC_KPREM(ctl), &r2);
+        bad = (done2 && (!done || gc_d2u(r2) != gc_d2u(r))) ? 2 : 0;
+    }
+    if (done) *out = r;
+    return (done ? 1 : 0) | bad;
+}
+
+// a record -> registers: the address is the same in every lane and the operands arrive in vector registers (where the
+// fp64 operations want them); the caller's scheduling barrier keeps the reads where they are written, one period
+// ahead of their use, and nothing waits for them before that
+__device__ __forceinline__ void plan4_rec_load(GcCarRec &R, int i)
+{
+    const GcCarRec &r = g_plan4.rec[i];
+    R.lo = r.lo;
+    R.hi = r.hi;
+#pragma unroll
+    for (int p = 0; p < GC_CLAIM_CWIN; p++) R.dmd[p] = r.dmd[p];
+    R.ctl = r.ctl;
+    R.key = r.key;
+}
+
+struct Plan4CarRun {            // the carrier chain's running values
+    double remcarr, phi;        // phi: lane i keeps the start of the block's period i
+    unsigned recwin, recone;    // periods served by the record's window step / one-binade step (they count in gc_plan_stats[3] too)
+    unsigned tally0, tally1, tally2, miss, mism, slow;
+    unsigned long long slowclk; // (GC_PLAN_PROF) clocks in the out-of-line paths
+};
+
+#ifdef GC_PLAN_PROF
+#define GC_PP_SLOW0(v) const unsigned long long v = __builtin_readcyclecounter()
+#define GC_PP_SLOW1(S, v) (S).slowclk += __builtin_readcyclecounter() - (v)
+#else
+#define GC_PP_SLOW0(v) do { } while (0)
+#define GC_PP_SLOW1(S, v) do { } while (0)
+#endif
+
+// One period of the carrier chain on its record
+__device__ __forceinline__ void plan4_car_period(Plan4CarRun &S, const GcCarRec &R, const GcCarPlan &PK, const GcCarStepC &CK, double ps, int nsamp,
+                                                 const Plan4Job &J, int e, int i, int lane)
+{
+    const int ctl = plan2_uni(R.ctl);
+    const int tag = GC_REC_TAG(ctl);
+    const double remcarr = S.remcarr;
+    const bool inside_u = plan4_bcopy(remcarr >= R.lo && remcarr <= R.hi) && (ctl & (3 | GC_REC_NMATCH)) == (1 | GC_REC_NMATCH);
+    S.phi = lane == i ? remcarr : S.phi;
+    if (!(ctl & GC_REC_WALK)) return;
+    double rp = remcarr;
+    bool done = false;
+    if (inside_u && !J.verify) {
+        rp = gc_carrier_value_step(PK, CK, remcarr, GC_REC_P0(ctl), GC_REC_PLAST(ctl), GC_REC_KPREM(ctl), R.dmd);     // the value; the bracket is the proof
+        done = true;
+        S.recwin++;
+    } else if (tag == 2) {
+        // a period inside one binade: the step carries its own conditions and is judged by them; the remainder's one
+        // claim is checked
+        if ((ctl & GC_REC_ONE) && !J.verify) {
+            double r2 = remcarr;
+            done = plan4_bcopy(gc_carrier_rec_step_one(PK.ydpi, remcarr, plan2_uni(R.key), (ctl & GC_REC_TIE) != 0, R.dmd[0], R.dmd[1], R.dmd[2],
+                                                       GC_REC_KPREM(ctl), &r2));
+            rp = done ? r2 : rp;
+            S.recone += done ? 1 : 0;
+        }
+        if (!done) {
+            double r1;
+            const int n = plan2_uni(g_plan4.nsh[e]);
+            GC_PP_SLOW0(pone_);
+            const int how = plan4_car_one(CK.s, CK.ex0, remcarr, n, ctl, R.key, R.dmd[0], R.dmd[1], R.dmd[2], J.verify, &r1);
+            GC_PP_SLOW1(S, pone_);
+            done = (how & 1) != 0;
+            S.slow++;
+            S.tally0 += done ? 1 : 0;
+            S.mism += (how & 2) ? 1 : 0;
+            if (done) rp = r1;
+        }
+    }
+    if (!done) {
+        // claims without a bracket around this start, none at all, or verify mode
+        double rs;
+        const int n = plan2_uni(g_plan4.nsh[e]);
+        GC_PP_SLOW0(pother_);
+        const int how = plan4_car_other(ps, nsamp, remcarr, n, lane, reinterpret_cast<const GcCarClaims *>(J.claims_car) + e, &rs);
+        GC_PP_SLOW1(S, pother_);
+        S.slow++;
+        S.tally0 += how == 0 ? 1 : 0;
+        S.tally1 += how == 1 ? 1 : 0;
+        S.tally2 += how == 2 ? 1 : 0;
+        S.mism += (inside_u && how != 0) ? 1 : 0;
+        S.miss += (!inside_u && (ctl & GC_REC_ROW1)) ? 1 : 0;
+        rp = rs;
+    }
+    S.remcarr = rp;
+}
+
+// The carrier NCO's chain, a block behind the code's.  Per block: the lanes ask for their periods' claims rows,
+// the wavefront waits (once) until the code chain has the block's sample counts, every lane turns (row, n) into a
+// chain-ready record in LDS (gc_car_rec_make), and the sequential loop runs on records read one period ahead --
+// no scalar row loads, no conversions and no progress poll between two dependent steps.
 __device__ __attribute__((noinline)) void plan4_car_wave(double ps_, int nsamp_, const Plan4Job *J_, int lane)
 {
     const int nsamp = plan2_uni(nsamp_);
@@ -750,92 +1047,69 @@ __device__ __attribute__((noinline)) void plan4_car_wave(double ps_, int nsamp_,
     gc_car_plan_init(PK, ps, false, false);
     GcCarStepC CK;
     gc_car_stepc_init(CK, PK, nsamp + 16);
-    const int ilo = plan2_uni(CK.ilo);
-    unsigned tally0 = 0, tally1 = 0, tally2 = 0, miss = 0, mism = 0;    // (scalars: an array indexed by a variable lives in memory)
+    const int ilo = plan2_uni(CK.ilo), ex0 = plan2_uni(CK.ex0);
     GC_GLOBAL GcTrkPlan *out = (GC_GLOBAL GcTrkPlan *)J.out;
-    double remcarr = J.s.remcarr;
+    Plan4CarRun S;
+    S.remcarr = J.s.remcarr;
+    S.phi = 0.0;
+    S.recwin = S.recone = S.tally0 = S.tally1 = S.tally2 = S.miss = S.mism = S.slow = 0;
+    S.slowclk = 0;
     int seen = 0;
     GC_PP_DECL;
     GC_PP_T0(ptot_);
     for (int b = 0; b < J.nblk; b++) {
         const int nb = plan4_nb(J, b), e0 = b * GC_P4_BLK;
-        const GC_CONST gc_v4i *rows = (const GC_CONST gc_v4i *)J.claims_car + (size_t)e0 * (GC_CLAIM_ROW / 4);
-        GcCarClaims row = plan4_car_row(rows);
-        for (int i = 0; i < nb; i++) {
-            GC_PP_T0(ptop_);
-            if (seen <= e0 + i) {
-                GC_PP_T0(pn_);
-                while (seen <= e0 + i) {
-                    seen = plan2_uni(plan4_progress());
-                    if (seen <= e0 + i) __builtin_amdgcn_s_sleep(1);
-                }
-                GC_PP_ADD(3, pn_);
+        GC_PP_T0(ptop_);
+        // rows first (they were written before this kernel started), then the wait for the block's sample counts
+        const int el = e0 + (lane < nb ? lane : nb - 1);
+        const GcCarClaims row = plan4_car_row((const GC_GLOBAL gc_v4i *)J.claims_car + (size_t)el * (GC_CLAIM_ROW / 4));
+        if (seen < e0 + nb) {
+            GC_PP_T0(pn_);
+            while (seen < e0 + nb) {
+                seen = plan2_uni(plan4_progress());
+                if (seen < e0 + nb) __builtin_amdgcn_s_sleep(1);
             }
-            const int n = plan2_uni(g_plan4.nsh[e0 + i]);
-            __builtin_amdgcn_s_waitcnt(0xC07F);        // lgkmcnt(0): n and the row are here
-            const int tag = row.tag;
-            const bool inside = tag == 1 && remcarr >= row.lo && remcarr <= row.hi && n == row.nl;
-            double dmd[GC_CLAIM_CWIN];
-            const int p0 = plan4_scopy(row.i0 - ilo);
-            const int plast = plan4_scopy(row.i0 - ilo + row.nseg - 1);
-            const int kprem = plan4_scopy(row.kprem);
-#pragma unroll
-            for (int k = 0; k < GC_CLAIM_CWIN; k++) {
-                dmd[k] = (double)row.dm[k];
-                GC_PIN_V(dmd[k]);
-            }
-            const bool inside_u = plan4_bcopy(inside);
-            const int tag_u = plan4_scopy(tag);
-            __builtin_amdgcn_sched_barrier(0);
-            if (i + 1 < nb) row = plan4_car_row(rows + (i + 1) * (GC_CLAIM_ROW / 4));       // (in flight during this period's step)
-            __builtin_amdgcn_sched_barrier(0);
-            if (lane == 0) g_plan4.vstart[1][i] = remcarr;
-            GC_PP_ADD(5, ptop_);
-            GC_PP_T0(pstep_);
-            if (n > 0 && n <= (1 << 24)) {
-                double rp = remcarr;
-                bool done = false;
-                if (inside_u && !J.verify) {
-                    rp = gc_carrier_value_step(PK, CK, remcarr, p0, plast, kprem, dmd);     // the value; the bracket is the proof
-                    done = true;
-                } else if (tag_u == 2) {
-                    // a period inside one binade: the step carries its own conditions (gc_one_binade_walk) and is judged by
-                    // them; the remainder's one claim is checked
-                    double r2 = remcarr;
-                    done = gc_carrier_value_step_one(PK, CK, remcarr, n, kprem, &r2);
-                    rp = done ? r2 : rp;
-                }
-                if (done) {
-                    tally0++;
-                } else {
-                    // claims without a bracket around this start, none at all, or verify mode
-                    double rs;
-                    GC_PP_T0(pslow_);
-                    const int how = plan4_car_other(ps, nsamp, remcarr, n, lane, reinterpret_cast<const GcCarClaims *>(J.claims_car) + e0 + i, &rs);
-                    GC_PP_ADD(1, pslow_);
-                    GC_PP_INC(4);
-                    tally0 += how == 0 ? 1 : 0;
-                    tally1 += how == 1 ? 1 : 0;
-                    tally2 += how == 2 ? 1 : 0;
-                    mism += (inside_u && how != 0) ? 1 : 0;
-                    miss += (!inside_u && tag_u == 1) ? 1 : 0;
-                    rp = rs;
-                }
-                remcarr = rp;
-            }
-            GC_PP_ADD(6, pstep_);
+            GC_PP_ADD(3, pn_);
         }
-        if (lane < nb) out[e0 + lane].phi0 = g_plan4.vstart[1][lane];
+        {
+            GcCarRec mine;
+            gc_car_rec_make(mine, row, g_plan4.nsh[el], ilo, ex0, CK.s, PK.ydpi);
+            if (lane < nb) g_plan4.rec[lane] = mine;
+        }
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+        GC_PP_ADD(5, ptop_);
+        GC_PP_T0(pstep_);
+        GcCarRec A, B;
+        plan4_rec_load(A, 0);
+        for (int i = 0; i < nb; i += 2) {
+            plan4_rec_load(B, i + 1 < nb ? i + 1 : i);
+            __builtin_amdgcn_sched_barrier(0);
+            plan4_car_period(S, A, PK, CK, ps, nsamp, J, e0 + i, i, lane);
+            if (i + 1 >= nb) break;
+            plan4_rec_load(A, i + 2 < nb ? i + 2 : i + 1);
+            __builtin_amdgcn_sched_barrier(0);
+            plan4_car_period(S, B, PK, CK, ps, nsamp, J, e0 + i + 1, i + 1, lane);
+        }
+        GC_PP_ADD(6, pstep_);
+        if (lane < nb) out[e0 + lane].phi0 = S.phi;
     }
     GC_PP_ADD(0, ptot_);
+    GC_PP_ADDN(1, S.slowclk);
+    GC_PP_ADDN(4, S.slow);
     GC_PP_OUT(1);
     if (lane == 0) {
-        ((GC_GLOBAL GcTrkState *)J.state_out)->remcarr = remcarr;
-        if (tally0) atomicAdd(&gc_plan_stats[3], (unsigned long long)tally0);
-        if (tally1) atomicAdd(&gc_plan_stats[4], (unsigned long long)tally1);
-        if (tally2) atomicAdd(&gc_plan_stats[5], (unsigned long long)tally2);
-        if (mism) atomicAdd(&gc_plan_stats[6], (unsigned long long)mism);
-        if (miss) atomicAdd(&gc_plan_stats[7], (unsigned long long)miss);
+        ((GC_GLOBAL GcTrkState *)J.state_out)->remcarr = S.remcarr;
+        S.tally0 += S.recwin + S.recone;
+        if (blockIdx.x < GC_PLAN_REC_CH) {
+            if (S.recwin) atomicAdd(&gc_plan_rec[blockIdx.x * 2], (unsigned long long)S.recwin);
+            if (S.recone) atomicAdd(&gc_plan_rec[blockIdx.x * 2 + 1], (unsigned long long)S.recone);
+        }
+        if (S.tally0) atomicAdd(&gc_plan_stats[3], (unsigned long long)S.tally0);
+        if (S.tally1) atomicAdd(&gc_plan_stats[4], (unsigned long long)S.tally1);
+        if (S.tally2) atomicAdd(&gc_plan_stats[5], (unsigned long long)S.tally2);
+        if (S.mism) atomicAdd(&gc_plan_stats[6], (unsigned long long)S.mism);
+        if (S.miss) atomicAdd(&gc_plan_stats[7], (unsigned long long)S.miss);
     }
 }
 
@@ -850,7 +1124,7 @@ __device__ __forceinline__ void plan4_code_dispatch(int tcls, double ci, double 
 __global__ __launch_bounds__(128) void trk_plan4_kernel(const GcChan *__restrict__ chan, const GcTrkState *__restrict__ state_in,
                                                         GcTrkState *__restrict__ state_out, GcTrkPlan *__restrict__ plan,
                                                         int nch, int nepoch, const int *__restrict__ claims_code,
-                                                        const int *__restrict__ claims_car, int verify)
+                                                        const int *__restrict__ claims_car, const GcCodeScanRow *__restrict__ scan, int verify)
 {
     const int ch = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (ch >= nch) return;
@@ -867,6 +1141,7 @@ __global__ __launch_bounds__(128) void trk_plan4_kernel(const GcChan *__restrict
     Plan4Job J;
     J.claims_code = reinterpret_cast<const int4 *>(claims_code) + (size_t)ch * nepoch * RW4;
     J.claims_car = reinterpret_cast<const int4 *>(claims_car) + (size_t)ch * nepoch * RW4;
+    J.scan = scan ? scan + (size_t)ch * nepoch : nullptr;
     J.out = plan + (size_t)ch * nepoch;
     J.state_out = state_out + ch;
     J.s = s;
@@ -906,6 +1181,28 @@ extern "C" int gnsscorr_debug_plan_stats(unsigned long long *dst, int reset)
     return 0;
 }
 
+// dst: 2 * 64 counters (gc_plan_rec); debug entry point beside gnsscorr_debug_plan_stats, not in the public header
+extern "C" int gnsscorr_debug_plan_rec(unsigned long long *dst, int reset)
+{
+    if (hipMemcpyFromSymbol(dst, HIP_SYMBOL(gc_plan_rec), sizeof(unsigned long long) * 2 * GC_PLAN_REC_CH) != hipSuccess) return -1;
+    if (reset) {
+        unsigned long long z[2 * GC_PLAN_REC_CH] = {0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(gc_plan_rec), z, sizeof(z)) != hipSuccess) return -1;
+    }
+    return 0;
+}
+
+// dst: 64 counters (gc_plan_scan); debug entry point beside gnsscorr_debug_plan_stats, not in the public header
+extern "C" int gnsscorr_debug_plan_scan(unsigned long long *dst, int reset)
+{
+    if (hipMemcpyFromSymbol(dst, HIP_SYMBOL(gc_plan_scan), sizeof(unsigned long long) * GC_PLAN_REC_CH) != hipSuccess) return -1;
+    if (reset) {
+        unsigned long long z[GC_PLAN_REC_CH] = {0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(gc_plan_scan), z, sizeof(z)) != hipSuccess) return -1;
+    }
+    return 0;
+}
+
 static bool trk_nospec()
 {
     static const bool nospec = getenv("GNSSCORR_TRK_NOSPEC") != nullptr;
@@ -914,7 +1211,10 @@ static bool trk_nospec()
 
 // claims: gc_trk_spec_ints(nch * nepoch) ints of scratch: code rows, carrier rows, then the deviations of the
 // e_off + nepoch <= 2 * nepoch periods between the state and the batch's end (two doubles per period)
-size_t gc_trk_spec_ints(size_t units) { return units * (2 * GC_CLAIM_ROW + 8); }
+// ... then the code chain's scan rows (32 bytes per period)
+size_t gc_trk_spec_ints(size_t units) { return units * (2 * GC_CLAIM_ROW + 8 + 8); }
+static_assert(sizeof(GcCodeScanRow) == 32 && ((2 * GC_CLAIM_ROW + 8) * 4) % 32 == 0, "scan rows lie 32-byte aligned behind the deviations");
+static GcCodeScanRow *trk_scan_rows(int *claims, size_t units) { return reinterpret_cast<GcCodeScanRow *>(claims + units * (2 * GC_CLAIM_ROW + 8)); }
 
 int gc_launch_trk_spec(hipStream_t st, const GcChan *chan, const GcTrkState *state_in, int nch, int nepoch, int *claims,
                        int e_off)
@@ -927,7 +1227,7 @@ int gc_launch_trk_spec(hipStream_t st, const GcChan *chan, const GcTrkState *sta
     GC_HIP(hipGetLastError());
     const int nchunk = (nepoch + GC_SPEC_CHUNK - 1) / GC_SPEC_CHUNK;
     hipLaunchKernelGGL(trk_spec_kernel, dim3(nch * nchunk), dim3(GC_SPEC_CHUNK), 0, st, chan, state_in, devc, devk, claims,
-                       claims + units * GC_CLAIM_ROW, nch, nepoch, e_off);
+                       claims + units * GC_CLAIM_ROW, trk_scan_rows(claims, units), nch, nepoch, e_off);
     GC_HIP(hipGetLastError());
     return 0;
 }
@@ -942,7 +1242,8 @@ int gc_launch_trk_plan(hipStream_t st, const GcChan *chan, const GcTrkState *sta
     const bool batch = claims && !trk_nospec() && nepoch <= GC_PLAN_MAXE;
     if (batch)
         hipLaunchKernelGGL(trk_plan4_kernel, dim3(nch), dim3(128), 0, st, chan, state_in, state_out, plan, nch, nepoch,
-                           claims, claims + (size_t)nch * nepoch * GC_CLAIM_ROW, verify);
+                           claims, claims + (size_t)nch * nepoch * GC_CLAIM_ROW,
+                           (const GcCodeScanRow *)trk_scan_rows(claims, (size_t)nch * nepoch), verify);
     else
         hipLaunchKernelGGL(trk_plan_kernel, dim3(nch), dim3(128), 0, st, chan, state_in, state_out, plan, nch, nepoch);
     GC_HIP(hipGetLastError());

@@ -1,7 +1,9 @@
 """debug: per-channel clocks per period of both planner chains (code, carrier: loop, slow path, waiting for n, in
 front of the step, the step) from a library built with -DGC_PLAN_PROF (GNSSCORR_LIB=... for an A/B build); the
 planner runs in front of the correlator, alone, 4 x 1000 periods of 32 channels at Dopplers within +-5 kHz.
-profiles/r4/*_plan_clocks.txt are its output."""
+profiles/r4/*_plan_clocks.txt and profiles/r7/*_plan_clocks.txt are its output.  Since the carrier chain runs on staged
+records (profiles/r7): "top" is, per block, the rows, the wait for the code chain's block ("waiting-for-n") and the
+staging, divided by the block's periods; "step" the sequential loop; "slow" the clocks in its out-of-line paths."""
 import ctypes, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
