@@ -28,6 +28,7 @@ FTYPE1, FTYPE2 = 1, 2
 FEND_RTLSDR, FEND_FRTLSDR, FEND_FILE = 3, 8, 10
 MEMBUFFLEN, FILE_BUFFSIZE = 5000, 65536      # ref src/sdr.h:134,137
 ACQTH = 3.0                                  # ref src/sdr.h:148
+MAXFREQ, MAXCOH = 1024, 20                   # GNSSCORR_MAXFREQ, GNSSCORR_MAXCOH
 
 
 class GnsscorrError(RuntimeError):
@@ -252,7 +253,8 @@ EXPORTS_GNSSCORR = [
     "gnsscorr_spec_run", "gnsscorr_spec_fetch", "gnsscorr_trk_loop_lapped",
     "gnsscorr_acq_run_subset", "gnsscorr_loop_start_from_acq", "gnsscorr_rx_start", "gnsscorr_rx_set",
     "gnsscorr_rx_step", "gnsscorr_rx_status", "gnsscorr_fec_run", "gnsscorr_sbasframe_replay",
-    "gnsscorr_lock_run", "gnsscorr_rx_lock_set", "gnsscorr_rx_lock_status"]
+    "gnsscorr_lock_run", "gnsscorr_rx_lock_set", "gnsscorr_rx_lock_status",
+    "gnsscorr_acq_set_coherent", "gnsscorr_acq_get_coherent"]
 EXPORTS_SDR = [
     "sdracquisition", "checkacquisition", "sdrtracking", "cumsumcorr", "clearcumsumcorr", "pll", "dll",
     "readinifile", "chk_initvalue", "initacqstruct", "inittrkprmstruct", "inittrkstruct", "initsdrch",
@@ -312,6 +314,9 @@ def lib():
     L.gnsscorr_rx_status.argtypes = [C.c_void_p, C.POINTER(RxStat)]
     L.gnsscorr_trk_start_from_acq.argtypes = [C.c_void_p]
     L.gnsscorr_acq_power.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(L, "gnsscorr_acq_set_coherent"):     # (absent from an A/B library built before it: tools/acq_coh_time.py)
+        L.gnsscorr_acq_set_coherent.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.gnsscorr_acq_get_coherent.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.gnsscorr_fft16k.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     L.gnsscorr_pspec.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.gnsscorr_timing_enable.argtypes = [C.c_void_p, C.c_int]
@@ -433,14 +438,23 @@ def spectrumanalyzer(data, dtype, f_sf, nfft=16384):
     return freq, pspec
 
 
+def coherent_step(ncoh, ctime=1e-3, step=200):
+    """The Doppler step (whole Hz) recommended for a search that integrates ncoh code periods of ctime seconds
+    coherently: the reference's `step` (ACQSTEP), but no more than 1/(2*ncoh*ctime) -- 200 / 100 / 50 Hz for 1 / 5 / 10
+    periods of 1 ms.  For Channel(hband=, step=coherent_step(ncoh), ncoh=ncoh)."""
+    return max(1, min(int(step), int(1.0 / (2.0 * ncoh * ctime) + 1e-6)))
+
+
 class Channel:
     """Constants of one receiver channel, derived exactly as initsdrch() does
     (ref src/sdrinit.c:583-657, acquisition grid :385-394,:633-635, taps :446-455).  fend / ppmerr stand for
-    sdrini.fend / sdrini.rtlsdrppmerr: RTL-SDR file replay (FEND_FRTLSDR) offsets the channel by f_cf*ppmerr*1e-6."""
+    sdrini.fend / sdrini.rtlsdrppmerr: RTL-SDR file replay (FEND_FRTLSDR) offsets the channel by f_cf*ppmerr*1e-6.
+    ncoh: code periods the search integrates coherently per group (gnsscorr_acq_set_coherent; 1: the reference's
+    integration); Engine.set_channels applies it."""
 
     def __init__(self, prn, ctype=CTYPE_L1CA, dtype=DTYPEIQ, ftype=FTYPE1, f_cf=1575.42e6,
                  f_sf=16.368e6, f_if=0.0, corrn=2, corrd=3, corrp=3, hband=7000, step=200, intg=10,
-                 fend=FEND_FILE, ppmerr=0):
+                 fend=FEND_FILE, ppmerr=0, ncoh=1):
         self.prn, self.ctype, self.dtype, self.ftype = prn, ctype, dtype, ftype
         self.code, self.crate = gencode(prn, ctype)
         self.clen = len(self.code)
@@ -458,6 +472,7 @@ class Channel:
         else:
             self.f_cf, self.foffset = f_cf, 0.0
         self.intg = intg
+        self.ncoh = ncoh
         self.nfreq = 2 * (hband // step) + 1
         self.nfft = 2 * self.nsamp
         self.freq = np.array([f_if + ((i - (self.nfreq - 1) // 2) * float(step)) + self.foffset
@@ -562,6 +577,9 @@ class Engine:
         arr = (ChanDesc * len(channels))(*[c.desc() for c in channels])
         _check(self._L.gnsscorr_set_channels(self.h, len(channels), arr))
         self.channels = list(channels)
+        ncoh = [getattr(c, "ncoh", 1) for c in channels]
+        if any(k != 1 for k in ncoh):
+            self.acq_set_coherent(ncoh)
 
     # -- tracking
     def trk_set_state(self, states, ch0=0):
@@ -655,6 +673,18 @@ class Engine:
         else:
             arr = (C.c_int * len(channels))(*channels)
             _check(self._L.gnsscorr_acq_run_subset(self.h, wrpos, arr, len(channels)))
+
+    def acq_set_coherent(self, ncoh, ch0=0):
+        """Code periods channels ch0 .. ch0+len(ncoh)-1 integrate coherently per group (gnsscorr_acq_set_coherent);
+        set_channels resets every channel to 1 and then applies the channels' own ncoh."""
+        arr = (C.c_int * len(ncoh))(*ncoh)
+        _check(self._L.gnsscorr_acq_set_coherent(self.h, ch0, len(ncoh), arr))
+
+    def acq_get_coherent(self, ch0=0, nch=None):
+        nch = len(self.channels) - ch0 if nch is None else nch
+        arr = (C.c_int * nch)()
+        _check(self._L.gnsscorr_acq_get_coherent(self.h, ch0, nch, arr))
+        return list(arr)
 
     def acq_fetch(self):
         arr = (AcqRes * len(self.channels))()

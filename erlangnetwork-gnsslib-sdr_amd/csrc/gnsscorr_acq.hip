@@ -26,6 +26,12 @@
 //   acq_final (per channel): the decision of checkacquisition() after each
 //            iteration, first success wins (ref src/sdracq.c:39-42).
 //
+// Coherent integration (gnsscorr_acq_set_coherent): a channel with ncoh > 1 has intg / ncoh groups
+// where the text above and below says iterations.  acq_fwd wipes the group's (ncoh + 1)*nsamp samples off with one
+// carrier walk and adds its ncoh windows of 2*nsamp samples, nsamp apart, as integers before the transform -- the
+// transforms are linear, so that is the coherent sum of the ncoh correlation results; acq_code, acq_corr and the row
+// statistics do not know, acq_final scales iters and cn0.  ncoh = 1 is the reference's integration bit for bit.
+//
 // Every run works on a channel list (gnsscorr_acq_run_subset; gnsscorr_acq_run is the list 0..nch-1): the
 // per-channel kernels take their channel from a compacted device list, acq_fwd its frequency grid from the
 // list of grids that have a listed channel, so grid sizes follow the list.  Everything a channel owns (code
@@ -47,8 +53,9 @@ using gcfft::cmul;
 using gcfft::cmulc;
 using gcfft::csub;
 
-// Carrier NCO of one Doppler bin over the 2*nsamp acquisition window, phase 0 at its first sample
-// (ref src/sdrcmn.c:761): the reference's running sum as a piece table (gnsscorr_nco.h)
+// Carrier NCO of one Doppler bin over the (ncoh + 1)*nsamp samples of a group (ncoh = 1: the 2*nsamp acquisition
+// window), phase 0 at its first sample (ref src/sdrcmn.c:761): the reference's running sum as a piece table
+// (gnsscorr_nco.h)
 struct GcAcqCar {
     int n, pad;
     int k0[GC_NCAR];
@@ -67,13 +74,14 @@ struct GcAcqWork {
     GcDevBuf<float2> tw64p3;    // exp(-2 pi i 3 freq_of(p)/65536), pass order (the 65536-point path)
     int L = GC_L;               // transform length of this channel set: 32768, or 65536 when a period exceeds 16384 samples
     GcDevBuf<float2> X;         // [grid][iter][bin][2][16384]: X[f] and X[f + 16384] at the pass position of f
+                                // (iter, here and below: an iteration of the search, a group of ncoh code periods)
     GcDevBuf<float2> C;         // [ch][2][16384]
     GcDevBuf<GcAcqRow> rows;    // [ch][iter][bin]
     GcDevBuf<int> arrive;       // [ch][iter] workgroups done with the iteration, then [ch] "acquired" flags
     GcDevBuf<int> iters;        // [ch] iteration limit for acq_corr
     GcDevBuf<gnsscorr_acqres_t> res;    // [ch]
     GcDevBuf<double> P;         // one channel's power array (on demand)
-    int ngrid = 0, maxfreq = 0, maxintg = 0;
+    int ngrid = 0, maxfreq = 0, maxintg = 0;    // maxintg: the largest iteration (group) count, intg / ncoh
     std::vector<int> grid_chan;         // a representative channel per grid
     GcDevBuf<int> d_grid_chan;          // device copy of grid_chan
     GcDevBuf<uint64_t> d_grid_wrpos;    // ring write position seen by each grid
@@ -86,6 +94,9 @@ struct GcAcqWork {
 };
 
 namespace {
+
+// iterations of a channel's search: groups of ncoh code periods
+__host__ __device__ __forceinline__ int acq_groups(const GcChan &c) { return c.ncoh > 1 ? c.intg / c.ncoh : c.intg; }
 
 // carrier LUT (ref src/sdrcmn.c:643-648)
 __constant__ signed char aCos32[32] = {32, 31, 30, 27, 23, 18, 12, 6, 0, -6, -12, -18, -23, -27, -30, -31,
@@ -236,12 +247,15 @@ __global__ void acq_nco_kernel(const GcChan *__restrict__ chan, const int *__res
     t->n = 0;
     if (bin >= c.nfreq) return;
     GcCarTable ct{t->k0, t->seg, GC_NCAR, 0, 0};
-    gc_carrier_walk(gc_carrier_phis(0.0), gc_carrier_ps(freqs[c.freq_off + bin], c.ti), 2 * c.nsamp, ct);
+    gc_carrier_walk(gc_carrier_phis(0.0), gc_carrier_ps(freqs[c.freq_off + bin], c.ti), (c.ncoh + 1) * c.nsamp, ct);
     t->n = ct.n;
     if (ct.overflow) atomicAdd(overflow, 1);
 }
 
-// acq_fwd: grid (bin, iteration, entry of the list of frequency grids in use)
+// acq_fwd: grid (bin, iteration, entry of the list of frequency grids in use).  COH: some listed grid integrates
+// coherently, and the sample functor adds the group's ncoh windows (for a grid with ncoh = 1 that is the same integer,
+// so the same float); the instance without COH is free of the loop.
+template <bool COH>
 __global__ __launch_bounds__(GC_FFT_THREADS) void acq_fwd_kernel(
     const GcChan *__restrict__ chan, const int *__restrict__ grid_chan, const int *__restrict__ glist,
     const GcAcqCar *__restrict__ car,
@@ -253,10 +267,11 @@ __global__ __launch_bounds__(GC_FFT_THREADS) void acq_fwd_kernel(
     float2 *lds = reinterpret_cast<float2 *>(smem);
     const int bin = blockIdx.x, it = blockIdx.y, g = glist[blockIdx.z], tid = threadIdx.x;
     const GcChan &c = chan[grid_chan[g]];
-    if (bin >= c.nfreq || it >= c.intg) return;
+    const int ncoh = COH ? c.ncoh : 1;
+    if (bin >= c.nfreq || it >= (COH ? acq_groups(c) : c.intg)) return;
     const int n = c.nsamp, n2 = 2 * n, dtype = c.dtype;
-    // window of iteration `it`: ref src/sdracq.c:24-32
-    const uint64_t buffloc = grid_wrpos[g] - (uint64_t)(c.intg + 1) * n + (uint64_t)it * n;
+    // window of iteration `it`: ref src/sdracq.c:24-32; a group starts ncoh windows after the one before
+    const uint64_t buffloc = grid_wrpos[g] - (uint64_t)(c.intg + 1) * n + (uint64_t)it * ((uint64_t)ncoh * n);
     const uint64_t base = buffloc % c.ringlen;
     const gc_gptr_i8 ring = (gc_gptr_i8)c.ring;
     const uint64_t ringlen = c.ringlen;
@@ -269,13 +284,12 @@ __global__ __launch_bounds__(GC_FFT_THREADS) void acq_fwd_kernel(
     __syncthreads();
     const float sc = (float)((1.0 / 32.0) / (double)c.nfft);     // CSCALE/m, ref src/sdrcmn.c:764
 
-    auto sample = [&](int s) -> float2 {
-        if (s >= n2) return make_float2(0.f, 0.f);
+    // wiped-off sample s of the group's span (s < (ncoh + 1)*n <= ringlen: the ring wraps at most once)
+    auto mixed = [&](int s, int &I, int &Q) {
         uint64_t pos = base + (uint64_t)s;
         if (pos >= ringlen) pos -= ringlen;
         const int idx = gc_carrier_idx_at(lk0, lseg, ncar, s);
         const int cs_ = aCos32[idx], sn_ = aSin32[idx];
-        int I, Q;
         if (dtype == 2) {
             const int d0 = ring[2 * pos], d1 = ring[2 * pos + 1];
             I = cs_ * d0 - sn_ * d1;
@@ -284,6 +298,20 @@ __global__ __launch_bounds__(GC_FFT_THREADS) void acq_fwd_kernel(
             const int d0 = ring[pos];
             I = cs_ * d0;
             Q = sn_ * d0;
+        }
+    };
+    auto sample = [&](int s) -> float2 {
+        if (s >= n2) return make_float2(0.f, 0.f);
+        int I, Q;
+        mixed(s, I, Q);
+        if constexpr (COH) {
+            // z[s] = sum over the windows j < ncoh of (I, Q)[j n + s]: |z| <= 20 * 2 * 32 * 128 < 2^24, exact as a float
+            for (int j = 1; j < ncoh; j++) {
+                int Ij, Qj;
+                mixed(j * n + s, Ij, Qj);
+                I += Ij;
+                Q += Qj;
+            }
         }
         return make_float2((float)I * sc, (float)Q * sc);
     };
@@ -744,37 +772,39 @@ __global__ __launch_bounds__(64) void acq_final_kernel(const GcChan *__restrict_
     if ((int)blockIdx.x >= nlist) return;
     const int ch = list[blockIdx.x];
     const GcChan &c = chan[ch];
-    const int n = c.nsamp;
+    const int n = c.nsamp, ngroup = acq_groups(c);
+    const double tcoh = (double)c.ncoh * c.ctime;               // a group's coherent time: 1 / its noise bandwidth
     gnsscorr_acqres_t r;
     r.acqcodei = 0; r.freqi = 0; r.acqfreq = 0; r.cn0 = 0; r.peakr = 0; r.flagacq = 0; r.iters = c.intg;
     const uint64_t b0 = grid_wrpos[c.grid] - (uint64_t)(c.intg + 1) * n;
     int it = 0;
-    for (; it < c.intg; it++) {
+    for (; it < ngroup; it++) {
         const GcAcqRow *row = rows + ((size_t)ch * maxintg + it) * maxfreq;
         const int fi = acq_best_row(row, c.nfreq, lane);
         const GcAcqRow w = row[fi];
         const int ne = 4 * c.nsampchip + 1;                     // samples inside the excluded window
         const double meanP = w.sum_out / (double)(n - ne);
-        r.cn0 = 10.0 * log10(w.rowmax / meanP / c.ctime);
+        r.cn0 = 10.0 * log10(w.rowmax / meanP / tcoh);
         r.peakr = w.rowmax / w.max_out;
         r.acqcodei = w.argmax;
         r.freqi = fi;
         r.acqfreq = freqs[c.freq_off + fi];
         if (acq_passes(w)) { r.flagacq = 1; break; }
     }
-    r.iters = r.flagacq ? it + 1 : c.intg;
+    // code periods consumed; acq_power re-runs the groups
+    r.iters = r.flagacq ? (it + 1) * c.ncoh : c.intg;
     // ref src/sdracq.c:51-53 / :62
     r.buffloc = r.flagacq ? b0 + (uint64_t)r.acqcodei : b0 + (uint64_t)c.intg * n;
     if (lane == 0) {
         res[ch] = r;
-        if (iters_out) iters_out[ch] = r.iters;
+        if (iters_out) iters_out[ch] = r.flagacq ? it + 1 : ngroup;
     }
 }
 
 __global__ void fill_int_kernel(int *p, const GcChan *__restrict__ chan, const int *__restrict__ list, int nlist)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < nlist) p[list[i]] = chan[list[i]].intg;
+    if (i < nlist) p[list[i]] = acq_groups(chan[list[i]]);
 }
 
 // stand-alone batch FFT (op-level entry point and tests): grid (batch); natural order in and out
@@ -853,7 +883,8 @@ static int acq_tables(gnsscorr_ctx *ctx)
     GC_HIP(hipGetLastError());
     {
         const int lds = GC_FFT_LDS + 256;
-        GC_HIP(hipFuncSetAttribute((const void *)acq_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds + GC_ACQ_CARLDS));
+        GC_HIP(hipFuncSetAttribute((const void *)acq_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + GC_ACQ_CARLDS));
+        GC_HIP(hipFuncSetAttribute((const void *)acq_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + GC_ACQ_CARLDS));
         GC_HIP(hipFuncSetAttribute((const void *)acq_code_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         GC_HIP(hipFuncSetAttribute((const void *)acq_corr_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, GC_ACQ_CORR_LDS));
         GC_HIP(hipFuncSetAttribute((const void *)acq_corr_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, GC_ACQ_CORR_LDS));
@@ -893,7 +924,7 @@ static int acq_prepare(gnsscorr_ctx *ctx)
         if (c.nsamp > GC_LH) w->L = 2 * GC_L;
         if (c.grid >= w->ngrid) { w->ngrid = c.grid + 1; w->grid_chan.push_back(i); }
         if (c.nfreq > w->maxfreq) w->maxfreq = c.nfreq;
-        if (c.intg > w->maxintg) w->maxintg = c.intg;
+        if (acq_groups(c) > w->maxintg) w->maxintg = acq_groups(c);
     }
     GC_RESERVE(ctx, w->X, (size_t)w->ngrid * w->maxintg * w->maxfreq * w->L);
     GC_RESERVE(ctx, w->rows, (size_t)nch * w->maxintg * w->maxfreq);
@@ -1014,9 +1045,12 @@ int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chl
     w->ran = false;                 // until every launch below is queued
     const int *dlist = w->d_list, *dglist = w->d_list + nch;
     const int lds = GC_FFT_LDS + 256;
+    bool coh = false;               // a listed grid integrates coherently
+    for (int g : glist) coh = coh || ctx->hchan[w->grid_chan[g]].ncoh > 1;
     {
         GcTimed t(ctx, "acq_fwd");
-        hipLaunchKernelGGL(acq_fwd_kernel, dim3(w->maxfreq, w->maxintg, ng), dim3(GC_FFT_THREADS), lds + GC_ACQ_CARLDS,
+        auto fwd = coh ? acq_fwd_kernel<true> : acq_fwd_kernel<false>;
+        hipLaunchKernelGGL(fwd, dim3(w->maxfreq, w->maxintg, ng), dim3(GC_FFT_THREADS), lds + GC_ACQ_CARLDS,
                            ctx->stream, ctx->dchan, w->d_grid_chan, dglist, w->car, w->d_grid_wrpos, w->tw16k, w->tw32p,
                            w->tw64p1, w->tw64p3, w->X, w->maxfreq, w->maxintg, w->L);
     }

@@ -425,6 +425,26 @@ static void retarget_rings(gnsscorr_ctx *ctx)
     upload_channels(ctx);
 }
 
+// acquisition grid = channels that share ring, sample grid, Doppler bins and coherent integration: they share the
+// forward spectra.  Grids are numbered in the order of their first channel.
+static void assign_acq_grids(gnsscorr_ctx *ctx)
+{
+    int ngrid = 0;
+    for (int i = 0; i < ctx->nch; i++) {
+        const gnsscorr_chan_t &d = ctx->hdesc[i];
+        GcChan &g = ctx->hchan[i];
+        g.grid = -1;
+        for (int j = 0; j < i && g.grid < 0; j++) {
+            const gnsscorr_chan_t &o = ctx->hdesc[j];
+            if (o.ftype == d.ftype && o.dtype == d.dtype && o.nsamp == d.nsamp && o.nfreq == d.nfreq &&
+                o.intg == d.intg && o.ti == d.ti && o.nfft == d.nfft && ctx->hchan[j].ncoh == g.ncoh &&
+                !memcmp(o.freq, d.freq, sizeof(double) * d.nfreq))
+                g.grid = ctx->hchan[j].grid;
+        }
+        if (g.grid < 0) g.grid = ngrid++;
+    }
+}
+
 extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_chan_t *ch)
 {
     if (!ctx || nch <= 0 || !ch) return gc_fail(GNSSCORR_EINVAL, "set_channels: bad arguments");
@@ -478,7 +498,6 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
     ctx->smax_max = 0;
     ctx->max_n = 0;
     for (bool &h : ctx->have_dtype) h = false;
-    int ngrid = 0;
     for (int i = 0; i < nch; i++) {
         gnsscorr_chan_t &d = ctx->hdesc[i];
         ctx->hcode[i].assign(d.code, d.code + d.clen);
@@ -499,16 +518,7 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
         g.nfreq = d.nfreq; g.intg = d.intg; g.nfft = d.nfft;
         g.freq_off = (int)freqs.size();
         freqs.insert(freqs.end(), d.freq, d.freq + d.nfreq);
-        // acquisition grid = channels that share ring, sample grid and Doppler bins
-        g.grid = -1;
-        for (int j = 0; j < i && g.grid < 0; j++) {
-            const gnsscorr_chan_t &o = ctx->hdesc[j];
-            if (o.ftype == d.ftype && o.dtype == d.dtype && o.nsamp == d.nsamp && o.nfreq == d.nfreq &&
-                o.intg == d.intg && o.ti == d.ti && o.nfft == d.nfft &&
-                !memcmp(o.freq, d.freq, sizeof(double) * d.nfreq))
-                g.grid = ctx->hchan[j].grid;
-        }
-        if (g.grid < 0) g.grid = ngrid++;
+        g.ncoh = 1;
         if (g.smax > ctx->smax_max) ctx->smax_max = g.smax;
         if (d.nsamp + 100 > ctx->max_n) ctx->max_n = d.nsamp + 100;   // ref src/sdrtrk.c:23
     }
@@ -533,7 +543,38 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
         ctx->hchan[i].ringlen = r.ringlen;
         ctx->hchan[i].code = ctx->dcodes + (size_t)i * GC_CODEBLOCK;
     }
+    assign_acq_grids(ctx);
     return upload_channels(ctx);
+}
+
+// Coherent integration per channel (include/gnsscorr.h).  The grids are numbered again, the channel table goes up and
+// what acquisition had prepared for the old setting (code spectra, carrier tables, forward spectra, cached lists, the
+// last results) is dropped: the next search prepares again.
+extern "C" int gnsscorr_acq_set_coherent(gnsscorr_ctx *ctx, int ch0, int nch, const int *ncoh)
+{
+    if (!ctx || !ncoh || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
+        return gc_fail(GNSSCORR_EINVAL, "acq_set_coherent: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    for (int i = 0; i < nch; i++) {
+        const int intg = ctx->hchan[ch0 + i].intg;
+        if (ncoh[i] < 1 || ncoh[i] > GNSSCORR_MAXCOH || intg % ncoh[i] != 0)
+            return gc_fail(GNSSCORR_EINVAL, "acq_set_coherent: channel %d: ncoh %d (1..%d, a divisor of intg %d)", ch0 + i,
+                           ncoh[i], GNSSCORR_MAXCOH, intg);
+    }
+    GC_HIP(hipSetDevice(ctx->device));
+    int rc = gc_quiesce(ctx);
+    if (rc) return rc;
+    for (int i = 0; i < nch; i++) ctx->hchan[ch0 + i].ncoh = ncoh[i];
+    assign_acq_grids(ctx);
+    gc_acq_free(ctx);
+    return upload_channels(ctx);
+}
+
+extern "C" int gnsscorr_acq_get_coherent(gnsscorr_ctx *ctx, int ch0, int nch, int *ncoh)
+{
+    if (!ctx || !ncoh || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
+        return gc_fail(GNSSCORR_EINVAL, "acq_get_coherent: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    for (int i = 0; i < nch; i++) ncoh[i] = ctx->hchan[ch0 + i].ncoh;
+    return GNSSCORR_OK;
 }
 
 extern "C" int gnsscorr_num_channels(gnsscorr_ctx *ctx) { return ctx ? ctx->nch : 0; }

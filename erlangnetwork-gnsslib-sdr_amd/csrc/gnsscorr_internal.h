@@ -31,7 +31,8 @@ struct GcChan {
     int    nfreq, intg, nfft, grid;    // grid = index of the (ring, freq grid) group
     int    freq_off;                   // offset into the frequency pool
     int    nedge;                      // chip edges per code period (entries of the edge list)
-    int    pm1, pad1;                  // pm1: every edge steps by +-2 (a +-1 code)
+    int    pm1;                        // pm1: every edge steps by +-2 (a +-1 code)
+    int    ncoh;                       // acquisition: code periods summed coherently per group (gnsscorr_acq_set_coherent)
 };
 
 // Code block = GC_CODEBLOCK bytes per channel:

@@ -40,7 +40,8 @@ extern "C" {
 #define GNSSCORR_ESTATE    -3   /* call order (no ring, no channels, ...)    */
 
 #define GNSSCORR_MAXTAPS   33   /* 1 + 2*corrn, corrn <= 16                  */
-#define GNSSCORR_MAXFREQ   256  /* Doppler bins per channel                  */
+#define GNSSCORR_MAXFREQ   1024 /* Doppler bins per channel                  */
+#define GNSSCORR_MAXCOH    20   /* code periods summed coherently per group  */
 
 typedef struct gnsscorr_ctx gnsscorr_ctx;
 
@@ -331,7 +332,7 @@ typedef struct {
     int      acqcodei, freqi;       /* ref sdracq_t                           */
     double   acqfreq, cn0, peakr;
     int      flagacq;               /* ref sdrch_t.flagacq                    */
-    int      iters;                 /* iterations the reference would run     */
+    int      iters;                 /* iterations the reference would run (code periods consumed) */
     uint64_t buffloc;               /* return value of sdracquisition()       */
 } gnsscorr_acqres_t;
 
@@ -360,6 +361,26 @@ int  gnsscorr_loop_start_from_acq(gnsscorr_ctx *ctx);
  * with the iteration count of the last gnsscorr_acq_run).  A channel the last
  * search did not list: GNSSCORR_ESTATE. */
 int  gnsscorr_acq_power(gnsscorr_ctx *ctx, int ch, double *power);
+/* Coherent integration over several code periods (opt-in; not in the reference, whose sdracquisition() the drop-in
+ * symbol keeps).  Channel ch0 + i integrates ncoh[i] code periods coherently per group and adds its intg / ncoh[i]
+ * groups non-coherently: group g covers the (ncoh + 1) * nsamp samples from b0 + g * ncoh * nsamp on (b0 = wrpos -
+ * (intg + 1) * nsamp, the look-back of the search is unchanged), is wiped off by one mixcarr() call per Doppler bin
+ * with phase 0 at its first sample, and the ncoh windows of 2 * nsamp wiped-off samples that start nsamp apart are
+ * added as integers before the forward transform -- which, the transforms being linear, is the coherent sum of their
+ * ncoh correlation results.  Everything after the forward transform runs once per group as it runs once per iteration
+ * without this call, checkacquisition()'s rules included; the first passing group wins.  In the result iters =
+ * (g + 1) * ncoh (intg when not acquired), buffloc is what it is without this call, and cn0 = 10 log10(maxP / meanP /
+ * (ncoh * ctime)), the noise bandwidth of a group being 1 / (ncoh * ctime).  ncoh = 1 is the reference's integration,
+ * bit for bit.
+ * Takes effect after gnsscorr_set_channels, which resets every channel to 1.  GNSSCORR_EINVAL, nothing touched: a
+ * channel range outside the table, ncoh < 1, ncoh > GNSSCORR_MAXCOH, intg % ncoh != 0.  Quiesces and drops the
+ * prepared acquisition work, so that the next search prepares again; channels share forward spectra only when their
+ * ncoh agree as well.
+ * Recommended Doppler grid: step <= 1 / (2 * ncoh * ctime) (500 / 100 / 50 Hz for 1 / 5 / 10 periods of 1 ms).  Data
+ * bit edges inside a group are not handled: they cost correlation, so keep ncoh * ctime <= 10 ms for L1 C/A unless
+ * the data is known; a retry (the receiver schedule's) lands on another alignment. */
+int  gnsscorr_acq_set_coherent(gnsscorr_ctx *ctx, int ch0, int nch, const int *ncoh);
+int  gnsscorr_acq_get_coherent(gnsscorr_ctx *ctx, int ch0, int nch, int *ncoh);
 
 /* ---- receiver schedule: acquire, hand over and track each channel by state ----
  * sdrthread()'s state machine (ref src/sdrmain.c:247-316) for every channel of the context: a channel calls
