@@ -1120,7 +1120,7 @@ extern "C" int gnsscorr_trk_start_from_acq(gnsscorr_ctx *ctx)
     int rc = gc_quiesce(ctx);
     if (rc) return rc;
     hipLaunchKernelGGL(acq_to_trk_kernel, dim3((ctx->nch + 63) / 64), dim3(64), 0, ctx->stream, ctx->dchan,
-                       ctx->acq->res, ctx->dstate2[ctx->state_cur], ctx->nch);
+                       ctx->acq->res, ctx->state.cur(), ctx->nch);
     GC_HIP(hipGetLastError());
     return GNSSCORR_OK;
 }
@@ -1159,7 +1159,7 @@ int gc_acq_handover(gnsscorr_ctx *ctx, bool quiesce)
     if (quiesce) { int rc = gc_quiesce(ctx); if (rc) return rc; }
     const int n = (int)ctx->acq->list.size();
     hipLaunchKernelGGL(acq_to_loop_kernel, dim3(n), dim3(64), 0, ctx->stream, ctx->dchan, ctx->acq->res,
-                       ctx->dstate2[ctx->state_cur], ctx->loop.dloop, ctx->acq->d_list, n);
+                       ctx->state.cur(), ctx->loop.dloop, ctx->acq->d_list, n);
     GC_HIP(hipGetLastError());
     return GNSSCORR_OK;
 }

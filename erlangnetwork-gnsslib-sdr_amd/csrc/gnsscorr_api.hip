@@ -1,7 +1,8 @@
 // gnsscorr_api.hip -- C-ABI layer of libgnsscorr.so: context, IF ring in HBM,
-// channel tables, batched tracking entry points, per-kernel timing.
-// (Acquisition entry points live in gnsscorr_acq.hip, the closed loop's in
-// gnsscorr_loop.hip, the reference-named per-call symbols in gnsscorr_compat.hip.)
+// channel tables, per-kernel timing, the default context.
+// (The batched tracker's entry points live in gnsscorr_trk.hip, acquisition's in
+// gnsscorr_acq.hip, the closed loop's in gnsscorr_loop.hip, the reference-named
+// per-call symbols in gnsscorr_compat.hip.)
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -41,8 +42,8 @@ static void destroy_handles(gnsscorr_ctx *ctx)
 {
     for (auto &kv : ctx->timers)
         for (auto &p : kv.second.pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-    for (GcPlanSlot &s : ctx->slot)
-        for (hipEvent_t e : {s.ev_plan, s.ev_used, s.ev_corr, s.ev_fin})
+    for (int i = 0; i < 2; i++)
+        for (hipEvent_t e : {ctx->ev_plan[i], ctx->ev_used[i], ctx->ev_corr[i], ctx->ev_fin[i]})
             if (e) hipEventDestroy(e);
     for (hipEvent_t e : {ctx->ev_spec, ctx->ev_chain, ctx->ev_pin[0], ctx->ev_pin[1], ctx->ev_in, ctx->ev_lock})
         if (e) hipEventDestroy(e);
@@ -72,9 +73,8 @@ extern "C" int gnsscorr_create(gnsscorr_ctx **out, int device, void *stream)
     }
     for (hipStream_t *s : {&ctx->stream_plan, &ctx->stream_finish, &ctx->stream_discover})
         if (e == hipSuccess) e = hipStreamCreateWithFlags(s, hipStreamNonBlocking);
-    for (hipEvent_t *ev : {&ctx->ev_spec, &ctx->ev_chain, &ctx->slot[0].ev_plan, &ctx->slot[0].ev_used, &ctx->slot[0].ev_corr,
-                           &ctx->slot[0].ev_fin, &ctx->slot[1].ev_plan, &ctx->slot[1].ev_used, &ctx->slot[1].ev_corr,
-                           &ctx->slot[1].ev_fin})
+    for (hipEvent_t *ev : {&ctx->ev_spec, &ctx->ev_chain, &ctx->ev_plan[0], &ctx->ev_used[0], &ctx->ev_corr[0], &ctx->ev_fin[0],
+                           &ctx->ev_plan[1], &ctx->ev_used[1], &ctx->ev_corr[1], &ctx->ev_fin[1]})
         if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
     for (hipEvent_t &ev : ctx->ev_burst)
         if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
@@ -87,32 +87,15 @@ extern "C" int gnsscorr_create(gnsscorr_ctx **out, int device, void *stream)
     return GNSSCORR_OK;
 }
 
-int gc_quiesce(gnsscorr_ctx *ctx, bool ingest)
-{
-    if (ingest && ctx->stream_in) GC_HIP(hipStreamSynchronize(ctx->stream_in));
-    for (hipStream_t s : {ctx->stream_plan, ctx->stream_finish, ctx->stream_discover, ctx->stream})
-        GC_HIP(hipStreamSynchronize(s));
-    ctx->ahead_valid = false;          // a look-ahead plan may have been in flight: it is dropped
-    ctx->state_touched = true;
-    return GNSSCORR_OK;
-}
-
 // the channel set's device buffers; the next set starts from nothing
 static void drop_channel_buffers(gnsscorr_ctx *ctx)
 {
     gc_acq_free(ctx);
     gc_spec_free(ctx);
-    for (GcPlanSlot &s : ctx->slot) {
-        s.plan.reset(); s.unit.reset(); s.rounds.reset(); s.segs.reset(); s.nsamp.reset(); s.partial.reset();
-        s.fin_pending = false;
-    }
-    for (int i = 0; i < 2; i++) { ctx->dstate2[i].reset(); ctx->dspec2[i].reset(); }
-    ctx->dchan.reset(); ctx->dcodes.reset(); ctx->dfreqs.reset(); ctx->detab.reset();
-    ctx->dcorrI.reset(); ctx->dcorrQ.reset(); ctx->dsumI.reset(); ctx->dsumQ.reset(); ctx->dfinish.reset();
-    ctx->dnco_overflow.reset(); ctx->dring_viol.reset();
-    ctx->spec_ahead_valid = false;
-    ctx->trk_units = 0;
-    ctx->state_cur = 0;
+    ctx->dchan.reset(); ctx->dcodes.reset(); ctx->dfreqs.reset();
+    ctx->state = GcTrkStateBuf();
+    ctx->batch = GcBatch();
+    ctx->out = GcTrkOut();
     ctx->loop = GcLoop();
     ctx->rx = GcRx();
     ctx->lock_pending = false;
@@ -131,20 +114,11 @@ extern "C" void gnsscorr_destroy(gnsscorr_ctx *ctx)
 
 extern "C" void *gnsscorr_stream(gnsscorr_ctx *ctx) { return ctx ? (void *)ctx->stream : nullptr; }
 
-// Makes the main stream wait for the tracking outputs of the last batch (its finish runs on a stream
-// of its own).
-static int outputs_ready(gnsscorr_ctx *ctx)
-{
-    const GcPlanSlot &last = ctx->slot[ctx->last_slot];
-    if (last.fin_pending) GC_HIP(hipStreamWaitEvent(ctx->stream, last.ev_fin, 0));
-    return GNSSCORR_OK;
-}
-
 extern "C" int gnsscorr_sync(gnsscorr_ctx *ctx)
 {
     if (!ctx) return gc_fail(GNSSCORR_EINVAL, "null context");
     GC_HIP(hipSetDevice(ctx->device));
-    int rc = outputs_ready(ctx);
+    int rc = gc_outputs_ready(ctx);
     if (rc) return rc;
     GC_HIP(hipStreamSynchronize(ctx->stream));
     return GNSSCORR_OK;
@@ -526,8 +500,8 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
     GC_RESERVE(ctx, ctx->dcodes, codes.size());
     GC_RESERVE(ctx, ctx->dfreqs, freqs.size());
     for (int i = 0; i < 2; i++) {
-        GC_RESERVE(ctx, ctx->dstate2[i], nch);
-        GC_HIP(hipMemsetAsync(ctx->dstate2[i], 0, sizeof(GcTrkState) * nch, ctx->stream));
+        GC_RESERVE(ctx, ctx->state.buf[i], nch);
+        GC_HIP(hipMemsetAsync(ctx->state.buf[i], 0, sizeof(GcTrkState) * nch, ctx->stream));
     }
     GC_RESERVE(ctx, ctx->loop.dloop, nch);
     GC_HIP(hipMemsetAsync(ctx->loop.dloop, 0, sizeof(gnsscorr_loop_t) * nch, ctx->stream));
@@ -579,77 +553,6 @@ extern "C" int gnsscorr_acq_get_coherent(gnsscorr_ctx *ctx, int ch0, int nch, in
 
 extern "C" int gnsscorr_num_channels(gnsscorr_ctx *ctx) { return ctx ? ctx->nch : 0; }
 
-// ---------------------------------------------------------------------------
-// tracking
-// ---------------------------------------------------------------------------
-extern "C" int gnsscorr_trk_set_state(gnsscorr_ctx *ctx, int ch0, int nch, const gnsscorr_trkstate_t *st)
-{
-    if (!ctx || !st || ch0 < 0 || nch <= 0 || ch0 + nch > ctx->nch)
-        return gc_fail(GNSSCORR_EINVAL, "trk_set_state: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
-    static_assert(sizeof(gnsscorr_trkstate_t) == sizeof(GcTrkState), "state layout");
-    GC_HIP(hipSetDevice(ctx->device));
-    int rc = gc_quiesce(ctx);
-    if (rc) return rc;
-    GC_HIP(hipMemcpyAsync(ctx->dstate2[ctx->state_cur] + ch0, st, sizeof(GcTrkState) * nch, hipMemcpyHostToDevice,
-                          ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    return GNSSCORR_OK;
-}
-
-extern "C" int gnsscorr_trk_get_state(gnsscorr_ctx *ctx, int ch0, int nch, gnsscorr_trkstate_t *st)
-{
-    if (!ctx || !st || ch0 < 0 || nch <= 0 || ch0 + nch > ctx->nch)
-        return gc_fail(GNSSCORR_EINVAL, "trk_get_state: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
-    GC_HIP(hipSetDevice(ctx->device));
-    // (drains like gc_quiesce but keeps the look-ahead: reading the committed state leaves it valid)
-    for (hipStream_t s : {ctx->stream_plan, ctx->stream_finish, ctx->stream_discover, ctx->stream})
-        GC_HIP(hipStreamSynchronize(s));
-    GC_HIP(hipMemcpyAsync(st, ctx->dstate2[ctx->state_cur] + ch0, sizeof(GcTrkState) * nch, hipMemcpyDeviceToHost,
-                          ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    return GNSSCORR_OK;
-}
-
-int gc_ensure_trk_buffers(gnsscorr_ctx *ctx, int nepoch)
-{
-    const size_t units = (size_t)ctx->nch * nepoch;
-    if (units <= ctx->trk_units) return GNSSCORR_OK;
-    // drains like gc_quiesce but leaves state_touched: the committed state is unchanged, so this batch still plans ahead
-    for (hipStream_t s : {ctx->stream_plan, ctx->stream_finish, ctx->stream_discover, ctx->stream})
-        GC_HIP(hipStreamSynchronize(s));
-    ctx->ahead_valid = false;          // (a look-ahead plan advanced the uncommitted state one batch: it is dropped)
-    ctx->spec_ahead_valid = false;
-    ctx->trk_units = 0;                // until every buffer below has its size
-    ctx->nseg = 1;
-    for (int i = 0; i < ctx->nch; i++) {
-        const int s = gc_trk_nseg(ctx->hchan[i].dtype, ctx->max_n);
-        if (s > ctx->nseg) ctx->nseg = s;
-    }
-    for (GcPlanSlot &s : ctx->slot) {
-        GC_RESERVE(ctx, s.plan, units);
-        GC_RESERVE(ctx, s.partial, units * ctx->nseg * 2 * ctx->ntap);
-        GC_RESERVE(ctx, s.unit, units);
-        GC_RESERVE(ctx, s.nsamp, units);
-        GC_RESERVE(ctx, s.rounds, units * ctx->nseg * GC_MAXR);
-        GC_RESERVE(ctx, s.segs, units);
-        s.fin_pending = false;
-    }
-    for (int i = 0; i < 2; i++) GC_RESERVE(ctx, ctx->dspec2[i], gc_trk_spec_ints(units));
-    GC_RESERVE(ctx, ctx->detab, units * GC_EDGTAB);
-    GC_RESERVE(ctx, ctx->dcorrI, units * ctx->ntap);
-    GC_RESERVE(ctx, ctx->dcorrQ, units * ctx->ntap);
-    GC_RESERVE(ctx, ctx->dsumI, (size_t)ctx->nch * ctx->ntap);
-    GC_RESERVE(ctx, ctx->dsumQ, (size_t)ctx->nch * ctx->ntap);
-    GC_RESERVE(ctx, ctx->dfinish, (size_t)ctx->nch * GC_FINISH_SCRATCH);
-    GC_HIP(hipMemsetAsync(ctx->dfinish, 0, sizeof(unsigned long long) * ctx->nch * GC_FINISH_SCRATCH, ctx->stream));
-    GC_RESERVE(ctx, ctx->dnco_overflow, 1);
-    GC_HIP(hipMemsetAsync(ctx->dnco_overflow, 0, sizeof(int), ctx->stream));
-    GC_RESERVE(ctx, ctx->dring_viol, 1);
-    GC_HIP(hipMemsetAsync(ctx->dring_viol, 0, sizeof(int), ctx->stream));
-    ctx->trk_units = units;
-    return GNSSCORR_OK;
-}
-
 // hipMalloc; with gnsscorr_debug_poison on, the new buffer is then filled with the poison byte (and the fill is over
 // before this returns, so that it cannot race any later write on another stream)
 int gc_dev_alloc(gnsscorr_ctx *ctx, void **p, size_t bytes)
@@ -670,209 +573,6 @@ extern "C" int gnsscorr_debug_poison(gnsscorr_ctx *ctx, int byte)
     if (!ctx) return gc_fail(GNSSCORR_EINVAL, "debug_poison: null context");
     if (byte < -1 || byte > 255) return gc_fail(GNSSCORR_EINVAL, "debug_poison: byte %d (0..255, or -1 for off)", byte);
     ctx->poison = byte;
-    return GNSSCORR_OK;
-}
-
-// (tools/debug) the claims rows of the batch planned last: code rows, then carrier rows, GC_CLAIM_ROW ints each;
-// returns the number of rows per NCO
-extern "C" int gnsscorr_debug_spec_rows(gnsscorr_ctx *ctx, int *dst, int max_ints)
-{
-    if (!ctx || !ctx->dspec2[ctx->spec_last_buf] || !ctx->spec_last_units) return -1;
-    GC_HIP(hipSetDevice(ctx->device));
-    GC_HIP(hipDeviceSynchronize());
-    const size_t ints = (size_t)2 * ctx->spec_last_units * GC_CLAIM_ROW;
-    if ((size_t)max_ints < ints) return -2;
-    GC_HIP(hipMemcpy(dst, ctx->dspec2[ctx->spec_last_buf], ints * sizeof(int), hipMemcpyDeviceToHost));
-    return ctx->spec_last_units;
-}
-
-extern "C" int gnsscorr_trk_run(gnsscorr_ctx *ctx, int nepoch)
-{
-    if (!ctx || nepoch <= 0) return gc_fail(GNSSCORR_EINVAL, "trk_run: nepoch %d", nepoch);
-    if (!ctx->nch) return gc_fail(GNSSCORR_ESTATE, "trk_run: no channels set");
-    GC_HIP(hipSetDevice(ctx->device));
-    int rc = gc_ensure_trk_buffers(ctx, nepoch);
-    if (rc) return rc;
-    uint64_t wr[2];             // what the ring check below may take as written
-    rc = gc_ring_positions(ctx, wr);
-    if (rc) return rc;
-    // ---- planner: use the look-ahead plan if it matches, else plan now ----
-    // plan = the sequential NCO chain per channel (discovery pass + chain), on the planner stream into the
-    // slot's plan buffer; ev_plan marks it ready
-    hipStream_t ps = ctx->stream_plan;
-    auto plan_into = [&](GcPlanSlot &sl) -> int {
-        // the slot's partial sums were last read by the finish of two batches ago: ordering the plan
-        // behind it lets ev_plan stand for "the slot is free and planned" on the main stream
-        if (sl.fin_pending) GC_HIP(hipStreamWaitEvent(ps, sl.ev_fin, 0));
-        // claims of this batch: discovered ahead (while the previous batch's chain ran, from that batch's
-        // input state) if nothing has touched the state since, else discovered now from the state itself
-        const GcTrkState *sin = ctx->dstate2[ctx->state_cur];
-        int buf;
-        if (ctx->spec_pending) GC_HIP(hipStreamWaitEvent(ps, ctx->ev_spec, 0));
-        if (ctx->spec_ahead_valid && !ctx->state_touched && ctx->spec_ahead_nepoch == nepoch && ctx->spec_ahead_state == (const void *)sin) {
-            buf = ctx->spec_ahead_buf;
-        } else {
-            buf = 0;
-            GcTimed t(ctx, "trk_spec", ps);
-            int r2 = gc_launch_trk_spec(ps, ctx->dchan, sin, ctx->nch, nepoch, ctx->dspec2[buf], 0);
-            if (r2) return r2;
-        }
-        ctx->spec_ahead_valid = false;
-        ctx->spec_pending = false;
-        ctx->spec_last_buf = buf;
-        ctx->spec_last_units = ctx->nch * nepoch;
-        // the next batch's claims, from the same input state, beside this batch's chain (the other buffer
-        // was last read by the chain in front of this one on the planner stream)
-        GC_HIP(hipEventRecord(ctx->ev_chain, ps));
-        GC_HIP(hipStreamWaitEvent(ctx->stream_discover, ctx->ev_chain, 0));
-        {
-            GcTimed t(ctx, "trk_spec", ctx->stream_discover);
-            int r2 = gc_launch_trk_spec(ctx->stream_discover, ctx->dchan, sin, ctx->nch, nepoch, ctx->dspec2[buf ^ 1], nepoch);
-            if (r2) return r2;
-            GC_HIP(hipEventRecord(ctx->ev_spec, ctx->stream_discover));
-        }
-        ctx->spec_pending = true;
-        ctx->spec_ahead_valid = true;
-        ctx->spec_ahead_buf = buf ^ 1;
-        ctx->spec_ahead_nepoch = nepoch;
-        ctx->spec_ahead_state = (const void *)ctx->dstate2[ctx->state_cur ^ 1];
-        {
-            GcTimed t(ctx, "trk_plan", ps);
-            int r2 = gc_launch_trk_plan(ps, ctx->dchan, sin, ctx->dstate2[ctx->state_cur ^ 1],
-                                        sl.plan, ctx->nch, nepoch, ctx->dspec2[buf]);
-            if (r2) return r2;
-        }
-        GC_HIP(hipEventRecord(sl.ev_plan, ps));
-        return 0;
-    };
-    const int slot = ctx->plan_slot;
-    GcPlanSlot &cur = ctx->slot[slot];
-    if (!(ctx->ahead_valid && ctx->ahead_nepoch == nepoch)) {
-        if (ctx->ahead_valid) {        // planned for another batch length: the committed state is untouched
-            GC_HIP(hipStreamSynchronize(ps));
-            ctx->ahead_valid = false;
-        }
-        // order after whatever the main stream did to the state / buffers
-        GC_HIP(hipEventRecord(cur.ev_used, ctx->stream));
-        GC_HIP(hipStreamWaitEvent(ps, cur.ev_used, 0));
-        rc = plan_into(cur);
-        if (rc) return rc;
-    }
-    GC_HIP(hipStreamWaitEvent(ctx->stream, cur.ev_plan, 0));
-    // the per-unit constants and NCO tables of the planned periods: on the main stream, in front of the
-    // correlator that reads them (the planner stream carries nothing but the sequential chain)
-    {
-        GcTimed t(ctx, "trk_expand");
-        int r2 = gc_launch_trk_expand(ctx->stream, ctx->dchan, cur.plan, cur.unit, cur.segs, cur.nsamp,
-                                      ctx->nch, nepoch, cur.rounds, ctx->nseg, ctx->max_n, ctx->dnco_overflow);
-        if (r2) return r2;
-    }
-    // the planned periods against what the rings hold now
-    // (the write positions travel as kernel arguments: no copy, no host synchronisation per batch)
-    rc = gc_launch_trk_ringcheck(ctx->stream, ctx->dchan, cur.plan, (const int8_t *)ctx->ring[0].mem, wr[0], wr[1], ctx->nch,
-                                 nepoch, ctx->dring_viol);
-    if (rc) return rc;
-    {
-        // start samples of the periods' chip edges, for the correlator's look-up phase
-        GcTimed t(ctx, "trk_edges");
-        rc = gc_launch_trk_edges(ctx->stream, ctx->dchan, cur.unit, cur.segs, ctx->detab, ctx->nch, nepoch);
-        if (rc) return rc;
-    }
-    for (int dtype = 1; dtype <= 2; dtype++) {
-        if (!ctx->have_dtype[dtype]) continue;
-        GcTimed t(ctx, "trk_corr");
-        rc = gc_launch_trk_corr(ctx->stream, ctx->dchan, cur.unit, cur.segs, cur.rounds, cur.partial,
-                                ctx->nch, nepoch, ctx->nseg, ctx->ntap, dtype, ctx->ntap, ctx->max_n, ctx->smax_max, ctx->detab);
-        if (rc) return rc;
-    }
-    GC_HIP(hipEventRecord(cur.ev_corr, ctx->stream));     // slot buffers consumed, partials ready
-    // every launch of the batch was issued: only now the plan's output state becomes the committed one
-    ctx->ahead_valid = false;
-    ctx->state_cur ^= 1;
-    ctx->plan_slot ^= 1;
-    // ---- look ahead: plan the next batch of the same length while this one is correlated ----
-    if (!ctx->state_touched) {
-        GcPlanSlot &next = ctx->slot[ctx->plan_slot];
-        GC_HIP(hipStreamWaitEvent(ps, next.ev_corr, 0));        // its previous contents were consumed
-        rc = plan_into(next);
-        if (rc) return rc;
-        ctx->ahead_valid = true;
-        ctx->ahead_nepoch = nepoch;
-    }
-    ctx->state_touched = false;
-    // ---- finish on its own stream: the main stream goes straight from this batch's correlator to the
-    // next one's, the outputs become valid at the slot's ev_fin ----
-    {
-        hipStream_t fs = ctx->stream_finish;
-        GC_HIP(hipStreamWaitEvent(fs, cur.ev_corr, 0));
-        GcTimed t(ctx, "trk_finish", fs);
-        rc = gc_launch_trk_finish(fs, cur.partial, ctx->dcorrI, ctx->dcorrQ, ctx->dsumI, ctx->dsumQ,
-                                  ctx->dfinish, ctx->nch, nepoch, ctx->nseg, ctx->ntap);
-        if (rc) return rc;
-        GC_HIP(hipEventRecord(cur.ev_fin, fs));
-        cur.fin_pending = true;
-    }
-    ctx->last_slot = slot;
-    ctx->last_nepoch = nepoch;
-    ctx->loop.last_nper = 0;
-    return GNSSCORR_OK;
-}
-
-// Units whose NCO piece tables overflowed (a code step that wraps the code more than ~twice per call, a
-// carrier that visits more than GC_NCAR binades) were not correlated: say so instead of handing out zeros.
-int gc_nco_check(gnsscorr_ctx *ctx)
-{
-    int n = 0, v = 0;
-    GC_HIP(hipMemcpy(&v, ctx->dring_viol, sizeof(int), hipMemcpyDeviceToHost));
-    if (v) {
-        GC_HIP(hipMemset(ctx->dring_viol, 0, sizeof(int)));
-        return gc_fail(GNSSCORR_ESTATE, "tracking: %d (channel, period) units lay outside what the IF ring holds "
-                       "(beyond the write position, or overwritten since): their sums are not the stream's", v);
-    }
-    GC_HIP(hipMemcpy(&n, ctx->dnco_overflow, sizeof(int), hipMemcpyDeviceToHost));
-    if (!n) return GNSSCORR_OK;
-    GC_HIP(hipMemset(ctx->dnco_overflow, 0, sizeof(int)));
-    return gc_fail(GNSSCORR_EINVAL, "tracking: %d (channel, period) units need more NCO pieces than the tables hold "
-                   "(more than two code periods per call, or a carrier crossing more than %d binades); their sums are zero",
-                   n, GC_NCAR);
-}
-
-// trk.II <- correlator's QQ (sum dataQ*code), trk.QQ <- its II: ref src/sdrtrk.c:42
-extern "C" int gnsscorr_trk_fetch(gnsscorr_ctx *ctx, double *trkII, double *trkQQ, int *nsamp_out)
-{
-    if (!ctx || !ctx->last_nepoch) return gc_fail(GNSSCORR_ESTATE, "trk_fetch: no completed trk_run");
-    GC_HIP(hipSetDevice(ctx->device));
-    { int rc = outputs_ready(ctx); if (rc) return rc; }
-    const size_t units = (size_t)ctx->nch * ctx->last_nepoch;
-    if (trkII)
-        GC_HIP(hipMemcpyAsync(trkII, ctx->dcorrQ, sizeof(double) * units * ctx->ntap, hipMemcpyDeviceToHost, ctx->stream));
-    if (trkQQ)
-        GC_HIP(hipMemcpyAsync(trkQQ, ctx->dcorrI, sizeof(double) * units * ctx->ntap, hipMemcpyDeviceToHost, ctx->stream));
-    if (nsamp_out)
-        GC_HIP(hipMemcpyAsync(nsamp_out, ctx->slot[ctx->last_slot].nsamp, sizeof(int) * units, hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    return gc_nco_check(ctx);
-}
-
-extern "C" int gnsscorr_trk_fetch_sums(gnsscorr_ctx *ctx, double *sumI, double *sumQ)
-{
-    if (!ctx || !ctx->last_nepoch) return gc_fail(GNSSCORR_ESTATE, "trk_fetch_sums: no completed trk_run");
-    if (ctx->loop.last_nper) return gc_fail(GNSSCORR_ESTATE, "trk_fetch_sums: the last run was closed loop (its sums are in gnsscorr_loop_get)");
-    GC_HIP(hipSetDevice(ctx->device));
-    { int rc = outputs_ready(ctx); if (rc) return rc; }
-    const size_t n = (size_t)ctx->nch * ctx->ntap;
-    if (sumI) GC_HIP(hipMemcpyAsync(sumI, ctx->dsumQ, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (sumQ) GC_HIP(hipMemcpyAsync(sumQ, ctx->dsumI, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    return GNSSCORR_OK;
-}
-
-extern "C" int gnsscorr_trk_devptrs(gnsscorr_ctx *ctx, void **trkII, void **trkQQ)
-{
-    if (!ctx || !ctx->dcorrI) return gc_fail(GNSSCORR_ESTATE, "trk_devptrs: no trk_run yet");
-    { int rc = outputs_ready(ctx); if (rc) return rc; }     // work queued on the context stream after this sees them
-    if (trkII) *trkII = ctx->dcorrQ;
-    if (trkQQ) *trkQQ = ctx->dcorrI;
     return GNSSCORR_OK;
 }
 

@@ -76,11 +76,13 @@ struct GcPinBuf {
     operator T *() const { return p; }
 };
 
-#define GC_RESERVE(ctx, buf, elems)                                             \
+// returns the call's error code from the calling function, if it gives one
+#define GC_TRY(call)                                                            \
     do {                                                                        \
-        int rc_ = (buf).reserve((ctx), (elems));                                \
+        int rc_ = (call);                                                       \
         if (rc_) return rc_;                                                    \
     } while (0)
+#define GC_RESERVE(ctx, buf, elems) GC_TRY((buf).reserve((ctx), (elems)))
 
 struct GcRing {
     int8_t  *mem = nullptr;   // own, or the caller's buffer
@@ -99,19 +101,62 @@ struct GcTimer {
 struct GcAcqWork;   // gnsscorr_acq.hip
 struct GcSpecWork;  // gnsscorr_spec.hip
 
+// The committed tracking state, ping-pong: a batch's planner chains cur() into next() and the batch commits it once every
+// launch is issued; the closed loop, both hand-overs and trk_set/get_state work on cur() in place
+struct GcTrkStateBuf {
+    GcDevBuf<GcTrkState> buf[2];   // [nch] each
+    int icur = 0;
+    bool touched = true;           // written outside gnsscorr_trk_run since its last batch: that batch does not look ahead
+    GcTrkState *cur() const { return buf[icur]; }
+    GcTrkState *next() const { return buf[icur ^ 1]; }
+    void commit() { icur ^= 1; }
+};
+
+// What a tracking run of either kind (gnsscorr_trk_run, gc_trk_run_loop) leaves for the fetch calls, per channel set
+// (gc_ensure_trk_outputs, gnsscorr_trk.hip).  Every writer and reader of nsamp is on the main stream.
+struct GcTrkOut {
+    GcDevBuf<double> dcorrI, dcorrQ;               // [unit][ntap]
+    GcDevBuf<double> dsumI, dsumQ;                 // [nch][ntap] batch sums
+    GcDevBuf<int> nsamp;                           // [unit]
+    GcDevBuf<int> dnco_overflow;                   // units whose NCO tables overflowed since the last fetch
+    GcDevBuf<int> dring_viol;                      // planned periods outside what the ring holds, since the last fetch
+    size_t units = 0;                              // (channel, period) units the per-unit buffers are sized for
+    int last_nepoch = 0;                           // periods per channel of the last completed run (0: none yet)
+    bool fin_pending = false;                      // the outputs become valid at the finish event of plan slot fin_slot
+    int fin_slot = 0;
+};
+
 // One plan slot: the planner stream expands batch k+1 into one slot while batch k is correlated from the other
 struct GcPlanSlot {
     GcDevBuf<GcTrkPlan> plan;      // [unit]
     GcDevBuf<GcTrkUnit> unit;      // [unit] per-unit constants
     GcDevBuf<GcRound> rounds;      // [unit][nseg][GC_MAXR]
     GcDevBuf<GcUnitSegs> segs;     // [unit]: the unit's carrier / code NCO piece tables
-    GcDevBuf<int> nsamp;           // [unit]
     GcDevBuf<int> partial;         // [ch][epoch][segment][2*ntap] int32 partial sums
-    hipEvent_t ev_plan = nullptr;  // plan finished (planner stream)
-    hipEvent_t ev_used = nullptr;  // the main stream is done with what the slot held before: the planner may write it
-    hipEvent_t ev_corr = nullptr;  // correlator finished (main stream): slot consumed, partials ready
-    hipEvent_t ev_fin = nullptr;   // finish done (finish stream): outputs valid
-    bool fin_pending = false;      // ev_fin has been recorded
+    bool fin_pending = false;      // the slot's ev_fin has been recorded and not been drained since
+};
+
+// The batched tracker (gnsscorr_trk.hip): what gnsscorr_trk_run owns, per channel set.  The planner (a short sequential
+// NCO chain per channel) runs one batch ahead on its own stream: plan entries and the chained state are double buffered,
+// so batch k+1 is planned while batch k is correlated.  A look-ahead plan is dropped when the caller changes the state
+// or the batch length.
+struct GcBatch {
+    GcPlanSlot slot[2];
+    size_t units = 0;                              // (channel, period) units every buffer here is sized for
+    int nseg = 1;
+    // claims of the batch being planned (discovery pass -> chain), two buffers: while the chain of one batch reads
+    // its claims the discovery pass of the NEXT batch fills the other one from the same input state, on its own stream
+    GcDevBuf<int> dspec2[2];
+    GcDevBuf<unsigned short> detab;                // [unit][GC_EDGTAB] start samples of the batch's chip edges (main stream: trk_edges -> trk_corr)
+    GcDevBuf<unsigned long long> dfinish;          // batch-sum scratch of trk_finish
+    bool spec_pending = false;                     // the discovery stream has work whose end ev_spec marks
+    bool spec_ahead_valid = false;                 // dspec2[spec_ahead_buf] holds claims for the batch that starts at spec_ahead_state
+    int spec_ahead_buf = 0, spec_ahead_nepoch = 0;
+    int spec_last_buf = 0, spec_last_units = 0;    // (tools/debug) the claims the last planned batch used
+    const void *spec_ahead_state = nullptr;
+    int plan_slot = 0;                             // slot the next trk_run consumes
+    bool ahead_valid = false;                      // slot[plan_slot] already planned (look-ahead)
+    int ahead_nepoch = 0;
 };
 
 #define GC_LOOP_AHEAD 3         // launch bursts gc_trk_run_loop keeps in flight
@@ -185,43 +230,24 @@ struct gnsscorr_ctx {
     int ntap = 0, smax_max = 0, max_n = 0;
     bool have_dtype[3] = {false, false, false};    // [dtype] some channel reads a ring of that dtype
 
-    // tracking.  The planner (a short sequential NCO chain per channel) runs one batch ahead on
-    // its own stream: plan entries and the chained state are double buffered, so batch k+1 is
-    // planned while batch k is correlated.  A look-ahead plan is dropped when the caller changes
-    // the state or the batch length.  Every stream and event below exists for the context's lifetime.
+    // tracking: the committed state, the batched tracker, the closed loop, the outputs of both.  The helper streams
+    // and every event exist for the context's lifetime; the structs hold none and are replaced whole per channel set.
     hipStream_t stream_plan = nullptr;             // planner: the sequential chain (and the direct discovery)
     hipStream_t stream_finish = nullptr;           // finish: partial sums -> outputs
     hipStream_t stream_discover = nullptr;         // discovery of the next batch's claims, beside the chain
-    GcDevBuf<GcTrkState> dstate2[2];               // ping-pong; cur = index of the committed state
-    int state_cur = 0;
-    GcPlanSlot slot[2];
-    size_t trk_units = 0;                          // (channel, period) units every tracking buffer below is sized for
-    // claims of the batch being planned (discovery pass -> chain), two buffers: while the chain of one batch reads
-    // its claims the discovery pass of the NEXT batch fills the other one from the same input state, on its own stream
-    GcDevBuf<int> dspec2[2];
-    GcDevBuf<unsigned short> detab;                // [unit][GC_EDGTAB] start samples of the batch's chip edges (main stream: trk_edges -> trk_corr)
+    hipEvent_t ev_plan[2] = {};                    // per plan slot: plan finished (planner stream)
+    hipEvent_t ev_used[2] = {};                    // the main stream is done with what the slot held before: the planner may write it
+    hipEvent_t ev_corr[2] = {};                    // correlator finished (main stream): slot consumed, partials ready
+    hipEvent_t ev_fin[2] = {};                     // finish done (finish stream): outputs valid
     hipEvent_t ev_spec = nullptr, ev_chain = nullptr;
-    bool spec_pending = false;                     // the discovery stream has work whose end ev_spec marks
-    bool spec_ahead_valid = false;                 // dspec2[spec_ahead_buf] holds claims for the batch that starts at spec_ahead_state
-    int spec_ahead_buf = 0, spec_ahead_nepoch = 0;
-    int spec_last_buf = 0, spec_last_units = 0;     // (tools/debug) the claims the last planned batch used
-    const void *spec_ahead_state = nullptr;
-    int plan_slot = 0;                             // slot the next trk_run consumes
-    bool ahead_valid = false;                      // slot[plan_slot] already planned (look-ahead)
-    int ahead_nepoch = 0;
-    bool state_touched = true;                     // set_state since the last run: do not look ahead
-    GcDevBuf<int> dnco_overflow;                   // units whose NCO tables overflowed since the last fetch
-    GcDevBuf<int> dring_viol;                      // planned periods outside what the ring holds, since the last fetch
+    GcTrkStateBuf state;
+    GcBatch batch;
+    GcTrkOut out;
     GcLoop loop;
     hipEvent_t ev_burst[GC_LOOP_AHEAD] = {};       // gc_trk_run_loop: the ends of the launch bursts in flight
     GcRx rx;
     hipEvent_t ev_lock = nullptr;                  // end of the last lock monitor launch (made on first use)
     bool lock_pending = false;                     // ev_lock is recorded and rx.lock_lost not read yet
-    int last_slot = 0;                             // slot of the last completed trk_run
-    GcDevBuf<double> dcorrI, dcorrQ, dsumI, dsumQ;
-    GcDevBuf<unsigned long long> dfinish;          // batch-sum scratch of trk_finish
-    int nseg = 1;
-    int last_nepoch = 0;
 
     // acquisition
     GcAcqWork *acq = nullptr;
@@ -268,8 +294,14 @@ struct GcTimed {
 
 void gc_acq_free(gnsscorr_ctx *ctx);
 void gc_spec_free(gnsscorr_ctx *ctx);
-// drains the helper streams and the main stream (and the ingest stream when `ingest`), then drops the look-ahead plan
+// gnsscorr_trk.hip.  gc_drain: the planner, finish, discovery and main streams are idle afterwards.  gc_quiesce: that
+// (and the ingest stream when `ingest`), then drops the look-ahead plan and marks the state touched
+int gc_drain(gnsscorr_ctx *ctx);
 int gc_quiesce(gnsscorr_ctx *ctx, bool ingest = false);
+// the outputs of a run of nperiod periods per channel; the main stream waits for the last batch's; a fetch's counters
+int gc_ensure_trk_outputs(gnsscorr_ctx *ctx, int nperiod);
+int gc_outputs_ready(gnsscorr_ctx *ctx);
+int gc_nco_check(gnsscorr_ctx *ctx);
 // the acquisition's forward twiddle tables (made on first use): exp(-2 pi i t/16384), exp(-2 pi i t/32768), t < 16384
 int gc_acq_twiddles(gnsscorr_ctx *ctx, const float2 **tw16k, const float2 **tw32k);
 int gc_ingest_fence(gnsscorr_ctx *ctx);      // orders the compute stream behind the last ring transfer
@@ -277,11 +309,8 @@ int gc_ingest_fence(gnsscorr_ctx *ctx);      // orders the compute stream behind
 // positions cover only samples whose transfer the compute stream is ordered behind
 int gc_ring_positions(gnsscorr_ctx *ctx, uint64_t wp_ring[2]);
 // the closed loop takes the tracking state: quiesces if the batched interface has a look-ahead plan or a finish pending;
-// either way no plan is valid afterwards and state_touched is set (the batched tracker plans afresh)
+// either way no plan is valid afterwards and the state is marked touched (the batched tracker plans afresh)
 int gc_loop_take_state(gnsscorr_ctx *ctx);
-// gnsscorr_api.hip: the batched tracker's buffers for nepoch periods per channel; the overflow / ring counters of a fetch
-int gc_ensure_trk_buffers(gnsscorr_ctx *ctx, int nepoch);
-int gc_nco_check(gnsscorr_ctx *ctx);
 // gnsscorr_acq.hip: one search over a channel list; the device hand-over of its acquired channels into the closed loop
 int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chlist, int n);
 int gc_acq_handover(gnsscorr_ctx *ctx, bool quiesce);

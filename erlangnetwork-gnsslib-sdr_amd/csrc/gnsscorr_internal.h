@@ -140,8 +140,6 @@ int gc_launch_trk_plan(hipStream_t st, const GcChan *chan, const GcTrkState *sta
 // nco_overflow: device counter of units whose NCO tables did not fit (their outputs are zero)
 int gc_launch_trk_expand(hipStream_t st, const GcChan *chan, const GcTrkPlan *plan, GcTrkUnit *unit, GcUnitSegs *segs,
                          int *nsamp_out, int nch, int nepoch, GcRound *rounds, int nseg, int max_n, int *nco_overflow);
-int gc_launch_trk_edges(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit, const GcUnitSegs *segs, unsigned short *etab,
-                        int nch, int nepoch);
 int gc_launch_trk_corr(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit, const GcUnitSegs *segs,
                        const GcRound *rounds, int *partial, int nch,
                        int nepoch, int nseg, int ntap_stride, int dtype, int ntap, int max_n, int smax_max,
@@ -151,8 +149,6 @@ int gc_launch_trk_corr(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit
 int gc_launch_trk_finish(hipStream_t st, const int *partial, double *corrI, double *corrQ, double *sumI,
                          double *sumQ, unsigned long long *scratch, int nch, int nepoch, int nseg, int ntap);
 int gc_trk_nseg(int dtype, int max_n);
-int gc_launch_trk_ringcheck(hipStream_t st, const GcChan *chan, const GcTrkPlan *plan, const int8_t *ring0, uint64_t wrpos0,
-                            uint64_t wrpos1, int nch, int nepoch, int *viol);
 
 // ---- closed loop in steps (gnsscorr_loop.hip) ---------------------------------------------------------------
 // One step = one filter interval per channel: the periods up to and including the next one after which pll()/dll()

@@ -329,7 +329,7 @@ int gc_rx_lock_launch(gnsscorr_ctx *ctx, int nperiod)
         hipLaunchKernelGGL(rx_lock_kernel, dim3((n + GC_LOCK_WAVES - 1) / GC_LOCK_WAVES), dim3(GC_LOCK_WAVES * 64), 0, ctx->stream,
                            (const int *)rx.lock_list.dev, n, (const gnsscorr_lockprm_t *)rx.dlockprm.p,
                            (const char *)ctx->loop.dloop.p + offsetof(gnsscorr_loop_t, rate), sizeof(gnsscorr_loop_t), rx.dlock.p,
-                           (const double *)ctx->dcorrQ.p, (const double *)ctx->dcorrI.p, (size_t)nperiod * ctx->ntap, (size_t)ctx->ntap,
+                           (const double *)ctx->out.dcorrQ.p, (const double *)ctx->out.dcorrI.p, (size_t)nperiod * ctx->ntap, (size_t)ctx->ntap,
                            (const gnsscorr_trklog_t *)ctx->loop.dlog.p, nperiod, (const int *)ctx->loop.ddone.p,
                            (const char *)ctx->loop.dloop.p + offsetof(gnsscorr_loop_t, cnt), sizeof(gnsscorr_loop_t), 1,
                            rx.lock_lost.dev);

@@ -1014,9 +1014,9 @@ int launch_step_tail(gnsscorr_ctx *ctx, int kcap, int plan)
     if (kcap < 1 || kcap > GC_STEP_KMAX) return gc_fail(GNSSCORR_EINVAL, "trk_step: %d periods per step (1..%d)", kcap, GC_STEP_KMAX);
     GcLoop &lp = ctx->loop;
     hipLaunchKernelGGL(trk_step_tail_kernel, dim3(ctx->nch), dim3(64 * GC_TAIL_NW), 0, ctx->stream, ctx->dchan.p,
-                       ctx->dstate2[ctx->state_cur].p, lp.dloop.p, lp.dstep_meta.p, lp.dwrpos.p, lp.dstep_partial.p, lp.dstep_unit.p,
-                       lp.dstep_segs.p, lp.dstep_rounds.p, ctx->dcorrI.p, ctx->dcorrQ.p, ctx->slot[0].nsamp.p, lp.dlog.p, lp.ddone.p,
-                       ctx->dnco_overflow.p, lp.dlapped.p, lp.hostflags.dev, ctx->nch, lp.run_nper, lp.step_nseg, ctx->ntap, ctx->max_n,
+                       ctx->state.cur(), lp.dloop.p, lp.dstep_meta.p, lp.dwrpos.p, lp.dstep_partial.p, lp.dstep_unit.p,
+                       lp.dstep_segs.p, lp.dstep_rounds.p, ctx->out.dcorrI.p, ctx->out.dcorrQ.p, ctx->out.nsamp.p, lp.dlog.p, lp.ddone.p,
+                       ctx->out.dnco_overflow.p, lp.dlapped.p, lp.hostflags.dev, ctx->nch, lp.run_nper, lp.step_nseg, ctx->ntap, ctx->max_n,
                        kcap, plan);
     GC_HIP(hipGetLastError());
     return 0;
@@ -1104,15 +1104,6 @@ static int ensure_step_buffers(gnsscorr_ctx *ctx)
     return GNSSCORR_OK;
 }
 
-int gc_loop_take_state(gnsscorr_ctx *ctx)
-{
-    // the look-ahead planner of the batched interface works on the same state: stop it, drop its plan (gc_quiesce
-    // clears ahead_valid and sets state_touched; without a plan ahead_valid is false already)
-    if (ctx->ahead_valid || ctx->slot[0].fin_pending || ctx->slot[1].fin_pending) return gc_quiesce(ctx);
-    ctx->state_touched = true;
-    return GNSSCORR_OK;
-}
-
 extern "C" int gnsscorr_trk_run_loop(gnsscorr_ctx *ctx, int nperiod) { return gc_trk_run_loop(ctx, nperiod, nullptr); }
 
 // wp_ch: nullptr, or the write position each channel is tracked up to ([nch]; 0 starves the channel at once: it plans
@@ -1122,26 +1113,22 @@ int gc_trk_run_loop(gnsscorr_ctx *ctx, int nperiod, const uint64_t *wp_ch)
     if (!ctx || nperiod <= 0) return gc_fail(GNSSCORR_EINVAL, "trk_run_loop: nperiod %d", nperiod);
     if (!ctx->nch) return gc_fail(GNSSCORR_ESTATE, "trk_run_loop: no channels set");
     GC_HIP(hipSetDevice(ctx->device));
-    int rc = gc_ensure_trk_buffers(ctx, nperiod);
-    if (rc) return rc;
-    rc = ensure_step_buffers(ctx);
-    if (rc) return rc;
-    rc = gc_loop_take_state(ctx);
-    if (rc) return rc;
+    GC_TRY(gc_ensure_trk_outputs(ctx, nperiod));
+    GC_TRY(ensure_step_buffers(ctx));
+    GC_TRY(gc_loop_take_state(ctx));
     GcLoop &L = ctx->loop;
     L.run_nper = nperiod;
     const size_t units = (size_t)ctx->nch * nperiod;
     GC_RESERVE(ctx, L.dlog, units);
     GC_HIP(hipMemsetAsync(L.dlog, 0, sizeof(gnsscorr_trklog_t) * units, ctx->stream));
-    GC_HIP(hipMemsetAsync(ctx->dcorrI, 0, sizeof(double) * units * ctx->ntap, ctx->stream));
-    GC_HIP(hipMemsetAsync(ctx->dcorrQ, 0, sizeof(double) * units * ctx->ntap, ctx->stream));
-    GC_HIP(hipMemsetAsync(ctx->slot[0].nsamp, 0, sizeof(int) * units, ctx->stream));
+    GC_HIP(hipMemsetAsync(ctx->out.dcorrI, 0, sizeof(double) * units * ctx->ntap, ctx->stream));
+    GC_HIP(hipMemsetAsync(ctx->out.dcorrQ, 0, sizeof(double) * units * ctx->ntap, ctx->stream));
+    GC_HIP(hipMemsetAsync(ctx->out.nsamp, 0, sizeof(int) * units, ctx->stream));
     GC_HIP(hipMemsetAsync(L.dstep_meta, 0, sizeof(GcStepMeta) * ctx->nch, ctx->stream));
     GC_HIP(hipMemsetAsync(L.dlapped, 0, sizeof(int), ctx->stream));
     // write position of each channel's ring (ref src/sdrtrk.c:26-28: fendbuffsize*buffcnt)
     uint64_t wpr[2];
-    rc = gc_ring_positions(ctx, wpr);
-    if (rc) return rc;
+    GC_TRY(gc_ring_positions(ctx, wpr));
     std::vector<uint64_t> wp(ctx->nch);
     for (int i = 0; i < ctx->nch; i++) wp[i] = wp_ch ? wp_ch[i] : wpr[ctx->hdesc[i].ftype - 1];
     GC_HIP(hipMemcpyAsync(L.dwrpos, wp.data(), sizeof(uint64_t) * ctx->nch, hipMemcpyHostToDevice, ctx->stream));
@@ -1163,19 +1150,16 @@ int gc_trk_run_loop(gnsscorr_ctx *ctx, int nperiod, const uint64_t *wp_ch)
         for (int b = 0; b < BURST && steps <= nperiod; b++, steps++) {
             // periods per step: 1 while no channel is synchronised (a performance hint only: the tail never plans more
             // than kcap periods, and any kcap >= 1 is correct)
-            rc = loop_step(ctx, L.hostflags[1] ? kmax : 1, 1);
-            if (rc) return rc;
+            GC_TRY(loop_step(ctx, L.hostflags[1] ? kmax : 1, 1));
         }
         GC_HIP(hipEventRecord(ctx->ev_burst[burst % AHEAD], ctx->stream));
         burst++;
     }
     // close whatever the last correlator launch produced
-    rc = loop_step(ctx, 1, 0);
-    if (rc) return rc;
+    GC_TRY(loop_step(ctx, 1, 0));
     if (L.hostflags[1]) L.sync_hint = true;
-    ctx->last_slot = 0;
-    ctx->slot[0].fin_pending = ctx->slot[1].fin_pending = false;
-    ctx->last_nepoch = nperiod;
+    ctx->out.fin_pending = false;           // the outputs are the main stream's own work
+    ctx->out.last_nepoch = nperiod;
     L.last_nper = nperiod;
     return GNSSCORR_OK;
 }

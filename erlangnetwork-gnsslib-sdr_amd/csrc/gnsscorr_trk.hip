@@ -18,11 +18,14 @@
 //              across the wavefront and the workgroup.  All sums are exact
 //              integers (|sum| < 2^31), scaled by 1/32 at the end like the
 //              reference's CSCALE.
+//   Below the kernels, the host driver of the batched tracker: gnsscorr_trk_run on its four streams, the buffers
+//   it and the closed loop reserve (GcBatch, GcTrkOut in gnsscorr_ctx.h), gc_drain / gc_quiesce, the fetch calls
+//   and trk_set/get_state.
 #include <cstdlib>
 #include <type_traits>
 
 
-#include "gnsscorr_internal.h"
+#include "gnsscorr_ctx.h"        // the host driver below the kernels
 #include "gnsscorr_ps.h"
 
 namespace {
@@ -646,14 +649,10 @@ __global__ __launch_bounds__(256) void trk_finish_kernel(const int *__restrict__
 int g_trk_nit = 0;      // groups per lane per segment workgroup (1, 2, 4 or 8); 0 = not yet chosen
 int g_trk_algo = 0;     // 1 = prefix-sum form (default), 2 = replica form (GNSSCORR_TRK_ALGO=replica)
 
-// the edge table of the launch being issued (set by gc_launch_trk_corr around the tap-bucket dispatch below)
-static thread_local const unsigned short *t_trk_etab = nullptr;
-
 template <int DTYPE, int NTAP, int NIT>
 int launch_corr_ps(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit, const GcUnitSegs *segs, const GcRound *rounds, int *partial,
-                   int nch, int nepoch, int nseg, int ntap_stride, int ntap_lo, int max_n)
+                   int nch, int nepoch, int nseg, int ntap_stride, int ntap_lo, int max_n, const unsigned short *etab)
 {
-    const unsigned short *etab = t_trk_etab;
     static_assert(PsLayout<DTYPE, NIT>::bytes(NTAP) <= 64 * 1024, "static LDS image");
     const int rpw = trk_ps_rounds(DTYPE, max_n, NIT);
     static const int ablate = getenv("GNSSCORR_TRK_ABLATE") ? atoi(getenv("GNSSCORR_TRK_ABLATE")) : 0;
@@ -689,12 +688,12 @@ int launch_corr(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit, const
 
 template <int DTYPE, int NTAP>
 int launch_corr_nit(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit, const GcUnitSegs *segs, const GcRound *rounds, int *partial, int nch, int nepoch,
-                    int nseg, int ntap_stride, int ntap_lo, int max_n, int smax_max)
+                    int nseg, int ntap_stride, int ntap_lo, int max_n, int smax_max, const unsigned short *etab)
 {
     if (g_trk_algo == 1) {
         if (g_trk_nit == 1 || DTYPE == 1)
-            return launch_corr_ps<DTYPE, NTAP, 1>(st, chan, unit, segs, rounds, partial, nch, nepoch, nseg, ntap_stride, ntap_lo, max_n);
-        return launch_corr_ps<DTYPE, NTAP, DTYPE == 1 ? 1 : 2>(st, chan, unit, segs, rounds, partial, nch, nepoch, nseg, ntap_stride, ntap_lo, max_n);
+            return launch_corr_ps<DTYPE, NTAP, 1>(st, chan, unit, segs, rounds, partial, nch, nepoch, nseg, ntap_stride, ntap_lo, max_n, etab);
+        return launch_corr_ps<DTYPE, NTAP, DTYPE == 1 ? 1 : 2>(st, chan, unit, segs, rounds, partial, nch, nepoch, nseg, ntap_stride, ntap_lo, max_n, etab);
     }
     switch (g_trk_nit) {
     default: return launch_corr<DTYPE, NTAP, 2>(st, chan, unit, segs, partial, nch, nepoch, nseg, ntap_stride, ntap_lo, max_n, smax_max);
@@ -705,10 +704,10 @@ int launch_corr_nit(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit, c
 
 template <int DTYPE>
 int launch_corr_taps(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit, const GcUnitSegs *segs, const GcRound *rounds, int *partial, int nch, int nepoch,
-                     int nseg, int ntap_stride, int ntap, int max_n, int smax_max)
+                     int nseg, int ntap_stride, int ntap, int max_n, int smax_max, const unsigned short *etab)
 {
     // smallest instantiation that holds ntap accumulators; it serves (lo, NTAP]
-#define GC_LC(N, LO) return launch_corr_nit<DTYPE, N>(st, chan, unit, segs, rounds, partial, nch, nepoch, nseg, ntap_stride, LO, max_n, smax_max)
+#define GC_LC(N, LO) return launch_corr_nit<DTYPE, N>(st, chan, unit, segs, rounds, partial, nch, nepoch, nseg, ntap_stride, LO, max_n, smax_max, etab)
     if (ntap <= 3)  GC_LC(3, 0);
     if (ntap <= 5)  GC_LC(5, 3);
     if (ntap <= 7)  GC_LC(7, 5);
@@ -760,7 +759,7 @@ int gc_launch_trk_expand(hipStream_t st, const GcChan *chan, const GcTrkPlan *pl
 
 // One launch serves every channel whose (dtype, tap bucket) matches; callers
 // invoke it once per distinct dtype present in the channel set.
-// etab: the start samples of the periods' chip edges (gc_launch_trk_edges on the same stream before this), or null
+// etab: the start samples of the periods' chip edges (launch_trk_edges on the same stream before this), or null
 int gc_launch_trk_corr(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit, const GcUnitSegs *segs,
                        const GcRound *rounds, int *partial, int nch,
                        int nepoch, int nseg, int ntap_stride, int dtype, int ntap, int max_n, int smax_max,
@@ -769,17 +768,15 @@ int gc_launch_trk_corr(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit
     trk_pick_nit();
     if (smax_max > 64) return gc_fail(GNSSCORR_EINVAL, "trk_corr: tap offset %d samples (<= 64 supported)", smax_max);
     static const bool noetab = getenv("GNSSCORR_TRK_NOEDGETAB") != nullptr;
-    t_trk_etab = (g_trk_algo == 1 && !noetab) ? etab : nullptr;
-    int rc = gc_fail(GNSSCORR_EINVAL, "trk_corr: dtype %d not 1 or 2", dtype);
+    if (g_trk_algo != 1 || noetab) etab = nullptr;
     if (dtype == 2)
-        rc = launch_corr_taps<2>(st, chan, unit, segs, rounds, partial, nch, nepoch, nseg, ntap_stride, ntap, max_n, smax_max);
-    else if (dtype == 1)
-        rc = launch_corr_taps<1>(st, chan, unit, segs, rounds, partial, nch, nepoch, nseg, ntap_stride, ntap, max_n, smax_max);
-    t_trk_etab = nullptr;
-    return rc;
+        return launch_corr_taps<2>(st, chan, unit, segs, rounds, partial, nch, nepoch, nseg, ntap_stride, ntap, max_n, smax_max, etab);
+    if (dtype == 1)
+        return launch_corr_taps<1>(st, chan, unit, segs, rounds, partial, nch, nepoch, nseg, ntap_stride, ntap, max_n, smax_max, etab);
+    return gc_fail(GNSSCORR_EINVAL, "trk_corr: dtype %d not 1 or 2", dtype);
 }
 
-int gc_launch_trk_edges(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit, const GcUnitSegs *segs, unsigned short *etab,
+static int launch_trk_edges(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit, const GcUnitSegs *segs, unsigned short *etab,
                         int nch, int nepoch)
 {
     static const bool noetab = getenv("GNSSCORR_TRK_NOEDGETAB") != nullptr;
@@ -806,7 +803,7 @@ __global__ void trk_ringcheck_kernel(const GcChan *__restrict__ chan, const GcTr
     if (p.buffloc + (uint64_t)p.n > wp || (wp > rl && p.buffloc < wp - rl)) atomicAdd(viol, 1);
 }
 
-int gc_launch_trk_ringcheck(hipStream_t st, const GcChan *chan, const GcTrkPlan *plan, const int8_t *ring0, uint64_t wrpos0,
+static int launch_trk_ringcheck(hipStream_t st, const GcChan *chan, const GcTrkPlan *plan, const int8_t *ring0, uint64_t wrpos0,
                             uint64_t wrpos1, int nch, int nepoch, int *viol)
 {
     const int total = nch * nepoch;
@@ -823,4 +820,329 @@ int gc_launch_trk_finish(hipStream_t st, const int *partial, double *corrI, doub
                        sumI, sumQ, scratch, nepoch, nseg, ntap);
     GC_HIP(hipGetLastError());
     return 0;
+}
+
+// ---- the host driver ("Four streams") ---------------------------------------------------------
+// The planner, finish, discovery and main streams are idle afterwards: no finish is pending any more.
+int gc_drain(gnsscorr_ctx *ctx)
+{
+    for (hipStream_t s : {ctx->stream_plan, ctx->stream_finish, ctx->stream_discover, ctx->stream})
+        GC_HIP(hipStreamSynchronize(s));
+    ctx->out.fin_pending = false;
+    for (GcPlanSlot &s : ctx->batch.slot) s.fin_pending = false;
+    return GNSSCORR_OK;
+}
+
+int gc_quiesce(gnsscorr_ctx *ctx, bool ingest)
+{
+    if (ingest && ctx->stream_in) GC_HIP(hipStreamSynchronize(ctx->stream_in));
+    GC_TRY(gc_drain(ctx));
+    ctx->batch.ahead_valid = false;    // a look-ahead plan may have been in flight: it is dropped
+    ctx->state.touched = true;
+    return GNSSCORR_OK;
+}
+
+int gc_loop_take_state(gnsscorr_ctx *ctx)
+{
+    // the look-ahead planner works on the same state: stop it, drop its plan (with neither a plan nor a finish in
+    // flight there is nothing to wait for)
+    if (ctx->batch.ahead_valid || ctx->out.fin_pending) return gc_quiesce(ctx);
+    ctx->state.touched = true;
+    return GNSSCORR_OK;
+}
+
+int gc_outputs_ready(gnsscorr_ctx *ctx)
+{
+    if (ctx->out.fin_pending) GC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_fin[ctx->out.fin_slot], 0));
+    return GNSSCORR_OK;
+}
+
+int gc_ensure_trk_outputs(gnsscorr_ctx *ctx, int nperiod)
+{
+    GcTrkOut &o = ctx->out;
+    const size_t units = (size_t)ctx->nch * nperiod;
+    if (units <= o.units) return GNSSCORR_OK;
+    // leaves the look-ahead plan and the claims valid: none of the planner's buffers is here
+    GC_TRY(gc_drain(ctx));
+    o.units = 0;                       // until every buffer below has its size
+    GC_RESERVE(ctx, o.dcorrI, units * ctx->ntap);
+    GC_RESERVE(ctx, o.dcorrQ, units * ctx->ntap);
+    GC_RESERVE(ctx, o.nsamp, units);
+    GC_RESERVE(ctx, o.dsumI, (size_t)ctx->nch * ctx->ntap);
+    GC_RESERVE(ctx, o.dsumQ, (size_t)ctx->nch * ctx->ntap);
+    for (GcDevBuf<int> *c : {&o.dnco_overflow, &o.dring_viol}) {
+        if (*c) continue;              // the counters keep what they hold when the other buffers grow
+        GC_RESERVE(ctx, *c, 1);
+        GC_HIP(hipMemsetAsync(*c, 0, sizeof(int), ctx->stream));
+    }
+    o.units = units;
+    return GNSSCORR_OK;
+}
+
+// the plan slots, claims, edge table and finish scratch for nepoch periods per channel
+static int ensure_batch_buffers(gnsscorr_ctx *ctx, int nepoch)
+{
+    GcBatch &b = ctx->batch;
+    const size_t units = (size_t)ctx->nch * nepoch;
+    if (units <= b.units) return GNSSCORR_OK;
+    // leaves state.touched: the committed state is unchanged, so this batch still plans ahead
+    GC_TRY(gc_drain(ctx));
+    b.ahead_valid = false;             // (a look-ahead plan advanced the uncommitted state one batch: it is dropped)
+    b.spec_ahead_valid = false;
+    b.units = 0;                       // until every buffer below has its size
+    b.nseg = 1;
+    for (int i = 0; i < ctx->nch; i++) {
+        const int s = gc_trk_nseg(ctx->hchan[i].dtype, ctx->max_n);
+        if (s > b.nseg) b.nseg = s;
+    }
+    for (GcPlanSlot &s : b.slot) {
+        GC_RESERVE(ctx, s.plan, units);
+        GC_RESERVE(ctx, s.partial, units * b.nseg * 2 * ctx->ntap);
+        GC_RESERVE(ctx, s.unit, units);
+        GC_RESERVE(ctx, s.rounds, units * b.nseg * GC_MAXR);
+        GC_RESERVE(ctx, s.segs, units);
+    }
+    for (int i = 0; i < 2; i++) GC_RESERVE(ctx, b.dspec2[i], gc_trk_spec_ints(units));
+    GC_RESERVE(ctx, b.detab, units * GC_EDGTAB);
+    GC_RESERVE(ctx, b.dfinish, (size_t)ctx->nch * GC_FINISH_SCRATCH);
+    GC_HIP(hipMemsetAsync(b.dfinish, 0, sizeof(unsigned long long) * ctx->nch * GC_FINISH_SCRATCH, ctx->stream));
+    b.units = units;
+    return GNSSCORR_OK;
+}
+
+// Plans a batch of nepoch periods from the committed state into slot s, on the planner stream: the batch's claims
+// (discovered ahead, or now), the next batch's discovery beside the chain, the chain; the slot's ev_plan marks it ready
+static int plan_into(gnsscorr_ctx *ctx, int s, int nepoch)
+{
+    GcBatch &b = ctx->batch;
+    GcPlanSlot &sl = b.slot[s];
+    hipStream_t ps = ctx->stream_plan;
+    // the slot's partial sums were last read by the finish of two batches ago: ordering the plan
+    // behind it lets ev_plan stand for "the slot is free and planned" on the main stream
+    if (sl.fin_pending) GC_HIP(hipStreamWaitEvent(ps, ctx->ev_fin[s], 0));
+    // claims of this batch: discovered ahead (while the previous batch's chain ran, from that batch's
+    // input state) if nothing has touched the state since, else discovered now from the state itself
+    const GcTrkState *sin = ctx->state.cur();
+    int buf;
+    if (b.spec_pending) GC_HIP(hipStreamWaitEvent(ps, ctx->ev_spec, 0));
+    if (b.spec_ahead_valid && !ctx->state.touched && b.spec_ahead_nepoch == nepoch && b.spec_ahead_state == (const void *)sin) {
+        buf = b.spec_ahead_buf;
+    } else {
+        buf = 0;
+        GcTimed t(ctx, "trk_spec", ps);
+        GC_TRY(gc_launch_trk_spec(ps, ctx->dchan, sin, ctx->nch, nepoch, b.dspec2[buf], 0));
+    }
+    b.spec_ahead_valid = false;
+    b.spec_pending = false;
+    b.spec_last_buf = buf;
+    b.spec_last_units = ctx->nch * nepoch;
+    // the next batch's claims, from the same input state, beside this batch's chain (the other buffer
+    // was last read by the chain in front of this one on the planner stream)
+    GC_HIP(hipEventRecord(ctx->ev_chain, ps));
+    GC_HIP(hipStreamWaitEvent(ctx->stream_discover, ctx->ev_chain, 0));
+    {
+        GcTimed t(ctx, "trk_spec", ctx->stream_discover);
+        GC_TRY(gc_launch_trk_spec(ctx->stream_discover, ctx->dchan, sin, ctx->nch, nepoch, b.dspec2[buf ^ 1], nepoch));
+        GC_HIP(hipEventRecord(ctx->ev_spec, ctx->stream_discover));
+    }
+    b.spec_pending = true;
+    b.spec_ahead_valid = true;
+    b.spec_ahead_buf = buf ^ 1;
+    b.spec_ahead_nepoch = nepoch;
+    b.spec_ahead_state = (const void *)ctx->state.next();
+    {
+        GcTimed t(ctx, "trk_plan", ps);
+        GC_TRY(gc_launch_trk_plan(ps, ctx->dchan, sin, ctx->state.next(), sl.plan, ctx->nch, nepoch, b.dspec2[buf]));
+    }
+    GC_HIP(hipEventRecord(ctx->ev_plan[s], ps));
+    return GNSSCORR_OK;
+}
+
+// The main-stream body of a batch planned into slot s: expand, ring check (wr: what it may take as written), edges, one
+// correlator launch per dtype; the slot's ev_corr marks the slot consumed and its partial sums ready
+static int correlate_slot(gnsscorr_ctx *ctx, int s, int nepoch, const uint64_t wr[2])
+{
+    GcBatch &b = ctx->batch;
+    GcPlanSlot &sl = b.slot[s];
+    // the per-unit constants and NCO tables of the planned periods: on the main stream, in front of the
+    // correlator that reads them (the planner stream carries nothing but the sequential chain)
+    {
+        GcTimed t(ctx, "trk_expand");
+        GC_TRY(gc_launch_trk_expand(ctx->stream, ctx->dchan, sl.plan, sl.unit, sl.segs, ctx->out.nsamp, ctx->nch, nepoch,
+                                    sl.rounds, b.nseg, ctx->max_n, ctx->out.dnco_overflow));
+    }
+    // the planned periods against what the rings hold now
+    // (the write positions travel as kernel arguments: no copy, no host synchronisation per batch)
+    GC_TRY(launch_trk_ringcheck(ctx->stream, ctx->dchan, sl.plan, (const int8_t *)ctx->ring[0].mem, wr[0], wr[1], ctx->nch,
+                                nepoch, ctx->out.dring_viol));
+    {
+        // start samples of the periods' chip edges, for the correlator's look-up phase
+        GcTimed t(ctx, "trk_edges");
+        GC_TRY(launch_trk_edges(ctx->stream, ctx->dchan, sl.unit, sl.segs, b.detab, ctx->nch, nepoch));
+    }
+    for (int dtype = 1; dtype <= 2; dtype++) {
+        if (!ctx->have_dtype[dtype]) continue;
+        GcTimed t(ctx, "trk_corr");
+        GC_TRY(gc_launch_trk_corr(ctx->stream, ctx->dchan, sl.unit, sl.segs, sl.rounds, sl.partial, ctx->nch, nepoch, b.nseg,
+                                  ctx->ntap, dtype, ctx->ntap, ctx->max_n, ctx->smax_max, b.detab));
+    }
+    GC_HIP(hipEventRecord(ctx->ev_corr[s], ctx->stream));     // slot buffers consumed, partials ready
+    return GNSSCORR_OK;
+}
+
+// The finish of slot s on its own stream: the main stream goes straight from this batch's correlator to the next
+// one's, the outputs become valid at the slot's ev_fin
+static int finish_slot(gnsscorr_ctx *ctx, int s, int nepoch)
+{
+    GcBatch &b = ctx->batch;
+    GcTrkOut &o = ctx->out;
+    hipStream_t fs = ctx->stream_finish;
+    GC_HIP(hipStreamWaitEvent(fs, ctx->ev_corr[s], 0));
+    GcTimed t(ctx, "trk_finish", fs);
+    GC_TRY(gc_launch_trk_finish(fs, b.slot[s].partial, o.dcorrI, o.dcorrQ, o.dsumI, o.dsumQ, b.dfinish, ctx->nch, nepoch,
+                                b.nseg, ctx->ntap));
+    GC_HIP(hipEventRecord(ctx->ev_fin[s], fs));
+    b.slot[s].fin_pending = true;
+    o.fin_pending = true;
+    o.fin_slot = s;
+    return GNSSCORR_OK;
+}
+
+extern "C" int gnsscorr_trk_run(gnsscorr_ctx *ctx, int nepoch)
+{
+    if (!ctx || nepoch <= 0) return gc_fail(GNSSCORR_EINVAL, "trk_run: nepoch %d", nepoch);
+    if (!ctx->nch) return gc_fail(GNSSCORR_ESTATE, "trk_run: no channels set");
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_TRY(gc_ensure_trk_outputs(ctx, nepoch));
+    GC_TRY(ensure_batch_buffers(ctx, nepoch));
+    uint64_t wr[2];             // what the ring check may take as written
+    GC_TRY(gc_ring_positions(ctx, wr));
+    GcBatch &b = ctx->batch;
+    hipStream_t ps = ctx->stream_plan;
+    // ---- planner: use the look-ahead plan if it matches, else plan now ----
+    const int cur = b.plan_slot;
+    if (!(b.ahead_valid && b.ahead_nepoch == nepoch)) {
+        if (b.ahead_valid) {           // planned for another batch length: the committed state is untouched
+            GC_HIP(hipStreamSynchronize(ps));
+            b.ahead_valid = false;
+        }
+        // order after whatever the main stream did to the state / buffers
+        GC_HIP(hipEventRecord(ctx->ev_used[cur], ctx->stream));
+        GC_HIP(hipStreamWaitEvent(ps, ctx->ev_used[cur], 0));
+        GC_TRY(plan_into(ctx, cur, nepoch));
+    }
+    GC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_plan[cur], 0));
+    GC_TRY(correlate_slot(ctx, cur, nepoch, wr));
+    // every launch of the batch was issued: only now the plan's output state becomes the committed one
+    b.ahead_valid = false;
+    ctx->state.commit();
+    b.plan_slot ^= 1;
+    // ---- look ahead: plan the next batch of the same length while this one is correlated ----
+    if (!ctx->state.touched) {
+        GC_HIP(hipStreamWaitEvent(ps, ctx->ev_corr[b.plan_slot], 0));        // its previous contents were consumed
+        GC_TRY(plan_into(ctx, b.plan_slot, nepoch));
+        b.ahead_valid = true;
+        b.ahead_nepoch = nepoch;
+    }
+    ctx->state.touched = false;
+    GC_TRY(finish_slot(ctx, cur, nepoch));
+    ctx->out.last_nepoch = nepoch;
+    ctx->loop.last_nper = 0;
+    return GNSSCORR_OK;
+}
+
+// Units whose NCO piece tables overflowed (a code step that wraps the code more than ~twice per call, a
+// carrier that visits more than GC_NCAR binades) were not correlated: say so instead of handing out zeros.
+int gc_nco_check(gnsscorr_ctx *ctx)
+{
+    GcTrkOut &o = ctx->out;
+    int n = 0, v = 0;
+    GC_HIP(hipMemcpy(&v, o.dring_viol, sizeof(int), hipMemcpyDeviceToHost));
+    if (v) {
+        GC_HIP(hipMemset(o.dring_viol, 0, sizeof(int)));
+        return gc_fail(GNSSCORR_ESTATE, "tracking: %d (channel, period) units lay outside what the IF ring holds "
+                       "(beyond the write position, or overwritten since): their sums are not the stream's", v);
+    }
+    GC_HIP(hipMemcpy(&n, o.dnco_overflow, sizeof(int), hipMemcpyDeviceToHost));
+    if (!n) return GNSSCORR_OK;
+    GC_HIP(hipMemset(o.dnco_overflow, 0, sizeof(int)));
+    return gc_fail(GNSSCORR_EINVAL, "tracking: %d (channel, period) units need more NCO pieces than the tables hold "
+                   "(more than two code periods per call, or a carrier crossing more than %d binades); their sums are zero",
+                   n, GC_NCAR);
+}
+
+// trk.II <- correlator's QQ (sum dataQ*code), trk.QQ <- its II: ref src/sdrtrk.c:42
+extern "C" int gnsscorr_trk_fetch(gnsscorr_ctx *ctx, double *trkII, double *trkQQ, int *nsamp_out)
+{
+    if (!ctx || !ctx->out.last_nepoch) return gc_fail(GNSSCORR_ESTATE, "trk_fetch: no completed trk_run");
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_TRY(gc_outputs_ready(ctx));
+    const GcTrkOut &o = ctx->out;
+    const size_t units = (size_t)ctx->nch * o.last_nepoch;
+    if (trkII) GC_HIP(hipMemcpyAsync(trkII, o.dcorrQ, sizeof(double) * units * ctx->ntap, hipMemcpyDeviceToHost, ctx->stream));
+    if (trkQQ) GC_HIP(hipMemcpyAsync(trkQQ, o.dcorrI, sizeof(double) * units * ctx->ntap, hipMemcpyDeviceToHost, ctx->stream));
+    if (nsamp_out) GC_HIP(hipMemcpyAsync(nsamp_out, o.nsamp, sizeof(int) * units, hipMemcpyDeviceToHost, ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));
+    return gc_nco_check(ctx);
+}
+
+extern "C" int gnsscorr_trk_fetch_sums(gnsscorr_ctx *ctx, double *sumI, double *sumQ)
+{
+    if (!ctx || !ctx->out.last_nepoch) return gc_fail(GNSSCORR_ESTATE, "trk_fetch_sums: no completed trk_run");
+    if (ctx->loop.last_nper) return gc_fail(GNSSCORR_ESTATE, "trk_fetch_sums: the last run was closed loop (its sums are in gnsscorr_loop_get)");
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_TRY(gc_outputs_ready(ctx));
+    const size_t n = (size_t)ctx->nch * ctx->ntap;
+    if (sumI) GC_HIP(hipMemcpyAsync(sumI, ctx->out.dsumQ, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (sumQ) GC_HIP(hipMemcpyAsync(sumQ, ctx->out.dsumI, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));
+    return GNSSCORR_OK;
+}
+
+extern "C" int gnsscorr_trk_devptrs(gnsscorr_ctx *ctx, void **trkII, void **trkQQ)
+{
+    if (!ctx || !ctx->out.dcorrI) return gc_fail(GNSSCORR_ESTATE, "trk_devptrs: no trk_run yet");
+    GC_TRY(gc_outputs_ready(ctx));     // work queued on the context stream after this sees them
+    if (trkII) *trkII = ctx->out.dcorrQ;
+    if (trkQQ) *trkQQ = ctx->out.dcorrI;
+    return GNSSCORR_OK;
+}
+
+extern "C" int gnsscorr_trk_set_state(gnsscorr_ctx *ctx, int ch0, int nch, const gnsscorr_trkstate_t *st)
+{
+    if (!ctx || !st || ch0 < 0 || nch <= 0 || ch0 + nch > ctx->nch)
+        return gc_fail(GNSSCORR_EINVAL, "trk_set_state: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    static_assert(sizeof(gnsscorr_trkstate_t) == sizeof(GcTrkState), "state layout");
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_TRY(gc_quiesce(ctx));
+    GC_HIP(hipMemcpyAsync(ctx->state.cur() + ch0, st, sizeof(GcTrkState) * nch, hipMemcpyHostToDevice, ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));
+    return GNSSCORR_OK;
+}
+
+extern "C" int gnsscorr_trk_get_state(gnsscorr_ctx *ctx, int ch0, int nch, gnsscorr_trkstate_t *st)
+{
+    if (!ctx || !st || ch0 < 0 || nch <= 0 || ch0 + nch > ctx->nch)
+        return gc_fail(GNSSCORR_EINVAL, "trk_get_state: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    GC_HIP(hipSetDevice(ctx->device));
+    // leaves the look-ahead plan valid: reading the committed state changes nothing
+    GC_TRY(gc_drain(ctx));
+    GC_HIP(hipMemcpyAsync(st, ctx->state.cur() + ch0, sizeof(GcTrkState) * nch, hipMemcpyDeviceToHost, ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));
+    return GNSSCORR_OK;
+}
+
+// (tools/debug) the claims rows of the batch planned last: code rows, then carrier rows, GC_CLAIM_ROW ints each;
+// returns the number of rows per NCO
+extern "C" int gnsscorr_debug_spec_rows(gnsscorr_ctx *ctx, int *dst, int max_ints)
+{
+    if (!ctx) return -1;
+    const GcBatch &b = ctx->batch;
+    if (!b.dspec2[b.spec_last_buf] || !b.spec_last_units) return -1;
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_HIP(hipDeviceSynchronize());
+    const size_t ints = (size_t)2 * b.spec_last_units * GC_CLAIM_ROW;
+    if ((size_t)max_ints < ints) return -2;
+    GC_HIP(hipMemcpy(dst, b.dspec2[b.spec_last_buf], ints * sizeof(int), hipMemcpyDeviceToHost));
+    return b.spec_last_units;
 }
