@@ -121,6 +121,28 @@ def frame_replay(state, log_rows, cnt0=0):
         raise RuntimeError("gnsscorr_frame_replay: error %d" % rc)
 
 
+class G1FrameState(C.Structure):
+    """gnsscorr_g1frame_t: frame synchronisation of GLONASS G1 on the decided symbols (ref src/sdrnav.c:40-82,
+    src/sdrnav_glo.c)."""
+    _fields_ = ([("fbits", C.c_int * 200)] +
+                [(n, C.c_int) for n in ("polarity", "flagsyncf", "flagtow", "flagdec", "id", "ephcnt", "s1cnt")] +
+                [("tk", C.c_int * 3)] + [(n, C.c_int) for n in ("nt", "slot", "n4", "iode", "update", "week")] +
+                [("str", C.c_ubyte * 11), ("pad", C.c_ubyte * 5),
+                 ("firstsf", C.c_uint64), ("firstsfcnt", C.c_uint64), ("firstsftow", C.c_double), ("tow_gpst", C.c_double)])
+
+
+def g1frame_replay(state, log_rows, cnt0=0):
+    """The symbols of one G1 channel's log rows through the time-mark search and the string decoder; `state`
+    (G1FrameState) is updated.  Host code only; the caller sets state.ephcnt = 0 to let the time merge again."""
+    L = lib()
+    L.gnsscorr_g1frame_replay.restype = C.c_int
+    L.gnsscorr_g1frame_replay.argtypes = [C.POINTER(G1FrameState), C.c_void_p, C.c_int, C.c_uint64]
+    log_rows = np.ascontiguousarray(log_rows)
+    rc = L.gnsscorr_g1frame_replay(C.byref(state), log_rows.ctypes.data, int(log_rows.shape[0]), int(cnt0))
+    if rc:
+        raise RuntimeError("gnsscorr_g1frame_replay: error %d" % rc)
+
+
 class SbasFrameState(C.Structure):
     """gnsscorr_sbasframe_t: frame synchronisation of SBAS L1 on the decided symbols (ref src/sdrnav.c:40-82)."""
     _fields_ = ([("fbits", C.c_int * 1512)] +
@@ -254,7 +276,7 @@ EXPORTS_GNSSCORR = [
     "gnsscorr_acq_run_subset", "gnsscorr_loop_start_from_acq", "gnsscorr_rx_start", "gnsscorr_rx_set",
     "gnsscorr_rx_step", "gnsscorr_rx_status", "gnsscorr_fec_run", "gnsscorr_sbasframe_replay",
     "gnsscorr_lock_run", "gnsscorr_rx_lock_set", "gnsscorr_rx_lock_status",
-    "gnsscorr_acq_set_coherent", "gnsscorr_acq_get_coherent"]
+    "gnsscorr_acq_set_coherent", "gnsscorr_acq_get_coherent", "gnsscorr_g1frame_replay"]
 EXPORTS_SDR = [
     "sdracquisition", "checkacquisition", "sdrtracking", "cumsumcorr", "clearcumsumcorr", "pll", "dll",
     "readinifile", "chk_initvalue", "initacqstruct", "inittrkprmstruct", "inittrkstruct", "initsdrch",

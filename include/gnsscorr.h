@@ -257,8 +257,42 @@ typedef struct {
     uint64_t firstsf, firstsfcnt;           /* ref sdrnav_t: sample / period counter of the frame's end   */
     double firstsftow, tow_gpst;            /* ref sdrnav_t.firstsftow, sdreph_t.tow_gpst                 */
 } gnsscorr_frame_t;
-/* log[nper]: one channel's rows; cnt0: sdrthread's cnt at log[0].  Returns 0, or GNSSCORR_EINVAL. */
+/* log[nper]: one channel's rows; cnt0: sdrthread's cnt at log[0].  Returns 0, or GNSSCORR_EINVAL.  This is the L1 C/A
+ * path: the state carries no code type, and the symbols of a GLONASS G1 channel belong to gnsscorr_g1frame_replay. */
 int  gnsscorr_frame_replay(gnsscorr_frame_t *st, const gnsscorr_trklog_t *log, int nper, uint64_t cnt0);
+
+/* Frame synchronisation of GLONASS G1 on the batched symbols: what sdrnavigation() does behind checkbit() for CTYPE_G1
+ * (ref src/sdrnav.c:40-82) -- the last 200 decided symbols (ref src/sdrinit.c:546-558), no FEC (ref src/sdrnav.c:296-299),
+ * the search for the 30-symbol time mark that ends a string (ref :391-408, src/sdrinit.c:494-496; the parity check
+ * passes every string, ref src/sdrnav.c:361-364), and every 2000 periods from the mark on decode_g1() (ref
+ * src/sdrnav_glo.c:199-224: meander and relative code removed, 85 bits packed) with the fields of strings 1, 2, 4 and 5
+ * that give the time (ref :26-37, :44-59, :82-107) and merge_g1()'s week and time of week (ref :118-165) -- replayed
+ * over the `navbit` column of a closed-loop log.  It yields what setobsdata() needs from the frame decoder: flagsyncf,
+ * polarity, firstsfcnt, firstsftow.  DESIGN.md section 3.6 states the semantics and the reference's quirks that are
+ * kept.  The Hamming check bits are not read (nor does the reference); ephemeris and almanac contents are not part of
+ * this library: `str` is there for a caller's decoder.  Plain host code without the device: csrc/sdr_g1.c links alone.
+ * The time is merged whenever ephcnt is exactly 5 after a string (ref src/sdrnav_glo.c:190); the reference's syncthread
+ * sets the counter back to 0 once it has taken the ephemeris (ref src/sdrsync.c:138-141).  Here that is the caller's
+ * job: set ephcnt = 0 between two calls to let the next five strings merge again.
+ * `slot` is what the reference copies into sdr->prn at flagdec (ref src/sdrnav.c:78-79); it is never written to the
+ * device. */
+typedef struct {
+    int    fbits[200];                      /* ref sdrnav_t.fbits (flen 200, addflen 0), newest last; 0: not filled */
+    int    polarity, flagsyncf, flagtow, flagdec;   /* ref sdrnav_t                                               */
+    int    id;                              /* string number decoded last (bits 1..4 of the string)                */
+    int    ephcnt, s1cnt;                   /* ref sdreph_t.cnt / .s1cnt                                           */
+    int    tk[3];                           /* string 1: hours - 3, minutes, seconds (ref sdreph_t.tk)             */
+    int    nt, slot, n4;                    /* string 4: day number, slot number; string 5: 4-year interval        */
+    int    iode, update;                    /* string 2: ref geph_t.iode, sdreph_t.update (ref src/sdrnav_glo.c:46-55) */
+    int    week;                            /* ref sdreph_t.week_gpst                                              */
+    unsigned char str[11];                  /* the 85 bits of the string decoded last, as decode_g1() packs them   */
+    unsigned char pad[5];
+    uint64_t firstsf, firstsfcnt;           /* ref sdrnav_t: sample / period counter of the time mark's last symbol */
+    double firstsftow, tow_gpst;            /* ref sdrnav_t.firstsftow, sdreph_t.tow_gpst: GPS time of the string's end */
+} gnsscorr_g1frame_t;
+/* log[nper]: one channel's rows; cnt0: sdrthread's cnt at log[0].  The caller zero-initialises st; a log may be replayed
+ * in pieces of any length.  Returns 0, or GNSSCORR_EINVAL (a NULL pointer, nper < 0) with nothing touched. */
+int  gnsscorr_g1frame_replay(gnsscorr_g1frame_t *st, const gnsscorr_trklog_t *log, int nper, uint64_t cnt0);
 
 /* ---- FEC: sliding-window Viterbi decoder (K = 7, rate 1/2) on the device ------
  * predecodefec() for CTYPE_L1SBAS (ref src/sdrnav.c:302-318): init_viterbi27(.., 0), update_blk over win/2 symbol
