@@ -53,45 +53,7 @@ using gcfft::cmul;
 using gcfft::cmulc;
 using gcfft::csub;
 
-// Carrier NCO of one Doppler bin over the (ncoh + 1)*nsamp samples of a group (ncoh = 1: the 2*nsamp acquisition
-// window), phase 0 at its first sample (ref src/sdrcmn.c:761): the reference's running sum as a piece table
-// (gnsscorr_nco.h)
-struct GcAcqCar {
-    int n, pad;
-    int k0[GC_NCAR];
-    GcCarSeg seg[GC_NCAR];
-};
-
 #define GC_ACQ_CARLDS (((GC_NCAR * 4 + 15) & ~15) + GC_NCAR * (int)sizeof(GcCarSeg))
-
-struct GcAcqWork {
-    GcDevBuf<GcAcqCar> car;     // [grid][bin]
-    GcDevBuf<int> car_overflow;
-    GcDevBuf<float2> tw16k;     // exp(-2 pi i t/16384), t < 16384
-    GcDevBuf<float2> tw32k;     // exp(-2 pi i t/32768), t < 16384
-    GcDevBuf<float2> tw32p;     // the same twiddles in pass order: exp(-2 pi i freq_of(p)/32768), p < 16384
-    GcDevBuf<float2> tw64p1;    // exp(-2 pi i freq_of(p)/65536) and
-    GcDevBuf<float2> tw64p3;    // exp(-2 pi i 3 freq_of(p)/65536), pass order (the 65536-point path)
-    int L = GC_L;               // transform length of this channel set: 32768, or 65536 when a period exceeds 16384 samples
-    GcDevBuf<float2> X;         // [grid][iter][bin][2][16384]: X[f] and X[f + 16384] at the pass position of f
-                                // (iter, here and below: an iteration of the search, a group of ncoh code periods)
-    GcDevBuf<float2> C;         // [ch][2][16384]
-    GcDevBuf<GcAcqRow> rows;    // [ch][iter][bin]
-    GcDevBuf<int> arrive;       // [ch][iter] workgroups done with the iteration, then [ch] "acquired" flags
-    GcDevBuf<int> iters;        // [ch] iteration limit for acq_corr
-    GcDevBuf<gnsscorr_acqres_t> res;    // [ch]
-    GcDevBuf<double> P;         // one channel's power array (on demand)
-    int ngrid = 0, maxfreq = 0, maxintg = 0;    // maxintg: the largest iteration (group) count, intg / ncoh
-    std::vector<int> grid_chan;         // a representative channel per grid
-    GcDevBuf<int> d_grid_chan;          // device copy of grid_chan
-    GcDevBuf<uint64_t> d_grid_wrpos;    // ring write position seen by each grid
-    GcDevBuf<int> d_list;               // [nch] channels of the last run, then [ngrid] the grids that have one of them
-    std::vector<int> list, glist;       // host copies of what d_list holds
-    std::vector<char> listed;           // [nch] channel was part of the last run
-    bool code_ready = false;
-    uint64_t last_wrpos[2] = {0, 0};
-    bool ran = false;
-};
 
 namespace {
 
@@ -862,24 +824,18 @@ __global__ __launch_bounds__(GC_FFT_THREADS) void pspec_kernel(const float2 *__r
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-void gc_acq_free(gnsscorr_ctx *ctx)
+// The FFT tables and the dynamic LDS sizes of the kernels that read them: once per context, whoever asks first
+int gc_acq_twiddles(gnsscorr_ctx *ctx)
 {
-    delete ctx->acq;
-    ctx->acq = nullptr;
-}
-
-static int acq_tables(gnsscorr_ctx *ctx)
-{
-    if (!ctx->acq) ctx->acq = new GcAcqWork();
-    GcAcqWork *w = ctx->acq;
-    if (w->tw16k) return GNSSCORR_OK;
-    GC_RESERVE(ctx, w->tw32k, GC_LH);
-    GC_RESERVE(ctx, w->tw32p, GC_LH);
-    GC_RESERVE(ctx, w->tw64p1, GC_LH);
-    GC_RESERVE(ctx, w->tw64p3, GC_LH);
-    GC_RESERVE(ctx, w->tw16k, GC_LH);              // last: the test above
-    hipLaunchKernelGGL(tw_init_kernel, dim3(GC_LH / 256), dim3(256), 0, ctx->stream, w->tw16k, w->tw32k, w->tw32p);
-    hipLaunchKernelGGL(tw64_init_kernel, dim3(GC_LH / 256), dim3(256), 0, ctx->stream, w->tw64p1, w->tw64p3);
+    GcFftTables &f = ctx->fft;
+    if (f.ready) return GNSSCORR_OK;
+    GC_RESERVE(ctx, f.tw16k, GC_LH);
+    GC_RESERVE(ctx, f.tw32k, GC_LH);
+    GC_RESERVE(ctx, f.tw32p, GC_LH);
+    GC_RESERVE(ctx, f.tw64p1, GC_LH);
+    GC_RESERVE(ctx, f.tw64p3, GC_LH);
+    hipLaunchKernelGGL(tw_init_kernel, dim3(GC_LH / 256), dim3(256), 0, ctx->stream, f.tw16k, f.tw32k, f.tw32p);
+    hipLaunchKernelGGL(tw64_init_kernel, dim3(GC_LH / 256), dim3(256), 0, ctx->stream, f.tw64p1, f.tw64p3);
     GC_HIP(hipGetLastError());
     {
         const int lds = GC_FFT_LDS + 256;
@@ -893,24 +849,16 @@ static int acq_tables(gnsscorr_ctx *ctx)
         GC_HIP(hipFuncSetAttribute((const void *)fft16k_kernel<+1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         GC_HIP(hipFuncSetAttribute((const void *)pspec_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     }
-    return GNSSCORR_OK;
-}
-
-int gc_acq_twiddles(gnsscorr_ctx *ctx, const float2 **tw16k, const float2 **tw32k)
-{
-    int rc = acq_tables(ctx);
-    if (rc) return rc;
-    *tw16k = ctx->acq->tw16k;
-    *tw32k = ctx->acq->tw32k;
+    f.ready = true;
     return GNSSCORR_OK;
 }
 
 static int acq_prepare(gnsscorr_ctx *ctx)
 {
-    int rc = acq_tables(ctx);
-    if (rc) return rc;
-    GcAcqWork *w = ctx->acq;
-    if (w->C) return GNSSCORR_OK;
+    GC_TRY(gc_acq_twiddles(ctx));
+    const GcFftTables &f = ctx->fft;
+    GcAcq *w = &ctx->acq;
+    if (w->prepared) return GNSSCORR_OK;
     const int nch = ctx->nch;
     w->ngrid = 0; w->maxfreq = 0; w->maxintg = 0;
     w->L = GC_L;
@@ -940,7 +888,7 @@ static int acq_prepare(gnsscorr_ctx *ctx)
                           ctx->stream));
     GC_RESERVE(ctx, w->car, (size_t)w->ngrid * w->maxfreq);
     GC_RESERVE(ctx, w->car_overflow, 1);
-    GC_RESERVE(ctx, w->C, (size_t)nch * w->L);     // last: the test above
+    GC_RESERVE(ctx, w->C, (size_t)nch * w->L);
     GC_HIP(hipMemsetAsync(w->car_overflow, 0, sizeof(int), ctx->stream));
     hipLaunchKernelGGL(acq_nco_kernel, dim3((w->ngrid * w->maxfreq + 63) / 64), dim3(64), 0, ctx->stream, ctx->dchan,
                        w->d_grid_chan, ctx->dfreqs, w->car, w->ngrid, w->maxfreq, w->car_overflow);
@@ -948,23 +896,24 @@ static int acq_prepare(gnsscorr_ctx *ctx)
     {
         GcTimed t(ctx, "acq_code");
         hipLaunchKernelGGL(acq_code_kernel, dim3(nch), dim3(GC_FFT_THREADS), GC_FFT_LDS + 256, ctx->stream,
-                           ctx->dchan, w->tw16k, w->tw32p, w->tw64p1, w->tw64p3, w->C, w->L);
+                           ctx->dchan, f.tw16k, f.tw32p, f.tw64p1, f.tw64p3, w->C, w->L);
     }
     GC_HIP(hipGetLastError());
     int over = 0;
     GC_HIP(hipMemcpyAsync(&over, w->car_overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
-    if (over) {
-        w->C.reset();       // not prepared
+    if (over)       // (not prepared)
         return gc_fail(GNSSCORR_EINVAL, "acquisition: %d Doppler bins need more carrier NCO pieces than the tables hold", over);
-    }
+    w->prepared = true;
     return GNSSCORR_OK;
 }
 
 // acq_corr over the list dlist[0..n) with early stop (Pout null), or the power array of channel pout_ch into Pout
 // (no early stop; always the 512-lane kernel).  GNSSCORR_ACQ_NT=1024: the 1024-lane variant of the 32768-point search.
-static void launch_acq_corr(gnsscorr_ctx *ctx, GcAcqWork *w, double *Pout, int pout_ch, const int *dlist, int n)
+static void launch_acq_corr(gnsscorr_ctx *ctx, double *Pout, int pout_ch, const int *dlist, int n)
 {
+    const GcFftTables &f = ctx->fft;
+    GcAcq *w = &ctx->acq;
     static const int nt = getenv("GNSSCORR_ACQ_NT") ? atoi(getenv("GNSSCORR_ACQ_NT")) : 512;
     const bool pout = Pout != nullptr;
     const int nbins = pout ? ctx->hchan[pout_ch].nfreq : w->maxfreq;
@@ -973,12 +922,12 @@ static void launch_acq_corr(gnsscorr_ctx *ctx, GcAcqWork *w, double *Pout, int p
     auto corr32 = [&](auto nt_tag) {
         constexpr int NT = decltype(nt_tag)::value;
         hipLaunchKernelGGL(acq_corr_kernel<NT>, dim3(acq_corr_blocks(nbins, n, pout)), dim3(NT), GC_ACQ_CORR_LDS,
-                           ctx->stream, ctx->dchan, w->tw16k, w->tw32p, w->X, w->C, w->iters, w->rows, Pout, pout_ch,
+                           ctx->stream, ctx->dchan, f.tw16k, f.tw32p, w->X, w->C, w->iters, w->rows, Pout, pout_ch,
                            w->maxfreq, w->maxintg, dlist, n, arrive, done);
     };
     if (w->L == 2 * GC_L)
         hipLaunchKernelGGL(acq_corr64_kernel, dim3(acq_corr64_blocks(nbins, n, pout)), dim3(512), GC_ACQ_CORR_LDS,
-                           ctx->stream, ctx->dchan, w->tw16k, w->tw32p, w->tw64p1, w->tw64p3, w->X, w->C, w->iters,
+                           ctx->stream, ctx->dchan, f.tw16k, f.tw32p, f.tw64p1, f.tw64p3, w->X, w->C, w->iters,
                            w->rows, Pout, pout_ch, w->maxfreq, w->maxintg, dlist, n);
     else if (nt == 1024 && !pout)
         corr32(std::integral_constant<int, 1024>{});
@@ -1009,7 +958,8 @@ int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chl
     if (rc) return rc;
     rc = gc_ingest_fence(ctx);
     if (rc) return rc;
-    GcAcqWork *w = ctx->acq;
+    const GcFftTables &f = ctx->fft;
+    GcAcq *w = &ctx->acq;
     // the grids that have a listed channel, in grid order
     std::vector<int> glist;
     for (int g = 0; g < w->ngrid; g++) {
@@ -1051,8 +1001,8 @@ int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chl
         GcTimed t(ctx, "acq_fwd");
         auto fwd = coh ? acq_fwd_kernel<true> : acq_fwd_kernel<false>;
         hipLaunchKernelGGL(fwd, dim3(w->maxfreq, w->maxintg, ng), dim3(GC_FFT_THREADS), lds + GC_ACQ_CARLDS,
-                           ctx->stream, ctx->dchan, w->d_grid_chan, dglist, w->car, w->d_grid_wrpos, w->tw16k, w->tw32p,
-                           w->tw64p1, w->tw64p3, w->X, w->maxfreq, w->maxintg, w->L);
+                           ctx->stream, ctx->dchan, w->d_grid_chan, dglist, w->car, w->d_grid_wrpos, f.tw16k, f.tw32p,
+                           f.tw64p1, f.tw64p3, w->X, w->maxfreq, w->maxintg, w->L);
     }
     GC_HIP(hipGetLastError());
     // channels that are not listed: no iterations, a zero result row
@@ -1065,7 +1015,7 @@ int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chl
     GC_HIP(hipMemsetAsync(w->arrive, 0, sizeof(int) * ((size_t)nch * w->maxintg + nch), ctx->stream));
     {
         GcTimed t(ctx, "acq_corr");
-        launch_acq_corr(ctx, w, nullptr, 0, dlist, n);
+        launch_acq_corr(ctx, nullptr, 0, dlist, n);
     }
     GC_HIP(hipGetLastError());
     {
@@ -1095,10 +1045,10 @@ extern "C" int gnsscorr_acq_run_subset(gnsscorr_ctx *ctx, uint64_t wrpos, const 
 
 extern "C" int gnsscorr_acq_fetch(gnsscorr_ctx *ctx, gnsscorr_acqres_t *res)
 {
-    if (!ctx || !ctx->acq || !ctx->acq->ran) return gc_fail(GNSSCORR_ESTATE, "acq_fetch: no acq_run yet");
+    if (!ctx || !ctx->acq.ran) return gc_fail(GNSSCORR_ESTATE, "acq_fetch: no acq_run yet");
     if (!res) return gc_fail(GNSSCORR_EINVAL, "acq_fetch: null result array");
     GC_HIP(hipSetDevice(ctx->device));
-    GC_HIP(hipMemcpyAsync(res, ctx->acq->res, sizeof(gnsscorr_acqres_t) * ctx->nch, hipMemcpyDeviceToHost,
+    GC_HIP(hipMemcpyAsync(res, ctx->acq.res, sizeof(gnsscorr_acqres_t) * ctx->nch, hipMemcpyDeviceToHost,
                           ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
     return GNSSCORR_OK;
@@ -1115,12 +1065,12 @@ __global__ void acq_to_trk_kernel(const GcChan *__restrict__ chan, const gnsscor
 
 extern "C" int gnsscorr_trk_start_from_acq(gnsscorr_ctx *ctx)
 {
-    if (!ctx || !ctx->acq || !ctx->acq->ran) return gc_fail(GNSSCORR_ESTATE, "trk_start_from_acq: no acq_run yet");
+    if (!ctx || !ctx->acq.ran) return gc_fail(GNSSCORR_ESTATE, "trk_start_from_acq: no acq_run yet");
     GC_HIP(hipSetDevice(ctx->device));
     int rc = gc_quiesce(ctx);
     if (rc) return rc;
     hipLaunchKernelGGL(acq_to_trk_kernel, dim3((ctx->nch + 63) / 64), dim3(64), 0, ctx->stream, ctx->dchan,
-                       ctx->acq->res, ctx->state.cur(), ctx->nch);
+                       ctx->acq.res, ctx->state.cur(), ctx->nch);
     GC_HIP(hipGetLastError());
     return GNSSCORR_OK;
 }
@@ -1154,12 +1104,12 @@ __global__ __launch_bounds__(64) void acq_to_loop_kernel(const GcChan *__restric
 
 int gc_acq_handover(gnsscorr_ctx *ctx, bool quiesce)
 {
-    if (!ctx || !ctx->acq || !ctx->acq->ran) return gc_fail(GNSSCORR_ESTATE, "loop_start_from_acq: no acq_run yet");
+    if (!ctx || !ctx->acq.ran) return gc_fail(GNSSCORR_ESTATE, "loop_start_from_acq: no acq_run yet");
     GC_HIP(hipSetDevice(ctx->device));
     if (quiesce) { int rc = gc_quiesce(ctx); if (rc) return rc; }
-    const int n = (int)ctx->acq->list.size();
-    hipLaunchKernelGGL(acq_to_loop_kernel, dim3(n), dim3(64), 0, ctx->stream, ctx->dchan, ctx->acq->res,
-                       ctx->state.cur(), ctx->loop.dloop, ctx->acq->d_list, n);
+    const int n = (int)ctx->acq.list.size();
+    hipLaunchKernelGGL(acq_to_loop_kernel, dim3(n), dim3(64), 0, ctx->stream, ctx->dchan, ctx->acq.res,
+                       ctx->state.cur(), ctx->loop.dloop, ctx->acq.d_list, n);
     GC_HIP(hipGetLastError());
     return GNSSCORR_OK;
 }
@@ -1168,17 +1118,17 @@ extern "C" int gnsscorr_loop_start_from_acq(gnsscorr_ctx *ctx) { return gc_acq_h
 
 extern "C" int gnsscorr_acq_power(gnsscorr_ctx *ctx, int ch, double *power)
 {
-    if (!ctx || !ctx->acq || !ctx->acq->ran) return gc_fail(GNSSCORR_ESTATE, "acq_power: no acq_run yet");
+    if (!ctx || !ctx->acq.ran) return gc_fail(GNSSCORR_ESTATE, "acq_power: no acq_run yet");
     if (ch < 0 || ch >= ctx->nch || !power) return gc_fail(GNSSCORR_EINVAL, "acq_power: channel %d", ch);
-    if (!ctx->acq->listed[ch]) return gc_fail(GNSSCORR_ESTATE, "acq_power: channel %d was not part of the last search", ch);
+    if (!ctx->acq.listed[ch]) return gc_fail(GNSSCORR_ESTATE, "acq_power: channel %d was not part of the last search", ch);
     GC_HIP(hipSetDevice(ctx->device));
-    GcAcqWork *w = ctx->acq;
+    GcAcq *w = &ctx->acq;
     const GcChan &c = ctx->hchan[ch];
     const size_t elems = (size_t)c.nfreq * c.nsamp;
     GC_RESERVE(ctx, w->P, elems);
     // iteration count of the last run is still in w->iters[ch]; rows of this channel are rewritten
     // with identical values
-    launch_acq_corr(ctx, w, w->P, ch, nullptr, 0);
+    launch_acq_corr(ctx, w->P, ch, nullptr, 0);
     GC_HIP(hipGetLastError());
     GC_HIP(hipMemcpyAsync(power, w->P, sizeof(double) * elems, hipMemcpyDeviceToHost, ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
@@ -1189,16 +1139,15 @@ extern "C" int gnsscorr_fft16k(gnsscorr_ctx *ctx, const void *in, void *out, int
 {
     if (!ctx || !in || !out || batch <= 0) return gc_fail(GNSSCORR_EINVAL, "fft16k: bad arguments");
     GC_HIP(hipSetDevice(ctx->device));
-    int rc = acq_tables(ctx);
-    if (rc) return rc;
-    GcAcqWork *w = ctx->acq;
+    GC_TRY(gc_acq_twiddles(ctx));
+    const GcFftTables &f = ctx->fft;
     GcTimed t(ctx, "fft16k");
     if (sign < 0)
         hipLaunchKernelGGL(fft16k_kernel<-1>, dim3(batch), dim3(GC_FFT_THREADS), GC_FFT_LDS + 256, ctx->stream,
-                           (const float2 *)in, (float2 *)out, w->tw16k);
+                           (const float2 *)in, (float2 *)out, f.tw16k);
     else
         hipLaunchKernelGGL(fft16k_kernel<+1>, dim3(batch), dim3(GC_FFT_THREADS), GC_FFT_LDS + 256, ctx->stream,
-                           (const float2 *)in, (float2 *)out, w->tw16k);
+                           (const float2 *)in, (float2 *)out, f.tw16k);
     GC_HIP(hipGetLastError());
     return GNSSCORR_OK;
 }
@@ -1208,9 +1157,8 @@ extern "C" int gnsscorr_pspec(gnsscorr_ctx *ctx, const float *cpx, int n, int fl
     if (!ctx || !cpx || !pspec) return gc_fail(GNSSCORR_EINVAL, "pspec: bad arguments");
     if (n != GC_LH && n != GC_L) return gc_fail(GNSSCORR_EINVAL, "pspec: n %d (16384 or 32768 supported)", n);
     GC_HIP(hipSetDevice(ctx->device));
-    int rc = acq_tables(ctx);
-    if (rc) return rc;
-    GcAcqWork *w = ctx->acq;
+    GC_TRY(gc_acq_twiddles(ctx));
+    const GcFftTables &f = ctx->fft;
     GcDevBuf<float2> din;
     GcDevBuf<double> dps;
     GC_RESERVE(ctx, din, n);
@@ -1218,7 +1166,7 @@ extern "C" int gnsscorr_pspec(gnsscorr_ctx *ctx, const float *cpx, int n, int fl
     hipMemcpyAsync(din, cpx, sizeof(float2) * n, hipMemcpyHostToDevice, ctx->stream);
     if (flagsum) hipMemcpyAsync(dps, pspec, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream);
     hipLaunchKernelGGL(pspec_kernel, dim3(1), dim3(GC_FFT_THREADS), GC_FFT_LDS + 256, ctx->stream, din, n,
-                       w->tw16k, w->tw32k, dps, flagsum);
+                       f.tw16k, f.tw32k, dps, flagsum);
     hipError_t e = hipGetLastError();
     hipMemcpyAsync(pspec, dps, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream);
     hipError_t e2 = hipStreamSynchronize(ctx->stream);

@@ -1,5 +1,7 @@
-// gnsscorr_api.hip -- C-ABI layer of libgnsscorr.so: context, IF ring in HBM,
-// channel tables, per-kernel timing, the default context.
+// gnsscorr_api.hip -- C-ABI layer of libgnsscorr.so: context, IF ring in HBM and
+// its ingest, channel tables, per-kernel timing, the default context.  The context
+// owns every buffer, stream and event by type (gnsscorr_ctx.h): creating it makes
+// the handles the trackers need, destroying it is `delete`.
 // (The batched tracker's entry points live in gnsscorr_trk.hip, acquisition's in
 // gnsscorr_acq.hip, the closed loop's in gnsscorr_loop.hip, the reference-named
 // per-call symbols in gnsscorr_compat.hip.)
@@ -37,21 +39,17 @@ extern "C" int gnsscorr_device_count(void)
     return n;
 }
 
-// every stream and event of the context (of a failed create: those made so far)
-static void destroy_handles(gnsscorr_ctx *ctx)
+// the streams and events every context has from the start (the ingest's and the lock monitor's are made on first use)
+static int create_handles(gnsscorr_ctx *ctx, hipStream_t stream)
 {
-    for (auto &kv : ctx->timers)
-        for (auto &p : kv.second.pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-    for (int i = 0; i < 2; i++)
-        for (hipEvent_t e : {ctx->ev_plan[i], ctx->ev_used[i], ctx->ev_corr[i], ctx->ev_fin[i]})
-            if (e) hipEventDestroy(e);
-    for (hipEvent_t e : {ctx->ev_spec, ctx->ev_chain, ctx->ev_pin[0], ctx->ev_pin[1], ctx->ev_in, ctx->ev_lock})
-        if (e) hipEventDestroy(e);
-    for (hipEvent_t e : ctx->ev_burst)
-        if (e) hipEventDestroy(e);
-    for (hipStream_t s : {ctx->stream_plan, ctx->stream_finish, ctx->stream_discover, ctx->stream_in})
-        if (s) hipStreamDestroy(s);
-    if (ctx->own_stream) hipStreamDestroy(ctx->stream);
+    if (stream) ctx->stream.borrow(stream);
+    else GC_TRY(ctx->stream.make());
+    for (GcStream *s : {&ctx->stream_plan, &ctx->stream_finish, &ctx->stream_discover}) GC_TRY(s->make());
+    for (GcEvent *ev : {&ctx->ev_spec, &ctx->ev_chain}) GC_TRY(ev->make());
+    for (GcEvent *ev : {ctx->ev_plan, ctx->ev_used, ctx->ev_corr, ctx->ev_fin})
+        for (int i = 0; i < 2; i++) GC_TRY(ev[i].make());
+    for (GcEvent &ev : ctx->ev_burst) GC_TRY(ev.make());
+    return GNSSCORR_OK;
 }
 
 extern "C" int gnsscorr_create(gnsscorr_ctx **out, int device, void *stream)
@@ -64,24 +62,10 @@ extern "C" int gnsscorr_create(gnsscorr_ctx **out, int device, void *stream)
     GC_HIP(hipSetDevice(device));
     gnsscorr_ctx *ctx = new gnsscorr_ctx();
     ctx->device = device;
-    hipError_t e = hipSuccess;
-    if (stream) {
-        ctx->stream = (hipStream_t)stream;
-    } else {
-        e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-        ctx->own_stream = e == hipSuccess;
-    }
-    for (hipStream_t *s : {&ctx->stream_plan, &ctx->stream_finish, &ctx->stream_discover})
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(s, hipStreamNonBlocking);
-    for (hipEvent_t *ev : {&ctx->ev_spec, &ctx->ev_chain, &ctx->ev_plan[0], &ctx->ev_used[0], &ctx->ev_corr[0], &ctx->ev_fin[0],
-                           &ctx->ev_plan[1], &ctx->ev_used[1], &ctx->ev_corr[1], &ctx->ev_fin[1]})
-        if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
-    for (hipEvent_t &ev : ctx->ev_burst)
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        destroy_handles(ctx);
-        delete ctx;
-        return gc_fail_hip(e, "gnsscorr_create: stream / event", __FILE__, __LINE__);
+    int rc = create_handles(ctx, (hipStream_t)stream);
+    if (rc) {
+        delete ctx;                        // with the handles made so far
+        return rc;
     }
     *out = ctx;
     return GNSSCORR_OK;
@@ -90,8 +74,8 @@ extern "C" int gnsscorr_create(gnsscorr_ctx **out, int device, void *stream)
 // the channel set's device buffers; the next set starts from nothing
 static void drop_channel_buffers(gnsscorr_ctx *ctx)
 {
-    gc_acq_free(ctx);
-    gc_spec_free(ctx);
+    ctx->acq = GcAcq();
+    ctx->spec = GcSpec();
     ctx->dchan.reset(); ctx->dcodes.reset(); ctx->dfreqs.reset();
     ctx->state = GcTrkStateBuf();
     ctx->batch = GcBatch();
@@ -106,10 +90,7 @@ extern "C" void gnsscorr_destroy(gnsscorr_ctx *ctx)
     if (!ctx) return;
     hipSetDevice(ctx->device);
     gc_quiesce(ctx, true);
-    gc_acq_free(ctx);
-    gc_spec_free(ctx);
-    destroy_handles(ctx);
-    delete ctx;                        // the buffers it owns go with it
+    delete ctx;                        // the buffers, streams and events it owns go with it
 }
 
 extern "C" void *gnsscorr_stream(gnsscorr_ctx *ctx) { return ctx ? (void *)ctx->stream : nullptr; }
@@ -149,7 +130,7 @@ extern "C" int gnsscorr_ring_create(gnsscorr_ctx *ctx, int ftype, int dtype, uin
     {
         std::lock_guard<std::mutex> lk(ctx->mtx);
         // transfers into the old ring (ingest stream) and kernels reading it (compute stream) are over before it goes
-        if (ctx->stream_in) GC_HIP(hipStreamSynchronize(ctx->stream_in));
+        if (ctx->in.stream) GC_HIP(hipStreamSynchronize(ctx->in.stream));
         GC_HIP(hipStreamSynchronize(ctx->stream));
         r->own.reset();
         r->mem = nullptr;
@@ -174,27 +155,30 @@ extern "C" int gnsscorr_ring_create(gnsscorr_ctx *ctx, int ftype, int dtype, uin
 // ---- ingest ----------------------------------------------------------------------------------------------
 #define GC_PIN_BYTES (8u << 20)         // per staging buffer
 
+// every step keeps what an earlier call made: a failed init is completed by the next call
 static int ingest_init(gnsscorr_ctx *ctx)
 {
-    if (ctx->ev_in) return GNSSCORR_OK;           // made last (a failed init is completed by the next call)
-    if (!ctx->stream_in) GC_HIP(hipStreamCreateWithFlags(&ctx->stream_in, hipStreamNonBlocking));
+    GcIngest &in = ctx->in;
+    if (in.ready) return GNSSCORR_OK;
+    GC_TRY(in.stream.make());
     for (int i = 0; i < 2; i++) {
-        int rc = ctx->pin[i].reserve(GC_PIN_BYTES);
-        if (rc) return rc;
-        GC_RESERVE(ctx, ctx->dstage[i], GC_PIN_BYTES);
-        if (!ctx->ev_pin[i]) GC_HIP(hipEventCreateWithFlags(&ctx->ev_pin[i], hipEventDisableTiming));
+        GC_TRY(in.pin[i].reserve(GC_PIN_BYTES));
+        GC_RESERVE(ctx, in.dstage[i], GC_PIN_BYTES);
+        GC_TRY(in.ev_pin[i].make());
     }
-    GC_HIP(hipEventCreateWithFlags(&ctx->ev_in, hipEventDisableTiming));
+    GC_TRY(in.ev_in.make());
+    in.ready = true;
     return GNSSCORR_OK;
 }
 
 // a free staging slot (waits for the transfer that last used it, never for the compute stream)
 static int ingest_slot(gnsscorr_ctx *ctx, int *slot)
 {
-    const int s = ctx->pin_next;
-    ctx->pin_next ^= 1;
-    if (ctx->pin_busy[s]) GC_HIP(hipEventSynchronize(ctx->ev_pin[s]));
-    ctx->pin_busy[s] = false;
+    GcIngest &in = ctx->in;
+    const int s = in.pin_next;
+    in.pin_next ^= 1;
+    if (in.pin_busy[s]) GC_HIP(hipEventSynchronize(in.ev_pin[s]));
+    in.pin_busy[s] = false;
     *slot = s;
     return GNSSCORR_OK;
 }
@@ -202,7 +186,7 @@ static int ingest_slot(gnsscorr_ctx *ctx, int *slot)
 // the compute stream reads the ring: order it behind the last transfer
 int gc_ingest_fence(gnsscorr_ctx *ctx)
 {
-    if (ctx->in_pending) GC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_in, 0));
+    if (ctx->in.in_pending) GC_HIP(hipStreamWaitEvent(ctx->stream, ctx->in.ev_in, 0));
     return GNSSCORR_OK;
 }
 
@@ -220,8 +204,8 @@ static int ring_write(gnsscorr_ctx *ctx, GcRing *r, uint64_t bytepos, const void
     const uint64_t rb = (uint64_t)r->dtype * r->ringlen;
     const uint64_t pos = bytepos % rb;
     const uint64_t first = pos + bytes <= rb ? bytes : rb - pos;
-    GC_HIP(hipMemcpyAsync(r->mem + pos, src, first, kind, ctx->stream_in));
-    if (first < bytes) GC_HIP(hipMemcpyAsync(r->mem, (const int8_t *)src + first, bytes - first, kind, ctx->stream_in));
+    GC_HIP(hipMemcpyAsync(r->mem + pos, src, first, kind, ctx->in.stream));
+    if (first < bytes) GC_HIP(hipMemcpyAsync(r->mem, (const int8_t *)src + first, bytes - first, kind, ctx->in.stream));
     return GNSSCORR_OK;
 }
 
@@ -243,15 +227,15 @@ extern "C" int gnsscorr_ring_push(gnsscorr_ctx *ctx, int ftype, const void *host
         int s;
         rc = ingest_slot(ctx, &s);
         if (rc) return rc;
-        memcpy(ctx->pin[s], h + done, piece);           // the caller's buffer is free again after this
-        rc = ring_write(ctx, r, d * r->wrpos + done, ctx->pin[s], piece, hipMemcpyHostToDevice);
+        memcpy(ctx->in.pin[s], h + done, piece);        // the caller's buffer is free again after this
+        rc = ring_write(ctx, r, d * r->wrpos + done, ctx->in.pin[s], piece, hipMemcpyHostToDevice);
         if (rc) return rc;
-        GC_HIP(hipEventRecord(ctx->ev_pin[s], ctx->stream_in));
-        ctx->pin_busy[s] = true;
+        GC_HIP(hipEventRecord(ctx->in.ev_pin[s], ctx->in.stream));
+        ctx->in.pin_busy[s] = true;
         done += piece;
     }
-    GC_HIP(hipEventRecord(ctx->ev_in, ctx->stream_in));
-    ctx->in_pending = true;
+    GC_HIP(hipEventRecord(ctx->in.ev_in, ctx->in.stream));
+    ctx->in.in_pending = true;
     r->wrpos += nsamp;
     return GNSSCORR_OK;
 }
@@ -311,23 +295,23 @@ extern "C" int gnsscorr_ring_push_packed(gnsscorr_ctx *ctx, int format, const vo
         int s;
         rc = ingest_slot(ctx, &s);
         if (rc) return rc;
-        memcpy(ctx->pin[s], h + done, piece);
-        GC_HIP(hipMemcpyAsync(ctx->dstage[s], ctx->pin[s], piece, hipMemcpyHostToDevice, ctx->stream_in));
+        memcpy(ctx->in.pin[s], h + done, piece);
+        GC_HIP(hipMemcpyAsync(ctx->in.dstage[s], ctx->in.pin[s], piece, hipMemcpyHostToDevice, ctx->in.stream));
         const unsigned blocks = (unsigned)((piece + 255) / 256);
         if (format == GNSSCORR_FMT_STEREO)
-            hipLaunchKernelGGL(unpack_stereo_kernel, dim3(blocks), dim3(256), 0, ctx->stream_in, ctx->dstage[s], piece,
+            hipLaunchKernelGGL(unpack_stereo_kernel, dim3(blocks), dim3(256), 0, ctx->in.stream, ctx->in.dstage[s], piece,
                                r1->mem, r1->mem ? r1->ringlen : 1, r1->wrpos + done, r2->mem, r2->mem ? r2->ringlen : 1,
                                r2->wrpos + done);
         else
-            hipLaunchKernelGGL(unpack_rtlsdr_kernel, dim3(blocks), dim3(256), 0, ctx->stream_in, ctx->dstage[s], piece,
+            hipLaunchKernelGGL(unpack_rtlsdr_kernel, dim3(blocks), dim3(256), 0, ctx->in.stream, ctx->in.dstage[s], piece,
                                r1->mem, 2 * r1->ringlen, 2 * r1->wrpos + done);
         GC_HIP(hipGetLastError());
-        GC_HIP(hipEventRecord(ctx->ev_pin[s], ctx->stream_in));
-        ctx->pin_busy[s] = true;
+        GC_HIP(hipEventRecord(ctx->in.ev_pin[s], ctx->in.stream));
+        ctx->in.pin_busy[s] = true;
         done += piece;
     }
-    GC_HIP(hipEventRecord(ctx->ev_in, ctx->stream_in));
-    ctx->in_pending = true;
+    GC_HIP(hipEventRecord(ctx->in.ev_in, ctx->in.stream));
+    ctx->in.in_pending = true;
     if (format == GNSSCORR_FMT_STEREO) {
         if (r1->mem) r1->wrpos += nsamp;
         if (r2->mem) r2->wrpos += nsamp;
@@ -344,7 +328,7 @@ extern "C" int gnsscorr_ring_read(gnsscorr_ctx *ctx, int ftype, uint64_t buffloc
     if (n <= 0 || (uint64_t)n > r->ringlen || !host) return gc_fail(GNSSCORR_EINVAL, "ring_read: n %d", n);
     GC_HIP(hipSetDevice(ctx->device));
     std::lock_guard<std::mutex> lk(ctx->mtx);
-    if (ctx->in_pending) GC_HIP(hipEventSynchronize(ctx->ev_in));
+    if (ctx->in.in_pending) GC_HIP(hipEventSynchronize(ctx->in.ev_in));
     GC_HIP(hipStreamSynchronize(ctx->stream));
     // ref src/sdrrcv.c:508-521
     const uint64_t d = (uint64_t)r->dtype, rb = d * r->ringlen, pos = (d * buffloc) % rb, nb = d * (uint64_t)n;
@@ -539,7 +523,7 @@ extern "C" int gnsscorr_acq_set_coherent(gnsscorr_ctx *ctx, int ch0, int nch, co
     if (rc) return rc;
     for (int i = 0; i < nch; i++) ctx->hchan[ch0 + i].ncoh = ncoh[i];
     assign_acq_grids(ctx);
-    gc_acq_free(ctx);
+    ctx->acq = GcAcq();
     return upload_channels(ctx);
 }
 
@@ -589,8 +573,6 @@ static void drain_timers(gnsscorr_ctx *ctx)
                 kv.second.total_ms += ms;
                 kv.second.launches++;
             }
-            hipEventDestroy(p.first);
-            hipEventDestroy(p.second);
         }
         kv.second.pending.clear();
     }

@@ -1,9 +1,11 @@
-// gnsscorr_ctx.h -- host-side context object behind the opaque gnsscorr_ctx.
+// gnsscorr_ctx.h -- host-side context object behind the opaque gnsscorr_ctx, and the move-only types it owns its
+// resources by: GcDevBuf / GcPinBuf (memory), GcEvent / GcStream (handles).  Deleting the context releases all of them.
 #pragma once
 
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -84,6 +86,67 @@ struct GcPinBuf {
     } while (0)
 #define GC_RESERVE(ctx, buf, elems) GC_TRY((buf).reserve((ctx), (elems)))
 
+// Owning event (hipEventCreateWithFlags / hipEventDestroy), move-only.  make() keeps an event it already has.
+struct GcEvent {
+    hipEvent_t e = nullptr;
+    GcEvent() = default;
+    GcEvent(GcEvent &&o) noexcept : e(o.e) { o.e = nullptr; }
+    GcEvent &operator=(GcEvent &&o) noexcept
+    {
+        if (this != &o) { reset(); e = o.e; o.e = nullptr; }
+        return *this;
+    }
+    ~GcEvent() { reset(); }
+    void reset()
+    {
+        if (e) hipEventDestroy(e);
+        e = nullptr;
+    }
+    int make(unsigned flags = hipEventDisableTiming)
+    {
+        if (!e) GC_HIP(hipEventCreateWithFlags(&e, flags));
+        return 0;
+    }
+    operator hipEvent_t() const { return e; }
+};
+
+// A stream, move-only: its own non-blocking one (make(), destroyed with it; keeps a stream it already has) or the
+// caller's (borrow(), never destroyed).
+struct GcStream {
+    hipStream_t s = nullptr;
+    bool own = false;
+    GcStream() = default;
+    GcStream(GcStream &&o) noexcept : s(o.s), own(o.own) { o.s = nullptr; o.own = false; }
+    GcStream &operator=(GcStream &&o) noexcept
+    {
+        if (this != &o) { reset(); s = o.s; own = o.own; o.s = nullptr; o.own = false; }
+        return *this;
+    }
+    ~GcStream() { reset(); }
+    void reset()
+    {
+        if (own) hipStreamDestroy(s);
+        s = nullptr;
+        own = false;
+    }
+    int make()
+    {
+        if (s) return 0;
+        GC_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        own = true;
+        return 0;
+    }
+    void borrow(hipStream_t callers)
+    {
+        reset();
+        s = callers;
+    }
+    operator hipStream_t() const { return s; }
+};
+
+static_assert(!std::is_copy_constructible<GcEvent>::value && !std::is_copy_assignable<GcEvent>::value, "GcEvent owns its event");
+static_assert(!std::is_copy_constructible<GcStream>::value && !std::is_copy_assignable<GcStream>::value, "GcStream owns its stream");
+
 struct GcRing {
     int8_t  *mem = nullptr;   // own, or the caller's buffer
     GcDevBuf<int8_t> own;
@@ -93,13 +156,24 @@ struct GcRing {
 };
 
 struct GcTimer {
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+    std::vector<std::pair<GcEvent, GcEvent>> pending;   // launches whose times are still to be read
     double total_ms = 0.0;
     int launches = 0;
 };
 
-struct GcAcqWork;   // gnsscorr_acq.hip
-struct GcSpecWork;  // gnsscorr_spec.hip
+// Ingest (gnsscorr_ring_push*, gnsscorr_api.hip): the copy stream, two pinned staging buffers (and device staging for
+// the packed formats).  Made on the first push, for the context's lifetime.
+struct GcIngest {
+    GcStream stream;
+    GcPinBuf<int8_t> pin[2];
+    GcDevBuf<uint8_t> dstage[2];
+    GcEvent ev_pin[2];                             // the transfer that last used the staging slot
+    bool pin_busy[2] = {false, false};
+    int pin_next = 0;
+    GcEvent ev_in;                                 // the last transfer: the compute stream waits on it before it reads the ring
+    bool in_pending = false;
+    bool ready = false;                            // everything above is made (a failed init is completed by the next call)
+};
 
 // The committed tracking state, ping-pong: a batch's planner chains cur() into next() and the batch commits it once every
 // launch is issued; the closed loop, both hand-overs and trk_set/get_state work on cur() in place
@@ -198,24 +272,76 @@ struct GcRx {
     GcPinBuf<unsigned> lock_lost;                  // mapped: [nch] 1: the launch declared the channel lost (kernel writes)
 };
 
+// The FFT twiddle tables (gc_acq_twiddles, gnsscorr_acq.hip), made once per context on first use: they depend on nothing
+// the caller configures.  Acquisition, gnsscorr_fft16k, gnsscorr_pspec and the IF monitor read them.
+struct GcFftTables {
+    GcDevBuf<float2> tw16k;     // exp(-2 pi i t/16384), t < 16384
+    GcDevBuf<float2> tw32k;     // exp(-2 pi i t/32768), t < 16384
+    GcDevBuf<float2> tw32p;     // the same twiddles in pass order: exp(-2 pi i freq_of(p)/32768), p < 16384
+    GcDevBuf<float2> tw64p1;    // exp(-2 pi i freq_of(p)/65536) and
+    GcDevBuf<float2> tw64p3;    // exp(-2 pi i 3 freq_of(p)/65536), pass order (the 65536-point path)
+    bool ready = false;         // the tables' init kernels are queued on the main stream, the kernels' LDS sizes are set
+};
+
+// Carrier NCO of one Doppler bin over the (ncoh + 1)*nsamp samples of a group (ncoh = 1: the 2*nsamp acquisition
+// window), phase 0 at its first sample (ref src/sdrcmn.c:761): the reference's running sum as a piece table
+// (gnsscorr_nco.h)
+struct GcAcqCar {
+    int n, pad;
+    int k0[GC_NCAR];
+    GcCarSeg seg[GC_NCAR];
+};
+
+// Acquisition (gnsscorr_acq.hip): what depends on the channel set and its coherent setting
+struct GcAcq {
+    bool prepared = false;      // acq_prepare has sized the buffers below and queued the carrier tables and code spectra
+    GcDevBuf<GcAcqCar> car;     // [grid][bin]
+    GcDevBuf<int> car_overflow;
+    int L = 32768;              // transform length of this channel set: 32768, or 65536 when a period exceeds 16384 samples
+    GcDevBuf<float2> X;         // [grid][iter][bin][2][16384]: X[f] and X[f + 16384] at the pass position of f
+                                // (iter, here and below: an iteration of the search, a group of ncoh code periods)
+    GcDevBuf<float2> C;         // [ch][2][16384]
+    GcDevBuf<GcAcqRow> rows;    // [ch][iter][bin]
+    GcDevBuf<int> arrive;       // [ch][iter] workgroups done with the iteration, then [ch] "acquired" flags
+    GcDevBuf<int> iters;        // [ch] iteration limit for acq_corr
+    GcDevBuf<gnsscorr_acqres_t> res;    // [ch]
+    GcDevBuf<double> P;         // one channel's power array (on demand)
+    int ngrid = 0, maxfreq = 0, maxintg = 0;    // maxintg: the largest iteration (group) count, intg / ncoh
+    std::vector<int> grid_chan;         // a representative channel per grid
+    GcDevBuf<int> d_grid_chan;          // device copy of grid_chan
+    GcDevBuf<uint64_t> d_grid_wrpos;    // ring write position seen by each grid
+    GcDevBuf<int> d_list;               // [nch] channels of the last run, then [ngrid] the grids that have one of them
+    std::vector<int> list, glist;       // host copies of what d_list holds
+    std::vector<char> listed;           // [nch] channel was part of the last run
+    bool ran = false;                   // a search has been queued: there are results to fetch
+};
+
+// IF monitor (gnsscorr_spec.hip): scratch and the shape of the last run
+struct GcSpec {
+    GcDevBuf<float> psd;        // [nsnap][nloop][2*nfft] fp32 power per segment
+    GcDevBuf<double> sum;       // [nsnap][2*nfft]
+    GcDevBuf<unsigned> hist;    // [nsnap][2][GC_SPEC_HIST]
+    GcDevBuf<int> maxd;         // [nsnap]
+    GcDevBuf<float> win;        // Hann window of the last nfft (hanning(nfft/2), computed on the host)
+    int win_n = 0;
+    GcDevBuf<uint64_t> loc;     // [nsnap] first sample of each snapshot
+    GcDevBuf<int> off;          // [nsnap][nloop] segment offsets
+    GcDevBuf<int8_t> stage;     // the drop-in's copy of the caller's samples
+    std::vector<uint64_t> hloc;
+    std::vector<int> hoff;
+    // the last run, for fetch
+    bool ran = false, has_hist = false;
+    int nsnap = 0, nfft = 0, nloop = 0, dtype = 0;
+    double f_sf = 0.0;
+};
+
 struct gnsscorr_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    GcStream stream;                               // the caller's, or the context's own
     std::mutex mtx;
 
     GcRing ring[2];
-
-    // ingest: copy stream + two pinned staging buffers (and device staging for packed formats); ev_in marks
-    // the last transfer, the compute stream waits on it before it reads the ring
-    hipStream_t stream_in = nullptr;
-    GcPinBuf<int8_t> pin[2];
-    GcDevBuf<uint8_t> dstage[2];
-    hipEvent_t ev_pin[2] = {nullptr, nullptr};
-    bool pin_busy[2] = {false, false};
-    int pin_next = 0;
-    hipEvent_t ev_in = nullptr;
-    bool in_pending = false;
+    GcIngest in;
 
     // channels
     int nch = 0;
@@ -231,29 +357,30 @@ struct gnsscorr_ctx {
     bool have_dtype[3] = {false, false, false};    // [dtype] some channel reads a ring of that dtype
 
     // tracking: the committed state, the batched tracker, the closed loop, the outputs of both.  The helper streams
-    // and every event exist for the context's lifetime; the structs hold none and are replaced whole per channel set.
-    hipStream_t stream_plan = nullptr;             // planner: the sequential chain (and the direct discovery)
-    hipStream_t stream_finish = nullptr;           // finish: partial sums -> outputs
-    hipStream_t stream_discover = nullptr;         // discovery of the next batch's claims, beside the chain
-    hipEvent_t ev_plan[2] = {};                    // per plan slot: plan finished (planner stream)
-    hipEvent_t ev_used[2] = {};                    // the main stream is done with what the slot held before: the planner may write it
-    hipEvent_t ev_corr[2] = {};                    // correlator finished (main stream): slot consumed, partials ready
-    hipEvent_t ev_fin[2] = {};                     // finish done (finish stream): outputs valid
-    hipEvent_t ev_spec = nullptr, ev_chain = nullptr;
+    // and their events are made by gnsscorr_create and live as long as the context; the structs hold no handle and are
+    // replaced whole per channel set.
+    GcStream stream_plan;                          // planner: the sequential chain (and the direct discovery)
+    GcStream stream_finish;                        // finish: partial sums -> outputs
+    GcStream stream_discover;                      // discovery of the next batch's claims, beside the chain
+    GcEvent ev_plan[2];                            // per plan slot: plan finished (planner stream)
+    GcEvent ev_used[2];                            // the main stream is done with what the slot held before: the planner may write it
+    GcEvent ev_corr[2];                            // correlator finished (main stream): slot consumed, partials ready
+    GcEvent ev_fin[2];                             // finish done (finish stream): outputs valid
+    GcEvent ev_spec, ev_chain;
     GcTrkStateBuf state;
     GcBatch batch;
     GcTrkOut out;
     GcLoop loop;
-    hipEvent_t ev_burst[GC_LOOP_AHEAD] = {};       // gc_trk_run_loop: the ends of the launch bursts in flight
+    GcEvent ev_burst[GC_LOOP_AHEAD];               // gc_trk_run_loop: the ends of the launch bursts in flight
     GcRx rx;
-    hipEvent_t ev_lock = nullptr;                  // end of the last lock monitor launch (made on first use)
+    GcEvent ev_lock;                               // end of the last lock monitor launch (made on first use)
     bool lock_pending = false;                     // ev_lock is recorded and rx.lock_lost not read yet
 
-    // acquisition
-    GcAcqWork *acq = nullptr;
-
-    // IF monitor (spectrum / histogram) scratch
-    GcSpecWork *spec = nullptr;
+    // FFT tables (context lifetime); acquisition and the IF monitor (replaced whole per channel set, acquisition also
+    // per coherent setting)
+    GcFftTables fft;
+    GcAcq acq;
+    GcSpec spec;
 
     // FEC (gnsscorr_fec.hip): staging of gnsscorr_fec_run's symbol streams and packed rows
     GcDevBuf<signed char> dfec_sym;                // [nch][nsym]
@@ -274,26 +401,24 @@ struct gnsscorr_ctx {
 // RAII helper: brackets one kernel launch with HIP events when timing is on.
 struct GcTimed {
     gnsscorr_ctx *ctx;
-    hipEvent_t a = nullptr, b = nullptr;
+    GcEvent a, b;
     const char *name;
     hipStream_t st;
     GcTimed(gnsscorr_ctx *c, const char *n, hipStream_t s = nullptr) : ctx(c), name(n), st(s ? s : c->stream)
     {
         if (!ctx->timing) return;
         if (ctx->timing == 2 && strcmp(n, "trk_corr") != 0 && strcmp(n, "acq_corr") != 0) return;
-        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
+        if (a.make(hipEventDefault) || b.make(hipEventDefault)) { a.reset(); return; }     // (timing-enabled events)
         hipEventRecord(a, st);
     }
     ~GcTimed()
     {
         if (!a) return;
         hipEventRecord(b, st);
-        ctx->timers[name].pending.emplace_back(a, b);
+        ctx->timers[name].pending.emplace_back(std::move(a), std::move(b));
     }
 };
 
-void gc_acq_free(gnsscorr_ctx *ctx);
-void gc_spec_free(gnsscorr_ctx *ctx);
 // gnsscorr_trk.hip.  gc_drain: the planner, finish, discovery and main streams are idle afterwards.  gc_quiesce: that
 // (and the ingest stream when `ingest`), then drops the look-ahead plan and marks the state touched
 int gc_drain(gnsscorr_ctx *ctx);
@@ -302,8 +427,8 @@ int gc_quiesce(gnsscorr_ctx *ctx, bool ingest = false);
 int gc_ensure_trk_outputs(gnsscorr_ctx *ctx, int nperiod);
 int gc_outputs_ready(gnsscorr_ctx *ctx);
 int gc_nco_check(gnsscorr_ctx *ctx);
-// the acquisition's forward twiddle tables (made on first use): exp(-2 pi i t/16384), exp(-2 pi i t/32768), t < 16384
-int gc_acq_twiddles(gnsscorr_ctx *ctx, const float2 **tw16k, const float2 **tw32k);
+// gnsscorr_acq.hip: makes ctx->fft on first use (tables, and the dynamic LDS sizes of the kernels that read them)
+int gc_acq_twiddles(gnsscorr_ctx *ctx);
 int gc_ingest_fence(gnsscorr_ctx *ctx);      // orders the compute stream behind the last ring transfer
 // both rings' write positions and the ingest fence together, under the lock (a grabber thread may be pushing): the
 // positions cover only samples whose transfer the compute stream is ordered behind

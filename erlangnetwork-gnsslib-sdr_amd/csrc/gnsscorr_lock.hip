@@ -285,7 +285,7 @@ extern "C" int gnsscorr_rx_lock_set(gnsscorr_ctx *ctx, int ch0, int nch, const g
     GC_RESERVE(ctx, rx.dlock, ctx->nch);
     { int rc = rx.lock_list.reserve(ctx->nch, hipHostMallocMapped); if (rc) return rc; }
     { int rc = rx.lock_lost.reserve(ctx->nch, hipHostMallocMapped); if (rc) return rc; }
-    if (!ctx->ev_lock) GC_HIP(hipEventCreateWithFlags(&ctx->ev_lock, hipEventDisableTiming));
+    GC_TRY(ctx->ev_lock.make());
     for (int i = 0; i < nch; i++) rx.lockprm[ch0 + i] = p;
     rx.lock_on = 0;
     for (int i = 0; i < ctx->nch; i++) rx.lock_on += rx.lockprm[i].kbits != 0;

@@ -1084,7 +1084,7 @@ extern "C" int gnsscorr_loop_get(gnsscorr_ctx *ctx, int ch0, int nch, gnsscorr_l
 static int ensure_step_buffers(gnsscorr_ctx *ctx)
 {
     GcLoop &L = ctx->loop;
-    if (L.dstep_meta) return GNSSCORR_OK;
+    if (L.step_nseg) return GNSSCORR_OK;           // set once every buffer below has its size
     int nseg = 1;
     for (int i = 0; i < ctx->nch; i++) {
         const int s = step_nseg(ctx->hchan[i].dtype, ctx->max_n);
@@ -1099,7 +1099,7 @@ static int ensure_step_buffers(gnsscorr_ctx *ctx)
     GC_RESERVE(ctx, L.dlapped, 1);
     int rc = L.hostflags.reserve(16, hipHostMallocMapped);
     if (rc) return rc;
-    GC_RESERVE(ctx, L.dstep_meta, ctx->nch);                   // last: the test above
+    GC_RESERVE(ctx, L.dstep_meta, ctx->nch);
     L.step_nseg = nseg;
     return GNSSCORR_OK;
 }

@@ -608,7 +608,7 @@ uint64_t sdracquisition(sdrch_t *sdr, double *power)
     gnsscorr_ctx *def = gnsscorr_default_ctx();
     if (def) {      // the private engine shares the default context's ring: its last block must have landed
         std::lock_guard<std::mutex> lk(def->mtx);
-        if (def->in_pending) hipEventSynchronize(def->ev_in);
+        if (def->in.in_pending) hipEventSynchronize(def->in.ev_in);
     }
     gnsscorr_ctx *eng = def ? acq_engine(sdr, def) : nullptr;
     gnsscorr_acqres_t r;

@@ -29,24 +29,6 @@
 #define GC_SPEC_HIST 9          // bins per row: the reference's 8 and the one it writes past yI/yQ (d == maxd > 7)
 #define GC_SPEC_HT   256        // threads of the histogram kernels
 
-struct GcSpecWork {
-    GcDevBuf<float> psd;        // [nsnap][nloop][2*nfft] fp32 power per segment
-    GcDevBuf<double> sum;       // [nsnap][2*nfft]
-    GcDevBuf<unsigned> hist;    // [nsnap][2][GC_SPEC_HIST]
-    GcDevBuf<int> maxd;         // [nsnap]
-    GcDevBuf<float> win;        // Hann window of the last nfft (hanning(nfft/2), computed on the host)
-    int win_n = 0;
-    GcDevBuf<uint64_t> loc;     // [nsnap] first sample of each snapshot
-    GcDevBuf<int> off;          // [nsnap][nloop] segment offsets
-    GcDevBuf<int8_t> stage;     // the drop-in's copy of the caller's samples
-    std::vector<uint64_t> hloc;
-    std::vector<int> hoff;
-    // the last run, for fetch
-    bool ran = false, has_hist = false;
-    int nsnap = 0, nfft = 0, nloop = 0, dtype = 0;
-    double f_sf = 0.0;
-};
-
 namespace {
 
 // ---------------------------------------------------------------------------
@@ -174,16 +156,10 @@ __global__ __launch_bounds__(GC_SPEC_HT) void spec_hist_count_kernel(const int8_
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-GcSpecWork *spec_work(gnsscorr_ctx *ctx)
-{
-    if (!ctx->spec) ctx->spec = new GcSpecWork();
-    return ctx->spec;
-}
-
 // everything spec_enqueue needs that does not depend on the samples
 int spec_prepare(gnsscorr_ctx *ctx, int nsnap, int nfft, int nloop)
 {
-    GcSpecWork *w = spec_work(ctx);
+    GcSpec *w = &ctx->spec;
     const size_t L = 2 * (size_t)nfft;
     GC_RESERVE(ctx, w->psd, (size_t)nsnap * nloop * L);
     GC_RESERVE(ctx, w->sum, (size_t)nsnap * L);
@@ -211,10 +187,8 @@ int spec_prepare(gnsscorr_ctx *ctx, int nsnap, int nfft, int nloop)
 int spec_enqueue(gnsscorr_ctx *ctx, const int8_t *ring, uint64_t rb, int dtype, int n, int nsnap, int nfft,
                  int nloop, double f_sf, bool hist)
 {
-    GcSpecWork *w = ctx->spec;
-    const float2 *tw16k = nullptr, *tw32k = nullptr;
-    int rc = gc_acq_twiddles(ctx, &tw16k, &tw32k);
-    if (rc) return rc;
+    GcSpec *w = &ctx->spec;
+    GC_TRY(gc_acq_twiddles(ctx));
     w->ran = false;
     // pageable sources: the copies are staged before the calls return
     GC_HIP(hipMemcpyAsync(w->loc, w->hloc.data(), sizeof(uint64_t) * nsnap, hipMemcpyHostToDevice, ctx->stream));
@@ -226,7 +200,7 @@ int spec_enqueue(gnsscorr_ctx *ctx, const int8_t *ring, uint64_t rb, int dtype, 
     {
         GcTimed t(ctx, "spec_psd");
         hipLaunchKernelGGL(spec_psd_kernel, dim3(nloop, nsnap), dim3(GC_FFT_THREADS), GC_FFT_LDS + 256, ctx->stream,
-                           ring, rb, dtype, w->loc, w->off, nloop, nfft, w->win, scale, tw16k, tw32k, w->psd);
+                           ring, rb, dtype, w->loc, w->off, nloop, nfft, w->win, scale, ctx->fft.tw16k, ctx->fft.tw32k, w->psd);
     }
     GC_HIP(hipGetLastError());
     {
@@ -273,12 +247,6 @@ bool spec_nfft_ok(int nfft) { return nfft == 8192 || nfft == 16384; }
 
 }  // namespace
 
-void gc_spec_free(gnsscorr_ctx *ctx)
-{
-    delete ctx->spec;
-    ctx->spec = nullptr;
-}
-
 extern "C" int gnsscorr_spec_run(gnsscorr_ctx *ctx, const gnsscorr_spec_t *sp, int nsnap, const uint64_t *buffloc,
                                  const int *offsets)
 {
@@ -314,7 +282,7 @@ extern "C" int gnsscorr_spec_run(gnsscorr_ctx *ctx, const gnsscorr_spec_t *sp, i
     if (rc) return rc;
     rc = gc_ingest_fence(ctx);
     if (rc) return rc;
-    GcSpecWork *w = ctx->spec;
+    GcSpec *w = &ctx->spec;
     w->hloc.assign(buffloc, buffloc + nsnap);
     w->hoff.assign(offsets, offsets + (size_t)nsnap * sp->nloop);
     return spec_enqueue(ctx, r.mem, (uint64_t)r.dtype * r.ringlen, r.dtype, sp->n, nsnap, sp->nfft, sp->nloop,
@@ -324,8 +292,8 @@ extern "C" int gnsscorr_spec_run(gnsscorr_ctx *ctx, const gnsscorr_spec_t *sp, i
 extern "C" int gnsscorr_spec_fetch(gnsscorr_ctx *ctx, double *s, size_t s_cap, double *pspec, size_t pspec_cap,
                                    double *freq, size_t freq_cap, int64_t *hist, size_t hist_cap)
 {
-    if (!ctx || !ctx->spec || !ctx->spec->ran) return gc_fail(GNSSCORR_ESTATE, "spec_fetch: no spec_run yet");
-    const GcSpecWork *w = ctx->spec;
+    if (!ctx || !ctx->spec.ran) return gc_fail(GNSSCORR_ESTATE, "spec_fetch: no spec_run yet");
+    const GcSpec *w = &ctx->spec;
     const size_t L = 2 * (size_t)w->nfft, np = (size_t)w->dtype * w->nfft;
     const size_t need_s = (size_t)w->nsnap * L, need_p = (size_t)w->nsnap * np;
     const size_t need_h = (size_t)w->nsnap * 2 * GC_SPEC_HIST;
@@ -399,7 +367,7 @@ extern "C" int spectrumanalyzer(const char *data, int dtype, int n, double f_sf,
     std::lock_guard<std::mutex> lk(ctx->mtx);
     int rc = hipSetDevice(ctx->device) == hipSuccess ? GNSSCORR_OK : gc_fail(GNSSCORR_EHIP, "spectrumanalyzer: hipSetDevice");
     if (!rc) rc = spec_prepare(ctx, 1, nfft, SPEC_NLOOP);
-    GcSpecWork *w = ctx->spec;
+    GcSpec *w = &ctx->spec;
     const size_t bytes = (size_t)dtype * n;
     if (!rc) rc = w->stage.reserve(ctx, (bytes + 15) & ~(size_t)15);
     if (!rc) {

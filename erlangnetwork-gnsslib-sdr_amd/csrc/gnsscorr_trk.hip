@@ -826,7 +826,7 @@ int gc_launch_trk_finish(hipStream_t st, const int *partial, double *corrI, doub
 // The planner, finish, discovery and main streams are idle afterwards: no finish is pending any more.
 int gc_drain(gnsscorr_ctx *ctx)
 {
-    for (hipStream_t s : {ctx->stream_plan, ctx->stream_finish, ctx->stream_discover, ctx->stream})
+    for (hipStream_t s : {ctx->stream_plan.s, ctx->stream_finish.s, ctx->stream_discover.s, ctx->stream.s})
         GC_HIP(hipStreamSynchronize(s));
     ctx->out.fin_pending = false;
     for (GcPlanSlot &s : ctx->batch.slot) s.fin_pending = false;
@@ -835,7 +835,7 @@ int gc_drain(gnsscorr_ctx *ctx)
 
 int gc_quiesce(gnsscorr_ctx *ctx, bool ingest)
 {
-    if (ingest && ctx->stream_in) GC_HIP(hipStreamSynchronize(ctx->stream_in));
+    if (ingest && ctx->in.stream) GC_HIP(hipStreamSynchronize(ctx->in.stream));
     GC_TRY(gc_drain(ctx));
     ctx->batch.ahead_valid = false;    // a look-ahead plan may have been in flight: it is dropped
     ctx->state.touched = true;
