@@ -276,7 +276,8 @@ EXPORTS_GNSSCORR = [
     "gnsscorr_acq_run_subset", "gnsscorr_loop_start_from_acq", "gnsscorr_rx_start", "gnsscorr_rx_set",
     "gnsscorr_rx_step", "gnsscorr_rx_status", "gnsscorr_fec_run", "gnsscorr_sbasframe_replay",
     "gnsscorr_lock_run", "gnsscorr_rx_lock_set", "gnsscorr_rx_lock_status",
-    "gnsscorr_acq_set_coherent", "gnsscorr_acq_get_coherent", "gnsscorr_g1frame_replay"]
+    "gnsscorr_acq_set_coherent", "gnsscorr_acq_get_coherent", "gnsscorr_g1frame_replay",
+    "gnsscorr_acq_set_bitedge", "gnsscorr_acq_get_bitedge", "gnsscorr_acq_fetch_edge"]
 EXPORTS_SDR = [
     "sdracquisition", "checkacquisition", "sdrtracking", "cumsumcorr", "clearcumsumcorr", "pll", "dll",
     "readinifile", "chk_initvalue", "initacqstruct", "inittrkprmstruct", "inittrkstruct", "initsdrch",
@@ -339,6 +340,10 @@ def lib():
     if hasattr(L, "gnsscorr_acq_set_coherent"):     # (absent from an A/B library built before it: tools/acq_coh_time.py)
         L.gnsscorr_acq_set_coherent.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.gnsscorr_acq_get_coherent.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    if hasattr(L, "gnsscorr_acq_set_bitedge"):      # (likewise: tools/acq_edge_time.py)
+        L.gnsscorr_acq_set_bitedge.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.gnsscorr_acq_get_bitedge.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.gnsscorr_acq_fetch_edge.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     L.gnsscorr_fft16k.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     L.gnsscorr_pspec.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.gnsscorr_timing_enable.argtypes = [C.c_void_p, C.c_int]
@@ -472,11 +477,12 @@ class Channel:
     (ref src/sdrinit.c:583-657, acquisition grid :385-394,:633-635, taps :446-455).  fend / ppmerr stand for
     sdrini.fend / sdrini.rtlsdrppmerr: RTL-SDR file replay (FEND_FRTLSDR) offsets the channel by f_cf*ppmerr*1e-6.
     ncoh: code periods the search integrates coherently per group (gnsscorr_acq_set_coherent; 1: the reference's
-    integration); Engine.set_channels applies it."""
+    integration); estep: step of the bit-edge hypotheses of a group (gnsscorr_acq_set_bitedge; 0: none, otherwise
+    1 .. ncoh-1 with ncoh >= 2); Engine.set_channels applies both, ncoh first."""
 
     def __init__(self, prn, ctype=CTYPE_L1CA, dtype=DTYPEIQ, ftype=FTYPE1, f_cf=1575.42e6,
                  f_sf=16.368e6, f_if=0.0, corrn=2, corrd=3, corrp=3, hband=7000, step=200, intg=10,
-                 fend=FEND_FILE, ppmerr=0, ncoh=1):
+                 fend=FEND_FILE, ppmerr=0, ncoh=1, estep=0):
         self.prn, self.ctype, self.dtype, self.ftype = prn, ctype, dtype, ftype
         self.code, self.crate = gencode(prn, ctype)
         self.clen = len(self.code)
@@ -495,6 +501,7 @@ class Channel:
             self.f_cf, self.foffset = f_cf, 0.0
         self.intg = intg
         self.ncoh = ncoh
+        self.estep = estep
         self.nfreq = 2 * (hband // step) + 1
         self.nfft = 2 * self.nsamp
         self.freq = np.array([f_if + ((i - (self.nfreq - 1) // 2) * float(step)) + self.foffset
@@ -602,6 +609,9 @@ class Engine:
         ncoh = [getattr(c, "ncoh", 1) for c in channels]
         if any(k != 1 for k in ncoh):
             self.acq_set_coherent(ncoh)
+        estep = [getattr(c, "estep", 0) for c in channels]
+        if any(k != 0 for k in estep):
+            self.acq_set_bitedge(estep)
 
     # -- tracking
     def trk_set_state(self, states, ch0=0):
@@ -706,6 +716,26 @@ class Engine:
         nch = len(self.channels) - ch0 if nch is None else nch
         arr = (C.c_int * nch)()
         _check(self._L.gnsscorr_acq_get_coherent(self.h, ch0, nch, arr))
+        return list(arr)
+
+    def acq_set_bitedge(self, estep, ch0=0):
+        """Bit-edge step of channels ch0 .. ch0+len(estep)-1 (gnsscorr_acq_set_bitedge: hypotheses h = 0, estep, ... <
+        ncoh per coherent group, 0: none).  set_channels and acq_set_coherent reset it to 0; set_channels then applies
+        the channels' own ncoh and estep, in that order."""
+        arr = (C.c_int * len(estep))(*estep)
+        _check(self._L.gnsscorr_acq_set_bitedge(self.h, ch0, len(estep), arr))
+
+    def acq_get_bitedge(self, ch0=0, nch=None):
+        nch = len(self.channels) - ch0 if nch is None else nch
+        arr = (C.c_int * nch)()
+        _check(self._L.gnsscorr_acq_get_bitedge(self.h, ch0, nch, arr))
+        return list(arr)
+
+    def acq_fetch_edge(self):
+        """Per channel the bit edge the last search decided on (gnsscorr_acq_fetch_edge): the hypothesis h* of the
+        deciding group's best row, 0 for no edge; -1 for a channel that was not listed, not acquired or has estep 0."""
+        arr = (C.c_int * len(self.channels))()
+        _check(self._L.gnsscorr_acq_fetch_edge(self.h, arr))
         return list(arr)
 
     def acq_fetch(self):

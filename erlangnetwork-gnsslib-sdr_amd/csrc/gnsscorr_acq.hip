@@ -32,6 +32,13 @@
 // transforms are linear, so that is the coherent sum of the ncoh correlation results; acq_code, acq_corr and the row
 // statistics do not know, acq_final scales iters and cn0.  ncoh = 1 is the reference's integration bit for bit.
 //
+// Bit-edge hypotheses (gnsscorr_acq_set_bitedge): a channel with estep > 0 has H = ceil(ncoh / estep)
+// sums per group, hypothesis h = 0, estep, ... negating the windows j >= h.  acq_fwd transforms all of them (X's slot =
+// group * H + hypothesis index).  acq_corr's EDGE instance runs a group's inverse transforms once per hypothesis into a
+// sink that keeps only the row's maximum, then once more for the hypothesis with the largest one (lowest h on ties)
+// into the power accumulators: that row alone is added.  Channels without hypotheses run the instances they always ran,
+// in a launch of their own.
+//
 // Every run works on a channel list (gnsscorr_acq_run_subset; gnsscorr_acq_run is the list 0..nch-1): the
 // per-channel kernels take their channel from a compacted device list, acq_fwd its frequency grid from the
 // list of grids that have a listed channel, so grid sizes follow the list.  Everything a channel owns (code
@@ -59,6 +66,8 @@ namespace {
 
 // iterations of a channel's search: groups of ncoh code periods
 __host__ __device__ __forceinline__ int acq_groups(const GcChan &c) { return c.ncoh > 1 ? c.intg / c.ncoh : c.intg; }
+// bit-edge hypotheses of a group: h = 0, estep, 2 estep, ... < ncoh (one, h = 0, without them)
+__host__ __device__ __forceinline__ int acq_hyps(const GcChan &c) { return c.estep > 0 ? (c.ncoh + c.estep - 1) / c.estep : 1; }
 
 // carrier LUT (ref src/sdrcmn.c:643-648)
 __constant__ signed char aCos32[32] = {32, 31, 30, 27, 23, 18, 12, 6, 0, -6, -12, -18, -23, -27, -30, -31,
@@ -214,22 +223,32 @@ __global__ void acq_nco_kernel(const GcChan *__restrict__ chan, const int *__res
     if (ct.overflow) atomicAdd(overflow, 1);
 }
 
-// acq_fwd: grid (bin, iteration, entry of the list of frequency grids in use).  COH: some listed grid integrates
-// coherently, and the sample functor adds the group's ncoh windows (for a grid with ncoh = 1 that is the same integer,
-// so the same float); the instance without COH is free of the loop.
-template <bool COH>
+// acq_fwd: grid (bin, slot, entry of the list of frequency grids in use); slot = iteration without hypotheses.  COH:
+// some listed grid integrates coherently, and the sample functor adds the group's ncoh windows (for a grid with ncoh = 1
+// that is the same integer, so the same float); the instance without COH is free of the loop.  EDGE (with COH): some
+// listed grid has bit-edge hypotheses; slot = iteration * H + hypothesis index, and the functor subtracts the windows
+// j >= h of hypothesis h > 0 (a grid without hypotheses has H = 1, h = 0: the same integers again).
+template <bool COH, bool EDGE = false>
 __global__ __launch_bounds__(GC_FFT_THREADS) void acq_fwd_kernel(
     const GcChan *__restrict__ chan, const int *__restrict__ grid_chan, const int *__restrict__ glist,
     const GcAcqCar *__restrict__ car,
     const uint64_t *__restrict__ grid_wrpos, const float2 *__restrict__ tw16k,
     const float2 *__restrict__ tw32p, const float2 *__restrict__ tw64p1, const float2 *__restrict__ tw64p3,
-    float2 *__restrict__ X, int maxfreq, int maxintg, int L)
+    float2 *__restrict__ X, int maxfreq, int maxslot, int L)
 {
+    static_assert(COH || !EDGE, "hypotheses belong to coherent groups");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2 *lds = reinterpret_cast<float2 *>(smem);
-    const int bin = blockIdx.x, it = blockIdx.y, g = glist[blockIdx.z], tid = threadIdx.x;
+    const int bin = blockIdx.x, slot = blockIdx.y, g = glist[blockIdx.z], tid = threadIdx.x;
     const GcChan &c = chan[grid_chan[g]];
     const int ncoh = COH ? c.ncoh : 1;
+    int it = slot, hneg = ncoh;         // hneg: the first window that is subtracted (ncoh: none)
+    if constexpr (EDGE) {
+        const int H = acq_hyps(c);
+        it = slot / H;
+        const int h = (slot - it * H) * c.estep;
+        if (h > 0) hneg = h;
+    }
     if (bin >= c.nfreq || it >= (COH ? acq_groups(c) : c.intg)) return;
     const int n = c.nsamp, n2 = 2 * n, dtype = c.dtype;
     // window of iteration `it`: ref src/sdracq.c:24-32; a group starts ncoh windows after the one before
@@ -271,13 +290,14 @@ __global__ __launch_bounds__(GC_FFT_THREADS) void acq_fwd_kernel(
             for (int j = 1; j < ncoh; j++) {
                 int Ij, Qj;
                 mixed(j * n + s, Ij, Qj);
+                if (EDGE && j >= hneg) { Ij = -Ij; Qj = -Qj; }       // s(h, j)
                 I += Ij;
                 Q += Qj;
             }
         }
         return make_float2((float)I * sc, (float)Q * sc);
     };
-    float2 *out = X + (((size_t)g * maxintg + it) * maxfreq + bin) * (size_t)L;
+    float2 *out = X + (((size_t)g * maxslot + slot) * maxfreq + bin) * (size_t)L;
     if (L == 2 * GC_L) fwd64k_store(sample, lds, tw16k, tw32p, tw64p1, tw64p3, out, tid);
     else fwd32k_store(sample, lds, tw16k, tw32p, out, tid);
 }
@@ -465,6 +485,35 @@ __device__ __forceinline__ auto acq_add_power(double (&P)[NP], float invL2)
     };
 }
 
+// dit() sink of a hypothesis's first pass: the same |y|^2/L^2 values, of which only the lane's maximum over the lags
+// 2 (o + 1024 q) + PAR < n is kept
+template <int PAR>
+__device__ __forceinline__ auto acq_max_power(float &mx, float invL2, int n)
+{
+    return [&mx, invL2, n](int, int o, float2 (&a)[16]) {
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const float pw = fmaf(a[q].x, a[q].x, a[q].y * a[q].y) * invL2;
+            if (2 * (o + 1024 * q) + PAR < n) mx = fmaxf(mx, pw);
+        }
+    };
+}
+
+// the workgroup's maximum of a float (sf: one slot per wavefront; every lane returns it)
+template <int NT>
+__device__ __forceinline__ float wg_maxf(float m, float *sf, int tid)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    __syncthreads();
+    if ((tid & 63) == 0) sf[tid >> 6] = m;
+    __syncthreads();
+    float r = sf[0];
+#pragma unroll
+    for (int w = 1; w < NT / 64; w++) r = fmaxf(r, sf[w]);
+    return r;
+}
+
 // the bin's power row, from the registers to Pout[bin][lag]
 template <int NP, class LagOf>
 __device__ __forceinline__ void acq_write_power(double *__restrict__ Pout, const double (&P)[NP], LagOf lag_of,
@@ -536,11 +585,15 @@ unsigned acq_corr64_blocks(int nbins, int nlist, bool pout)
 // Lags k < nsamp <= 16384 are wanted, i.e. j < 8192: of a lane's outputs j = o + 1024 q those with
 // q < 8.  Nothing has to wait for the other transform, so the only long-lived registers are the
 // power accumulators.
-template <int NT>
+// EDGE: every channel of the launch has bit-edge hypotheses, H >= 2 spectra per (iteration, bin) in
+// X's slots iteration * H + i.  Two passes per iteration: the transform pair of every hypothesis into acq_max_power
+// and a workgroup maximum, then the pair of the hypothesis with the largest row maximum (lowest on ties) into the
+// accumulators -- H + 1 pairs, a few floats of state, no second row in registers.  The row record carries the choice.
+template <int NT, bool EDGE = false>
 __global__ __launch_bounds__(NT) void acq_corr_kernel(
     const GcChan *__restrict__ chan, const float2 *__restrict__ tw16k, const float2 *__restrict__ tw32p,
     const float2 *__restrict__ X, const float2 *__restrict__ C, const int *__restrict__ iters,
-    GcAcqRow *rows, double *__restrict__ Pout, int pout_ch, int maxfreq, int maxintg,
+    GcAcqRow *rows, double *__restrict__ Pout, int pout_ch, int maxfreq, int maxintg, int maxslot,
     const int *__restrict__ list, int nlist, int *arrive, int *done)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -567,12 +620,8 @@ __global__ __launch_bounds__(NT) void acq_corr_kernel(
     for (int s = 0; s < NP; s++) P[s] = 0.0;
     auto lag_of = [](int tid, int s) { return 2 * (tid + NT * ((s % NPH) >> 3) + 1024 * (s & 7)) + s / NPH; };
 
-    for (int it = 0; it < nit; it++) {
-        // Opaque copy of the lane id: keeps the address computations of one iteration from being
-        // hoisted out of the loop (they would be spilled to scratch, not kept in VGPRs).
-        int tid = tid0;
-        asm volatile("" : "+v"(tid));
-        const float2 *Xb = X + (((size_t)c.grid * maxintg + it) * maxfreq + bin) * GC_L;
+    // the two inverse transforms of the spectrum at Xb, their results to the sinks of the even and of the odd lags
+    auto inverse = [&](const float2 *Xb, int &tid, auto sink_even, auto sink_odd) {
         // even lags
         gcfft::dit<+1, NT, CHUNK>([Xb, Cc](int p) { return acq_load<2>(Xb, Cc, p); },
                        [](const RawXC<2> &r, float2 &x0, float2 &x1, float2 &x2, float2 &x3) {
@@ -581,9 +630,9 @@ __global__ __launch_bounds__(NT) void acq_corr_kernel(
                            x2 = cadd(acq_y(r, 0, 2), acq_y(r, 1, 2));
                            x3 = cadd(acq_y(r, 0, 3), acq_y(r, 1, 3));
                        },
-                       acq_add_power<0>(P, invL2), lds, tw16k, tid);
+                       sink_even, lds, tw16k, tid);
         __syncthreads();
-        asm volatile("" : "+v"(tid));            // (as above: the second transform recomputes its addresses)
+        asm volatile("" : "+v"(tid));            // (as below: the second transform recomputes its addresses)
         // odd lags; exp(+2 pi i f/L) = conj of the forward twiddle
         gcfft::dit<+1, NT, CHUNK>([Xb, Cc, tw32p](int p) { return acq_load_tw<2>(Xb, Cc, tw32p, p); },
                        [](const RawXCT<2> &t, float2 &x0, float2 &x1, float2 &x2, float2 &x3) {
@@ -592,9 +641,33 @@ __global__ __launch_bounds__(NT) void acq_corr_kernel(
                            x2 = cmulc(csub(acq_y(t.r, 0, 2), acq_y(t.r, 1, 2)), acq_w(t, 2));
                            x3 = cmulc(csub(acq_y(t.r, 0, 3), acq_y(t.r, 1, 3)), acq_w(t, 3));
                        },
-                       acq_add_power<NPH>(P, invL2), lds, tw16k, tid);
+                       sink_odd, lds, tw16k, tid);
+    };
+    const int H = EDGE ? acq_hyps(c) : 1;
 
-        const GcAcqRow r = acq_row_stats<NT>(P, lag_of, n, nsc2, sd, si, tid);
+    for (int it = 0; it < nit; it++) {
+        // Opaque copy of the lane id: keeps the address computations of one iteration from being
+        // hoisted out of the loop (they would be spilled to scratch, not kept in VGPRs).
+        int tid = tid0;
+        asm volatile("" : "+v"(tid));
+        const float2 *Xb = X + (((size_t)c.grid * maxslot + (size_t)it * H) * maxfreq + bin) * GC_L;
+        int hsel = 0;                            // index of the hypothesis whose row is added
+        if constexpr (EDGE) {
+            const size_t hstride = (size_t)maxfreq * GC_L;
+            float best = -1.0f;
+            for (int hi = 0; hi < H; hi++) {
+                float mx = -1.0f;
+                inverse(Xb + hi * hstride, tid, acq_max_power<0>(mx, invL2, n), acq_max_power<1>(mx, invL2, n));
+                mx = wg_maxf<NT>(mx, reinterpret_cast<float *>(sd), tid);       // (its barriers free the LDS image)
+                if (mx > best) { best = mx; hsel = hi; }
+                asm volatile("" : "+v"(tid));
+            }
+            Xb += hsel * hstride;
+        }
+        inverse(Xb, tid, acq_add_power<0>(P, invL2), acq_add_power<NPH>(P, invL2));
+
+        GcAcqRow r = acq_row_stats<NT>(P, lag_of, n, nsc2, sd, si, tid);
+        if constexpr (EDGE) r.pad = hsel * c.estep;
         if (tid == 0) rows[((size_t)ch * maxintg + it) * maxfreq + bin] = r;
         // The reference stops a channel at the first iteration whose peak ratio passes the threshold
         // (ref src/sdracq.c:39-42); so does this: the workgroup that finishes an iteration of its channel
@@ -722,11 +795,13 @@ __device__ __forceinline__ GcTrkState acq_start_state(const gnsscorr_acqres_t &r
     return s;
 }
 
-// acq_final: one wavefront per listed channel; the lanes share the bins of an iteration
+// acq_final: one wavefront per listed channel; the lanes share the bins of an iteration.  edge_out[ch]: the hypothesis
+// of the deciding iteration's best row for an acquired channel that has hypotheses, -1 otherwise.
 __global__ __launch_bounds__(64) void acq_final_kernel(const GcChan *__restrict__ chan, const double *__restrict__ freqs,
                                                        const GcAcqRow *__restrict__ rows,
                                                        const uint64_t *__restrict__ grid_wrpos,
                                                        gnsscorr_acqres_t *__restrict__ res, int *__restrict__ iters_out,
+                                                       int *__restrict__ edge_out,
                                                        const int *__restrict__ list, int nlist, int maxfreq,
                                                        int maxintg)
 {
@@ -739,11 +814,12 @@ __global__ __launch_bounds__(64) void acq_final_kernel(const GcChan *__restrict_
     gnsscorr_acqres_t r;
     r.acqcodei = 0; r.freqi = 0; r.acqfreq = 0; r.cn0 = 0; r.peakr = 0; r.flagacq = 0; r.iters = c.intg;
     const uint64_t b0 = grid_wrpos[c.grid] - (uint64_t)(c.intg + 1) * n;
-    int it = 0;
+    int it = 0, edge = -1;
     for (; it < ngroup; it++) {
         const GcAcqRow *row = rows + ((size_t)ch * maxintg + it) * maxfreq;
         const int fi = acq_best_row(row, c.nfreq, lane);
         const GcAcqRow w = row[fi];
+        edge = w.pad;
         const int ne = 4 * c.nsampchip + 1;                     // samples inside the excluded window
         const double meanP = w.sum_out / (double)(n - ne);
         r.cn0 = 10.0 * log10(w.rowmax / meanP / tcoh);
@@ -759,6 +835,7 @@ __global__ __launch_bounds__(64) void acq_final_kernel(const GcChan *__restrict_
     r.buffloc = r.flagacq ? b0 + (uint64_t)r.acqcodei : b0 + (uint64_t)c.intg * n;
     if (lane == 0) {
         res[ch] = r;
+        edge_out[ch] = r.flagacq && c.estep > 0 ? edge : -1;
         if (iters_out) iters_out[ch] = r.flagacq ? it + 1 : ngroup;
     }
 }
@@ -841,9 +918,11 @@ int gc_acq_twiddles(gnsscorr_ctx *ctx)
         const int lds = GC_FFT_LDS + 256;
         GC_HIP(hipFuncSetAttribute((const void *)acq_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + GC_ACQ_CARLDS));
         GC_HIP(hipFuncSetAttribute((const void *)acq_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + GC_ACQ_CARLDS));
+        GC_HIP(hipFuncSetAttribute((const void *)acq_fwd_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + GC_ACQ_CARLDS));
         GC_HIP(hipFuncSetAttribute((const void *)acq_code_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         GC_HIP(hipFuncSetAttribute((const void *)acq_corr_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, GC_ACQ_CORR_LDS));
         GC_HIP(hipFuncSetAttribute((const void *)acq_corr_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, GC_ACQ_CORR_LDS));
+        GC_HIP(hipFuncSetAttribute((const void *)acq_corr_kernel<512, true>, hipFuncAttributeMaxDynamicSharedMemorySize, GC_ACQ_CORR_LDS));
         GC_HIP(hipFuncSetAttribute((const void *)acq_corr64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GC_ACQ_CORR_LDS));
         GC_HIP(hipFuncSetAttribute((const void *)fft16k_kernel<-1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         GC_HIP(hipFuncSetAttribute((const void *)fft16k_kernel<+1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -860,7 +939,7 @@ static int acq_prepare(gnsscorr_ctx *ctx)
     GcAcq *w = &ctx->acq;
     if (w->prepared) return GNSSCORR_OK;
     const int nch = ctx->nch;
-    w->ngrid = 0; w->maxfreq = 0; w->maxintg = 0;
+    w->ngrid = 0; w->maxfreq = 0; w->maxintg = 0; w->maxslot = 0;
     w->L = GC_L;
     w->grid_chan.clear();
     for (int i = 0; i < nch; i++) {
@@ -873,15 +952,18 @@ static int acq_prepare(gnsscorr_ctx *ctx)
         if (c.grid >= w->ngrid) { w->ngrid = c.grid + 1; w->grid_chan.push_back(i); }
         if (c.nfreq > w->maxfreq) w->maxfreq = c.nfreq;
         if (acq_groups(c) > w->maxintg) w->maxintg = acq_groups(c);
+        // X's slots: the largest groups x hypotheses of one grid, not the product of the two maxima
+        if (acq_groups(c) * acq_hyps(c) > w->maxslot) w->maxslot = acq_groups(c) * acq_hyps(c);
     }
-    GC_RESERVE(ctx, w->X, (size_t)w->ngrid * w->maxintg * w->maxfreq * w->L);
+    GC_RESERVE(ctx, w->X, (size_t)w->ngrid * w->maxslot * w->maxfreq * w->L);
     GC_RESERVE(ctx, w->rows, (size_t)nch * w->maxintg * w->maxfreq);
     GC_RESERVE(ctx, w->arrive, (size_t)nch * w->maxintg + nch);
     GC_RESERVE(ctx, w->iters, nch);
     GC_RESERVE(ctx, w->res, nch);
+    GC_RESERVE(ctx, w->edge, nch);
     GC_RESERVE(ctx, w->d_grid_chan, w->ngrid);
     GC_RESERVE(ctx, w->d_grid_wrpos, w->ngrid);
-    GC_RESERVE(ctx, w->d_list, (size_t)nch + w->ngrid);
+    GC_RESERVE(ctx, w->d_list, (size_t)2 * nch + w->ngrid);
     w->list.clear();
     w->glist.clear();
     GC_HIP(hipMemcpyAsync(w->d_grid_chan, w->grid_chan.data(), sizeof(int) * w->ngrid, hipMemcpyHostToDevice,
@@ -910,7 +992,8 @@ static int acq_prepare(gnsscorr_ctx *ctx)
 
 // acq_corr over the list dlist[0..n) with early stop (Pout null), or the power array of channel pout_ch into Pout
 // (no early stop; always the 512-lane kernel).  GNSSCORR_ACQ_NT=1024: the 1024-lane variant of the 32768-point search.
-static void launch_acq_corr(gnsscorr_ctx *ctx, double *Pout, int pout_ch, const int *dlist, int n)
+// edge: the list's channels (or pout_ch) have bit-edge hypotheses -- the EDGE instance, 512 lanes.
+static void launch_acq_corr(gnsscorr_ctx *ctx, double *Pout, int pout_ch, const int *dlist, int n, bool edge)
 {
     const GcFftTables &f = ctx->fft;
     GcAcq *w = &ctx->acq;
@@ -919,20 +1002,22 @@ static void launch_acq_corr(gnsscorr_ctx *ctx, double *Pout, int pout_ch, const 
     const int nbins = pout ? ctx->hchan[pout_ch].nfreq : w->maxfreq;
     int *arrive = pout ? nullptr : (int *)w->arrive;         // [ch][iter] arrival counters, then [ch] "acquired" flags
     int *done = pout ? nullptr : w->arrive + (size_t)ctx->nch * w->maxintg;
-    auto corr32 = [&](auto nt_tag) {
+    auto corr32 = [&](auto nt_tag, auto edge_tag) {
         constexpr int NT = decltype(nt_tag)::value;
-        hipLaunchKernelGGL(acq_corr_kernel<NT>, dim3(acq_corr_blocks(nbins, n, pout)), dim3(NT), GC_ACQ_CORR_LDS,
-                           ctx->stream, ctx->dchan, f.tw16k, f.tw32p, w->X, w->C, w->iters, w->rows, Pout, pout_ch,
-                           w->maxfreq, w->maxintg, dlist, n, arrive, done);
+        hipLaunchKernelGGL((acq_corr_kernel<NT, decltype(edge_tag)::value>), dim3(acq_corr_blocks(nbins, n, pout)),
+                           dim3(NT), GC_ACQ_CORR_LDS, ctx->stream, ctx->dchan, f.tw16k, f.tw32p, w->X, w->C, w->iters,
+                           w->rows, Pout, pout_ch, w->maxfreq, w->maxintg, w->maxslot, dlist, n, arrive, done);
     };
-    if (w->L == 2 * GC_L)
+    if (edge)       // (gnsscorr_acq_set_bitedge refuses the 65536-point path)
+        corr32(std::integral_constant<int, 512>{}, std::true_type{});
+    else if (w->L == 2 * GC_L)
         hipLaunchKernelGGL(acq_corr64_kernel, dim3(acq_corr64_blocks(nbins, n, pout)), dim3(512), GC_ACQ_CORR_LDS,
                            ctx->stream, ctx->dchan, f.tw16k, f.tw32p, f.tw64p1, f.tw64p3, w->X, w->C, w->iters,
                            w->rows, Pout, pout_ch, w->maxfreq, w->maxintg, dlist, n);
     else if (nt == 1024 && !pout)
-        corr32(std::integral_constant<int, 1024>{});
+        corr32(std::integral_constant<int, 1024>{}, std::false_type{});
     else
-        corr32(std::integral_constant<int, 512>{});
+        corr32(std::integral_constant<int, 512>{}, std::false_type{});
 }
 
 // One search over the channels chlist[0..n) (distinct; nullptr: all of them).  wp_ring[r]: write position of ring
@@ -982,9 +1067,18 @@ int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chl
     }
     // pageable sources: the copies are staged before the call returns.  The lists go up only when they change.
     const int ng = (int)glist.size();
+    // acq_corr's order of the list: the channels without bit-edge hypotheses, then those with (a launch each)
+    std::vector<int> part;
+    for (int pass = 0; pass < 2; pass++) {
+        for (int ch : list)
+            if ((ctx->hchan[ch].estep > 0) == (pass == 1)) part.push_back(ch);
+        if (pass == 0) w->nplain = (int)part.size();
+    }
     if (list != w->list || glist != w->glist) {
         GC_HIP(hipMemcpyAsync(w->d_list, list.data(), sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
         GC_HIP(hipMemcpyAsync(w->d_list + nch, glist.data(), sizeof(int) * ng, hipMemcpyHostToDevice, ctx->stream));
+        GC_HIP(hipMemcpyAsync(w->d_list + nch + w->ngrid, part.data(), sizeof(int) * n, hipMemcpyHostToDevice,
+                              ctx->stream));
         w->list.clear();            // (until the copies are staged)
     }
     GC_HIP(hipMemcpyAsync(w->d_grid_wrpos, gw.data(), sizeof(uint64_t) * w->ngrid, hipMemcpyHostToDevice,
@@ -995,33 +1089,39 @@ int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chl
     w->ran = false;                 // until every launch below is queued
     const int *dlist = w->d_list, *dglist = w->d_list + nch;
     const int lds = GC_FFT_LDS + 256;
-    bool coh = false;               // a listed grid integrates coherently
-    for (int g : glist) coh = coh || ctx->hchan[w->grid_chan[g]].ncoh > 1;
+    const int *dpart = w->d_list + nch + w->ngrid;
+    bool coh = false, edge = false; // a listed grid integrates coherently / has bit-edge hypotheses
+    for (int g : glist) {
+        coh = coh || ctx->hchan[w->grid_chan[g]].ncoh > 1;
+        edge = edge || ctx->hchan[w->grid_chan[g]].estep > 0;
+    }
     {
         GcTimed t(ctx, "acq_fwd");
-        auto fwd = coh ? acq_fwd_kernel<true> : acq_fwd_kernel<false>;
-        hipLaunchKernelGGL(fwd, dim3(w->maxfreq, w->maxintg, ng), dim3(GC_FFT_THREADS), lds + GC_ACQ_CARLDS,
+        auto fwd = edge ? acq_fwd_kernel<true, true> : coh ? acq_fwd_kernel<true> : acq_fwd_kernel<false>;
+        hipLaunchKernelGGL(fwd, dim3(w->maxfreq, w->maxslot, ng), dim3(GC_FFT_THREADS), lds + GC_ACQ_CARLDS,
                            ctx->stream, ctx->dchan, w->d_grid_chan, dglist, w->car, w->d_grid_wrpos, f.tw16k, f.tw32p,
-                           f.tw64p1, f.tw64p3, w->X, w->maxfreq, w->maxintg, w->L);
+                           f.tw64p1, f.tw64p3, w->X, w->maxfreq, w->maxslot, w->L);
     }
     GC_HIP(hipGetLastError());
     // channels that are not listed: no iterations, a zero result row
     if (n < nch) {
         GC_HIP(hipMemsetAsync(w->iters, 0, sizeof(int) * nch, ctx->stream));
         GC_HIP(hipMemsetAsync(w->res, 0, sizeof(gnsscorr_acqres_t) * nch, ctx->stream));
+        GC_HIP(hipMemsetAsync(w->edge, 0xff, sizeof(int) * nch, ctx->stream));      // -1
     }
     hipLaunchKernelGGL(fill_int_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, w->iters, ctx->dchan, dlist, n);
     // arrival counters per (channel, iteration) and the channels' "acquired" flags
     GC_HIP(hipMemsetAsync(w->arrive, 0, sizeof(int) * ((size_t)nch * w->maxintg + nch), ctx->stream));
     {
         GcTimed t(ctx, "acq_corr");
-        launch_acq_corr(ctx, nullptr, 0, dlist, n);
+        if (w->nplain) launch_acq_corr(ctx, nullptr, 0, dpart, w->nplain, false);
+        if (n > w->nplain) launch_acq_corr(ctx, nullptr, 0, dpart + w->nplain, n - w->nplain, true);
     }
     GC_HIP(hipGetLastError());
     {
         GcTimed t(ctx, "acq_final");
         hipLaunchKernelGGL(acq_final_kernel, dim3(n), dim3(64), 0, ctx->stream, ctx->dchan,
-                           ctx->dfreqs, w->rows, w->d_grid_wrpos, w->res, w->iters, dlist, n, w->maxfreq,
+                           ctx->dfreqs, w->rows, w->d_grid_wrpos, w->res, w->iters, w->edge, dlist, n, w->maxfreq,
                            w->maxintg);
     }
     GC_HIP(hipGetLastError());
@@ -1050,6 +1150,16 @@ extern "C" int gnsscorr_acq_fetch(gnsscorr_ctx *ctx, gnsscorr_acqres_t *res)
     GC_HIP(hipSetDevice(ctx->device));
     GC_HIP(hipMemcpyAsync(res, ctx->acq.res, sizeof(gnsscorr_acqres_t) * ctx->nch, hipMemcpyDeviceToHost,
                           ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));
+    return GNSSCORR_OK;
+}
+
+extern "C" int gnsscorr_acq_fetch_edge(gnsscorr_ctx *ctx, int *edge)
+{
+    if (!ctx || !edge) return gc_fail(GNSSCORR_EINVAL, "acq_fetch_edge: null context or result array");
+    if (!ctx->acq.ran) return gc_fail(GNSSCORR_ESTATE, "acq_fetch_edge: no acq_run yet");
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_HIP(hipMemcpyAsync(edge, ctx->acq.edge, sizeof(int) * ctx->nch, hipMemcpyDeviceToHost, ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
     return GNSSCORR_OK;
 }
@@ -1128,7 +1238,7 @@ extern "C" int gnsscorr_acq_power(gnsscorr_ctx *ctx, int ch, double *power)
     GC_RESERVE(ctx, w->P, elems);
     // iteration count of the last run is still in w->iters[ch]; rows of this channel are rewritten
     // with identical values
-    launch_acq_corr(ctx, w->P, ch, nullptr, 0);
+    launch_acq_corr(ctx, w->P, ch, nullptr, 0, c.estep > 0);
     GC_HIP(hipGetLastError());
     GC_HIP(hipMemcpyAsync(power, w->P, sizeof(double) * elems, hipMemcpyDeviceToHost, ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));

@@ -383,8 +383,8 @@ static void retarget_rings(gnsscorr_ctx *ctx)
     upload_channels(ctx);
 }
 
-// acquisition grid = channels that share ring, sample grid, Doppler bins and coherent integration: they share the
-// forward spectra.  Grids are numbered in the order of their first channel.
+// acquisition grid = channels that share ring, sample grid, Doppler bins, coherent integration and bit-edge step: they
+// share the forward spectra.  Grids are numbered in the order of their first channel.
 static void assign_acq_grids(gnsscorr_ctx *ctx)
 {
     int ngrid = 0;
@@ -396,6 +396,7 @@ static void assign_acq_grids(gnsscorr_ctx *ctx)
             const gnsscorr_chan_t &o = ctx->hdesc[j];
             if (o.ftype == d.ftype && o.dtype == d.dtype && o.nsamp == d.nsamp && o.nfreq == d.nfreq &&
                 o.intg == d.intg && o.ti == d.ti && o.nfft == d.nfft && ctx->hchan[j].ncoh == g.ncoh &&
+                ctx->hchan[j].estep == g.estep &&
                 !memcmp(o.freq, d.freq, sizeof(double) * d.nfreq))
                 g.grid = ctx->hchan[j].grid;
         }
@@ -477,6 +478,7 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
         g.freq_off = (int)freqs.size();
         freqs.insert(freqs.end(), d.freq, d.freq + d.nfreq);
         g.ncoh = 1;
+        g.estep = 0;
         if (g.smax > ctx->smax_max) ctx->smax_max = g.smax;
         if (d.nsamp + 100 > ctx->max_n) ctx->max_n = d.nsamp + 100;   // ref src/sdrtrk.c:23
     }
@@ -521,7 +523,10 @@ extern "C" int gnsscorr_acq_set_coherent(gnsscorr_ctx *ctx, int ch0, int nch, co
     GC_HIP(hipSetDevice(ctx->device));
     int rc = gc_quiesce(ctx);
     if (rc) return rc;
-    for (int i = 0; i < nch; i++) ctx->hchan[ch0 + i].ncoh = ncoh[i];
+    for (int i = 0; i < nch; i++) {
+        ctx->hchan[ch0 + i].ncoh = ncoh[i];
+        ctx->hchan[ch0 + i].estep = 0;          // the hypotheses depend on ncoh: gnsscorr_acq_set_bitedge comes after
+    }
     assign_acq_grids(ctx);
     ctx->acq = GcAcq();
     return upload_channels(ctx);
@@ -532,6 +537,39 @@ extern "C" int gnsscorr_acq_get_coherent(gnsscorr_ctx *ctx, int ch0, int nch, in
     if (!ctx || !ncoh || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
         return gc_fail(GNSSCORR_EINVAL, "acq_get_coherent: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
     for (int i = 0; i < nch; i++) ncoh[i] = ctx->hchan[ch0 + i].ncoh;
+    return GNSSCORR_OK;
+}
+
+// Bit-edge hypotheses per channel (include/gnsscorr.h); what changes and what is dropped: as gnsscorr_acq_set_coherent
+extern "C" int gnsscorr_acq_set_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, const int *estep)
+{
+    if (!ctx || !estep || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
+        return gc_fail(GNSSCORR_EINVAL, "acq_set_bitedge: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    // the hypotheses are served by the 32768-point transform only, and the transform length is the context's
+    for (int i = 0; i < ctx->nch; i++)
+        if (ctx->hchan[i].nsamp > 16384)
+            return gc_fail(GNSSCORR_EINVAL, "acq_set_bitedge: channel %d: nsamp %d puts the context on the 65536-point "
+                           "transform, which has no bit-edge hypotheses", i, ctx->hchan[i].nsamp);
+    for (int i = 0; i < nch; i++) {
+        const int ncoh = ctx->hchan[ch0 + i].ncoh;
+        if (estep[i] < 0 || (estep[i] >= 1 && (ncoh < 2 || estep[i] >= ncoh)))
+            return gc_fail(GNSSCORR_EINVAL, "acq_set_bitedge: channel %d: estep %d (0, or 1..ncoh-1 with ncoh %d >= 2)",
+                           ch0 + i, estep[i], ncoh);
+    }
+    GC_HIP(hipSetDevice(ctx->device));
+    int rc = gc_quiesce(ctx);
+    if (rc) return rc;
+    for (int i = 0; i < nch; i++) ctx->hchan[ch0 + i].estep = estep[i];
+    assign_acq_grids(ctx);
+    ctx->acq = GcAcq();
+    return upload_channels(ctx);
+}
+
+extern "C" int gnsscorr_acq_get_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, int *estep)
+{
+    if (!ctx || !estep || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
+        return gc_fail(GNSSCORR_EINVAL, "acq_get_bitedge: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    for (int i = 0; i < nch; i++) estep[i] = ctx->hchan[ch0 + i].estep;
     return GNSSCORR_OK;
 }
 

@@ -298,19 +298,24 @@ struct GcAcq {
     GcDevBuf<GcAcqCar> car;     // [grid][bin]
     GcDevBuf<int> car_overflow;
     int L = 32768;              // transform length of this channel set: 32768, or 65536 when a period exceeds 16384 samples
-    GcDevBuf<float2> X;         // [grid][iter][bin][2][16384]: X[f] and X[f + 16384] at the pass position of f
-                                // (iter, here and below: an iteration of the search, a group of ncoh code periods)
+    GcDevBuf<float2> X;         // [grid][slot][bin][2][16384]: X[f] and X[f + 16384] at the pass position of f
+                                // (iter, here and below: an iteration of the search, a group of ncoh code periods;
+                                // slot = iter * H + hypothesis index, H the grid's bit-edge hypotheses, 1 without)
     GcDevBuf<float2> C;         // [ch][2][16384]
     GcDevBuf<GcAcqRow> rows;    // [ch][iter][bin]
     GcDevBuf<int> arrive;       // [ch][iter] workgroups done with the iteration, then [ch] "acquired" flags
     GcDevBuf<int> iters;        // [ch] iteration limit for acq_corr
     GcDevBuf<gnsscorr_acqres_t> res;    // [ch]
+    GcDevBuf<int> edge;         // [ch] bit edge of the deciding group's best row (gnsscorr_acq_fetch_edge), -1: none
     GcDevBuf<double> P;         // one channel's power array (on demand)
     int ngrid = 0, maxfreq = 0, maxintg = 0;    // maxintg: the largest iteration (group) count, intg / ncoh
+    int maxslot = 0;                    // the largest iterations x H of a grid: X's slots (maxintg without hypotheses)
     std::vector<int> grid_chan;         // a representative channel per grid
     GcDevBuf<int> d_grid_chan;          // device copy of grid_chan
     GcDevBuf<uint64_t> d_grid_wrpos;    // ring write position seen by each grid
-    GcDevBuf<int> d_list;               // [nch] channels of the last run, then [ngrid] the grids that have one of them
+    GcDevBuf<int> d_list;               // [nch] channels of the last run, then [ngrid] the grids that have one of them,
+                                        // then [nch] the run's channels again, those without hypotheses first
+    int nplain = 0;                     // how many of the last run's channels have no hypotheses
     std::vector<int> list, glist;       // host copies of what d_list holds
     std::vector<char> listed;           // [nch] channel was part of the last run
     bool ran = false;                   // a search has been queued: there are results to fetch

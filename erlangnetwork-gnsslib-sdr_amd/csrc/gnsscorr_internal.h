@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "../../include/gnsscorr.h"
 #include "gnsscorr_nco.h"
@@ -26,6 +27,8 @@ struct GcChan {
     int    dtype, clen, nsamp, nsampchip;
     int    ntap, smax;
     int    tapoff[GNSSCORR_MAXTAPS];   // tap offsets in samples: 0,-s0,+s0,-s1,+s1,...
+    int    estep;                      // acquisition: step of the bit-edge hypotheses, 0: none (gnsscorr_acq_set_bitedge).
+                                       // It fills the hole in front of the doubles: the table's stride is unchanged.
     double ti, f_sf, crate, ctime;
     // acquisition
     int    nfreq, intg, nfft, grid;    // grid = index of the (ring, freq grid) group
@@ -34,6 +37,7 @@ struct GcChan {
     int    pm1;                        // pm1: every edge steps by +-2 (a +-1 code)
     int    ncoh;                       // acquisition: code periods summed coherently per group (gnsscorr_acq_set_coherent)
 };
+static_assert(offsetof(GcChan, estep) + sizeof(int) == offsetof(GcChan, ti), "estep sits in the hole behind tapoff");
 
 // Code block = GC_CODEBLOCK bytes per channel:
 //   [0, 1024)     int8 chips (clen of them, zero padded)

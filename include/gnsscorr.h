@@ -410,11 +410,43 @@ int  gnsscorr_acq_power(gnsscorr_ctx *ctx, int ch, double *power);
  * channel range outside the table, ncoh < 1, ncoh > GNSSCORR_MAXCOH, intg % ncoh != 0.  Quiesces and drops the
  * prepared acquisition work, so that the next search prepares again; channels share forward spectra only when their
  * ncoh agree as well.
- * Recommended Doppler grid: step <= 1 / (2 * ncoh * ctime) (500 / 100 / 50 Hz for 1 / 5 / 10 periods of 1 ms).  Data
- * bit edges inside a group are not handled: they cost correlation, so keep ncoh * ctime <= 10 ms for L1 C/A unless
- * the data is known; a retry (the receiver schedule's) lands on another alignment. */
+ * Recommended Doppler grid: step <= 1 / (2 * ncoh * ctime) (500 / 100 / 50 Hz for 1 / 5 / 10 periods of 1 ms).  A data
+ * bit edge inside a group costs correlation: gnsscorr_acq_set_bitedge (below) searches over its position; without it
+ * keep ncoh * ctime <= 10 ms for L1 C/A unless the data is known, and a retry (the receiver schedule's) lands on
+ * another alignment.  This call resets the bit-edge step of the channels it names to 0 (the hypotheses depend on
+ * ncoh): call it first, gnsscorr_acq_set_bitedge second. */
 int  gnsscorr_acq_set_coherent(gnsscorr_ctx *ctx, int ch0, int nch, const int *ncoh);
 int  gnsscorr_acq_get_coherent(gnsscorr_ctx *ctx, int ch0, int nch, int *ncoh);
+/* Bit-edge hypotheses for coherent groups (opt-in per channel).  Channel ch0 + i, which must have
+ * ncoh >= 2, gets the edge step estep[i], 1 <= estep < ncoh; 0 switches the hypotheses off and is the default (and what
+ * gnsscorr_set_channels and gnsscorr_acq_set_coherent reset to).  Its hypotheses are h = 0, estep, 2 * estep, ... < ncoh,
+ * H of them.  Everything not named here is the coherent search above, unchanged:
+ *   - per hypothesis h the group's windows are summed with signs, z_h[k] = sum_{j < ncoh} s(h, j) (I, Q)[j * nsamp + k],
+ *     s(h, j) = -1 when h > 0 and j >= h, +1 otherwise (exact integers below 2^24; h = 0 is the sum without this call),
+ *     and go through the forward transform, the product with the code spectrum, the inverse transform and
+ *     pw_h[k] = |y_h[k]|^2 / L^2 as before;
+ *   - per (group, Doppler bin) the hypothesis h* with the largest max_{k < nsamp} pw_h[k] is chosen, the lowest h on
+ *     ties, and its whole row is added to the power, P[bin][k] += pw_{h*}[k]; the other hypotheses add nothing;
+ *   - row statistics, the early stop and checkacquisition()'s rules run on P after every group as before, and iters,
+ *     buffloc, acqfreq and cn0 are what they are above.  A noise row's maximum is the best of H hypotheses while its
+ *     mean is that of one, so on noise peakr and cn0 read slightly high (an absent PRN: peakr 1.5 .. 1.9 with ten).
+ * The edge of an acquired channel (gnsscorr_acq_fetch_edge) is h* of the deciding group's best row.  For edge > 0 the
+ * satellite's data changes sign at sample buffloc + ((iters / ncoh - 1) * ncoh + edge) * nsamp.  The edge is -1 for a
+ * channel that was not listed, was not acquired, or has estep = 0.
+ * With estep = 0 for every listed channel, results, rows and power arrays are bit for bit those of the search without
+ * this call; gnsscorr_acq_power follows the same row rule.
+ * One edge per span is assumed and not enforced: exact for L1 C/A up to 20 periods; GLONASS G1 (10 ms meander) wants
+ * ncoh <= 10.  The cost is H + 1 inverse transform pairs per (group, bin) instead of one and H forward transforms; the
+ * forward spectra take groups * H slots.  Only the 32768-point transform is served, and the transform length is the
+ * context's: GNSSCORR_EINVAL when any channel of the context has nsamp > 16384.  Also GNSSCORR_EINVAL, nothing touched
+ * and the channel named: a range outside the channel table, estep < 0, estep >= 1 on a channel with ncoh < 2, estep >=
+ * ncoh.  Quiesces and drops the prepared acquisition work; channels share forward spectra only when their estep agree
+ * as well.  Not included: data wipe-off, code-Doppler compensation, a bit-synchronisation preset from the edge; the
+ * drop-in sdracquisition() is untouched. */
+int  gnsscorr_acq_set_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, const int *estep);
+int  gnsscorr_acq_get_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, int *estep);
+/* edge[nch] of the last search (above); synchronises.  GNSSCORR_ESTATE before a search. */
+int  gnsscorr_acq_fetch_edge(gnsscorr_ctx *ctx, int *edge);
 
 /* ---- receiver schedule: acquire, hand over and track each channel by state ----
  * sdrthread()'s state machine (ref src/sdrmain.c:247-316) for every channel of the context: a channel calls
