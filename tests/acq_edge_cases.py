@@ -1,6 +1,8 @@
 """Bit-edge hypotheses for coherent groups (gnsscorr_acq_set_bitedge): a restatement of their
 semantics on the host, and the scenarios of tests/test_acq_edge_host.py (which shows on the restatement alone that
-each is decided with room) and tests/test_gpu_acq_bitedge.py (which runs them on the device).  Helpers; not a conftest.
+each is decided with room), tests/test_gpu_acq_bitedge.py (which runs them on the device, the ring being the span) and
+tests/test_gpu_acq_bitedge_positions.py (which runs them elsewhere in a stream and a ring: `position`, `moved_stream`,
+and `rule6`, the documented meaning of an edge held against where the bit was flipped).  Helpers; not a conftest.
 
 The restatement (`edge_acq`) is acq_coh_cases.coh_acq with, per group and Doppler bin:
   1./2. the span and its one mixcarr() wipe-off (acq_coh_cases.group_sum: the integers I, Q of the (ncoh+1)*n samples);
@@ -192,6 +194,30 @@ SCEN = {
                         (14, 3000, 400.0, 44.0, 1.7, _flip(3000, 12)), (22, 3210, -150.0, 42.0, 2.5, _flip(3210, 5))],
                   chans=[(3, 2000, 200, 10, 1, 0), (8, 2000, 100, 10, 5, 0), (14, 2000, 100, 10, 5, 1),
                          (22, 1500, 50, 20, 10, 5)]),
+    # edge steps that do not divide ncoh: hypotheses {0,3,6,9}, {0,4,8}, {0,9} of 10 and {0,4} of 5 (H = ceil(ncoh /
+    # estep) = 4, 3, 2, 2), each acquired channel's edge on the *last* of them, the one a floor would drop; an absent PRN
+    "odd": dict(f_sf=4.092e6, f_if=0.0, dtype=2, seed=13,
+                sats=[(22, 2345, -150.0, 42.0, 2.6, _flip(2345, 9)), (7, 3000, 100.0, 42.0, 0.7, _flip(3000, 8)),
+                      (9, 3210, 100.0, 42.0, 0.2, _flip(3210, 4))],
+                chans=[(22, 200, 50, 10, 10, 3), (7, 200, 50, 10, 10, 4), (22, 200, 50, 10, 10, 9),
+                       (9, 400, 100, 10, 5, 4), (5, 200, 50, 10, 10, 3)]),
+    # the smallest H: ncoh 2, estep 1, five groups of two slots.  The 40 dB-Hz satellite passes at group 3 with rows
+    # of hypotheses 0, 0, 1 summed; the 46 dB-Hz one at group 1; an absent PRN runs all five
+    "two": dict(f_sf=4.092e6, f_if=0.0, dtype=2, seed=12,
+                sats=[(7, 2345, 250.0, 40.0, 0.7, _flip(2345, 5)), (11, 3000, -250.0, 46.0, 1.9, _flip(3000, 1))],
+                chans=[(7, 500, 250, 10, 2, 1), (11, 500, 250, 10, 2, 1), (5, 500, 250, 10, 2, 1)]),
+    # the largest: ncoh 20 = GNSSCORR_MAXCOH with every hypothesis, H = maxslot = 20, a carrier walk of 21 periods;
+    # an edge at 19 (all windows but one negated) and one at 10
+    "twenty": dict(f_sf=4.092e6, f_if=0.0, dtype=2, seed=13,
+                   sats=[(9, 3210, 25.0, 40.0, 0.2, _flip(3210, 19)), (14, 2345, -50.0, 40.0, 1.1, _flip(2345, 10))],
+                   chans=[(9, 100, 25, 20, 20, 1), (14, 100, 25, 20, 20, 1), (5, 100, 25, 20, 20, 1)]),
+    # a span of 13 periods searched twice by intg 10 channels, at its periods 0..10 and 2..12: the edges move with the
+    # search (3 -> 1, outside -> 9, none, 1 -> before the span).  The satellites run through both searches
+    "moved": dict(f_sf=4.092e6, f_if=0.0, dtype=2, seed=28, periods=13,
+                  sats=[(22, 2345, -150.0, 42.0, 2.6, _flip(2345, 3)), (7, 3000, 100.0, 42.0, 0.7, _flip(3000, 11)),
+                        (11, 3210, -100.0, 42.0, 1.9), (9, 2345, 50.0, 42.0, 0.2, _flip(2345, 1))],
+                  chans=[(22, 200, 50, 10, 10, 1), (7, 200, 50, 10, 10, 1), (11, 200, 50, 10, 10, 1),
+                         (9, 200, 50, 10, 10, 1), (5, 200, 50, 10, 10, 1)]),
 }
 
 
@@ -202,6 +228,21 @@ def pair(gc, orc, sc, chan):
     return c, o
 
 
+def make_span(gc, synth, sc):
+    """The scenario's span: acq_coh_cases.make_span, (max intg + 1)*n samples, or sc["periods"] code periods where the
+    scenario names a length (sized as a search of periods - 1 windows would size it: the satellites are on their lags
+    in its middle and run through all of it)."""
+    if "periods" in sc:
+        sc = dict(sc, chans=list(sc["chans"]) + [(0, 0, 1, sc["periods"] - 1, 1, 0)])
+    return cc.make_span(gc, synth, sc)
+
+
+def restate(orc, pairs, ring_buf, ringlen, wrpos):
+    """The restated search of every (Channel, oracle channel) of `pairs` that ends at write position wrpos of a ring."""
+    return ac.run_oracles([lambda c=c, o=o: edge_acq(orc, o, ring_buf, ringlen, wrpos, c.ncoh, c.estep)
+                           for c, o in pairs])
+
+
 _cache = {}
 
 
@@ -210,9 +251,123 @@ def scenario(gc, orc, synth, name):
     ending at its last sample: computed once per process."""
     if name not in _cache:
         sc = SCEN[name]
-        W = cc.make_span(gc, synth, sc)
+        W = make_span(gc, synth, sc)
         pairs = [pair(gc, orc, sc, ch) for ch in sc["chans"]]
-        jobs = [lambda o=o, ch=ch: edge_acq(orc, o, W, len(W), len(W), ch[4], ch[5])
-                for (_, o), ch in zip(pairs, sc["chans"])]
-        _cache[name] = (W, pairs, ac.run_oracles(jobs))
+        _cache[name] = (W, pairs, restate(orc, pairs, W, len(W), len(W)))
     return _cache[name]
+
+
+# ---- positions: the same span elsewhere in a stream and in a ring ---------------------------------------------------
+def granule(nsamples, dtype):
+    """nsamples rounded up to the ring's 16-byte granule."""
+    g = 16 // dtype
+    return -(-nsamples // g) * g
+
+
+def placed(W, dtype, ringlen, b0, seed=77):
+    """The span W from sample b0 of a stream on, noise in front of it: (stream, ringlen, wrpos = b0 + len(W)).  After
+    the stream went in, the ring's last slot holds span sample ringlen - 1 - b0 when b0 < ringlen."""
+    assert ringlen >= len(W) and b0 >= 0
+    return np.concatenate([ac.noise(b0, dtype, seed), W]), ringlen, b0 + len(W)
+
+
+def wrap_layouts(n, intg, dtype):
+    """name -> (ringlen, b0) for a span of (intg+1)*n samples: rings of 13 periods that end 3.5 and 7.5 periods into
+    the span, and a ring of exactly the span (rounded up to the granule) in front of which an odd number of samples
+    went by (2 1/3 periods: the ring's end falls two thirds into the span's window intg - 2)."""
+    r13, rx = granule((intg + 3) * n, dtype), granule((intg + 1) * n, dtype)
+    return {"3.5": (r13, r13 - (3 * n + n // 2)), "7.5": (r13, r13 - (7 * n + n // 2)),
+            "exact": (rx, (2 * n + n // 3) | 1)}
+
+
+POSITIONS = [("groups5", "3.5"), ("groups5", "7.5"), ("groups5", "exact"), ("odd", "3.5"), ("real", "odd"),
+             ("groups5", "2^32")]
+
+
+def position(gc, orc, synth, name, layout):
+    """Scenario `name` away from the origin: dict(stream, buf = the ring as the device holds it, ringlen, wrpos, b0 =
+    where the span begins in the stream, K = ring lengths to commit after pushing the stream (the 2^32 layout only),
+    wants = the restatement over buf), computed once per process.
+    Layouts: those of wrap_layouts; "odd": a ring of intg + 3 periods that ends an odd number of samples, 2.5 periods
+    and one, into the span; "2^32": the ring of tests/test_gpu_positions.py, 2^32 between the span's periods 3 and 4."""
+    key = (name, layout)
+    if key not in _cache:
+        sc = SCEN[name]
+        W, pairs, _ = scenario(gc, orc, synth, name)
+        n, dtype = cc.nsamp(sc), sc["dtype"]
+        intg = len(W) // n - 1
+        K = None
+        if layout == "2^32":
+            from test_gpu_positions import high_layout
+            T = 1 << 32
+            ringlen, K = high_layout(T, (intg + 2) * n, 16 // dtype, (intg - 3) * n, (intg - 2) * n)
+            wrpos = (K + 1) * ringlen
+            b0 = wrpos - len(W)
+            assert b0 + 2 * n < T < b0 + 5 * n
+            buf = stream = np.concatenate([ac.noise(ringlen - len(W), dtype, 78), W])
+        else:
+            if layout == "odd":
+                ringlen = granule((intg + 3) * n, dtype)
+                b0 = ringlen - (2 * n + n // 2 + 1)
+                assert b0 % 2 == 1
+            else:
+                ringlen, b0 = wrap_layouts(n, intg, dtype)[layout]
+            stream, ringlen, wrpos = placed(W, dtype, ringlen, b0)
+            assert b0 < ringlen < wrpos             # the ring's end lies inside the span
+            buf = ac.ring_order(stream, ringlen, wrpos)
+        _cache[key] = dict(stream=stream, buf=buf, ringlen=ringlen, wrpos=wrpos, b0=b0, K=K,
+                           wants=restate(orc, pairs, buf, ringlen, wrpos))
+    return _cache[key]
+
+
+MOVED_B0 = 5 * N4 + 123       # where the span of `moved` begins in its stream
+
+
+def moved_origin(gc, orc, synth):
+    """`moved` restated on its span alone: [results of the search that ends at period 11, at period 13 (the
+    scenario's own)], computed once per process."""
+    if "moved@11" not in _cache:
+        W, pairs, _ = scenario(gc, orc, synth, "moved")
+        _cache["moved@11"] = restate(orc, pairs, W, len(W), 11 * N4)
+    return [_cache["moved@11"], scenario(gc, orc, synth, "moved")[2]]
+
+
+def moved_stream(gc, orc, synth):
+    """(stream = noise(MOVED_B0) ++ W, ringlen: the ring holds it whole, the two write positions searched)."""
+    W = scenario(gc, orc, synth, "moved")[0]
+    stream, ringlen, wrpos = placed(W, 2, granule(MOVED_B0 + len(W), 2), MOVED_B0, seed=79)
+    return stream, ringlen, [MOVED_B0 + 11 * N4, wrpos]
+
+
+def same_search(want, ref, b0):
+    """The restatement at another position (span from sample b0 on) against the one at the origin: the same samples,
+    hence the same search -- every group's figures, the chosen hypotheses, the edge; positions moved by b0."""
+    assert want["b0"] == ref["b0"] + b0, (want["b0"], ref["b0"], b0)
+    assert want["steps"] == ref["steps"] and want["buffloc"] == ref["buffloc"] + b0
+    assert all(np.array_equal(a, b) for a, b in zip(want["hsel"], ref["hsel"])) and want["edge"] == ref["edge"]
+    assert all(want[k] == ref[k] for k in ("flagacq", "iters", "acqcodei", "freqi", "acqfreq", "groups"))
+
+
+def rule6(sc, chan, r, edge, w0):
+    """Rule 6 of DESIGN.md 3.2d on a fetched result `r` and edge of channel `chan` of scenario `sc`, whose span W
+    begins at stream sample w0: with the satellite's flip on one of its own period boundaries, inside the deciding
+    group and on a hypothesis, buffloc + ((iters // ncoh - 1) * ncoh + edge) * nsamp is where the bit was flipped, to
+    the +-1 sample that acqcodei may be off the placed lag; edge 0 says no flip lies inside the deciding group.
+    Returns "edge", "none" or None (rule 6 says nothing: not acquired, no hypotheses, a flip off the hypotheses)."""
+    prn, _, _, intg, ncoh, estep = chan
+    sat = {s[0]: s for s in sc["sats"]}.get(prn)
+    if sat is None or not r["flagacq"] or estep == 0:
+        return None
+    n, lag = cc.nsamp(sc), sat[1]
+    assert abs(r["acqcodei"] - lag) <= 1, (chan, r["acqcodei"], lag)
+    gstart = r["buffloc"] - r["acqcodei"] + (r["iters"] // ncoh - 1) * ncoh * n     # the deciding group's first sample
+    first, end = gstart + lag, gstart + lag + ncoh * n      # the satellite's ncoh periods that the group sums
+    flip = w0 + sat[5] if len(sat) > 5 else None
+    if flip is None or not first < flip < end:
+        assert edge == 0, (chan, "no flip inside the deciding group", edge)
+        return "none"
+    if (flip - first) % n or ((flip - first) // n) % estep:
+        return None
+    said = r["buffloc"] + ((r["iters"] // ncoh - 1) * ncoh + edge) * n
+    assert edge > 0 and abs(said - flip) <= abs(r["acqcodei"] - lag), (chan, edge, said, flip)
+    return "edge"

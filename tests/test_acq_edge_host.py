@@ -1,7 +1,8 @@
 """Bit-edge hypotheses for coherent groups (gnsscorr_acq_set_bitedge) on the host: that the restatement of their
 semantics (tests/acq_edge_cases.py) is acq_coh_cases.coh_acq for estep = 0 and costs an unflipped satellite nothing, the
-sensitivity claim behind the feature on the literal LUT path, that every scenario tests/test_gpu_acq_bitedge.py runs on
-the device is decided on the restatement with room, and that the library exports the entry points.  No GPU.
+sensitivity claim behind the feature on the literal LUT path, that every scenario tests/test_gpu_acq_bitedge.py and
+tests/test_gpu_acq_bitedge_positions.py run on the device is decided on the restatement with room, that a span moved in
+its stream and ring is the same search, and that the library exports the entry points.  No GPU.
 
 Figures (restatement, 4.092 Msps IQ, PRN 1 at +1000 Hz and lag 1234, sigma 8, intg 10, ncoh 10, +-5 kHz / 50 Hz, 36
 dB-Hz, the data bit flipped at sample 1234 + 5 * 4092 of the span), seeds 0 / 1 / 2 / 3:
@@ -20,7 +21,18 @@ others run on their first seed and C/N0.  Where the checked satellites' lags com
           absent: 1.67, 1.90; 0.065, 0.068, 0.195
   step2   edge 4: 41.13 (edge 4); edge 5: 20.12 (edge 6, 1.2 % ahead of hypothesis 4); 0.367, 0.285, 0.012
   real    7.293 (edge 2); 0.171, 0.447, 0.698
-  mixed   4.516 / 6.880 / 8.709 (edge 2) / 15.04 (edge 5); 0.010, 0.049, 0.547"""
+  mixed   4.516 / 6.880 / 8.709 (edge 2) / 15.04 (edge 5); 0.010, 0.049, 0.547
+The scenarios of tests/test_gpu_acq_bitedge_positions.py (asserted in test_figures_of_the_new_scenarios; no row of
+any of them is tied).  Seeds 11 and 12 of odd and 21 to 27 of moved had a channel with one of its nine rows tied:
+  odd     estep 3 / 4 / 9 on ncoh 10: 17.42 (edge 9) / 22.19 (edge 8) / 17.42 (edge 9); estep 4 on ncoh 5: 5.893 at
+          group 1 (edge 4); absent: 1.312; 0.233, 0.037, 0.032 (0.340 over the acquired channels)
+  two     40 dB-Hz: 1.40, 2.32, 3.54 (hypotheses 0, 0, 1; edge 1, iters 6); 46 dB-Hz: 10.71 at group 1 (edge 1);
+          absent: 1.23, 1.04, 1.19, 1.08, 1.14; lag gap 0.038, row gap 0.0031, hypothesis gap 0.0094 (all the absent PRN's)
+  twenty  26.0 (edge 19) / 17.04 (edge 10) / absent 1.678; hypothesis gaps 0.136 / 0.176 / 0.075
+  moved   periods 0..10: 15.04 (edge 3) / 12.49 (0) / 17.16 (0) / 16.40 (1) / absent 1.525, hypothesis gaps >= 0.298, 0.123;
+          periods 2..12: 17.35 (edge 1) / 19.66 (9) / 18.98 (0) / 16.25 (0) / absent 1.705, >= 0.282, 0.0082
+The same scenarios away from the origin (rings that end inside the span, an odd offset, 2^32) give these figures again,
+group by group (test_positions_reproduce_the_origin)."""
 import ctypes as C
 import os
 
@@ -113,8 +125,10 @@ def test_every_scenario_is_decided_with_room(scen, name):
               "tied rows", int(ec.tied_rows(r).sum()), "of", len(r["hgap"][0]))
 
 
-def test_scenarios_are_what_the_device_tests_need(scen):
+def test_scenarios_are_what_the_device_tests_need(scen, gc, orc, synth):
     """Each scenario's satellites are found at the placed lag (+-1) and bin with the placed edge."""
+    moved_at = ec.moved_origin(gc, orc, synth)
+
     def found(r, sat, ch, edge, iters):
         prn, hband, step = ch[:3]
         assert r["flagacq"] and abs(r["acqcodei"] - sat[1]) <= 1 and r["iters"] == iters, (ch, r["acqcodei"], r["iters"])
@@ -125,10 +139,17 @@ def test_scenarios_are_what_the_device_tests_need(scen):
                        # an edge between two hypotheses: 4 and 6 each get one period wrong; 6 leads by 1.2 % here
                        ("step2", [(4, 10), (6, 10)]),
                        ("real", [(2, 4)]),
-                       ("mixed", [(-1, 1), (-1, 5), (2, 5), (5, 10)])):
-        sc = ec.SCEN[name]
+                       ("mixed", [(-1, 1), (-1, 5), (2, 5), (5, 10)]),
+                       # every edge on the last hypothesis of a step that does not divide ncoh
+                       ("odd", [(9, 10), (8, 10), (9, 10), (4, 5), None]),
+                       ("two", [(1, 6), (1, 2), None]),
+                       ("twenty", [(19, 20), (10, 20), None]),
+                       ("moved@11", [(3, 10), (0, 10), (0, 10), (1, 10), None]),
+                       ("moved", [(1, 10), (9, 10), (0, 10), (0, 10), None])):
+        sc = ec.SCEN[name.split("@")[0]]
         placed = {s[0]: s for s in sc["sats"]}
-        for ch, r, w in zip(sc["chans"], scen(name)[2], want):
+        results = moved_at[0] if name == "moved@11" else scen(name)[2]
+        for ch, r, w in zip(sc["chans"], results, want):
             if w is None:
                 assert not r["flagacq"] and r["edge"] == -1 and r["iters"] == ch[3], (name, ch)
             else:
@@ -140,6 +161,99 @@ def test_scenarios_are_what_the_device_tests_need(scen):
     assert [int(h[late["freqi"]]) for h in late["hsel"]] == [3, 0] and late["steps"][0][0] < 3.0 < late["steps"][1][0]
     # mixed: the intg-10 channels' spans start 10 periods into the intg-20 channel's
     assert [r["b0"] for r in scen("mixed")[2]] == [10 * 4092] * 3 + [0]
+    # odd: H = ceil(ncoh / estep), the last hypothesis the one a floor would drop
+    assert [r["hs"] for r in scen("odd")[2]] == [[0, 3, 6, 9], [0, 4, 8], [0, 9], [0, 4], [0, 3, 6, 9]]
+    # two: the smallest H; three differently chosen rows are summed, the third group decides.  twenty: the largest
+    slow, fast, absent = scen("two")[2]
+    assert slow["hs"] == [0, 1] and [int(h[slow["freqi"]]) for h in slow["hsel"]] == [0, 0, 1]
+    assert [s[0] < 3.0 for s in slow["steps"]] == [True, True, False] and fast["groups"] == 1 and absent["groups"] == 5
+    assert all(r["hs"] == list(range(20)) and r["groups"] == 1 for r in scen("twenty")[2])
+    # moved: a span of 13 periods, the searches begin at its periods 0 and 2
+    assert len(scen("moved")[0]) == 13 * 4092 and [[r["b0"] for r in rs] for rs in moved_at] == [[0] * 5, [2 * 4092] * 5]
+
+
+PEAKR = {   # peak ratio per group of every channel, the figures of this module's docstring (to 0.5 %)
+    "odd": [[17.4], [22.2], [17.4], [5.89], [1.31]],
+    "two": [[1.40, 2.32, 3.54], [10.7], [1.227, 1.04, 1.185, 1.078, 1.136]],
+    "twenty": [[26.0], [17.0], [1.68]],
+    "moved@11": [[15.0], [12.5], [17.2], [16.4], [1.52]],
+    "moved": [[17.4], [19.7], [19.0], [16.3], [1.70]],
+}
+
+
+def test_figures_of_the_new_scenarios(scen, gc, orc, synth):
+    """The restatement's peak ratios of odd, two, twenty and both searches of moved are the recorded ones: a change of
+    the synthesiser, of a seed or of the restatement is noticed here, not on the device."""
+    for name, want in PEAKR.items():
+        res = ec.moved_origin(gc, orc, synth)[0] if name == "moved@11" else scen(name)[2]
+        for i, (r, w) in enumerate(zip(res, want)):
+            got = [s[0] for s in r["steps"]]
+            print(name, i, [round(g, 3) for g in got])
+            assert len(got) == len(w) and all(abs(g - x) <= 0.005 * x + 0.005 for g, x in zip(got, w)), (name, i, got)
+
+
+def test_moved_searches_two_positions_with_room(gc, orc, synth):
+    """The 13-period span of `moved` searched at its periods 0..10 and 2..12: both decided with room, the edges where
+    the flips were placed relative to each search (rule 6 of DESIGN.md 3.2d on the restatement), and the same two
+    searches on the stream the device test pushes (5 periods and 123 samples of noise in front)."""
+    sc = ec.SCEN["moved"]
+    W, pairs, _ = ec.scenario(gc, orc, synth, "moved")
+    first, second = ec.moved_origin(gc, orc, synth)
+    assert [r["edge"] for r in first] == [3, 0, 0, 1, -1] and [r["edge"] for r in second] == [1, 9, 0, 0, -1]
+    for k, res in enumerate((first, second)):
+        for ch, r in zip(sc["chans"], res):
+            ec.check_margins(r, ("moved", k, ch))
+            print("moved", k, ch, "edge", r["edge"], "peak ratio", round(r["peakr"], 3), "hypothesis gap",
+                  round(float(r["hgap"][-1][r["freqi"]]), 4))
+        assert [ec.rule6(sc, ch, r, r["edge"], 0) for ch, r in zip(sc["chans"], res)] == \
+            [["edge", "none", "none", "edge", None], ["edge", "edge", "none", "none", None]][k]
+    stream, ringlen, wrpos = ec.moved_stream(gc, orc, synth)
+    assert ringlen >= len(stream) == ec.MOVED_B0 + 13 * 4092 and wrpos == [ec.MOVED_B0 + 11 * 4092, len(stream)]
+    buf = ac.ring_order(stream, ringlen, len(stream))
+    for wp, ref in zip(wrpos, (first, second)):
+        for w, r in zip(ec.restate(orc, pairs, buf, ringlen, wp), ref):
+            ec.same_search(w, r, ec.MOVED_B0)
+
+
+@pytest.mark.parametrize("name,layout", ec.POSITIONS, ids=["-".join(p) for p in ec.POSITIONS])
+def test_positions_reproduce_the_origin(gc, orc, synth, name, layout):
+    """The scenarios away from the origin -- a ring end inside the span, real samples at an odd offset, a span across
+    2^32 -- are the same search on the same samples: every group's figures, hypotheses and edges are the origin's, the
+    positions moved by where the span begins.  So room is inherited.  And rule 6 holds on the restatement there."""
+    sc = ec.SCEN[name]
+    W, pairs, ref = ec.scenario(gc, orc, synth, name)
+    p = ec.position(gc, orc, synth, name, layout)
+    n = pairs[0][0].nsamp
+    assert p["wrpos"] - p["b0"] == len(W) and p["ringlen"] >= len(W)
+    into = (-p["b0"]) % p["ringlen"]              # span sample at the ring's slot 0
+    print(name, layout, "ringlen", p["ringlen"], "b0", p["b0"], "the ring ends %.3f periods into the span" % (into / n))
+    if layout == "2^32":
+        assert p["b0"] + 2 * n < 1 << 32 < p["b0"] + 5 * n
+    else:
+        assert 0 < into < len(W)
+        want = {"3.5": 3.5, "7.5": 7.5, "odd": 2.5}.get(layout)
+        assert want is None or 0 <= into - want * n <= 1
+        assert layout not in ("exact", "odd") or p["b0"] % 2 == 1
+    for w, r in zip(p["wants"], ref):
+        ec.same_search(w, r, p["b0"])
+    said = [ec.rule6(sc, ch, w, w["edge"], p["b0"]) for ch, w in zip(sc["chans"], p["wants"])]
+    assert said == {"groups5": ["edge", "none", None], "odd": ["edge"] * 4 + [None], "real": ["edge"]}[name]
+
+
+def test_rule6_on_the_origin_scenarios(scen):
+    """Rule 6 of DESIGN.md 3.2d against the synthesiser on the restatement: every acquired channel of odd, two and
+    twenty names the sample at which its satellite's bit was flipped."""
+    for name, want in (("odd", ["edge"] * 4 + [None]), ("two", ["edge", "edge", None]),
+                       ("twenty", ["edge", "edge", None])):
+        sc = ec.SCEN[name]
+        assert [ec.rule6(sc, ch, r, r["edge"], 0) for ch, r in zip(sc["chans"], scen(name)[2])] == want, name
+    # and it tells an edge off by one hypothesis, or a position that forgot where the span begins
+    sc, (r, *_) = ec.SCEN["odd"], scen("odd")[2]
+    with pytest.raises(AssertionError):
+        ec.rule6(sc, sc["chans"][0], r, r["edge"] - 3, 0)
+    with pytest.raises(AssertionError):
+        ec.rule6(sc, sc["chans"][0], r, r["edge"], 3 * 4092)
+    assert ec.rule6(sc, sc["chans"][0], r, r["edge"], 123) is None      # (callers assert what rule 6 said)
 
 
 def test_library_exports_and_mirror(gc):
