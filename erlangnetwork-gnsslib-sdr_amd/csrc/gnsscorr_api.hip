@@ -44,9 +44,9 @@ static int create_handles(gnsscorr_ctx *ctx, hipStream_t stream)
 {
     if (stream) ctx->stream.borrow(stream);
     else GC_TRY(ctx->stream.make());
-    for (GcStream *s : {&ctx->stream_plan, &ctx->stream_finish, &ctx->stream_discover}) GC_TRY(s->make());
-    for (GcEvent *ev : {&ctx->ev_spec, &ctx->ev_chain}) GC_TRY(ev->make());
-    for (GcEvent *ev : {ctx->ev_plan, ctx->ev_used, ctx->ev_corr, ctx->ev_fin})
+    for (GcStream *s : {&ctx->stream_plan, &ctx->stream_tables, &ctx->stream_discover}) GC_TRY(s->make());
+    GC_TRY(ctx->ev_spec.make());
+    for (GcEvent *ev : {ctx->ev_plan, ctx->ev_tab, ctx->ev_used, ctx->ev_corr})
         for (int i = 0; i < 2; i++) GC_TRY(ev[i].make());
     for (GcEvent &ev : ctx->ev_burst) GC_TRY(ev.make());
     return GNSSCORR_OK;
@@ -99,8 +99,6 @@ extern "C" int gnsscorr_sync(gnsscorr_ctx *ctx)
 {
     if (!ctx) return gc_fail(GNSSCORR_EINVAL, "null context");
     GC_HIP(hipSetDevice(ctx->device));
-    int rc = gc_outputs_ready(ctx);
-    if (rc) return rc;
     GC_HIP(hipStreamSynchronize(ctx->stream));
     return GNSSCORR_OK;
 }

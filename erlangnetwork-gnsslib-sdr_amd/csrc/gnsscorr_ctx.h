@@ -187,7 +187,9 @@ struct GcTrkStateBuf {
 };
 
 // What a tracking run of either kind (gnsscorr_trk_run, gc_trk_run_loop) leaves for the fetch calls, per channel set
-// (gc_ensure_trk_outputs, gnsscorr_trk.hip).  Every writer and reader of nsamp is on the main stream.
+// (gc_ensure_trk_outputs, gnsscorr_trk.hip).  nsamp and the two counters are written by the batched tracker's table
+// kernels on the tables stream (the closed loop's are on the main stream); their readers are on the main stream behind
+// the last batch's correlator, which stands behind every table kernel queued so far.
 struct GcTrkOut {
     GcDevBuf<double> dcorrI, dcorrQ;               // [unit][ntap]
     GcDevBuf<double> dsumI, dsumQ;                 // [nch][ntap] batch sums
@@ -196,8 +198,7 @@ struct GcTrkOut {
     GcDevBuf<int> dring_viol;                      // planned periods outside what the ring holds, since the last fetch
     size_t units = 0;                              // (channel, period) units the per-unit buffers are sized for
     int last_nepoch = 0;                           // periods per channel of the last completed run (0: none yet)
-    bool fin_pending = false;                      // the outputs become valid at the finish event of plan slot fin_slot
-    int fin_slot = 0;
+    bool fin_pending = false;                      // a batched run was issued and the streams have not been drained since
 };
 
 // One plan slot: the planner stream expands batch k+1 into one slot while batch k is correlated from the other
@@ -207,7 +208,7 @@ struct GcPlanSlot {
     GcDevBuf<GcRound> rounds;      // [unit][nseg][GC_MAXR]
     GcDevBuf<GcUnitSegs> segs;     // [unit]: the unit's carrier / code NCO piece tables
     GcDevBuf<int> partial;         // [ch][epoch][segment][2*ntap] int32 partial sums
-    bool fin_pending = false;      // the slot's ev_fin has been recorded and not been drained since
+    GcDevBuf<unsigned short> etab; // [unit][GC_EDGTAB] start samples of the batch's chip edges (trk_edges -> trk_corr)
 };
 
 // The batched tracker (gnsscorr_trk.hip): what gnsscorr_trk_run owns, per channel set.  The planner (a short sequential
@@ -221,7 +222,6 @@ struct GcBatch {
     // claims of the batch being planned (discovery pass -> chain), two buffers: while the chain of one batch reads
     // its claims the discovery pass of the NEXT batch fills the other one from the same input state, on its own stream
     GcDevBuf<int> dspec2[2];
-    GcDevBuf<unsigned short> detab;                // [unit][GC_EDGTAB] start samples of the batch's chip edges (main stream: trk_edges -> trk_corr)
     GcDevBuf<unsigned long long> dfinish;          // batch-sum scratch of trk_finish
     bool spec_pending = false;                     // the discovery stream has work whose end ev_spec marks
     bool spec_ahead_valid = false;                 // dspec2[spec_ahead_buf] holds claims for the batch that starts at spec_ahead_state
@@ -365,13 +365,13 @@ struct gnsscorr_ctx {
     // and their events are made by gnsscorr_create and live as long as the context; the structs hold no handle and are
     // replaced whole per channel set.
     GcStream stream_plan;                          // planner: the sequential chain (and the direct discovery)
-    GcStream stream_finish;                        // finish: partial sums -> outputs
+    GcStream stream_tables;                        // a batch's table kernels (expand, ring check, edges), beside the previous correlator
     GcStream stream_discover;                      // discovery of the next batch's claims, beside the chain
     GcEvent ev_plan[2];                            // per plan slot: plan finished (planner stream)
+    GcEvent ev_tab[2];                             // the slot's tables are built (tables stream): the correlator may read them
     GcEvent ev_used[2];                            // the main stream is done with what the slot held before: the planner may write it
-    GcEvent ev_corr[2];                            // correlator finished (main stream): slot consumed, partials ready
-    GcEvent ev_fin[2];                             // finish done (finish stream): outputs valid
-    GcEvent ev_spec, ev_chain;
+    GcEvent ev_corr[2];                            // correlator finished (main stream): the slot's tables are consumed
+    GcEvent ev_spec;                               // the claims made ahead are ready, and the tables that read the plan entries their chain rewrites are done (discovery stream)
     GcTrkStateBuf state;
     GcBatch batch;
     GcTrkOut out;
@@ -424,13 +424,12 @@ struct GcTimed {
     }
 };
 
-// gnsscorr_trk.hip.  gc_drain: the planner, finish, discovery and main streams are idle afterwards.  gc_quiesce: that
+// gnsscorr_trk.hip.  gc_drain: the planner, tables, discovery and main streams are idle afterwards.  gc_quiesce: that
 // (and the ingest stream when `ingest`), then drops the look-ahead plan and marks the state touched
 int gc_drain(gnsscorr_ctx *ctx);
 int gc_quiesce(gnsscorr_ctx *ctx, bool ingest = false);
-// the outputs of a run of nperiod periods per channel; the main stream waits for the last batch's; a fetch's counters
+// the outputs of a run of nperiod periods per channel; a fetch's counters
 int gc_ensure_trk_outputs(gnsscorr_ctx *ctx, int nperiod);
-int gc_outputs_ready(gnsscorr_ctx *ctx);
 int gc_nco_check(gnsscorr_ctx *ctx);
 // gnsscorr_acq.hip: makes ctx->fft on first use (tables, and the dynamic LDS sizes of the kernels that read them)
 int gc_acq_twiddles(gnsscorr_ctx *ctx);
@@ -438,7 +437,7 @@ int gc_ingest_fence(gnsscorr_ctx *ctx);      // orders the compute stream behind
 // both rings' write positions and the ingest fence together, under the lock (a grabber thread may be pushing): the
 // positions cover only samples whose transfer the compute stream is ordered behind
 int gc_ring_positions(gnsscorr_ctx *ctx, uint64_t wp_ring[2]);
-// the closed loop takes the tracking state: quiesces if the batched interface has a look-ahead plan or a finish pending;
+// the closed loop takes the tracking state: quiesces if the batched interface has a look-ahead plan or a batch in flight;
 // either way no plan is valid afterwards and the state is marked touched (the batched tracker plans afresh)
 int gc_loop_take_state(gnsscorr_ctx *ctx);
 // gnsscorr_acq.hip: one search over a channel list; the device hand-over of its acquired channels into the closed loop

@@ -823,13 +823,12 @@ int gc_launch_trk_finish(hipStream_t st, const int *partial, double *corrI, doub
 }
 
 // ---- the host driver ("Four streams") ---------------------------------------------------------
-// The planner, finish, discovery and main streams are idle afterwards: no finish is pending any more.
+// The planner, tables, discovery and main streams are idle afterwards: no batch is in flight any more.
 int gc_drain(gnsscorr_ctx *ctx)
 {
-    for (hipStream_t s : {ctx->stream_plan.s, ctx->stream_finish.s, ctx->stream_discover.s, ctx->stream.s})
+    for (hipStream_t s : {ctx->stream_plan.s, ctx->stream_tables.s, ctx->stream_discover.s, ctx->stream.s})
         GC_HIP(hipStreamSynchronize(s));
     ctx->out.fin_pending = false;
-    for (GcPlanSlot &s : ctx->batch.slot) s.fin_pending = false;
     return GNSSCORR_OK;
 }
 
@@ -844,16 +843,10 @@ int gc_quiesce(gnsscorr_ctx *ctx, bool ingest)
 
 int gc_loop_take_state(gnsscorr_ctx *ctx)
 {
-    // the look-ahead planner works on the same state: stop it, drop its plan (with neither a plan nor a finish in
+    // the look-ahead planner works on the same state: stop it, drop its plan (with neither a plan nor a batch in
     // flight there is nothing to wait for)
     if (ctx->batch.ahead_valid || ctx->out.fin_pending) return gc_quiesce(ctx);
     ctx->state.touched = true;
-    return GNSSCORR_OK;
-}
-
-int gc_outputs_ready(gnsscorr_ctx *ctx)
-{
-    if (ctx->out.fin_pending) GC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_fin[ctx->out.fin_slot], 0));
     return GNSSCORR_OK;
 }
 
@@ -901,9 +894,9 @@ static int ensure_batch_buffers(gnsscorr_ctx *ctx, int nepoch)
         GC_RESERVE(ctx, s.unit, units);
         GC_RESERVE(ctx, s.rounds, units * b.nseg * GC_MAXR);
         GC_RESERVE(ctx, s.segs, units);
+        GC_RESERVE(ctx, s.etab, units * GC_EDGTAB);
     }
     for (int i = 0; i < 2; i++) GC_RESERVE(ctx, b.dspec2[i], gc_trk_spec_ints(units));
-    GC_RESERVE(ctx, b.detab, units * GC_EDGTAB);
     GC_RESERVE(ctx, b.dfinish, (size_t)ctx->nch * GC_FINISH_SCRATCH);
     GC_HIP(hipMemsetAsync(b.dfinish, 0, sizeof(unsigned long long) * ctx->nch * GC_FINISH_SCRATCH, ctx->stream));
     b.units = units;
@@ -911,15 +904,19 @@ static int ensure_batch_buffers(gnsscorr_ctx *ctx, int nepoch)
 }
 
 // Plans a batch of nepoch periods from the committed state into slot s, on the planner stream: the batch's claims
-// (discovered ahead, or now), the next batch's discovery beside the chain, the chain; the slot's ev_plan marks it ready
-static int plan_into(gnsscorr_ctx *ctx, int s, int nepoch)
+// (discovered ahead, or now), the next batch's discovery beside the chain, the chain; the slot's ev_plan marks it ready.
+// gate: what the planner stream's work in front of this plan ends with (the previous chain's ev_plan; ev_used for a
+// plan made on the spot).  Between two chains the planner stream carries one wait (for the claims) and one record
+// (ev_plan), nothing else: the chains bound the step, and every packet between them is microseconds of it.
+static int plan_into(gnsscorr_ctx *ctx, int s, int nepoch, hipEvent_t gate)
 {
     GcBatch &b = ctx->batch;
     GcPlanSlot &sl = b.slot[s];
     hipStream_t ps = ctx->stream_plan;
-    // the slot's partial sums were last read by the finish of two batches ago: ordering the plan
-    // behind it lets ev_plan stand for "the slot is free and planned" on the main stream
-    if (sl.fin_pending) GC_HIP(hipStreamWaitEvent(ps, ctx->ev_fin[s], 0));
+    // The chain writes nothing of the slot but its plan entries, last read by the tables of two batches ago (ev_tab[s]);
+    // the slot's other buffers are waited for by the streams that write them (correlate_slot).  Claims discovered ahead
+    // carry that wait: ev_spec was recorded behind it (below, a batch ago).  A plan made on the spot stands behind
+    // ev_used, which has seen every ev_tab.
     // claims of this batch: discovered ahead (while the previous batch's chain ran, from that batch's
     // input state) if nothing has touched the state since, else discovered now from the state itself
     const GcTrkState *sin = ctx->state.cur();
@@ -929,6 +926,7 @@ static int plan_into(gnsscorr_ctx *ctx, int s, int nepoch)
         buf = b.spec_ahead_buf;
     } else {
         buf = 0;
+        GC_HIP(hipStreamWaitEvent(ps, ctx->ev_tab[s], 0));
         GcTimed t(ctx, "trk_spec", ps);
         GC_TRY(gc_launch_trk_spec(ps, ctx->dchan, sin, ctx->nch, nepoch, b.dspec2[buf], 0));
     }
@@ -936,15 +934,17 @@ static int plan_into(gnsscorr_ctx *ctx, int s, int nepoch)
     b.spec_pending = false;
     b.spec_last_buf = buf;
     b.spec_last_units = ctx->nch * nepoch;
-    // the next batch's claims, from the same input state, beside this batch's chain (the other buffer
-    // was last read by the chain in front of this one on the planner stream)
-    GC_HIP(hipEventRecord(ctx->ev_chain, ps));
-    GC_HIP(hipStreamWaitEvent(ctx->stream_discover, ctx->ev_chain, 0));
+    // the next batch's claims, from the same input state, beside this batch's chain: behind the gate (the other buffer
+    // was last read, and the input state written, by the chain in front of this one on the planner stream).  ev_spec
+    // is recorded behind the tables that read the plan entries the chain on these claims will rewrite (the other slot's,
+    // as last queued): the discovery itself does not wait for them, and they end long before it does.
+    GC_HIP(hipStreamWaitEvent(ctx->stream_discover, gate, 0));
     {
         GcTimed t(ctx, "trk_spec", ctx->stream_discover);
         GC_TRY(gc_launch_trk_spec(ctx->stream_discover, ctx->dchan, sin, ctx->nch, nepoch, b.dspec2[buf ^ 1], nepoch));
-        GC_HIP(hipEventRecord(ctx->ev_spec, ctx->stream_discover));
     }
+    GC_HIP(hipStreamWaitEvent(ctx->stream_discover, ctx->ev_tab[s ^ 1], 0));
+    GC_HIP(hipEventRecord(ctx->ev_spec, ctx->stream_discover));
     b.spec_pending = true;
     b.spec_ahead_valid = true;
     b.spec_ahead_buf = buf ^ 1;
@@ -958,53 +958,63 @@ static int plan_into(gnsscorr_ctx *ctx, int s, int nepoch)
     return GNSSCORR_OK;
 }
 
-// The main-stream body of a batch planned into slot s: expand, ring check (wr: what it may take as written), edges, one
-// correlator launch per dtype; the slot's ev_corr marks the slot consumed and its partial sums ready
+// A batch planned into slot s.  Its table kernels -- expand, ring check (wr: what it may take as written), edges -- go
+// to the tables stream, behind the slot's plan and behind the correlator that last read the slot's tables (two
+// batches ago) -- and, for now, behind the previous batch's correlator (below) -- off the main stream, beside the next
+// chain and the previous batch's finish; the slot's ev_tab marks them built.  The main stream carries one correlator launch per dtype, behind ev_tab; the slot's ev_corr marks the
+// tables consumed.
 static int correlate_slot(gnsscorr_ctx *ctx, int s, int nepoch, const uint64_t wr[2])
 {
     GcBatch &b = ctx->batch;
     GcPlanSlot &sl = b.slot[s];
-    // the per-unit constants and NCO tables of the planned periods: on the main stream, in front of the
-    // correlator that reads them (the planner stream carries nothing but the sequential chain)
+    hipStream_t ts = ctx->stream_tables;
+    GC_HIP(hipStreamWaitEvent(ts, ctx->ev_plan[s], 0));
+    GC_HIP(hipStreamWaitEvent(ts, ctx->ev_corr[s], 0));        // (never recorded, or drained since: no wait)
+    // Not a data dependency: the tables also start behind the previous batch's correlator.  While the chain bounds the
+    // step that correlator ends ~25 us after the plan is ready; tables that start in those 25 us run beside the
+    // correlator's tail at the moment the next chain is launched, end no earlier (trk_expand 92 us there, 64 alone),
+    // and the chain is ~16 us longer for it (measured: DESIGN 6).  Once the chain is shorter than tables + correlator
+    // this wait puts the tables back into the cycle and has to go.
+    GC_HIP(hipStreamWaitEvent(ts, ctx->ev_corr[s ^ 1], 0));
+    // the per-unit constants and NCO tables of the planned periods
     {
-        GcTimed t(ctx, "trk_expand");
-        GC_TRY(gc_launch_trk_expand(ctx->stream, ctx->dchan, sl.plan, sl.unit, sl.segs, ctx->out.nsamp, ctx->nch, nepoch,
+        GcTimed t(ctx, "trk_expand", ts);
+        GC_TRY(gc_launch_trk_expand(ts, ctx->dchan, sl.plan, sl.unit, sl.segs, ctx->out.nsamp, ctx->nch, nepoch,
                                     sl.rounds, b.nseg, ctx->max_n, ctx->out.dnco_overflow));
     }
     // the planned periods against what the rings hold now
     // (the write positions travel as kernel arguments: no copy, no host synchronisation per batch)
-    GC_TRY(launch_trk_ringcheck(ctx->stream, ctx->dchan, sl.plan, (const int8_t *)ctx->ring[0].mem, wr[0], wr[1], ctx->nch,
+    GC_TRY(launch_trk_ringcheck(ts, ctx->dchan, sl.plan, (const int8_t *)ctx->ring[0].mem, wr[0], wr[1], ctx->nch,
                                 nepoch, ctx->out.dring_viol));
     {
         // start samples of the periods' chip edges, for the correlator's look-up phase
-        GcTimed t(ctx, "trk_edges");
-        GC_TRY(launch_trk_edges(ctx->stream, ctx->dchan, sl.unit, sl.segs, b.detab, ctx->nch, nepoch));
+        GcTimed t(ctx, "trk_edges", ts);
+        GC_TRY(launch_trk_edges(ts, ctx->dchan, sl.unit, sl.segs, sl.etab, ctx->nch, nepoch));
     }
+    GC_HIP(hipEventRecord(ctx->ev_tab[s], ts));                // tables built, plan entries consumed
+    GC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_tab[s], 0));
     for (int dtype = 1; dtype <= 2; dtype++) {
         if (!ctx->have_dtype[dtype]) continue;
         GcTimed t(ctx, "trk_corr");
         GC_TRY(gc_launch_trk_corr(ctx->stream, ctx->dchan, sl.unit, sl.segs, sl.rounds, sl.partial, ctx->nch, nepoch, b.nseg,
-                                  ctx->ntap, dtype, ctx->ntap, ctx->max_n, ctx->smax_max, b.detab));
+                                  ctx->ntap, dtype, ctx->ntap, ctx->max_n, ctx->smax_max, sl.etab));
     }
-    GC_HIP(hipEventRecord(ctx->ev_corr[s], ctx->stream));     // slot buffers consumed, partials ready
+    GC_HIP(hipEventRecord(ctx->ev_corr[s], ctx->stream));     // the slot's tables are consumed
     return GNSSCORR_OK;
 }
 
-// The finish of slot s on its own stream: the main stream goes straight from this batch's correlator to the next
-// one's, the outputs become valid at the slot's ev_fin
+// The finish of slot s, on the main stream behind the slot's correlator: the stream has room for it (the planner's
+// chain is longer than correlator + finish), and the next batch's correlator, which rewrites the other slot's partial
+// sums, needs no event to stand behind the finish that read them.  What the caller queues on the main stream after
+// trk_run sees the outputs.
 static int finish_slot(gnsscorr_ctx *ctx, int s, int nepoch)
 {
     GcBatch &b = ctx->batch;
     GcTrkOut &o = ctx->out;
-    hipStream_t fs = ctx->stream_finish;
-    GC_HIP(hipStreamWaitEvent(fs, ctx->ev_corr[s], 0));
-    GcTimed t(ctx, "trk_finish", fs);
-    GC_TRY(gc_launch_trk_finish(fs, b.slot[s].partial, o.dcorrI, o.dcorrQ, o.dsumI, o.dsumQ, b.dfinish, ctx->nch, nepoch,
-                                b.nseg, ctx->ntap));
-    GC_HIP(hipEventRecord(ctx->ev_fin[s], fs));
-    b.slot[s].fin_pending = true;
+    GcTimed t(ctx, "trk_finish");
+    GC_TRY(gc_launch_trk_finish(ctx->stream, b.slot[s].partial, o.dcorrI, o.dcorrQ, o.dsumI, o.dsumQ, b.dfinish, ctx->nch,
+                                nepoch, b.nseg, ctx->ntap));
     o.fin_pending = true;
-    o.fin_slot = s;
     return GNSSCORR_OK;
 }
 
@@ -1029,9 +1039,8 @@ extern "C" int gnsscorr_trk_run(gnsscorr_ctx *ctx, int nepoch)
         // order after whatever the main stream did to the state / buffers
         GC_HIP(hipEventRecord(ctx->ev_used[cur], ctx->stream));
         GC_HIP(hipStreamWaitEvent(ps, ctx->ev_used[cur], 0));
-        GC_TRY(plan_into(ctx, cur, nepoch));
+        GC_TRY(plan_into(ctx, cur, nepoch, ctx->ev_used[cur]));
     }
-    GC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_plan[cur], 0));
     GC_TRY(correlate_slot(ctx, cur, nepoch, wr));
     // every launch of the batch was issued: only now the plan's output state becomes the committed one
     b.ahead_valid = false;
@@ -1039,8 +1048,9 @@ extern "C" int gnsscorr_trk_run(gnsscorr_ctx *ctx, int nepoch)
     b.plan_slot ^= 1;
     // ---- look ahead: plan the next batch of the same length while this one is correlated ----
     if (!ctx->state.touched) {
-        GC_HIP(hipStreamWaitEvent(ps, ctx->ev_corr[b.plan_slot], 0));        // its previous contents were consumed
-        GC_TRY(plan_into(ctx, b.plan_slot, nepoch));
+        // (the chain does not wait for the correlator or the finish of the batch the slot held, and for the tables
+        // that read its plan entries only through its claims: plan_into)
+        GC_TRY(plan_into(ctx, b.plan_slot, nepoch, ctx->ev_plan[cur]));
         b.ahead_valid = true;
         b.ahead_nepoch = nepoch;
     }
@@ -1076,7 +1086,6 @@ extern "C" int gnsscorr_trk_fetch(gnsscorr_ctx *ctx, double *trkII, double *trkQ
 {
     if (!ctx || !ctx->out.last_nepoch) return gc_fail(GNSSCORR_ESTATE, "trk_fetch: no completed trk_run");
     GC_HIP(hipSetDevice(ctx->device));
-    GC_TRY(gc_outputs_ready(ctx));
     const GcTrkOut &o = ctx->out;
     const size_t units = (size_t)ctx->nch * o.last_nepoch;
     if (trkII) GC_HIP(hipMemcpyAsync(trkII, o.dcorrQ, sizeof(double) * units * ctx->ntap, hipMemcpyDeviceToHost, ctx->stream));
@@ -1091,7 +1100,6 @@ extern "C" int gnsscorr_trk_fetch_sums(gnsscorr_ctx *ctx, double *sumI, double *
     if (!ctx || !ctx->out.last_nepoch) return gc_fail(GNSSCORR_ESTATE, "trk_fetch_sums: no completed trk_run");
     if (ctx->loop.last_nper) return gc_fail(GNSSCORR_ESTATE, "trk_fetch_sums: the last run was closed loop (its sums are in gnsscorr_loop_get)");
     GC_HIP(hipSetDevice(ctx->device));
-    GC_TRY(gc_outputs_ready(ctx));
     const size_t n = (size_t)ctx->nch * ctx->ntap;
     if (sumI) GC_HIP(hipMemcpyAsync(sumI, ctx->out.dsumQ, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
     if (sumQ) GC_HIP(hipMemcpyAsync(sumQ, ctx->out.dsumI, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -1102,7 +1110,7 @@ extern "C" int gnsscorr_trk_fetch_sums(gnsscorr_ctx *ctx, double *sumI, double *
 extern "C" int gnsscorr_trk_devptrs(gnsscorr_ctx *ctx, void **trkII, void **trkQQ)
 {
     if (!ctx || !ctx->out.dcorrI) return gc_fail(GNSSCORR_ESTATE, "trk_devptrs: no trk_run yet");
-    GC_TRY(gc_outputs_ready(ctx));     // work queued on the context stream after this sees them
+    // (the finish is the context stream's own work: what is queued there after this sees the outputs)
     if (trkII) *trkII = ctx->out.dcorrQ;
     if (trkQQ) *trkQQ = ctx->out.dcorrI;
     return GNSSCORR_OK;

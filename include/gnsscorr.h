@@ -571,7 +571,7 @@ int  gnsscorr_spec_fetch(gnsscorr_ctx *ctx, double *s, size_t s_cap,
  * "trk_finish", "acq_fwd", "acq_corr", "acq_code", "acq_final", "spec_psd",
  * "spec_sum", "spec_hist", "fec_viterbi27", "rx_lock").
  * on = 1: every kernel; on = 2: only the two correlator kernels ("trk_corr",
- * "acq_corr"), leaving the planner and finish streams free of events; 0: off */
+ * "acq_corr"), leaving the planner and tables streams free of events; 0: off */
 int  gnsscorr_timing_enable(gnsscorr_ctx *ctx, int on);
 int  gnsscorr_timing_read(gnsscorr_ctx *ctx, const char *kernel,
                           double *total_ms, int *launches);
