@@ -29,6 +29,7 @@ FEND_RTLSDR, FEND_FRTLSDR, FEND_FILE = 3, 8, 10
 MEMBUFFLEN, FILE_BUFFSIZE = 5000, 65536      # ref src/sdr.h:134,137
 ACQTH = 3.0                                  # ref src/sdr.h:148
 MAXFREQ, MAXCOH = 1024, 20                   # GNSSCORR_MAXFREQ, GNSSCORR_MAXCOH
+FINE_BINS = 256                              # GNSSCORR_FINE_BINS
 
 
 class GnsscorrError(RuntimeError):
@@ -169,6 +170,11 @@ class AcqRes(C.Structure):
                 ("iters", C.c_int), ("buffloc", C.c_uint64)]
 
 
+class AcqFine(C.Structure):
+    """gnsscorr_acqfine_t: the refined carrier frequency of one channel (gnsscorr_acq_fetch_fine)."""
+    _fields_ = [("finefreq", C.c_double), ("quality", C.c_double), ("q", C.c_int), ("nref", C.c_int)]
+
+
 CH_IDLE, CH_SEARCH, CH_TRACK = 0, 1, 2
 ACQSLEEP = 2000                              # ms, ref src/sdr.h:149
 
@@ -277,7 +283,8 @@ EXPORTS_GNSSCORR = [
     "gnsscorr_rx_step", "gnsscorr_rx_status", "gnsscorr_fec_run", "gnsscorr_sbasframe_replay",
     "gnsscorr_lock_run", "gnsscorr_rx_lock_set", "gnsscorr_rx_lock_status",
     "gnsscorr_acq_set_coherent", "gnsscorr_acq_get_coherent", "gnsscorr_g1frame_replay",
-    "gnsscorr_acq_set_bitedge", "gnsscorr_acq_get_bitedge", "gnsscorr_acq_fetch_edge"]
+    "gnsscorr_acq_set_bitedge", "gnsscorr_acq_get_bitedge", "gnsscorr_acq_fetch_edge",
+    "gnsscorr_acq_set_refine", "gnsscorr_acq_get_refine", "gnsscorr_acq_fetch_fine"]
 EXPORTS_SDR = [
     "sdracquisition", "checkacquisition", "sdrtracking", "cumsumcorr", "clearcumsumcorr", "pll", "dll",
     "readinifile", "chk_initvalue", "initacqstruct", "inittrkprmstruct", "inittrkstruct", "initsdrch",
@@ -344,6 +351,10 @@ def lib():
         L.gnsscorr_acq_set_bitedge.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.gnsscorr_acq_get_bitedge.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.gnsscorr_acq_fetch_edge.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    if hasattr(L, "gnsscorr_acq_set_refine"):       # (likewise: tools/acq_fine_time.py)
+        L.gnsscorr_acq_set_refine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.gnsscorr_acq_get_refine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.gnsscorr_acq_fetch_fine.argtypes = [C.c_void_p, C.POINTER(AcqFine), C.c_void_p]
     L.gnsscorr_fft16k.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     L.gnsscorr_pspec.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.gnsscorr_timing_enable.argtypes = [C.c_void_p, C.c_int]
@@ -478,11 +489,13 @@ class Channel:
     sdrini.fend / sdrini.rtlsdrppmerr: RTL-SDR file replay (FEND_FRTLSDR) offsets the channel by f_cf*ppmerr*1e-6.
     ncoh: code periods the search integrates coherently per group (gnsscorr_acq_set_coherent; 1: the reference's
     integration); estep: step of the bit-edge hypotheses of a group (gnsscorr_acq_set_bitedge; 0: none, otherwise
-    1 .. ncoh-1 with ncoh >= 2); Engine.set_channels applies both, ncoh first."""
+    1 .. ncoh-1 with ncoh >= 2); nref: code periods an acquired channel's carrier frequency is refined over
+    (gnsscorr_acq_set_refine; 0: none, otherwise 2 .. min(intg, MAXCOH)); Engine.set_channels applies them, in that
+    order."""
 
     def __init__(self, prn, ctype=CTYPE_L1CA, dtype=DTYPEIQ, ftype=FTYPE1, f_cf=1575.42e6,
                  f_sf=16.368e6, f_if=0.0, corrn=2, corrd=3, corrp=3, hband=7000, step=200, intg=10,
-                 fend=FEND_FILE, ppmerr=0, ncoh=1, estep=0):
+                 fend=FEND_FILE, ppmerr=0, ncoh=1, estep=0, nref=0):
         self.prn, self.ctype, self.dtype, self.ftype = prn, ctype, dtype, ftype
         self.code, self.crate = gencode(prn, ctype)
         self.clen = len(self.code)
@@ -502,6 +515,7 @@ class Channel:
         self.intg = intg
         self.ncoh = ncoh
         self.estep = estep
+        self.nref = nref
         self.nfreq = 2 * (hband // step) + 1
         self.nfft = 2 * self.nsamp
         self.freq = np.array([f_if + ((i - (self.nfreq - 1) // 2) * float(step)) + self.foffset
@@ -612,6 +626,9 @@ class Engine:
         estep = [getattr(c, "estep", 0) for c in channels]
         if any(k != 0 for k in estep):
             self.acq_set_bitedge(estep)
+        nref = [getattr(c, "nref", 0) for c in channels]
+        if any(k != 0 for k in nref):
+            self.acq_set_refine(nref)
 
     # -- tracking
     def trk_set_state(self, states, ch0=0):
@@ -737,6 +754,30 @@ class Engine:
         arr = (C.c_int * len(self.channels))()
         _check(self._L.gnsscorr_acq_fetch_edge(self.h, arr))
         return list(arr)
+
+    def acq_set_refine(self, nref, ch0=0):
+        """Code periods channels ch0 .. ch0+len(nref)-1 refine their carrier frequency over after a search acquires
+        them (gnsscorr_acq_set_refine: 0 off, else 2 .. min(intg, MAXCOH)); set_channels resets every channel to 0 and
+        then applies the channels' own nref."""
+        arr = (C.c_int * len(nref))(*nref)
+        _check(self._L.gnsscorr_acq_set_refine(self.h, ch0, len(nref), arr))
+
+    def acq_get_refine(self, ch0=0, nch=None):
+        nch = len(self.channels) - ch0 if nch is None else nch
+        arr = (C.c_int * nch)()
+        _check(self._L.gnsscorr_acq_get_refine(self.h, ch0, nch, arr))
+        return list(arr)
+
+    def acq_fetch_fine(self, prompts=False):
+        """Per channel the refinement of the last search (gnsscorr_acq_fetch_fine): dicts of finefreq, quality, q and
+        nref (nref 0: none, finefreq is the bin centre).  prompts=True: also the prompt sums, int32 [nch][MAXCOH][2]
+        (I, Q of P_m, zero beyond nref)."""
+        nch = len(self.channels)
+        arr = (AcqFine * nch)()
+        P = np.zeros((nch, MAXCOH, 2), np.int32) if prompts else None
+        _check(self._L.gnsscorr_acq_fetch_fine(self.h, arr, P.ctypes.data if prompts else None))
+        fine = [dict(finefreq=a.finefreq, quality=a.quality, q=a.q, nref=a.nref) for a in arr]
+        return (fine, P) if prompts else fine
 
     def acq_fetch(self):
         arr = (AcqRes * len(self.channels))()

@@ -39,6 +39,11 @@
 // into the power accumulators: that row alone is added.  Channels without hypotheses run the instances they always ran,
 // in a launch of their own.
 //
+// Carrier refinement (gnsscorr_acq_set_refine): a listed channel with nref > 0 that acq_final acquired
+// gets, behind it, the nref prompt correlations from its buffloc on at the bin centre (acq_fine_nco, acq_prompt) and a
+// line search over their squares (acq_fine); both hand-overs then start from that frequency.  No result row is
+// written, and a search without such a channel queues none of the three.
+//
 // Every run works on a channel list (gnsscorr_acq_run_subset; gnsscorr_acq_run is the list 0..nch-1): the
 // per-channel kernels take their channel from a compacted device list, acq_fwd its frequency grid from the
 // list of grids that have a listed channel, so grid sizes follow the list.  Everything a channel owns (code
@@ -783,11 +788,11 @@ __global__ __launch_bounds__(512) void acq_corr64_kernel(
 
 // The tracking state an acquired channel starts with, where sdracquisition() leaves it (ref src/sdracq.c:51-55:
 // trk.carrfreq = acq.acqfreq, trk.codefreq = crate, code and carrier remainders zero, tracking from the returned
-// buffloc)
-__device__ __forceinline__ GcTrkState acq_start_state(const gnsscorr_acqres_t &r, const GcChan &c)
+// buffloc).  carrfreq: r.acqfreq, or the refined frequency of a channel that has one (acq_start_freq)
+__device__ __forceinline__ GcTrkState acq_start_state(const gnsscorr_acqres_t &r, const GcChan &c, double carrfreq)
 {
     GcTrkState s;
-    s.carrfreq = r.acqfreq;
+    s.carrfreq = carrfreq;
     s.codefreq = c.crate;
     s.remcode = 0.0;
     s.remcarr = 0.0;
@@ -838,6 +843,166 @@ __global__ __launch_bounds__(64) void acq_final_kernel(const GcChan *__restrict_
         edge_out[ch] = r.flagacq && c.estep > 0 ? edge : -1;
         if (iters_out) iters_out[ch] = r.flagacq ? it + 1 : ngroup;
     }
+}
+
+// ---- carrier refinement of the acquired channels (gnsscorr_acq_set_refine) ---------------------------
+// Behind acq_final, for the listed channels with nref > 0 that it acquired: the nref*nsamp samples from the returned
+// buffloc on are wiped off at the bin centre by one carrier walk (acq_fine_nco), correlated period by period with the
+// search's replica (acq_prompt: the hot path, one read of the span), and the squared prompt sums are searched for
+// their line on K = GNSSCORR_FINE_BINS frequencies (acq_fine).  Nothing here writes a gnsscorr_acqres_t.
+
+// the frequency a hand-over starts tracking from: the refined one where the last search refined the channel
+__device__ __forceinline__ double acq_start_freq(const gnsscorr_acqres_t &r, const gnsscorr_acqfine_t *__restrict__ fine,
+                                                 int ch)
+{
+    return fine && fine[ch].nref > 0 ? fine[ch].finefreq : r.acqfreq;
+}
+
+// one lane per list entry: the carrier piece table of the channel's refine span, in the form of acq_nco_kernel.  n = 0:
+// the channel is not refined (nref = 0, not acquired, or a table that overflowed -- counted, the run is reported)
+__global__ void acq_fine_nco_kernel(const GcChan *__restrict__ chan, const gnsscorr_acqres_t *__restrict__ res,
+                                    const int *__restrict__ list, int nlist, GcAcqCar *__restrict__ fcar,
+                                    int *__restrict__ overflow)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nlist) return;
+    const int ch = list[i];
+    const GcChan &c = chan[ch];
+    GcAcqCar *t = fcar + ch;
+    t->n = 0;
+    if (c.nref <= 0 || !res[ch].flagacq) return;
+    GcCarTable ct{t->k0, t->seg, GC_NCAR, 0, 0};
+    gc_carrier_walk(gc_carrier_phis(0.0), gc_carrier_ps(res[ch].acqfreq, c.ti), c.nref * c.nsamp, ct);
+    if (ct.overflow) atomicAdd(overflow, 1);
+    else t->n = ct.n;
+}
+
+typedef const __attribute__((address_space(1))) short *gc_gptr_i16;
+#define GC_PROMPT_NT 512
+
+// acq_prompt: grid (period m, list entry).  P_m = sum_k c[k] (I + iQ)[m n + k] over the wiped-off samples of period m of
+// the span, c the replica acq_code transforms; consecutive lanes read consecutive ring samples (an IQ pair as one
+// 16-bit load), int32 partial sums per lane (|I|, |Q| <= 2*32*128, n <= 32768: |P| < 2^28).
+__global__ __launch_bounds__(GC_PROMPT_NT) void acq_prompt_kernel(const GcChan *__restrict__ chan,
+                                                                  const gnsscorr_acqres_t *__restrict__ res,
+                                                                  const GcAcqCar *__restrict__ fcar,
+                                                                  const int *__restrict__ list, int nlist,
+                                                                  int *__restrict__ prompt)
+{
+    __shared__ int lk0[GC_NCAR];
+    __shared__ GcCarSeg lseg[GC_NCAR];
+    __shared__ int red[2][GC_PROMPT_NT / 64];
+    const int m = blockIdx.x, tid = threadIdx.x;
+    if ((int)blockIdx.y >= nlist) return;
+    const int ch = list[blockIdx.y];
+    const GcChan &c = chan[ch];
+    if (m >= c.nref || !res[ch].flagacq) return;
+    const GcAcqCar *gt = fcar + ch;
+    const int ncar = gt->n;
+    if (ncar <= 0) return;
+    if (tid < ncar) { lk0[tid] = gt->k0[tid]; lseg[tid] = gt->seg[tid]; }
+    __syncthreads();
+    const int n = c.nsamp, clen = c.clen, dtype = c.dtype;
+    const uint64_t ringlen = c.ringlen, base = res[ch].buffloc % ringlen;
+    const gc_gptr_i8 ring = (gc_gptr_i8)c.ring, code = (gc_gptr_i8)c.code;
+    const gc_gptr_i16 ring2 = (gc_gptr_i16)c.ring;
+    const double ci = __dmul_rn(c.ti, c.crate);
+    int sI = 0, sQ = 0;
+    for (int k = tid; k < n; k += GC_PROMPT_NT) {
+        // sample s of the span (s < nref*n <= intg*n < ringlen: the ring wraps at most once, as in acq_fwd's mixed())
+        const int s = m * n + k;
+        uint64_t pos = base + (uint64_t)s;
+        if (pos >= ringlen) pos -= ringlen;
+        const int idx = gc_carrier_idx_at(lk0, lseg, ncar, s);
+        const int cs_ = aCos32[idx], sn_ = aSin32[idx];
+        int I, Q;
+        if (dtype == 2) {
+            const int v = ring2[pos];
+            const int d0 = (signed char)(v & 0xff), d1 = v >> 8;
+            I = cs_ * d0 - sn_ * d1;
+            Q = sn_ * d0 + cs_ * d1;
+        } else {
+            const int d0 = ring[pos];
+            I = cs_ * d0;
+            Q = sn_ * d0;
+        }
+        long long t = (long long)__dmul_rn((double)k, ci);         // the replica value, as acq_code forms it
+        while (t >= clen) t -= clen;
+        const int cv = code[(int)t];
+        sI += cv * I;
+        sQ += cv * Q;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        sI += __shfl_xor(sI, o, 64);
+        sQ += __shfl_xor(sQ, o, 64);
+    }
+    if ((tid & 63) == 0) { red[0][tid >> 6] = sI; red[1][tid >> 6] = sQ; }
+    __syncthreads();
+    if (tid == 0) {
+        int pI = 0, pQ = 0;
+#pragma unroll
+        for (int w = 0; w < GC_PROMPT_NT / 64; w++) { pI += red[0][w]; pQ += red[1][w]; }
+        reinterpret_cast<int2 *>(prompt)[(size_t)ch * GNSSCORR_MAXCOH + m] = make_int2(pI, pQ);
+    }
+}
+
+// acq_fine: one wavefront per list entry.  S_m = P_m^2 (exact in int64, then fp64), Z[q] = sum_m S_m exp(+2 pi i
+// ((q m) mod K)/K) with the lanes over q = -K/2 .. K/2-1, the largest |Z|^2 (lowest q on ties) over the wavefront, one
+// gnsscorr_acqfine_t; a listed channel without refinement gets finefreq = acqfreq and zeros (its prompt row was cleared
+// with the others' tails before acq_prompt).
+__global__ __launch_bounds__(64) void acq_fine_kernel(const GcChan *__restrict__ chan,
+                                                      const gnsscorr_acqres_t *__restrict__ res,
+                                                      const GcAcqCar *__restrict__ fcar, const int *__restrict__ list,
+                                                      int nlist, const int *__restrict__ prompt,
+                                                      gnsscorr_acqfine_t *__restrict__ fine)
+{
+    constexpr int K = GNSSCORR_FINE_BINS;
+    __shared__ double sr[GNSSCORR_MAXCOH], si[GNSSCORR_MAXCOH], sa[GNSSCORR_MAXCOH];
+    const int lane = threadIdx.x;
+    if ((int)blockIdx.x >= nlist) return;
+    const int ch = list[blockIdx.x];
+    const GcChan &c = chan[ch];
+    const gnsscorr_acqres_t r = res[ch];
+    gnsscorr_acqfine_t f;
+    f.finefreq = r.acqfreq; f.quality = 0.0; f.q = 0; f.nref = 0;
+    const int nref = c.nref;
+    if (nref > 0 && r.flagacq && fcar[ch].n > 0) {
+        if (lane < nref) {
+            const long long I = prompt[((size_t)ch * GNSSCORR_MAXCOH + lane) * 2];
+            const long long Q = prompt[((size_t)ch * GNSSCORR_MAXCOH + lane) * 2 + 1];
+            sr[lane] = (double)(I * I - Q * Q);
+            si[lane] = (double)(2 * I * Q);
+            sa[lane] = (double)(I * I + Q * Q);      // |S_m| = |P_m|^2
+        }
+        __syncthreads();
+        double den = 0.0;
+        for (int m = 0; m < nref; m++) den += sa[m];
+        MaxIdx best; best.v = -1.0; best.k = 0x7fffffff;
+        for (int q = lane - K / 2; q < K / 2; q += 64) {
+            double zr = 0.0, zi = 0.0;
+            for (int m = 0; m < nref; m++) {
+                double sn, cs;
+                sincospi(2.0 * (double)((q * m) & (K - 1)) / (double)K, &sn, &cs);
+                zr += sr[m] * cs - si[m] * sn;
+                zi += sr[m] * sn + si[m] * cs;
+            }
+            MaxIdx t; t.v = zr * zr + zi * zi; t.k = q;
+            best = better(best, t);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            MaxIdx t;
+            t.v = __shfl_xor(best.v, o, 64);
+            t.k = __shfl_xor(best.k, o, 64);
+            best = better(best, t);
+        }
+        f.q = best.k;
+        f.nref = nref;
+        f.finefreq = __dadd_rn(r.acqfreq, __ddiv_rn((double)best.k, 2.0 * (double)K * c.ctime));
+        f.quality = den > 0.0 ? best.v / (den * den) : 0.0;
+    }
+    if (lane == 0) fine[ch] = f;
 }
 
 __global__ void fill_int_kernel(int *p, const GcChan *__restrict__ chan, const int *__restrict__ list, int nlist)
@@ -1045,6 +1210,15 @@ int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chl
     if (rc) return rc;
     const GcFftTables &f = ctx->fft;
     GcAcq *w = &ctx->acq;
+    // carrier refinement: only when a listed channel asks for it (the buffers are made by the first such search)
+    int maxref = 0;
+    for (int ch : list) maxref = ctx->hchan[ch].nref > maxref ? ctx->hchan[ch].nref : maxref;
+    if (maxref) {
+        GC_RESERVE(ctx, w->fcar, nch);
+        GC_RESERVE(ctx, w->fcar_overflow, 1);
+        GC_RESERVE(ctx, w->prompt, (size_t)nch * GNSSCORR_MAXCOH * 2);
+        GC_RESERVE(ctx, w->fine, nch);
+    }
     // the grids that have a listed channel, in grid order
     std::vector<int> glist;
     for (int g = 0; g < w->ngrid; g++) {
@@ -1125,6 +1299,31 @@ int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chl
                            w->maxintg);
     }
     GC_HIP(hipGetLastError());
+    w->refined = false;
+    if (maxref) {
+        // unlisted channels: a zero row, as in res; every prompt row starts from zero (rows without refinement and
+        // the periods beyond a channel's nref stay so)
+        if (n < nch) GC_HIP(hipMemsetAsync(w->fine, 0, sizeof(gnsscorr_acqfine_t) * nch, ctx->stream));
+        GC_HIP(hipMemsetAsync(w->prompt, 0, sizeof(int) * (size_t)nch * GNSSCORR_MAXCOH * 2, ctx->stream));
+        GC_HIP(hipMemsetAsync(w->fcar_overflow, 0, sizeof(int), ctx->stream));
+        {
+            GcTimed t(ctx, "acq_fine_nco");
+            hipLaunchKernelGGL(acq_fine_nco_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, ctx->dchan, w->res,
+                               dlist, n, w->fcar, w->fcar_overflow);
+        }
+        {
+            GcTimed t(ctx, "acq_prompt");
+            hipLaunchKernelGGL(acq_prompt_kernel, dim3(maxref, n), dim3(GC_PROMPT_NT), 0, ctx->stream, ctx->dchan,
+                               w->res, w->fcar, dlist, n, w->prompt);
+        }
+        {
+            GcTimed t(ctx, "acq_fine");
+            hipLaunchKernelGGL(acq_fine_kernel, dim3(n), dim3(64), 0, ctx->stream, ctx->dchan, w->res, w->fcar, dlist, n,
+                               w->prompt, w->fine);
+        }
+        GC_HIP(hipGetLastError());
+        w->refined = true;
+    }
     w->listed = listed;
     w->ran = true;
     return GNSSCORR_OK;
@@ -1164,13 +1363,46 @@ extern "C" int gnsscorr_acq_fetch_edge(gnsscorr_ctx *ctx, int *edge)
     return GNSSCORR_OK;
 }
 
+// The refinement of the last search (include/gnsscorr.h).  A search that queued none (no listed channel with nref > 0)
+// left rule 8 for every channel: finefreq = acqfreq of its result row, zeros.
+extern "C" int gnsscorr_acq_fetch_fine(gnsscorr_ctx *ctx, gnsscorr_acqfine_t *fine, int32_t *prompt)
+{
+    if (!ctx || !ctx->acq.ran) return gc_fail(GNSSCORR_ESTATE, "acq_fetch_fine: no acq_run yet");
+    if (!fine) return gc_fail(GNSSCORR_EINVAL, "acq_fetch_fine: null result array");
+    GC_HIP(hipSetDevice(ctx->device));
+    GcAcq *w = &ctx->acq;
+    const int nch = ctx->nch;
+    const size_t np = (size_t)nch * GNSSCORR_MAXCOH * 2;
+    if (!w->refined) {
+        std::vector<gnsscorr_acqres_t> res(nch);
+        GC_TRY(gnsscorr_acq_fetch(ctx, res.data()));
+        for (int i = 0; i < nch; i++) {
+            fine[i].finefreq = res[i].acqfreq;
+            fine[i].quality = 0.0;
+            fine[i].q = 0;
+            fine[i].nref = 0;
+        }
+        if (prompt) memset(prompt, 0, sizeof(int32_t) * np);
+        return GNSSCORR_OK;
+    }
+    int over = 0;
+    GC_HIP(hipMemcpyAsync(fine, w->fine, sizeof(gnsscorr_acqfine_t) * nch, hipMemcpyDeviceToHost, ctx->stream));
+    if (prompt) GC_HIP(hipMemcpyAsync(prompt, w->prompt, sizeof(int32_t) * np, hipMemcpyDeviceToHost, ctx->stream));
+    GC_HIP(hipMemcpyAsync(&over, w->fcar_overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));
+    if (over)
+        return gc_fail(GNSSCORR_EINVAL, "acquisition: %d refine spans need more carrier NCO pieces than the tables hold", over);
+    return GNSSCORR_OK;
+}
+
 // Acquired channels start tracking from acq_start_state(); channels that were not acquired keep their state.
+// fine: the last search's refinement, null when it queued none.
 __global__ void acq_to_trk_kernel(const GcChan *__restrict__ chan, const gnsscorr_acqres_t *__restrict__ res,
-                                  GcTrkState *__restrict__ state, int nch)
+                                  const gnsscorr_acqfine_t *__restrict__ fine, GcTrkState *__restrict__ state, int nch)
 {
     const int ch = blockIdx.x * blockDim.x + threadIdx.x;
     if (ch >= nch || !res[ch].flagacq) return;
-    state[ch] = acq_start_state(res[ch], chan[ch]);
+    state[ch] = acq_start_state(res[ch], chan[ch], acq_start_freq(res[ch], fine, ch));
 }
 
 extern "C" int gnsscorr_trk_start_from_acq(gnsscorr_ctx *ctx)
@@ -1180,7 +1412,7 @@ extern "C" int gnsscorr_trk_start_from_acq(gnsscorr_ctx *ctx)
     int rc = gc_quiesce(ctx);
     if (rc) return rc;
     hipLaunchKernelGGL(acq_to_trk_kernel, dim3((ctx->nch + 63) / 64), dim3(64), 0, ctx->stream, ctx->dchan,
-                       ctx->acq.res, ctx->state.cur(), ctx->nch);
+                       ctx->acq.res, ctx->acq.refined ? ctx->acq.fine.p : nullptr, ctx->state.cur(), ctx->nch);
     GC_HIP(hipGetLastError());
     return GNSSCORR_OK;
 }
@@ -1191,6 +1423,7 @@ extern "C" int gnsscorr_trk_start_from_acq(gnsscorr_ctx *ctx)
 // / initnavstruct() leave it (ref src/sdrinit.c:432-480,485-560: zero) and cnt = 0.  That is gnsscorr_loop_t from
 // flagsync up to prn and from biti to the end.
 __global__ __launch_bounds__(64) void acq_to_loop_kernel(const GcChan *__restrict__ chan, const gnsscorr_acqres_t *__restrict__ res,
+                                                         const gnsscorr_acqfine_t *__restrict__ fine,
                                                          GcTrkState *__restrict__ state, gnsscorr_loop_t *__restrict__ loop,
                                                          const int *__restrict__ list, int nlist)
 {
@@ -1207,8 +1440,9 @@ __global__ __launch_bounds__(64) void acq_to_loop_kernel(const GcChan *__restric
     for (int k = a0 + tid; k < a1; k += 64) w[k] = 0;
     for (int k = b0 + tid; k < b1; k += 64) w[k] = 0;
     if (tid == 0) {
-        loop[ch].acqfreq = r.acqfreq;
-        state[ch] = acq_start_state(r, chan[ch]);
+        const double freq = acq_start_freq(r, fine, ch);
+        loop[ch].acqfreq = freq;
+        state[ch] = acq_start_state(r, chan[ch], freq);
     }
 }
 
@@ -1219,7 +1453,7 @@ int gc_acq_handover(gnsscorr_ctx *ctx, bool quiesce)
     if (quiesce) { int rc = gc_quiesce(ctx); if (rc) return rc; }
     const int n = (int)ctx->acq.list.size();
     hipLaunchKernelGGL(acq_to_loop_kernel, dim3(n), dim3(64), 0, ctx->stream, ctx->dchan, ctx->acq.res,
-                       ctx->state.cur(), ctx->loop.dloop, ctx->acq.d_list, n);
+                       ctx->acq.refined ? ctx->acq.fine.p : nullptr, ctx->state.cur(), ctx->loop.dloop, ctx->acq.d_list, n);
     GC_HIP(hipGetLastError());
     return GNSSCORR_OK;
 }

@@ -477,6 +477,7 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
         freqs.insert(freqs.end(), d.freq, d.freq + d.nfreq);
         g.ncoh = 1;
         g.estep = 0;
+        g.nref = 0;
         if (g.smax > ctx->smax_max) ctx->smax_max = g.smax;
         if (d.nsamp + 100 > ctx->max_n) ctx->max_n = d.nsamp + 100;   // ref src/sdrtrk.c:23
     }
@@ -568,6 +569,33 @@ extern "C" int gnsscorr_acq_get_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, int
     if (!ctx || !estep || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
         return gc_fail(GNSSCORR_EINVAL, "acq_get_bitedge: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
     for (int i = 0; i < nch; i++) estep[i] = ctx->hchan[ch0 + i].estep;
+    return GNSSCORR_OK;
+}
+
+// Carrier refinement per channel (include/gnsscorr.h).  The forward spectra do not depend on it: the grids keep their
+// numbers, and what acquisition has prepared and the last search's results stay.
+extern "C" int gnsscorr_acq_set_refine(gnsscorr_ctx *ctx, int ch0, int nch, const int *nref)
+{
+    if (!ctx || !nref || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
+        return gc_fail(GNSSCORR_EINVAL, "acq_set_refine: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    for (int i = 0; i < nch; i++) {
+        const int intg = ctx->hchan[ch0 + i].intg, top = intg < GNSSCORR_MAXCOH ? intg : GNSSCORR_MAXCOH;
+        if (nref[i] < 0 || nref[i] == 1 || nref[i] > top)
+            return gc_fail(GNSSCORR_EINVAL, "acq_set_refine: channel %d: nref %d (0, or 2..%d = min(intg %d, %d))", ch0 + i,
+                           nref[i], top, intg, GNSSCORR_MAXCOH);
+    }
+    GC_HIP(hipSetDevice(ctx->device));
+    int rc = gc_quiesce(ctx);
+    if (rc) return rc;
+    for (int i = 0; i < nch; i++) ctx->hchan[ch0 + i].nref = nref[i];
+    return upload_channels(ctx);
+}
+
+extern "C" int gnsscorr_acq_get_refine(gnsscorr_ctx *ctx, int ch0, int nch, int *nref)
+{
+    if (!ctx || !nref || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
+        return gc_fail(GNSSCORR_EINVAL, "acq_get_refine: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    for (int i = 0; i < nch; i++) nref[i] = ctx->hchan[ch0 + i].nref;
     return GNSSCORR_OK;
 }
 

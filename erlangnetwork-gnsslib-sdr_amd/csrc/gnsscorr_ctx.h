@@ -308,6 +308,12 @@ struct GcAcq {
     GcDevBuf<gnsscorr_acqres_t> res;    // [ch]
     GcDevBuf<int> edge;         // [ch] bit edge of the deciding group's best row (gnsscorr_acq_fetch_edge), -1: none
     GcDevBuf<double> P;         // one channel's power array (on demand)
+    // carrier refinement (gnsscorr_acq_set_refine; made by the first search that lists a channel with nref > 0)
+    GcDevBuf<GcAcqCar> fcar;    // [ch] carrier table of the refine span: res[ch].acqfreq over nref*nsamp samples (n 0: none)
+    GcDevBuf<int> fcar_overflow;
+    GcDevBuf<int> prompt;       // [ch][GNSSCORR_MAXCOH][2] prompt sums (I, Q) of the span's periods, zero beyond nref
+    GcDevBuf<gnsscorr_acqfine_t> fine;  // [ch]
+    bool refined = false;       // the last search queued the refinement: fine and prompt hold its results
     int ngrid = 0, maxfreq = 0, maxintg = 0;    // maxintg: the largest iteration (group) count, intg / ncoh
     int maxslot = 0;                    // the largest iterations x H of a grid: X's slots (maxintg without hypotheses)
     std::vector<int> grid_chan;         // a representative channel per grid

@@ -447,6 +447,45 @@ int  gnsscorr_acq_set_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, const int *es
 int  gnsscorr_acq_get_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, int *estep);
 /* edge[nch] of the last search (above); synchronises.  GNSSCORR_ESTATE before a search. */
 int  gnsscorr_acq_fetch_edge(gnsscorr_ctx *ctx, int *edge);
+/* Carrier frequency refinement of acquired channels (opt-in per channel).  A search returns acqfreq as
+ * the centre of the best Doppler bin; a channel with nref > 0 that the search lists and acquires also gets a refined
+ * frequency, and both hand-overs and the receiver schedule then start tracking from it (carrfreq and the loop's
+ * acqfreq).  nref = 0 switches it off, is the default and what gnsscorr_set_channels resets to; otherwise 2 <= nref <=
+ * min(intg, GNSSCORR_MAXCOH).  gnsscorr_acqres_t is never touched: results, edges and power arrays are bit for bit what
+ * they are without this call, and a channel with nref = 0 is handed over exactly as before.  With n = nsamp, K =
+ * GNSSCORR_FINE_BINS and r the channel's result of this search:
+ *   1. span: the nref * n ring samples from s0 = r.buffloc on (b0 + acqcodei also with ncoh > 1 and with bit-edge
+ *      hypotheses; s0 + nref * n <= wrpos, the samples the search looked back over);
+ *   2. carrier wipe-off: one mixcarr() call over the span at r.acqfreq, phase 0 at s0 (ref src/sdrcmn.c:633-669, the
+ *      reference's sequential fp64 phase sum): integers (I, Q)[s];
+ *   3. code: the replica of the search, c[k] = code[floor(k * ci) mod clen], k < n, ci = ti * crate, the same n values
+ *      for every period (code Doppler ignored: at most 0.03 chip over 10 ms);
+ *   4. prompt sums P_m = sum_{k < n} c[k] (I + iQ)[m n + k], m < nref: exact integers below 2^28;
+ *   5. data removal S_m = P_m^2 (I^2 - Q^2, 2 I Q: exact in int64, then converted to double): the BPSK data, the G1
+ *      meander and the SBAS symbols drop out, the residual frequency doubles;
+ *   6. line search Z[q] = sum_m S_m exp(+2 pi i ((q m) mod K) / K), q = -K/2 .. K/2 - 1, in fp64; q* is the q with
+ *      the largest |Z[q]|^2, the lowest q on ties;
+ *   7. finefreq = r.acqfreq + q* / (2 K ctime) (steps of 1.953 Hz at 1 ms), quality = |Z[q*]|^2 / (sum_m |S_m|)^2 in
+ *      (0, 1] (1: a clean line; 0 when every prompt sum is zero), nref = the periods used;
+ *   8. a channel that was not listed, not acquired or has nref = 0: finefreq = r.acqfreq (0 for the zero row of an
+ *      unlisted channel), quality = 0, q = 0, nref = 0, prompt sums zero.
+ * The estimate is unambiguous for |f - acqfreq| < 1 / (4 ctime), 250 Hz at 1 ms: every Doppler grid with a step below
+ * 1 / (2 ctime) qualifies (the reference's 200 Hz, every coherent_step); coarser grids alias, which is not checked.
+ * gnsscorr_acq_set_refine: GNSSCORR_EINVAL, nothing touched and the channel named, for a range outside the channel
+ * table, nref < 0, nref == 1, nref > min(intg, GNSSCORR_MAXCOH).  Quiesces and uploads the channel table; the prepared
+ * acquisition work and the last search's results stay.  A search without a listed channel with nref > 0 queues exactly
+ * the launches it queued before.  Not included: interpolation between the estimator's bins, code-Doppler
+ * compensation, data wipe-off; the drop-in sdracquisition() is untouched. */
+#define GNSSCORR_FINE_BINS 256
+typedef struct {
+    double finefreq, quality;
+    int    q, nref;                 /* the chosen bin q*; periods used (0: no refinement, rule 8) */
+} gnsscorr_acqfine_t;
+int  gnsscorr_acq_set_refine(gnsscorr_ctx *ctx, int ch0, int nch, const int *nref);
+int  gnsscorr_acq_get_refine(gnsscorr_ctx *ctx, int ch0, int nch, int *nref);
+/* fine[nch] of the last search; prompt may be NULL, else nch * GNSSCORR_MAXCOH * 2 int32 (I, Q of P_m, zero beyond
+ * nref); synchronises.  GNSSCORR_ESTATE before a search. */
+int  gnsscorr_acq_fetch_fine(gnsscorr_ctx *ctx, gnsscorr_acqfine_t *fine, int32_t *prompt);
 
 /* ---- receiver schedule: acquire, hand over and track each channel by state ----
  * sdrthread()'s state machine (ref src/sdrmain.c:247-316) for every channel of the context: a channel calls
