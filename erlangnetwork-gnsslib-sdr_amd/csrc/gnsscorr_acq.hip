@@ -49,6 +49,12 @@
 // list of grids that have a listed channel, so grid sizes follow the list.  Everything a channel owns (code
 // spectrum, rows, arrival counters, result) stays indexed by the channel itself: what a listed channel computes
 // does not depend on who else is listed.
+//
+// Stated once: the carrier LUT, a span's ring positions and a sample's wipe-off (gc_span_pos, gc_wipeoff: gnsscorr_lut.h);
+// a span's carrier table, that table into LDS, the replica sample (acq_span_table, acq_table_to_lds, acq_replica); where a
+// row, an X slot, a code spectrum, a prompt pair and the sections of d_list and arrive are (GcAcqDims, GcAcq:
+// gnsscorr_ctx.h).  A search is gc_acq_run_list: its plan, the upload, the search's queue and the refinement's.
+#include <algorithm>
 #include <cstddef>
 #include <cstdlib>
 #include <type_traits>
@@ -56,8 +62,9 @@
 
 #include "gnsscorr_ctx.h"
 #include "gnsscorr_fft.h"
+#include "gnsscorr_lut.h"
 
-#define GC_L        32768
+#define GC_L       32768
 #define GC_LH       16384
 
 using gcfft::cadd;
@@ -73,12 +80,6 @@ namespace {
 __host__ __device__ __forceinline__ int acq_groups(const GcChan &c) { return c.ncoh > 1 ? c.intg / c.ncoh : c.intg; }
 // bit-edge hypotheses of a group: h = 0, estep, 2 estep, ... < ncoh (one, h = 0, without them)
 __host__ __device__ __forceinline__ int acq_hyps(const GcChan &c) { return c.estep > 0 ? (c.ncoh + c.estep - 1) / c.estep : 1; }
-
-// carrier LUT (ref src/sdrcmn.c:643-648)
-__constant__ signed char aCos32[32] = {32, 31, 30, 27, 23, 18, 12, 6, 0, -6, -12, -18, -23, -27, -30, -31,
-                                       -32, -31, -30, -27, -23, -18, -12, -6, 0, 6, 12, 18, 23, 27, 30, 31};
-__constant__ signed char aSin32[32] = {0, 6, 12, 18, 23, 27, 30, 31, 32, 31, 30, 27, 23, 18, 12, 6,
-                                       0, -6, -12, -18, -23, -27, -30, -31, -32, -31, -30, -27, -23, -18, -12, -6};
 
 __global__ void tw64_init_kernel(float2 *tw64p1, float2 *tw64p3)
 {
@@ -210,7 +211,33 @@ __device__ __forceinline__ void fwd64k_store(F sample, float2 *lds, const float2
                    lds, tw16k, tid);
 }
 
-// one lane per (grid, bin): the bin's carrier piece table
+// ---- what the kernels below share: a span's carrier table, its samples in the ring, the replica ----------------------
+// The carrier piece table of a span of `samples` samples at `freq`, phase 0 at its first sample (ref src/sdrcmn.c:761),
+// by one lane.  A span that needs more pieces than the table holds has none (n = 0) and is counted in *overflow.
+__device__ __forceinline__ void acq_span_table(GcAcqCar *t, double freq, double ti, int samples, int *overflow)
+{
+    GcCarTable ct{t->k0, t->seg, GC_NCAR, 0, 0};
+    gc_carrier_walk(gc_carrier_phis(0.0), gc_carrier_ps(freq, ti), samples, ct);
+    t->n = ct.overflow ? 0 : ct.n;
+    if (ct.overflow) atomicAdd(overflow, 1);
+}
+// that table into the workgroup's LDS, a piece per lane; returns the number of pieces (a barrier follows)
+__device__ __forceinline__ int acq_table_to_lds(const GcAcqCar *gt, int *lk0, GcCarSeg *lseg, int tid)
+{
+    const int ncar = gt->n;
+    if (tid < ncar) { lk0[tid] = gt->k0[tid]; lseg[tid] = gt->seg[tid]; }
+    return ncar;
+}
+// Sample s of the replica rescode(code, clen, 0, 0, ci, nsamp) (ref src/sdrinit.c:650-651), ci = __dmul_rn(ti, crate)
+// (sdr->ci, ref src/sdrinit.c:605): acq_code transforms it, acq_prompt correlates with it
+__device__ __forceinline__ int acq_replica(gc_gptr_i8 code, int clen, double ci, int s)
+{
+    long long t = (long long)__dmul_rn((double)s, ci);
+    while (t >= clen) t -= clen;
+    return code[(int)t];
+}
+
+// one lane per (grid, bin): the carrier table of the bin's wipe-off span
 __global__ void acq_nco_kernel(const GcChan *__restrict__ chan, const int *__restrict__ grid_chan,
                                const double *__restrict__ freqs, GcAcqCar *__restrict__ car, int ngrid, int maxfreq,
                                int *__restrict__ overflow)
@@ -219,13 +246,8 @@ __global__ void acq_nco_kernel(const GcChan *__restrict__ chan, const int *__res
     if (i >= ngrid * maxfreq) return;
     const GcChan &c = chan[grid_chan[i / maxfreq]];
     const int bin = i % maxfreq;
-    GcAcqCar *t = car + i;
-    t->n = 0;
-    if (bin >= c.nfreq) return;
-    GcCarTable ct{t->k0, t->seg, GC_NCAR, 0, 0};
-    gc_carrier_walk(gc_carrier_phis(0.0), gc_carrier_ps(freqs[c.freq_off + bin], c.ti), (c.ncoh + 1) * c.nsamp, ct);
-    t->n = ct.n;
-    if (ct.overflow) atomicAdd(overflow, 1);
+    if (bin >= c.nfreq) { car[i].n = 0; return; }
+    acq_span_table(car + i, freqs[c.freq_off + bin], c.ti, (c.ncoh + 1) * c.nsamp, overflow);
 }
 
 // acq_fwd: grid (bin, slot, entry of the list of frequency grids in use); slot = iteration without hypotheses.  COH:
@@ -244,6 +266,7 @@ __global__ __launch_bounds__(GC_FFT_THREADS) void acq_fwd_kernel(
     static_assert(COH || !EDGE, "hypotheses belong to coherent groups");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2 *lds = reinterpret_cast<float2 *>(smem);
+    const GcAcqDims d = {maxfreq, 0, maxslot, L};       // (scalar arguments, as acq_corr; no rows here)
     const int bin = blockIdx.x, slot = blockIdx.y, g = glist[blockIdx.z], tid = threadIdx.x;
     const GcChan &c = chan[grid_chan[g]];
     const int ncoh = COH ? c.ncoh : 1;
@@ -261,21 +284,21 @@ __global__ __launch_bounds__(GC_FFT_THREADS) void acq_fwd_kernel(
     const uint64_t base = buffloc % c.ringlen;
     const gc_gptr_i8 ring = (gc_gptr_i8)c.ring;
     const uint64_t ringlen = c.ringlen;
-    // the bin's carrier table (phase starts at 0 for every bin and iteration, :761) behind the FFT image
+    // the bin's carrier table (phase starts at 0 for every bin and iteration, :761) behind the FFT image: acq_table_to_lds
+    // and, below, gc_wipeoff's look-up and arithmetic spelled out, which this kernel's register budget needs
     int *lk0 = reinterpret_cast<int *>(smem + GC_FFT_LDS + 256);
     GcCarSeg *lseg = reinterpret_cast<GcCarSeg *>(smem + GC_FFT_LDS + 256 + ((GC_NCAR * 4 + 15) & ~15));
-    const GcAcqCar *gt = car + (size_t)g * maxfreq + bin;
+    const GcAcqCar *gt = car + (size_t)g * d.maxfreq + bin;
     const int ncar = gt->n;
     if (tid < ncar) { lk0[tid] = gt->k0[tid]; lseg[tid] = gt->seg[tid]; }
     __syncthreads();
     const float sc = (float)((1.0 / 32.0) / (double)c.nfft);     // CSCALE/m, ref src/sdrcmn.c:764
 
-    // wiped-off sample s of the group's span (s < (ncoh + 1)*n <= ringlen: the ring wraps at most once)
+    // wiped-off sample s of the group's span, loaded byte by byte
     auto mixed = [&](int s, int &I, int &Q) {
-        uint64_t pos = base + (uint64_t)s;
-        if (pos >= ringlen) pos -= ringlen;
+        const uint64_t pos = gc_span_pos(base, s, ringlen);
         const int idx = gc_carrier_idx_at(lk0, lseg, ncar, s);
-        const int cs_ = aCos32[idx], sn_ = aSin32[idx];
+        const int cs_ = gcCos32[idx], sn_ = gcSin32[idx];
         if (dtype == 2) {
             const int d0 = ring[2 * pos], d1 = ring[2 * pos + 1];
             I = cs_ * d0 - sn_ * d1;
@@ -302,35 +325,30 @@ __global__ __launch_bounds__(GC_FFT_THREADS) void acq_fwd_kernel(
         }
         return make_float2((float)I * sc, (float)Q * sc);
     };
-    float2 *out = X + (((size_t)g * maxslot + slot) * maxfreq + bin) * (size_t)L;
-    if (L == 2 * GC_L) fwd64k_store(sample, lds, tw16k, tw32p, tw64p1, tw64p3, out, tid);
+    float2 *out = d.x(X, g, slot, bin);
+    if (d.L == 2 * GC_L) fwd64k_store(sample, lds, tw16k, tw32p, tw64p1, tw64p3, out, tid);
     else fwd32k_store(sample, lds, tw16k, tw32p, out, tid);
 }
 
 // acq_code: grid (channel)
-__global__ __launch_bounds__(GC_FFT_THREADS) void acq_code_kernel(const GcChan *__restrict__ chan,
-                                                                  const float2 *__restrict__ tw16k,
-                                                                  const float2 *__restrict__ tw32p,
-                                                                  const float2 *__restrict__ tw64p1,
-                                                                  const float2 *__restrict__ tw64p3,
-                                                                  float2 *__restrict__ C, int L)
+__global__ __launch_bounds__(GC_FFT_THREADS) void acq_code_kernel(
+    const GcChan *__restrict__ chan, const float2 *__restrict__ tw16k, const float2 *__restrict__ tw32p,
+    const float2 *__restrict__ tw64p1, const float2 *__restrict__ tw64p3, float2 *__restrict__ C, GcAcqDims d)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2 *lds = reinterpret_cast<float2 *>(smem);
     const int ch = blockIdx.x, tid = threadIdx.x;
     const GcChan &c = chan[ch];
     const int n = c.nsamp, clen = c.clen;
-    const double ci = __dmul_rn(c.ti, c.crate);      // sdr->ci, ref src/sdrinit.c:605
+    const double ci = __dmul_rn(c.ti, c.crate);
     const gc_gptr_i8 code = (gc_gptr_i8)c.code;
-    // rescode(code, clen, 0, 0, ci, nsamp) zero-padded (ref src/sdrinit.c:650-651)
+    // the replica, zero-padded
     auto sample = [&](int s) -> float2 {
         if (s >= n) return make_float2(0.f, 0.f);
-        long long t = (long long)__dmul_rn((double)s, ci);
-        while (t >= clen) t -= clen;
-        return make_float2((float)code[(int)t], 0.f);
+        return make_float2((float)acq_replica(code, clen, ci, s), 0.f);
     };
-    if (L == 2 * GC_L) fwd64k_store(sample, lds, tw16k, tw32p, tw64p1, tw64p3, C + (size_t)ch * L, tid);
-    else fwd32k_store(sample, lds, tw16k, tw32p, C + (size_t)ch * L, tid);
+    if (d.L == 2 * GC_L) fwd64k_store(sample, lds, tw16k, tw32p, tw64p1, tw64p3, d.code(C, ch), tid);
+    else fwd32k_store(sample, lds, tw16k, tw32p, d.code(C, ch), tid);
 }
 
 // ---- workgroup reductions used by acq_corr --------------------------------
@@ -406,7 +424,7 @@ __device__ __forceinline__ GcAcqRow acq_row_stats(const double (&P)[NP], LagOf l
     }
     wg_sum_max<NT>(so, mo, sd, tid);
     GcAcqRow r;
-    r.rowmax = m.v; r.sum_out = so; r.max_out = mo; r.argmax = m.k; r.pad = 0;
+    r.rowmax = m.v; r.sum_out = so; r.max_out = mo; r.argmax = m.k; r.edge = 0;
     return r;
 }
 
@@ -606,14 +624,16 @@ __global__ __launch_bounds__(NT) void acq_corr_kernel(
     double *sd = reinterpret_cast<double *>(smem + GC_ACQ_SD);
     int *si = reinterpret_cast<int *>(smem + GC_ACQ_SI);
     const int tid0 = threadIdx.x;
-    const AcqBlock blk = acq_corr_block(blockIdx.x, maxfreq, Pout != nullptr);
+    // (scalar arguments: the argument block this kernel's register budget was tuned with; L is the kernel's own constant)
+    const GcAcqDims d = {maxfreq, maxintg, maxslot, GC_L};
+    const AcqBlock blk = acq_corr_block(blockIdx.x, d.maxfreq, Pout != nullptr);
     const int bin = blk.bin;
-    if (bin >= maxfreq || (!Pout && blk.li >= nlist)) return;
+    if (bin >= d.maxfreq || (!Pout && blk.li >= nlist)) return;
     const int ch = Pout ? pout_ch : list[blk.li];
     const GcChan &c = chan[ch];
     if (bin >= c.nfreq) return;
     const int n = c.nsamp, nit = iters[ch], nsc2 = 2 * c.nsampchip;
-    const float2 *Cc = C + (size_t)ch * GC_L;
+    const float2 *Cc = d.code(C, ch);
     const float invL2 = 1.0f / ((float)GC_L * (float)GC_L);
 
     // lane `tid` owns lags k = 2 (tid + NT*h + 1024*q) + par (par < 2, h < 1024/NT, q < 8):
@@ -655,10 +675,10 @@ __global__ __launch_bounds__(NT) void acq_corr_kernel(
         // hoisted out of the loop (they would be spilled to scratch, not kept in VGPRs).
         int tid = tid0;
         asm volatile("" : "+v"(tid));
-        const float2 *Xb = X + (((size_t)c.grid * maxslot + (size_t)it * H) * maxfreq + bin) * GC_L;
+        const float2 *Xb = d.x(X, c.grid, (size_t)it * H, bin);    // the iteration's first slot
         int hsel = 0;                            // index of the hypothesis whose row is added
         if constexpr (EDGE) {
-            const size_t hstride = (size_t)maxfreq * GC_L;
+            const size_t hstride = d.x_slot_stride();       // hypothesis hi is slot hi of the iteration
             float best = -1.0f;
             for (int hi = 0; hi < H; hi++) {
                 float mx = -1.0f;
@@ -672,8 +692,8 @@ __global__ __launch_bounds__(NT) void acq_corr_kernel(
         inverse(Xb, tid, acq_add_power<0>(P, invL2), acq_add_power<NPH>(P, invL2));
 
         GcAcqRow r = acq_row_stats<NT>(P, lag_of, n, nsc2, sd, si, tid);
-        if constexpr (EDGE) r.pad = hsel * c.estep;
-        if (tid == 0) rows[((size_t)ch * maxintg + it) * maxfreq + bin] = r;
+        if constexpr (EDGE) r.edge = hsel * c.estep;
+        if (tid == 0) *d.row(rows, ch, it, bin) = r;
         // The reference stops a channel at the first iteration whose peak ratio passes the threshold
         // (ref src/sdracq.c:39-42); so does this: the workgroup that finishes an iteration of its channel
         // last takes acq_final's decision from the same rows (acq_best_row, acq_passes), and the channel's
@@ -683,12 +703,12 @@ __global__ __launch_bounds__(NT) void acq_corr_kernel(
             int last = 0;
             if (tid == 0) {
                 __threadfence();
-                last = atomicAdd(&arrive[ch * maxintg + it], 1) == c.nfreq - 1;
+                last = atomicAdd(d.arrival(arrive, ch, it), 1) == c.nfreq - 1;
             }
             last = __shfl(last, 0);
             if (last) {
                 __threadfence();
-                const GcAcqRow *row = rows + ((size_t)ch * maxintg + it) * maxfreq;
+                const GcAcqRow *row = d.row(rows, ch, it);
                 const GcAcqRow w = row[acq_best_row(row, c.nfreq, tid)];
                 if (tid == 0 && acq_passes(w))
                     __hip_atomic_store(&done[ch], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
@@ -720,14 +740,15 @@ __global__ __launch_bounds__(512) void acq_corr64_kernel(
     double *sd = reinterpret_cast<double *>(smem + GC_ACQ_SD);
     int *si = reinterpret_cast<int *>(smem + GC_ACQ_SI);
     const int tid0 = threadIdx.x;
-    const AcqBlock blk = acq_corr64_block(blockIdx.x, maxfreq, Pout != nullptr);
+    const GcAcqDims d = {maxfreq, maxintg, maxintg, L};     // (scalar arguments, as acq_corr; no hypotheses: GcAcqDims::x)
+    const AcqBlock blk = acq_corr64_block(blockIdx.x, d.maxfreq, Pout != nullptr);
     const int bin = blk.bin;
-    if (bin >= maxfreq || (!Pout && blk.li >= nlist)) return;
+    if (bin >= d.maxfreq || (!Pout && blk.li >= nlist)) return;
     const int ch = Pout ? pout_ch : list[blk.li];
     const GcChan &c = chan[ch];
     if (bin >= c.nfreq) return;
     const int n = c.nsamp, nit = iters[ch], nsc2 = 2 * c.nsampchip;
-    const float2 *Cc = C + (size_t)ch * L;
+    const float2 *Cc = d.code(C, ch);
     const float invL2 = 1.0f / ((float)L * (float)L);
     double P[NP];
 #pragma unroll
@@ -736,7 +757,7 @@ __global__ __launch_bounds__(512) void acq_corr64_kernel(
     for (int it = 0; it < nit; it++) {
         int tid = tid0;
         asm volatile("" : "+v"(tid));
-        const float2 *Xb = X + (((size_t)c.grid * maxintg + it) * maxfreq + bin) * (size_t)L;
+        const float2 *Xb = d.x(X, c.grid, it, bin);         // (slot = iteration: no hypotheses at this length)
         // Lags 4 j + S.  The twiddle w^(-f S) = conj(twp[p]) (S > 0) has to be applied per input: dit() hands `make`
         // only the raw operands, so the twiddled residues fetch their factors with the operands.
         auto residue = [&](auto s_tag, const float2 *__restrict__ twp) {
@@ -780,7 +801,7 @@ __global__ __launch_bounds__(512) void acq_corr64_kernel(
         residue(std::integral_constant<int, 3>{}, tw64p3);
 
         const GcAcqRow r = acq_row_stats<NT>(P, lag_of, n, nsc2, sd, si, tid);
-        if (tid == 0) rows[((size_t)ch * maxintg + it) * maxfreq + bin] = r;
+        if (tid == 0) *d.row(rows, ch, it, bin) = r;
         __syncthreads();
     }
     if (Pout) acq_write_power(Pout, P, lag_of, tid0, bin, n);
@@ -802,13 +823,10 @@ __device__ __forceinline__ GcTrkState acq_start_state(const gnsscorr_acqres_t &r
 
 // acq_final: one wavefront per listed channel; the lanes share the bins of an iteration.  edge_out[ch]: the hypothesis
 // of the deciding iteration's best row for an acquired channel that has hypotheses, -1 otherwise.
-__global__ __launch_bounds__(64) void acq_final_kernel(const GcChan *__restrict__ chan, const double *__restrict__ freqs,
-                                                       const GcAcqRow *__restrict__ rows,
-                                                       const uint64_t *__restrict__ grid_wrpos,
-                                                       gnsscorr_acqres_t *__restrict__ res, int *__restrict__ iters_out,
-                                                       int *__restrict__ edge_out,
-                                                       const int *__restrict__ list, int nlist, int maxfreq,
-                                                       int maxintg)
+__global__ __launch_bounds__(64) void acq_final_kernel(
+    const GcChan *__restrict__ chan, const double *__restrict__ freqs, const GcAcqRow *__restrict__ rows,
+    const uint64_t *__restrict__ grid_wrpos, gnsscorr_acqres_t *__restrict__ res, int *__restrict__ iters_out,
+    int *__restrict__ edge_out, const int *__restrict__ list, int nlist, GcAcqDims d)
 {
     const int lane = threadIdx.x;
     if ((int)blockIdx.x >= nlist) return;
@@ -821,10 +839,10 @@ __global__ __launch_bounds__(64) void acq_final_kernel(const GcChan *__restrict_
     const uint64_t b0 = grid_wrpos[c.grid] - (uint64_t)(c.intg + 1) * n;
     int it = 0, edge = -1;
     for (; it < ngroup; it++) {
-        const GcAcqRow *row = rows + ((size_t)ch * maxintg + it) * maxfreq;
+        const GcAcqRow *row = d.row(rows, ch, it);
         const int fi = acq_best_row(row, c.nfreq, lane);
         const GcAcqRow w = row[fi];
-        edge = w.pad;
+        edge = w.edge;
         const int ne = 4 * c.nsampchip + 1;                     // samples inside the excluded window
         const double meanP = w.sum_out / (double)(n - ne);
         r.cn0 = 10.0 * log10(w.rowmax / meanP / tcoh);
@@ -841,7 +859,7 @@ __global__ __launch_bounds__(64) void acq_final_kernel(const GcChan *__restrict_
     if (lane == 0) {
         res[ch] = r;
         edge_out[ch] = r.flagacq && c.estep > 0 ? edge : -1;
-        if (iters_out) iters_out[ch] = r.flagacq ? it + 1 : ngroup;
+        iters_out[ch] = r.flagacq ? it + 1 : ngroup;
     }
 }
 
@@ -858,8 +876,8 @@ __device__ __forceinline__ double acq_start_freq(const gnsscorr_acqres_t &r, con
     return fine && fine[ch].nref > 0 ? fine[ch].finefreq : r.acqfreq;
 }
 
-// one lane per list entry: the carrier piece table of the channel's refine span, in the form of acq_nco_kernel.  n = 0:
-// the channel is not refined (nref = 0, not acquired, or a table that overflowed -- counted, the run is reported)
+// one lane per list entry: the carrier table of the channel's refine span.  n = 0: the channel is not refined (nref = 0,
+// not acquired, or a span without a table -- the fetch reports the run)
 __global__ void acq_fine_nco_kernel(const GcChan *__restrict__ chan, const gnsscorr_acqres_t *__restrict__ res,
                                     const int *__restrict__ list, int nlist, GcAcqCar *__restrict__ fcar,
                                     int *__restrict__ overflow)
@@ -868,13 +886,8 @@ __global__ void acq_fine_nco_kernel(const GcChan *__restrict__ chan, const gnssc
     if (i >= nlist) return;
     const int ch = list[i];
     const GcChan &c = chan[ch];
-    GcAcqCar *t = fcar + ch;
-    t->n = 0;
-    if (c.nref <= 0 || !res[ch].flagacq) return;
-    GcCarTable ct{t->k0, t->seg, GC_NCAR, 0, 0};
-    gc_carrier_walk(gc_carrier_phis(0.0), gc_carrier_ps(res[ch].acqfreq, c.ti), c.nref * c.nsamp, ct);
-    if (ct.overflow) atomicAdd(overflow, 1);
-    else t->n = ct.n;
+    if (c.nref <= 0 || !res[ch].flagacq) { fcar[ch].n = 0; return; }
+    acq_span_table(fcar + ch, res[ch].acqfreq, c.ti, c.nref * c.nsamp, overflow);
 }
 
 typedef const __attribute__((address_space(1))) short *gc_gptr_i16;
@@ -883,11 +896,9 @@ typedef const __attribute__((address_space(1))) short *gc_gptr_i16;
 // acq_prompt: grid (period m, list entry).  P_m = sum_k c[k] (I + iQ)[m n + k] over the wiped-off samples of period m of
 // the span, c the replica acq_code transforms; consecutive lanes read consecutive ring samples (an IQ pair as one
 // 16-bit load), int32 partial sums per lane (|I|, |Q| <= 2*32*128, n <= 32768: |P| < 2^28).
-__global__ __launch_bounds__(GC_PROMPT_NT) void acq_prompt_kernel(const GcChan *__restrict__ chan,
-                                                                  const gnsscorr_acqres_t *__restrict__ res,
-                                                                  const GcAcqCar *__restrict__ fcar,
-                                                                  const int *__restrict__ list, int nlist,
-                                                                  int *__restrict__ prompt)
+__global__ __launch_bounds__(GC_PROMPT_NT) void acq_prompt_kernel(
+    const GcChan *__restrict__ chan, const gnsscorr_acqres_t *__restrict__ res, const GcAcqCar *__restrict__ fcar,
+    const int *__restrict__ list, int nlist, int *__restrict__ prompt)
 {
     __shared__ int lk0[GC_NCAR];
     __shared__ GcCarSeg lseg[GC_NCAR];
@@ -897,10 +908,8 @@ __global__ __launch_bounds__(GC_PROMPT_NT) void acq_prompt_kernel(const GcChan *
     const int ch = list[blockIdx.y];
     const GcChan &c = chan[ch];
     if (m >= c.nref || !res[ch].flagacq) return;
-    const GcAcqCar *gt = fcar + ch;
-    const int ncar = gt->n;
+    const int ncar = acq_table_to_lds(fcar + ch, lk0, lseg, tid);
     if (ncar <= 0) return;
-    if (tid < ncar) { lk0[tid] = gt->k0[tid]; lseg[tid] = gt->seg[tid]; }
     __syncthreads();
     const int n = c.nsamp, clen = c.clen, dtype = c.dtype;
     const uint64_t ringlen = c.ringlen, base = res[ch].buffloc % ringlen;
@@ -909,26 +918,13 @@ __global__ __launch_bounds__(GC_PROMPT_NT) void acq_prompt_kernel(const GcChan *
     const double ci = __dmul_rn(c.ti, c.crate);
     int sI = 0, sQ = 0;
     for (int k = tid; k < n; k += GC_PROMPT_NT) {
-        // sample s of the span (s < nref*n <= intg*n < ringlen: the ring wraps at most once, as in acq_fwd's mixed())
-        const int s = m * n + k;
-        uint64_t pos = base + (uint64_t)s;
-        if (pos >= ringlen) pos -= ringlen;
-        const int idx = gc_carrier_idx_at(lk0, lseg, ncar, s);
-        const int cs_ = aCos32[idx], sn_ = aSin32[idx];
+        const int s = m * n + k;        // sample k of period m: sample s of the span
+        const uint64_t pos = gc_span_pos(base, s, ringlen);
         int I, Q;
-        if (dtype == 2) {
-            const int v = ring2[pos];
-            const int d0 = (signed char)(v & 0xff), d1 = v >> 8;
-            I = cs_ * d0 - sn_ * d1;
-            Q = sn_ * d0 + cs_ * d1;
-        } else {
-            const int d0 = ring[pos];
-            I = cs_ * d0;
-            Q = sn_ * d0;
-        }
-        long long t = (long long)__dmul_rn((double)k, ci);         // the replica value, as acq_code forms it
-        while (t >= clen) t -= clen;
-        const int cv = code[(int)t];
+        gc_wipeoff(gc_carrier_idx_at(lk0, lseg, ncar, s), dtype,
+                   [&] { const int v = ring2[pos]; return make_int2((signed char)(v & 0xff), v >> 8); },
+                   [&] { return (int)ring[pos]; }, I, Q);
+        const int cv = acq_replica(code, clen, ci, k);
         sI += cv * I;
         sQ += cv * Q;
     }
@@ -943,7 +939,7 @@ __global__ __launch_bounds__(GC_PROMPT_NT) void acq_prompt_kernel(const GcChan *
         int pI = 0, pQ = 0;
 #pragma unroll
         for (int w = 0; w < GC_PROMPT_NT / 64; w++) { pI += red[0][w]; pQ += red[1][w]; }
-        reinterpret_cast<int2 *>(prompt)[(size_t)ch * GNSSCORR_MAXCOH + m] = make_int2(pI, pQ);
+        *reinterpret_cast<int2 *>(GcAcqDims::prompt(prompt, ch, m)) = make_int2(pI, pQ);
     }
 }
 
@@ -951,11 +947,9 @@ __global__ __launch_bounds__(GC_PROMPT_NT) void acq_prompt_kernel(const GcChan *
 // ((q m) mod K)/K) with the lanes over q = -K/2 .. K/2-1, the largest |Z|^2 (lowest q on ties) over the wavefront, one
 // gnsscorr_acqfine_t; a listed channel without refinement gets finefreq = acqfreq and zeros (its prompt row was cleared
 // with the others' tails before acq_prompt).
-__global__ __launch_bounds__(64) void acq_fine_kernel(const GcChan *__restrict__ chan,
-                                                      const gnsscorr_acqres_t *__restrict__ res,
-                                                      const GcAcqCar *__restrict__ fcar, const int *__restrict__ list,
-                                                      int nlist, const int *__restrict__ prompt,
-                                                      gnsscorr_acqfine_t *__restrict__ fine)
+__global__ __launch_bounds__(64) void acq_fine_kernel(
+    const GcChan *__restrict__ chan, const gnsscorr_acqres_t *__restrict__ res, const GcAcqCar *__restrict__ fcar,
+    const int *__restrict__ list, int nlist, const int *__restrict__ prompt, gnsscorr_acqfine_t *__restrict__ fine)
 {
     constexpr int K = GNSSCORR_FINE_BINS;
     __shared__ double sr[GNSSCORR_MAXCOH], si[GNSSCORR_MAXCOH], sa[GNSSCORR_MAXCOH];
@@ -969,8 +963,8 @@ __global__ __launch_bounds__(64) void acq_fine_kernel(const GcChan *__restrict__
     const int nref = c.nref;
     if (nref > 0 && r.flagacq && fcar[ch].n > 0) {
         if (lane < nref) {
-            const long long I = prompt[((size_t)ch * GNSSCORR_MAXCOH + lane) * 2];
-            const long long Q = prompt[((size_t)ch * GNSSCORR_MAXCOH + lane) * 2 + 1];
+            const int *pm = GcAcqDims::prompt(prompt, ch, lane);
+            const long long I = pm[0], Q = pm[1];
             sr[lane] = (double)(I * I - Q * Q);
             si[lane] = (double)(2 * I * Q);
             sa[lane] = (double)(I * I + Q * Q);      // |S_m| = |P_m|^2
@@ -1005,10 +999,11 @@ __global__ __launch_bounds__(64) void acq_fine_kernel(const GcChan *__restrict__
     if (lane == 0) fine[ch] = f;
 }
 
-__global__ void fill_int_kernel(int *p, const GcChan *__restrict__ chan, const int *__restrict__ list, int nlist)
+// acq_corr's iteration limit of the listed channels: all of their groups
+__global__ void acq_iters_kernel(int *iters, const GcChan *__restrict__ chan, const int *__restrict__ list, int nlist)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < nlist) p[list[i]] = acq_groups(chan[list[i]]);
+    if (i < nlist) iters[list[i]] = acq_groups(chan[list[i]]);
 }
 
 // stand-alone batch FFT (op-level entry point and tests): grid (batch); natural order in and out
@@ -1079,20 +1074,14 @@ int gc_acq_twiddles(gnsscorr_ctx *ctx)
     hipLaunchKernelGGL(tw_init_kernel, dim3(GC_LH / 256), dim3(256), 0, ctx->stream, f.tw16k, f.tw32k, f.tw32p);
     hipLaunchKernelGGL(tw64_init_kernel, dim3(GC_LH / 256), dim3(256), 0, ctx->stream, f.tw64p1, f.tw64p3);
     GC_HIP(hipGetLastError());
-    {
-        const int lds = GC_FFT_LDS + 256;
-        GC_HIP(hipFuncSetAttribute((const void *)acq_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + GC_ACQ_CARLDS));
-        GC_HIP(hipFuncSetAttribute((const void *)acq_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + GC_ACQ_CARLDS));
-        GC_HIP(hipFuncSetAttribute((const void *)acq_fwd_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + GC_ACQ_CARLDS));
-        GC_HIP(hipFuncSetAttribute((const void *)acq_code_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        GC_HIP(hipFuncSetAttribute((const void *)acq_corr_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, GC_ACQ_CORR_LDS));
-        GC_HIP(hipFuncSetAttribute((const void *)acq_corr_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, GC_ACQ_CORR_LDS));
-        GC_HIP(hipFuncSetAttribute((const void *)acq_corr_kernel<512, true>, hipFuncAttributeMaxDynamicSharedMemorySize, GC_ACQ_CORR_LDS));
-        GC_HIP(hipFuncSetAttribute((const void *)acq_corr64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GC_ACQ_CORR_LDS));
-        GC_HIP(hipFuncSetAttribute((const void *)fft16k_kernel<-1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        GC_HIP(hipFuncSetAttribute((const void *)fft16k_kernel<+1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        GC_HIP(hipFuncSetAttribute((const void *)pspec_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
+    const int lds = GC_FFT_LDS + 256, fwd = lds + GC_ACQ_CARLDS, corr = GC_ACQ_CORR_LDS;
+    const struct { const void *kernel; int lds; } dyn[] = {
+        {(const void *)acq_fwd_kernel<false>, fwd}, {(const void *)acq_fwd_kernel<true>, fwd},
+        {(const void *)acq_fwd_kernel<true, true>, fwd}, {(const void *)acq_code_kernel, lds},
+        {(const void *)acq_corr_kernel<512>, corr}, {(const void *)acq_corr_kernel<1024>, corr},
+        {(const void *)acq_corr_kernel<512, true>, corr}, {(const void *)acq_corr64_kernel, corr},
+        {(const void *)fft16k_kernel<-1>, lds}, {(const void *)fft16k_kernel<+1>, lds}, {(const void *)pspec_kernel, lds}};
+    for (const auto &k : dyn) GC_HIP(hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds));
     f.ready = true;
     return GNSSCORR_OK;
 }
@@ -1104,8 +1093,9 @@ static int acq_prepare(gnsscorr_ctx *ctx)
     GcAcq *w = &ctx->acq;
     if (w->prepared) return GNSSCORR_OK;
     const int nch = ctx->nch;
-    w->ngrid = 0; w->maxfreq = 0; w->maxintg = 0; w->maxslot = 0;
-    w->L = GC_L;
+    GcAcqDims d = {0, 0, 0, GC_L};
+    w->nch = nch;
+    w->ngrid = 0;
     w->grid_chan.clear();
     for (int i = 0; i < nch; i++) {
         const GcChan &c = ctx->hchan[i];
@@ -1113,37 +1103,40 @@ static int acq_prepare(gnsscorr_ctx *ctx)
         // period, 65536 (20 / 26 Msps front ends) up to 32768
         if (c.nsamp > GC_L)
             return gc_fail(GNSSCORR_EINVAL, "acquisition: nsamp %d needs an FFT longer than 65536", c.nsamp);
-        if (c.nsamp > GC_LH) w->L = 2 * GC_L;
+        if (c.nsamp > GC_LH) d.L = 2 * GC_L;
         if (c.grid >= w->ngrid) { w->ngrid = c.grid + 1; w->grid_chan.push_back(i); }
-        if (c.nfreq > w->maxfreq) w->maxfreq = c.nfreq;
-        if (acq_groups(c) > w->maxintg) w->maxintg = acq_groups(c);
-        // X's slots: the largest groups x hypotheses of one grid, not the product of the two maxima
-        if (acq_groups(c) * acq_hyps(c) > w->maxslot) w->maxslot = acq_groups(c) * acq_hyps(c);
+        if (c.nfreq > d.maxfreq) d.maxfreq = c.nfreq;
+        if (acq_groups(c) > d.maxintg) d.maxintg = acq_groups(c);
+        if (acq_groups(c) * acq_hyps(c) > d.maxslot) d.maxslot = acq_groups(c) * acq_hyps(c);
     }
-    GC_RESERVE(ctx, w->X, (size_t)w->ngrid * w->maxslot * w->maxfreq * w->L);
-    GC_RESERVE(ctx, w->rows, (size_t)nch * w->maxintg * w->maxfreq);
-    GC_RESERVE(ctx, w->arrive, (size_t)nch * w->maxintg + nch);
+    // acq_corr64 reads X by iteration (GcAcqDims::x)
+    if (d.L == 2 * GC_L && d.maxslot != d.maxintg)
+        return gc_fail(GNSSCORR_ESTATE, "acquisition: bit-edge hypotheses on the 65536-point transform");
+    w->dims = d;
+    GC_RESERVE(ctx, w->X, (size_t)w->ngrid * d.maxslot * d.maxfreq * d.L);
+    GC_RESERVE(ctx, w->rows, (size_t)nch * d.maxintg * d.maxfreq);
+    GC_RESERVE(ctx, w->arrive, w->arrive_ints());
     GC_RESERVE(ctx, w->iters, nch);
     GC_RESERVE(ctx, w->res, nch);
     GC_RESERVE(ctx, w->edge, nch);
     GC_RESERVE(ctx, w->d_grid_chan, w->ngrid);
     GC_RESERVE(ctx, w->d_grid_wrpos, w->ngrid);
-    GC_RESERVE(ctx, w->d_list, (size_t)2 * nch + w->ngrid);
+    GC_RESERVE(ctx, w->d_list, w->list_ints());
     w->list.clear();
     w->glist.clear();
     GC_HIP(hipMemcpyAsync(w->d_grid_chan, w->grid_chan.data(), sizeof(int) * w->ngrid, hipMemcpyHostToDevice,
                           ctx->stream));
-    GC_RESERVE(ctx, w->car, (size_t)w->ngrid * w->maxfreq);
+    GC_RESERVE(ctx, w->car, (size_t)w->ngrid * d.maxfreq);
     GC_RESERVE(ctx, w->car_overflow, 1);
-    GC_RESERVE(ctx, w->C, (size_t)nch * w->L);
+    GC_RESERVE(ctx, w->C, (size_t)nch * d.L);
     GC_HIP(hipMemsetAsync(w->car_overflow, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(acq_nco_kernel, dim3((w->ngrid * w->maxfreq + 63) / 64), dim3(64), 0, ctx->stream, ctx->dchan,
-                       w->d_grid_chan, ctx->dfreqs, w->car, w->ngrid, w->maxfreq, w->car_overflow);
+    hipLaunchKernelGGL(acq_nco_kernel, dim3((w->ngrid * d.maxfreq + 63) / 64), dim3(64), 0, ctx->stream, ctx->dchan,
+                       w->d_grid_chan, ctx->dfreqs, w->car, w->ngrid, d.maxfreq, w->car_overflow);
     GC_HIP(hipGetLastError());
     {
         GcTimed t(ctx, "acq_code");
         hipLaunchKernelGGL(acq_code_kernel, dim3(nch), dim3(GC_FFT_THREADS), GC_FFT_LDS + 256, ctx->stream,
-                           ctx->dchan, f.tw16k, f.tw32p, f.tw64p1, f.tw64p3, w->C, w->L);
+                           ctx->dchan, f.tw16k, f.tw32p, f.tw64p1, f.tw64p3, w->C, d);
     }
     GC_HIP(hipGetLastError());
     int over = 0;
@@ -1164,147 +1157,147 @@ static void launch_acq_corr(gnsscorr_ctx *ctx, double *Pout, int pout_ch, const 
     GcAcq *w = &ctx->acq;
     static const int nt = getenv("GNSSCORR_ACQ_NT") ? atoi(getenv("GNSSCORR_ACQ_NT")) : 512;
     const bool pout = Pout != nullptr;
-    const int nbins = pout ? ctx->hchan[pout_ch].nfreq : w->maxfreq;
-    int *arrive = pout ? nullptr : (int *)w->arrive;         // [ch][iter] arrival counters, then [ch] "acquired" flags
-    int *done = pout ? nullptr : w->arrive + (size_t)ctx->nch * w->maxintg;
-    auto corr32 = [&](auto nt_tag, auto edge_tag) {
-        constexpr int NT = decltype(nt_tag)::value;
-        hipLaunchKernelGGL((acq_corr_kernel<NT, decltype(edge_tag)::value>), dim3(acq_corr_blocks(nbins, n, pout)),
-                           dim3(NT), GC_ACQ_CORR_LDS, ctx->stream, ctx->dchan, f.tw16k, f.tw32p, w->X, w->C, w->iters,
-                           w->rows, Pout, pout_ch, w->maxfreq, w->maxintg, w->maxslot, dlist, n, arrive, done);
+    const int nbins = pout ? ctx->hchan[pout_ch].nfreq : w->dims.maxfreq;
+    int *arrive = pout ? nullptr : w->arrivals(), *done = pout ? nullptr : w->done();
+    auto corr32 = [&](auto kernel, int lanes) {
+        hipLaunchKernelGGL(kernel, dim3(acq_corr_blocks(nbins, n, pout)), dim3(lanes), GC_ACQ_CORR_LDS, ctx->stream,
+                           ctx->dchan, f.tw16k, f.tw32p, w->X, w->C, w->iters, w->rows, Pout, pout_ch, w->dims.maxfreq,
+                           w->dims.maxintg, w->dims.maxslot, dlist, n, arrive, done);
     };
     if (edge)       // (gnsscorr_acq_set_bitedge refuses the 65536-point path)
-        corr32(std::integral_constant<int, 512>{}, std::true_type{});
-    else if (w->L == 2 * GC_L)
+        corr32(acq_corr_kernel<512, true>, 512);
+    else if (w->dims.L == 2 * GC_L)
         hipLaunchKernelGGL(acq_corr64_kernel, dim3(acq_corr64_blocks(nbins, n, pout)), dim3(512), GC_ACQ_CORR_LDS,
                            ctx->stream, ctx->dchan, f.tw16k, f.tw32p, f.tw64p1, f.tw64p3, w->X, w->C, w->iters,
-                           w->rows, Pout, pout_ch, w->maxfreq, w->maxintg, dlist, n);
+                           w->rows, Pout, pout_ch, w->dims.maxfreq, w->dims.maxintg, dlist, n);
     else if (nt == 1024 && !pout)
-        corr32(std::integral_constant<int, 1024>{}, std::false_type{});
+        corr32(acq_corr_kernel<1024>, 1024);
     else
-        corr32(std::integral_constant<int, 512>{}, std::false_type{});
+        corr32(acq_corr_kernel<512>, 512);
 }
 
 // One search over the channels chlist[0..n) (distinct; nullptr: all of them).  wp_ring[r]: write position of ring
-// r + 1 the search ends at, 0: the ring's current one.
+// r + 1 the search ends at, 0: the ring's current one.  The steps are local functions over the search's host-side plan;
+// the function's last lines are their order.
 int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chlist, int n)
 {
     if (!ctx) return gc_fail(GNSSCORR_EINVAL, "null context");
     if (!ctx->nch) return gc_fail(GNSSCORR_ESTATE, "acq_run: no channels set");
     const int nch = ctx->nch;
-    if (!chlist) n = nch;
-    if (n < 1 || n > nch) return gc_fail(GNSSCORR_EINVAL, "acq_run: list of %d channels (1..%d)", n, nch);
-    std::vector<int> list(n);
-    std::vector<char> listed(nch, 0);
-    for (int i = 0; i < n; i++) {
-        const int ch = chlist ? chlist[i] : i;
-        if (ch < 0 || ch >= nch || listed[ch])
-            return gc_fail(GNSSCORR_EINVAL, "acq_run: list entry %d: channel %d (0..%d, each once)", i, ch, nch - 1);
-        list[i] = ch;
-        listed[ch] = 1;
-    }
-    GC_HIP(hipSetDevice(ctx->device));
-    int rc = acq_prepare(ctx);
-    if (rc) return rc;
-    rc = gc_ingest_fence(ctx);
-    if (rc) return rc;
     const GcFftTables &f = ctx->fft;
     GcAcq *w = &ctx->acq;
-    // carrier refinement: only when a listed channel asks for it (the buffers are made by the first such search)
-    int maxref = 0;
-    for (int ch : list) maxref = ctx->hchan[ch].nref > maxref ? ctx->hchan[ch].nref : maxref;
-    if (maxref) {
-        GC_RESERVE(ctx, w->fcar, nch);
-        GC_RESERVE(ctx, w->fcar_overflow, 1);
-        GC_RESERVE(ctx, w->prompt, (size_t)nch * GNSSCORR_MAXCOH * 2);
-        GC_RESERVE(ctx, w->fine, nch);
-    }
-    // the grids that have a listed channel, in grid order
-    std::vector<int> glist;
-    for (int g = 0; g < w->ngrid; g++) {
-        bool used = false;
-        for (int i = 0; i < n && !used; i++) used = ctx->hchan[list[i]].grid == g;
-        if (used) glist.push_back(g);
-    }
-    std::vector<uint64_t> gw(w->ngrid, 0);
-    for (int g : glist) {
-        const GcChan &c = ctx->hchan[w->grid_chan[g]];
-        const int ft = ctx->hdesc[w->grid_chan[g]].ftype;
-        const uint64_t wp = wp_ring[ft - 1] ? wp_ring[ft - 1] : ctx->ring[ft - 1].wrpos;
-        if (wp < (uint64_t)(c.intg + 1) * c.nsamp)
-            return gc_fail(GNSSCORR_ESTATE, "acq_run: ring %d holds %llu samples, %llu needed", ft,
-                           (unsigned long long)wp, (unsigned long long)((uint64_t)(c.intg + 1) * c.nsamp));
-        if (c.ringlen < (uint64_t)(c.intg + 1) * c.nsamp)
-            return gc_fail(GNSSCORR_EINVAL, "acq_run: ring %d (%llu samples) is shorter than the %d code periods the search looks back",
-                           ft, (unsigned long long)c.ringlen, c.intg + 1);
-        gw[g] = wp;
-    }
-    // pageable sources: the copies are staged before the call returns.  The lists go up only when they change.
-    const int ng = (int)glist.size();
-    // acq_corr's order of the list: the channels without bit-edge hypotheses, then those with (a launch each)
-    std::vector<int> part;
-    for (int pass = 0; pass < 2; pass++) {
-        for (int ch : list)
-            if ((ctx->hchan[ch].estep > 0) == (pass == 1)) part.push_back(ch);
-        if (pass == 0) w->nplain = (int)part.size();
-    }
-    if (list != w->list || glist != w->glist) {
-        GC_HIP(hipMemcpyAsync(w->d_list, list.data(), sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
-        GC_HIP(hipMemcpyAsync(w->d_list + nch, glist.data(), sizeof(int) * ng, hipMemcpyHostToDevice, ctx->stream));
-        GC_HIP(hipMemcpyAsync(w->d_list + nch + w->ngrid, part.data(), sizeof(int) * n, hipMemcpyHostToDevice,
-                              ctx->stream));
-        w->list.clear();            // (until the copies are staged)
-    }
-    GC_HIP(hipMemcpyAsync(w->d_grid_wrpos, gw.data(), sizeof(uint64_t) * w->ngrid, hipMemcpyHostToDevice,
-                          ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    w->list = list;
-    w->glist = glist;
-    w->ran = false;                 // until every launch below is queued
-    const int *dlist = w->d_list, *dglist = w->d_list + nch;
-    const int lds = GC_FFT_LDS + 256;
-    const int *dpart = w->d_list + nch + w->ngrid;
+    if (!chlist) n = nch;
+    std::vector<int> list, glist;   // the listed channels in the caller's order; the grids that have one, in grid order
+    std::vector<char> listed(nch, 0);       // the channel is listed
+    std::vector<uint64_t> gw;       // [ngrid] the ring write position a listed grid's search ends at
+    std::vector<int> part;          // acq_corr's order of the list: the nplain channels without bit-edge hypotheses,
+    int nplain = 0;                 // then those with (a launch each)
     bool coh = false, edge = false; // a listed grid integrates coherently / has bit-edge hypotheses
-    for (int g : glist) {
-        coh = coh || ctx->hchan[w->grid_chan[g]].ncoh > 1;
-        edge = edge || ctx->hchan[w->grid_chan[g]].estep > 0;
-    }
-    {
-        GcTimed t(ctx, "acq_fwd");
-        auto fwd = edge ? acq_fwd_kernel<true, true> : coh ? acq_fwd_kernel<true> : acq_fwd_kernel<false>;
-        hipLaunchKernelGGL(fwd, dim3(w->maxfreq, w->maxslot, ng), dim3(GC_FFT_THREADS), lds + GC_ACQ_CARLDS,
-                           ctx->stream, ctx->dchan, w->d_grid_chan, dglist, w->car, w->d_grid_wrpos, f.tw16k, f.tw32p,
-                           f.tw64p1, f.tw64p3, w->X, w->maxfreq, w->maxslot, w->L);
-    }
-    GC_HIP(hipGetLastError());
-    // channels that are not listed: no iterations, a zero result row
-    if (n < nch) {
-        GC_HIP(hipMemsetAsync(w->iters, 0, sizeof(int) * nch, ctx->stream));
-        GC_HIP(hipMemsetAsync(w->res, 0, sizeof(gnsscorr_acqres_t) * nch, ctx->stream));
-        GC_HIP(hipMemsetAsync(w->edge, 0xff, sizeof(int) * nch, ctx->stream));      // -1
-    }
-    hipLaunchKernelGGL(fill_int_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, w->iters, ctx->dchan, dlist, n);
-    // arrival counters per (channel, iteration) and the channels' "acquired" flags
-    GC_HIP(hipMemsetAsync(w->arrive, 0, sizeof(int) * ((size_t)nch * w->maxintg + nch), ctx->stream));
-    {
-        GcTimed t(ctx, "acq_corr");
-        if (w->nplain) launch_acq_corr(ctx, nullptr, 0, dpart, w->nplain, false);
-        if (n > w->nplain) launch_acq_corr(ctx, nullptr, 0, dpart + w->nplain, n - w->nplain, true);
-    }
-    GC_HIP(hipGetLastError());
-    {
-        GcTimed t(ctx, "acq_final");
-        hipLaunchKernelGGL(acq_final_kernel, dim3(n), dim3(64), 0, ctx->stream, ctx->dchan,
-                           ctx->dfreqs, w->rows, w->d_grid_wrpos, w->res, w->iters, w->edge, dlist, n, w->maxfreq,
-                           w->maxintg);
-    }
-    GC_HIP(hipGetLastError());
-    w->refined = false;
-    if (maxref) {
+    int maxref = 0;                 // the longest refine span of a listed channel, 0: no refinement
+    // The caller's list and wp_ring into the plan above.  A valid list prepares the channel set and fences the rings'
+    // transfers: the grids are acq_prepare's, a ring's write position the fence's.
+    auto plan = [&]() -> int {
+        if (n < 1 || n > nch) return gc_fail(GNSSCORR_EINVAL, "acq_run: list of %d channels (1..%d)", n, nch);
+        for (int i = 0; i < n; i++) {
+            const int ch = chlist ? chlist[i] : i;
+            if (ch < 0 || ch >= nch || listed[ch])
+                return gc_fail(GNSSCORR_EINVAL, "acq_run: list entry %d: channel %d (0..%d, each once)", i, ch, nch - 1);
+            list.push_back(ch);
+            listed[ch] = 1;
+        }
+        GC_HIP(hipSetDevice(ctx->device));
+        GC_TRY(acq_prepare(ctx));
+        GC_TRY(gc_ingest_fence(ctx));
+        for (int ch : list) maxref = std::max(maxref, (int)ctx->hchan[ch].nref);
+        if (maxref) {               // the refinement's buffers are made by the first search that asks for it
+            GC_RESERVE(ctx, w->fcar, nch);
+            GC_RESERVE(ctx, w->fcar_overflow, 1);
+            GC_RESERVE(ctx, w->prompt, GcAcqDims::prompt_ints(nch));
+            GC_RESERVE(ctx, w->fine, nch);
+        }
+        for (int g = 0; g < w->ngrid; g++)
+            if (std::any_of(list.begin(), list.end(), [&](int ch) { return ctx->hchan[ch].grid == g; })) glist.push_back(g);
+        gw.assign(w->ngrid, 0);
+        for (int g : glist) {
+            const GcChan &c = ctx->hchan[w->grid_chan[g]];
+            const int ft = ctx->hdesc[w->grid_chan[g]].ftype;
+            const uint64_t wp = wp_ring[ft - 1] ? wp_ring[ft - 1] : ctx->ring[ft - 1].wrpos;
+            if (wp < (uint64_t)(c.intg + 1) * c.nsamp)
+                return gc_fail(GNSSCORR_ESTATE, "acq_run: ring %d holds %llu samples, %llu needed", ft,
+                               (unsigned long long)wp, (unsigned long long)((uint64_t)(c.intg + 1) * c.nsamp));
+            if (c.ringlen < (uint64_t)(c.intg + 1) * c.nsamp)
+                return gc_fail(GNSSCORR_EINVAL, "acq_run: ring %d (%llu samples) is shorter than the %d code periods the search looks back",
+                               ft, (unsigned long long)c.ringlen, c.intg + 1);
+            gw[g] = wp;
+            coh = coh || c.ncoh > 1;
+            edge = edge || c.estep > 0;
+        }
+        part = list;
+        nplain = (int)(std::stable_partition(part.begin(), part.end(), [&](int ch) { return ctx->hchan[ch].estep <= 0; }) -
+                       part.begin());
+        return GNSSCORR_OK;
+    };
+    // What changed since the last search goes up: the three lists when they differ, the write positions always; returns
+    // when the copies are staged (pageable sources)
+    auto upload = [&]() -> int {
+        w->nplain = nplain;
+        if (list != w->list || glist != w->glist) {
+            GC_HIP(hipMemcpyAsync(w->d_chans(), list.data(), sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
+            GC_HIP(hipMemcpyAsync(w->d_grids(), glist.data(), sizeof(int) * glist.size(), hipMemcpyHostToDevice,
+                                  ctx->stream));
+            GC_HIP(hipMemcpyAsync(w->d_parts(), part.data(), sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
+            w->list.clear();            // (until the copies are staged)
+        }
+        GC_HIP(hipMemcpyAsync(w->d_grid_wrpos, gw.data(), sizeof(uint64_t) * w->ngrid, hipMemcpyHostToDevice,
+                              ctx->stream));
+        GC_HIP(hipStreamSynchronize(ctx->stream));
+        w->list = list;
+        w->glist = glist;
+        return GNSSCORR_OK;
+    };
+    // acq_fwd over the listed grids, the clears, acq_corr over each part of the list, acq_final
+    auto queue_search = [&]() -> int {
+        const GcAcqDims &d = w->dims;
+        {
+            GcTimed t(ctx, "acq_fwd");
+            auto fwd = edge ? acq_fwd_kernel<true, true> : coh ? acq_fwd_kernel<true> : acq_fwd_kernel<false>;
+            hipLaunchKernelGGL(fwd, dim3(d.maxfreq, d.maxslot, glist.size()), dim3(GC_FFT_THREADS),
+                               GC_FFT_LDS + 256 + GC_ACQ_CARLDS, ctx->stream, ctx->dchan, w->d_grid_chan, w->d_grids(),
+                               w->car, w->d_grid_wrpos, f.tw16k, f.tw32p, f.tw64p1, f.tw64p3, w->X, d.maxfreq, d.maxslot,
+                               d.L);
+        }
+        GC_HIP(hipGetLastError());
+        // channels that are not listed: no iterations, a zero result row
+        if (n < nch) {
+            GC_HIP(hipMemsetAsync(w->iters, 0, sizeof(int) * nch, ctx->stream));
+            GC_HIP(hipMemsetAsync(w->res, 0, sizeof(gnsscorr_acqres_t) * nch, ctx->stream));
+            GC_HIP(hipMemsetAsync(w->edge, 0xff, sizeof(int) * nch, ctx->stream));      // -1
+        }
+        hipLaunchKernelGGL(acq_iters_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, w->iters, ctx->dchan,
+                           w->d_chans(), n);
+        GC_HIP(hipMemsetAsync(w->arrive, 0, sizeof(int) * w->arrive_ints(), ctx->stream));
+        {
+            GcTimed t(ctx, "acq_corr");
+            if (nplain) launch_acq_corr(ctx, nullptr, 0, w->d_parts(), nplain, false);
+            if (n > nplain) launch_acq_corr(ctx, nullptr, 0, w->d_parts() + nplain, n - nplain, true);
+        }
+        GC_HIP(hipGetLastError());
+        {
+            GcTimed t(ctx, "acq_final");
+            hipLaunchKernelGGL(acq_final_kernel, dim3(n), dim3(64), 0, ctx->stream, ctx->dchan, ctx->dfreqs, w->rows,
+                               w->d_grid_wrpos, w->res, w->iters, w->edge, w->d_chans(), n, d);
+        }
+        GC_HIP(hipGetLastError());
+        return GNSSCORR_OK;
+    };
+
+    // behind acq_final: the clears, acq_fine_nco, acq_prompt, acq_fine over the list
+    auto queue_refine = [&]() -> int {
+        const int *dlist = w->d_chans();
         // unlisted channels: a zero row, as in res; every prompt row starts from zero (rows without refinement and
         // the periods beyond a channel's nref stay so)
         if (n < nch) GC_HIP(hipMemsetAsync(w->fine, 0, sizeof(gnsscorr_acqfine_t) * nch, ctx->stream));
-        GC_HIP(hipMemsetAsync(w->prompt, 0, sizeof(int) * (size_t)nch * GNSSCORR_MAXCOH * 2, ctx->stream));
+        GC_HIP(hipMemsetAsync(w->prompt, 0, sizeof(int) * GcAcqDims::prompt_ints(nch), ctx->stream));
         GC_HIP(hipMemsetAsync(w->fcar_overflow, 0, sizeof(int), ctx->stream));
         {
             GcTimed t(ctx, "acq_fine_nco");
@@ -1318,12 +1311,19 @@ int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chl
         }
         {
             GcTimed t(ctx, "acq_fine");
-            hipLaunchKernelGGL(acq_fine_kernel, dim3(n), dim3(64), 0, ctx->stream, ctx->dchan, w->res, w->fcar, dlist, n,
-                               w->prompt, w->fine);
+            hipLaunchKernelGGL(acq_fine_kernel, dim3(n), dim3(64), 0, ctx->stream, ctx->dchan, w->res, w->fcar, dlist,
+                               n, w->prompt, w->fine);
         }
         GC_HIP(hipGetLastError());
         w->refined = true;
-    }
+        return GNSSCORR_OK;
+    };
+    GC_TRY(plan());
+    GC_TRY(upload());
+    w->ran = false;                 // until every launch below is queued
+    GC_TRY(queue_search());
+    w->refined = false;
+    if (maxref) GC_TRY(queue_refine());
     w->listed = listed;
     w->ran = true;
     return GNSSCORR_OK;
@@ -1342,25 +1342,27 @@ extern "C" int gnsscorr_acq_run_subset(gnsscorr_ctx *ctx, uint64_t wrpos, const 
     return gc_acq_run_list(ctx, wp, chlist, n);
 }
 
+// a fetch call's device array to the host (a null destination is skipped) and, behind a call's last one, the wait
+static int acq_copy_out(gnsscorr_ctx *ctx, void *dst, const void *src, size_t bytes, bool last = true)
+{
+    GC_HIP(hipSetDevice(ctx->device));
+    if (dst) GC_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (last) GC_HIP(hipStreamSynchronize(ctx->stream));
+    return GNSSCORR_OK;
+}
+
 extern "C" int gnsscorr_acq_fetch(gnsscorr_ctx *ctx, gnsscorr_acqres_t *res)
 {
     if (!ctx || !ctx->acq.ran) return gc_fail(GNSSCORR_ESTATE, "acq_fetch: no acq_run yet");
     if (!res) return gc_fail(GNSSCORR_EINVAL, "acq_fetch: null result array");
-    GC_HIP(hipSetDevice(ctx->device));
-    GC_HIP(hipMemcpyAsync(res, ctx->acq.res, sizeof(gnsscorr_acqres_t) * ctx->nch, hipMemcpyDeviceToHost,
-                          ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    return GNSSCORR_OK;
+    return acq_copy_out(ctx, res, ctx->acq.res, sizeof(gnsscorr_acqres_t) * ctx->nch);
 }
 
 extern "C" int gnsscorr_acq_fetch_edge(gnsscorr_ctx *ctx, int *edge)
 {
     if (!ctx || !edge) return gc_fail(GNSSCORR_EINVAL, "acq_fetch_edge: null context or result array");
     if (!ctx->acq.ran) return gc_fail(GNSSCORR_ESTATE, "acq_fetch_edge: no acq_run yet");
-    GC_HIP(hipSetDevice(ctx->device));
-    GC_HIP(hipMemcpyAsync(edge, ctx->acq.edge, sizeof(int) * ctx->nch, hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    return GNSSCORR_OK;
+    return acq_copy_out(ctx, edge, ctx->acq.edge, sizeof(int) * ctx->nch);
 }
 
 // The refinement of the last search (include/gnsscorr.h).  A search that queued none (no listed channel with nref > 0)
@@ -1369,27 +1371,21 @@ extern "C" int gnsscorr_acq_fetch_fine(gnsscorr_ctx *ctx, gnsscorr_acqfine_t *fi
 {
     if (!ctx || !ctx->acq.ran) return gc_fail(GNSSCORR_ESTATE, "acq_fetch_fine: no acq_run yet");
     if (!fine) return gc_fail(GNSSCORR_EINVAL, "acq_fetch_fine: null result array");
-    GC_HIP(hipSetDevice(ctx->device));
     GcAcq *w = &ctx->acq;
     const int nch = ctx->nch;
-    const size_t np = (size_t)nch * GNSSCORR_MAXCOH * 2;
+    const size_t np = GcAcqDims::prompt_ints(nch);
     if (!w->refined) {
         std::vector<gnsscorr_acqres_t> res(nch);
         GC_TRY(gnsscorr_acq_fetch(ctx, res.data()));
-        for (int i = 0; i < nch; i++) {
-            fine[i].finefreq = res[i].acqfreq;
-            fine[i].quality = 0.0;
-            fine[i].q = 0;
-            fine[i].nref = 0;
-        }
+        memset(fine, 0, sizeof(gnsscorr_acqfine_t) * nch);
+        for (int i = 0; i < nch; i++) fine[i].finefreq = res[i].acqfreq;
         if (prompt) memset(prompt, 0, sizeof(int32_t) * np);
         return GNSSCORR_OK;
     }
     int over = 0;
-    GC_HIP(hipMemcpyAsync(fine, w->fine, sizeof(gnsscorr_acqfine_t) * nch, hipMemcpyDeviceToHost, ctx->stream));
-    if (prompt) GC_HIP(hipMemcpyAsync(prompt, w->prompt, sizeof(int32_t) * np, hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipMemcpyAsync(&over, w->fcar_overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
+    GC_TRY(acq_copy_out(ctx, fine, w->fine, sizeof(gnsscorr_acqfine_t) * nch, false));
+    GC_TRY(acq_copy_out(ctx, prompt, w->prompt, sizeof(int32_t) * np, false));
+    GC_TRY(acq_copy_out(ctx, &over, w->fcar_overflow, sizeof(int)));
     if (over)
         return gc_fail(GNSSCORR_EINVAL, "acquisition: %d refine spans need more carrier NCO pieces than the tables hold", over);
     return GNSSCORR_OK;
@@ -1453,7 +1449,7 @@ int gc_acq_handover(gnsscorr_ctx *ctx, bool quiesce)
     if (quiesce) { int rc = gc_quiesce(ctx); if (rc) return rc; }
     const int n = (int)ctx->acq.list.size();
     hipLaunchKernelGGL(acq_to_loop_kernel, dim3(n), dim3(64), 0, ctx->stream, ctx->dchan, ctx->acq.res,
-                       ctx->acq.refined ? ctx->acq.fine.p : nullptr, ctx->state.cur(), ctx->loop.dloop, ctx->acq.d_list, n);
+                       ctx->acq.refined ? ctx->acq.fine.p : nullptr, ctx->state.cur(), ctx->loop.dloop, ctx->acq.d_chans(), n);
     GC_HIP(hipGetLastError());
     return GNSSCORR_OK;
 }

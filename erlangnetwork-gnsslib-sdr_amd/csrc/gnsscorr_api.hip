@@ -506,44 +506,58 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
     return upload_channels(ctx);
 }
 
-// Coherent integration per channel (include/gnsscorr.h).  The grids are numbered again, the channel table goes up and
-// what acquisition had prepared for the old setting (code spectra, carrier tables, forward spectra, cached lists, the
-// last results) is dropped: the next search prepares again.
+// The per-channel acquisition settings below take a channel range [ch0, ch0 + nch) and an array of nch values
+static int acq_setting_range(const char *fn, gnsscorr_ctx *ctx, int ch0, int nch, const int *values)
+{
+    if (!ctx || !values || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
+        return gc_fail(GNSSCORR_EINVAL, "%s: channel range [%d,%d) of %d", fn, ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    return GNSSCORR_OK;
+}
+
+// A setting the forward spectra depend on: once nothing is in flight, write() changes the host channel table, the grids
+// are numbered again, the table goes up, and what acquisition had prepared for the old setting (code spectra, carrier
+// tables, forward spectra, cached lists, the last results) is dropped: the next search prepares again.
+template <class Write>
+static int acq_change_grids(gnsscorr_ctx *ctx, Write write)
+{
+    GC_HIP(hipSetDevice(ctx->device));
+    int rc = gc_quiesce(ctx);
+    if (rc) return rc;
+    write();
+    assign_acq_grids(ctx);
+    ctx->acq = GcAcq();
+    return upload_channels(ctx);
+}
+
+// Coherent integration per channel (include/gnsscorr.h)
 extern "C" int gnsscorr_acq_set_coherent(gnsscorr_ctx *ctx, int ch0, int nch, const int *ncoh)
 {
-    if (!ctx || !ncoh || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
-        return gc_fail(GNSSCORR_EINVAL, "acq_set_coherent: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    GC_TRY(acq_setting_range("acq_set_coherent", ctx, ch0, nch, ncoh));
     for (int i = 0; i < nch; i++) {
         const int intg = ctx->hchan[ch0 + i].intg;
         if (ncoh[i] < 1 || ncoh[i] > GNSSCORR_MAXCOH || intg % ncoh[i] != 0)
             return gc_fail(GNSSCORR_EINVAL, "acq_set_coherent: channel %d: ncoh %d (1..%d, a divisor of intg %d)", ch0 + i,
                            ncoh[i], GNSSCORR_MAXCOH, intg);
     }
-    GC_HIP(hipSetDevice(ctx->device));
-    int rc = gc_quiesce(ctx);
-    if (rc) return rc;
-    for (int i = 0; i < nch; i++) {
-        ctx->hchan[ch0 + i].ncoh = ncoh[i];
-        ctx->hchan[ch0 + i].estep = 0;          // the hypotheses depend on ncoh: gnsscorr_acq_set_bitedge comes after
-    }
-    assign_acq_grids(ctx);
-    ctx->acq = GcAcq();
-    return upload_channels(ctx);
+    return acq_change_grids(ctx, [&] {
+        for (int i = 0; i < nch; i++) {
+            ctx->hchan[ch0 + i].ncoh = ncoh[i];
+            ctx->hchan[ch0 + i].estep = 0;      // the hypotheses depend on ncoh: gnsscorr_acq_set_bitedge comes after
+        }
+    });
 }
 
 extern "C" int gnsscorr_acq_get_coherent(gnsscorr_ctx *ctx, int ch0, int nch, int *ncoh)
 {
-    if (!ctx || !ncoh || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
-        return gc_fail(GNSSCORR_EINVAL, "acq_get_coherent: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    GC_TRY(acq_setting_range("acq_get_coherent", ctx, ch0, nch, ncoh));
     for (int i = 0; i < nch; i++) ncoh[i] = ctx->hchan[ch0 + i].ncoh;
     return GNSSCORR_OK;
 }
 
-// Bit-edge hypotheses per channel (include/gnsscorr.h); what changes and what is dropped: as gnsscorr_acq_set_coherent
+// Bit-edge hypotheses per channel (include/gnsscorr.h)
 extern "C" int gnsscorr_acq_set_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, const int *estep)
 {
-    if (!ctx || !estep || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
-        return gc_fail(GNSSCORR_EINVAL, "acq_set_bitedge: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    GC_TRY(acq_setting_range("acq_set_bitedge", ctx, ch0, nch, estep));
     // the hypotheses are served by the 32768-point transform only, and the transform length is the context's
     for (int i = 0; i < ctx->nch; i++)
         if (ctx->hchan[i].nsamp > 16384)
@@ -555,19 +569,14 @@ extern "C" int gnsscorr_acq_set_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, con
             return gc_fail(GNSSCORR_EINVAL, "acq_set_bitedge: channel %d: estep %d (0, or 1..ncoh-1 with ncoh %d >= 2)",
                            ch0 + i, estep[i], ncoh);
     }
-    GC_HIP(hipSetDevice(ctx->device));
-    int rc = gc_quiesce(ctx);
-    if (rc) return rc;
-    for (int i = 0; i < nch; i++) ctx->hchan[ch0 + i].estep = estep[i];
-    assign_acq_grids(ctx);
-    ctx->acq = GcAcq();
-    return upload_channels(ctx);
+    return acq_change_grids(ctx, [&] {
+        for (int i = 0; i < nch; i++) ctx->hchan[ch0 + i].estep = estep[i];
+    });
 }
 
 extern "C" int gnsscorr_acq_get_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, int *estep)
 {
-    if (!ctx || !estep || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
-        return gc_fail(GNSSCORR_EINVAL, "acq_get_bitedge: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    GC_TRY(acq_setting_range("acq_get_bitedge", ctx, ch0, nch, estep));
     for (int i = 0; i < nch; i++) estep[i] = ctx->hchan[ch0 + i].estep;
     return GNSSCORR_OK;
 }
@@ -576,8 +585,7 @@ extern "C" int gnsscorr_acq_get_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, int
 // numbers, and what acquisition has prepared and the last search's results stay.
 extern "C" int gnsscorr_acq_set_refine(gnsscorr_ctx *ctx, int ch0, int nch, const int *nref)
 {
-    if (!ctx || !nref || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
-        return gc_fail(GNSSCORR_EINVAL, "acq_set_refine: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    GC_TRY(acq_setting_range("acq_set_refine", ctx, ch0, nch, nref));
     for (int i = 0; i < nch; i++) {
         const int intg = ctx->hchan[ch0 + i].intg, top = intg < GNSSCORR_MAXCOH ? intg : GNSSCORR_MAXCOH;
         if (nref[i] < 0 || nref[i] == 1 || nref[i] > top)
@@ -593,8 +601,7 @@ extern "C" int gnsscorr_acq_set_refine(gnsscorr_ctx *ctx, int ch0, int nch, cons
 
 extern "C" int gnsscorr_acq_get_refine(gnsscorr_ctx *ctx, int ch0, int nch, int *nref)
 {
-    if (!ctx || !nref || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
-        return gc_fail(GNSSCORR_EINVAL, "acq_get_refine: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    GC_TRY(acq_setting_range("acq_get_refine", ctx, ch0, nch, nref));
     for (int i = 0; i < nch; i++) nref[i] = ctx->hchan[ch0 + i].nref;
     return GNSSCORR_OK;
 }

@@ -292,18 +292,49 @@ struct GcAcqCar {
     GcCarSeg seg[GC_NCAR];
 };
 
+// The dimensions of a prepared search and the layout of its arrays, handed to the kernels by value (acq_fwd, acq_corr and
+// acq_corr64 build theirs from scalar arguments).  iter: an iteration of the search, a group of ncoh code periods; slot =
+// iter * H + hypothesis index, H the grid's bit-edge hypotheses (1 without).
+struct GcAcqDims {
+    int maxfreq;                // the largest bin count of a channel
+    int maxintg;                // the largest iteration count, intg / ncoh
+    int maxslot;                // the largest iterations x H of a grid (not the product of the two maxima)
+    int L;                      // transform length of the channel set: 32768, or 65536 when a period exceeds 16384 samples
+    // rows[ch][iter][bin]: one bin's record (bin 0: the bins of the iteration)
+    template <class T> GC_HDM T *row(T *rows, int ch, int it, int bin = 0) const
+    {
+        return rows + (((size_t)ch * maxintg + it) * maxfreq + bin);
+    }
+    // arrivals[ch][iter]: the workgroups of the channel that are done with the iteration
+    GC_HDM int *arrival(int *arrivals, int ch, int it) const { return arrivals + (ch * maxintg + it); }
+    // X[grid][slot][bin][L]: X[f + 16384 q] at [q][pass position of f].  A 65536-point channel set has no hypotheses
+    // (gnsscorr_acq_set_bitedge refuses it; acq_prepare checks): there slot = iter and maxslot == maxintg.
+    template <class T> GC_HDM T *x(T *X, int grid, size_t slot, int bin) const
+    {
+        return X + (((size_t)grid * maxslot + slot) * maxfreq + bin) * (size_t)L;
+    }
+    GC_HDM size_t x_slot_stride() const { return (size_t)maxfreq * L; }     // from a slot to the next, same grid and bin
+    // C[ch][L]: the channel's code spectrum, laid out as a slot of X
+    template <class T> GC_HDM T *code(T *C, int ch) const { return C + (size_t)ch * L; }
+    // prompt[ch][GNSSCORR_MAXCOH][2]: the prompt sum (I, Q) of period m of the channel's refine span
+    template <class T> GC_HDM static T *prompt(T *prompt, int ch, int m) { return prompt + ((size_t)ch * GNSSCORR_MAXCOH + m) * 2; }
+    static size_t prompt_ints(int nch) { return (size_t)nch * GNSSCORR_MAXCOH * 2; }
+};
+
 // Acquisition (gnsscorr_acq.hip): what depends on the channel set and its coherent setting
 struct GcAcq {
     bool prepared = false;      // acq_prepare has sized the buffers below and queued the carrier tables and code spectra
+    int nch = 0, ngrid = 0;     // channels and frequency grids the buffers are sized for
+    GcAcqDims dims = {0, 0, 0, 32768};
     GcDevBuf<GcAcqCar> car;     // [grid][bin]
     GcDevBuf<int> car_overflow;
-    int L = 32768;              // transform length of this channel set: 32768, or 65536 when a period exceeds 16384 samples
-    GcDevBuf<float2> X;         // [grid][slot][bin][2][16384]: X[f] and X[f + 16384] at the pass position of f
-                                // (iter, here and below: an iteration of the search, a group of ncoh code periods;
-                                // slot = iter * H + hypothesis index, H the grid's bit-edge hypotheses, 1 without)
-    GcDevBuf<float2> C;         // [ch][2][16384]
-    GcDevBuf<GcAcqRow> rows;    // [ch][iter][bin]
-    GcDevBuf<int> arrive;       // [ch][iter] workgroups done with the iteration, then [ch] "acquired" flags
+    GcDevBuf<float2> X;         // forward spectra (GcAcqDims::x)
+    GcDevBuf<float2> C;         // code spectra (GcAcqDims::code)
+    GcDevBuf<GcAcqRow> rows;    // row statistics (GcAcqDims::row)
+    GcDevBuf<int> arrive;       // one buffer, one clear per search: arrivals(), then done()
+    int *arrivals() const { return arrive; }                                // [ch][iter] workgroups done with the iteration
+    int *done() const { return arrive + (size_t)nch * dims.maxintg; }       // [ch] "acquired" flags
+    size_t arrive_ints() const { return (size_t)nch * dims.maxintg + nch; }
     GcDevBuf<int> iters;        // [ch] iteration limit for acq_corr
     GcDevBuf<gnsscorr_acqres_t> res;    // [ch]
     GcDevBuf<int> edge;         // [ch] bit edge of the deciding group's best row (gnsscorr_acq_fetch_edge), -1: none
@@ -311,18 +342,19 @@ struct GcAcq {
     // carrier refinement (gnsscorr_acq_set_refine; made by the first search that lists a channel with nref > 0)
     GcDevBuf<GcAcqCar> fcar;    // [ch] carrier table of the refine span: res[ch].acqfreq over nref*nsamp samples (n 0: none)
     GcDevBuf<int> fcar_overflow;
-    GcDevBuf<int> prompt;       // [ch][GNSSCORR_MAXCOH][2] prompt sums (I, Q) of the span's periods, zero beyond nref
+    GcDevBuf<int> prompt;       // prompt sums of the span's periods (GcAcqDims::prompt), zero beyond nref
     GcDevBuf<gnsscorr_acqfine_t> fine;  // [ch]
     bool refined = false;       // the last search queued the refinement: fine and prompt hold its results
-    int ngrid = 0, maxfreq = 0, maxintg = 0;    // maxintg: the largest iteration (group) count, intg / ncoh
-    int maxslot = 0;                    // the largest iterations x H of a grid: X's slots (maxintg without hypotheses)
     std::vector<int> grid_chan;         // a representative channel per grid
     GcDevBuf<int> d_grid_chan;          // device copy of grid_chan
     GcDevBuf<uint64_t> d_grid_wrpos;    // ring write position seen by each grid
-    GcDevBuf<int> d_list;               // [nch] channels of the last run, then [ngrid] the grids that have one of them,
-                                        // then [nch] the run's channels again, those without hypotheses first
+    GcDevBuf<int> d_list;               // the last run's lists, one buffer:
+    int *d_chans() const { return d_list; }                 // [nch] its channels, as listed
+    int *d_grids() const { return d_list + nch; }           // [ngrid] the grids that have one of them
+    int *d_parts() const { return d_list + nch + ngrid; }   // [nch] its channels again, those without hypotheses first
+    size_t list_ints() const { return (size_t)2 * nch + ngrid; }
     int nplain = 0;                     // how many of the last run's channels have no hypotheses
-    std::vector<int> list, glist;       // host copies of what d_list holds
+    std::vector<int> list, glist;       // host copies of d_chans() and d_grids()
     std::vector<char> listed;           // [nch] channel was part of the last run
     bool ran = false;                   // a search has been queued: there are results to fetch
 };

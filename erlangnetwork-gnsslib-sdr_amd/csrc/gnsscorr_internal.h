@@ -118,8 +118,9 @@ struct GcAcqRow {
     double sum_out;     // sum outside the +-2 chip window around argmax
     double max_out;     // maxvd() outside the window (element 0 always a candidate)
     int    argmax;
-    int    pad;
+    int    edge;        // bit-edge hypothesis h whose row was added this iteration (0 without hypotheses)
 };
+static_assert(sizeof(GcAcqRow) == 32 && offsetof(GcAcqRow, edge) == 28, "row record layout");
 
 #define GC_HIP(call)                                                           \
     do {                                                                       \

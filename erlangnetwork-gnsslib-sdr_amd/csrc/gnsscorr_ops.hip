@@ -20,15 +20,11 @@
 
 #include "../../include/sdr_compat.h"
 #include "gnsscorr_ctx.h"
+#include "gnsscorr_lut.h"
 
 #define SDRPRINTF printf
 
 namespace {
-
-__constant__ signed char oCos32[32] = {32, 31, 30, 27, 23, 18, 12, 6, 0, -6, -12, -18, -23, -27, -30, -31,
-                                       -32, -31, -30, -27, -23, -18, -12, -6, 0, 6, 12, 18, 23, 27, 30, 31};
-__constant__ signed char oSin32[32] = {0, 6, 12, 18, 23, 27, 30, 31, 32, 31, 30, 27, 23, 18, 12, 6,
-                                       0, -6, -12, -18, -23, -27, -30, -31, -32, -31, -30, -27, -23, -18, -12, -6};
 
 // out[f] = sum_j in[j] exp(sign*2*pi*i*f*j/m), one output per lane, inputs
 // staged through LDS, twiddle advanced by rotation in fp64 and re-seeded from
@@ -123,17 +119,8 @@ __global__ void mix_kernel(const int8_t *__restrict__ data, int dtype, int n, co
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     const int idx = gc_carrier_idx_at(t->k0, t->car, t->ncar, k);
-    const int c = oCos32[idx], s = oSin32[idx];
     int vi, vq;
-    if (dtype == 2) {
-        const int d0 = data[2 * k], d1 = data[2 * k + 1];
-        vi = c * d0 - s * d1;
-        vq = s * d0 + c * d1;
-    } else {
-        const int d0 = data[k];
-        vi = c * d0;
-        vq = s * d0;
-    }
+    gc_wipeoff(idx, dtype, [&] { return make_int2(data[2 * k], data[2 * k + 1]); }, [&] { return (int)data[k]; }, vi, vq);
     if (I) I[k] = (short)vi;
     if (Q) Q[k] = (short)vq;
     if (cpx) cpx[k] = make_float2((float)vi * scale, (float)vq * scale);

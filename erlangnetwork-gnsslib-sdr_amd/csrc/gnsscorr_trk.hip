@@ -26,6 +26,7 @@
 
 
 #include "gnsscorr_ctx.h"        // the host driver below the kernels
+#include "gnsscorr_lut.h"        // the carrier LUT (trk_corr builds its dot-product operands from it)
 #include "gnsscorr_ps.h"
 
 namespace {
@@ -229,12 +230,6 @@ __global__ __launch_bounds__(GC_EXP_LANES) void trk_expand_kernel(const GcChan *
 // ---------------------------------------------------------------------------
 // correlator
 // ---------------------------------------------------------------------------
-// carrier LUT: cost[i] = floor(32 cos(2 pi i/32) + 0.5) (ref src/sdrcmn.c:643-648)
-__constant__ signed char kCos32[32] = {32, 31, 30, 27, 23, 18, 12, 6, 0, -6, -12, -18, -23, -27, -30, -31,
-                                       -32, -31, -30, -27, -23, -18, -12, -6, 0, 6, 12, 18, 23, 27, 30, 31};
-__constant__ signed char kSin32[32] = {0, 6, 12, 18, 23, 27, 30, 31, 32, 31, 30, 27, 23, 18, 12, 6,
-                                       0, -6, -12, -18, -23, -27, -30, -31, -32, -31, -30, -27, -23, -18, -12, -6};
-
 typedef short gc_s2 __attribute__((ext_vector_type(2)));
 
 // Phase time stamps of sampled workgroups (debug builds only: -DGC_TRK_TRACE; tools/trk_trace.py)
@@ -335,7 +330,7 @@ __global__ __launch_bounds__(256) void trk_corr_kernel(const GcChan *__restrict_
 
     if (tid < 32 * LUTPOS) {
         const int idx = tid & 31, pos = tid >> 5;
-        const int cs_ = kCos32[idx], sn_ = kSin32[idx];
+        const int cs_ = gcCos32[idx], sn_ = gcSin32[idx];
         uint2 v;
         if (DTYPE == 2) {   // bytes [c,-s] -> I ; [s,c] -> Q for one IQ sample
             v.x = ((unsigned)(cs_ & 0xFF) | ((unsigned)((-sn_) & 0xFF) << 8)) << (16 * pos);
