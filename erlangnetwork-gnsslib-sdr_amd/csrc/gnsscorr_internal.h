@@ -140,6 +140,40 @@ struct GcRound {
     int hint;           // code piece that holds the round's first replica position
 };
 
+// What trk_expand_kernel (gnsscorr_trk.hip) and the closed loop's tail (gnsscorr_loop.hip) both state of a period.
+// The period's place in the channel's ring: first sample buffloc, n samples of c.dtype bytes, taps out to c.smax samples.
+// (The channel by reference: its fields are then read where they are used, as trk_expand_kernel read them before; what
+// its code still differs by from before the helpers: DESIGN.md section 6.)
+__device__ __forceinline__ void gc_unit_geometry(GcTrkUnit &u, const GcChan &c, uint64_t buffloc, int n)
+{
+    const uint64_t a0 = (buffloc % c.ringlen) * (uint64_t)c.dtype;
+    u.a_al = a0 & ~(uint64_t)15;
+    u.head = (int)(a0 - u.a_al);
+    u.G = (u.head + n * c.dtype + 15) >> 4;
+    u.nt = n + 2 * c.smax;
+}
+// The replica positions a round of rsamp samples from sample kl on can touch: its first sample's .. its last sample's + 2 smax.
+__device__ __forceinline__ void gc_round_span(int kl, int rsamp, int n, int smax, int *jfirst, int *jlast)
+{
+    const int kend = kl + rsamp < n ? kl + rsamp : n;
+    *jfirst = kl > 0 ? kl : 0;
+    *jlast = kend - 1 + 2 * smax;
+}
+// The round's record from the chips at those two positions: chip ma after wa code wraps, chip mb after wb; hint: ma's piece;
+// code: the channel's code block (GcChan::code, read once by the caller), nedge its edges per period.
+// (The chips come from the caller's own chip_at: a performance form per table layout.)
+__device__ __forceinline__ GcRound gc_round_make(const int8_t *code, int nedge, int ma, int wa, int mb, int wb, int hint)
+{
+    const unsigned short *rank = (const unsigned short *)(code + 1024);
+    GcRound ro;
+    ro.q0 = wa * nedge + (int)rank[ma];
+    ro.q1 = wb * nedge + (int)rank[mb];
+    ro.clast = (short)code[mb];
+    ro.w0 = (short)wa;
+    ro.hint = hint;
+    return ro;
+}
+
 // kernel launchers (definitions in gnsscorr_trk.hip / gnsscorr_plan.hip / gnsscorr_acq.hip)
 size_t gc_trk_spec_ints(size_t units);
 int gc_launch_trk_spec(hipStream_t st, const GcChan *chan, const GcTrkState *state_in, int nch, int nepoch, int *claims,

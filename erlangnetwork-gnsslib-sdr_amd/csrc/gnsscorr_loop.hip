@@ -10,10 +10,11 @@
 // interval": 1 period before bit sync, up to loopms after) are open-loop work: they are planned in one go and
 // correlated side by side.  A run is a chain of launch pairs on one stream, no host round trip:
 //
-//   trk_step_tail  one wavefront per channel: closes the interval the previous correlator launch produced
-//                  (partial sums -> II/QQ, sdrnavigation's bit sync / bit decision, cumsumcorr, pll/dll where due,
-//                  log rows) and plans the next one (the exact NCO chain of gnsscorr_nco.h with the piece tables of
-//                  every period, unit constants and rounds, written for the correlator).
+//   trk_step_tail  one workgroup of eight wavefronts per channel: closes the interval the previous correlator launch
+//                  produced (partial sums -> II/QQ, sdrnavigation's bit sync / bit decision, cumsumcorr, pll/dll where
+//                  due, log rows) and plans the next one: the exact NCO chains of gnsscorr_nco.h on two wavefronts, then
+//                  every (period, NCO) piece table as a task from a queue all wavefronts serve, then unit constants
+//                  and rounds, written for the correlator.
 //   trk_step_corr  (channel, period of the interval, quarter) -> one 256-lane workgroup running ps_unit
 //                  (gnsscorr_ps.h) on four rounds of 1024 IQ samples, one per wavefront; int32 partial sums per workgroup.
 //
@@ -30,6 +31,8 @@
 
 #ifdef GC_TAIL_PROF     // (tools/debug: shader-clock stamps of channel 0's tail wavefront, summed over the launches)
 __device__ unsigned long long gc_tail_prof[16];
+__shared__ unsigned long long tprev_;       // (thread 0's last stamp: the phases are functions of their own)
+#define GC_TSTART() do { if (threadIdx.x == 0) tprev_ = __builtin_readcyclecounter(); } while (0)
 #define GC_TSTAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) { const unsigned long long t_ = __builtin_readcyclecounter(); \
         gc_tail_prof[i] += t_ - tprev_; tprev_ = t_; } } while (0)
 extern "C" int gnsscorr_debug_tail_prof(unsigned long long *dst, int reset)
@@ -39,6 +42,7 @@ extern "C" int gnsscorr_debug_tail_prof(unsigned long long *dst, int reset)
     return 0;
 }
 #else
+#define GC_TSTART() do { } while (0)
 #define GC_TSTAMP(i) do { } while (0)
 #endif
 
@@ -311,17 +315,35 @@ __device__ __forceinline__ void fast_init_lanes(GcNcoFast &f, double s, bool wit
         f.ex0 = ok ? es + 2 : GC_NO_TABLE;
     }
 }
+// what one lane of a wavefront wrote to LDS, every lane of it reads afterwards
+__device__ __forceinline__ void tail_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 // gc_code_plan_init(P, ci, len, smax) around fast_init_lanes
 __device__ __forceinline__ void code_plan_init_lanes(GcCodePlan &P, double ci, int len, int smax, int lane)
 {
     GC_FP_STRICT
     fast_init_lanes(P.f, ci, true, lane);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    tail_wave_sync();
     if (lane == 0) gc_code_plan_shape(P, ci, len, smax);
 }
-
+// Progress words (LDS): lane 0 publishes how many periods its wavefront has finished, with all it stored for them, and
+// TAIL_DONE once it stops.  prog_wait_past: until period e is finished; TAIL_DONE seen with e >= S.k: e never comes.
+constexpr int TAIL_DONE = 0x7fffffff;
+__device__ __forceinline__ void prog_publish(int *word, int count) { __hip_atomic_store(word, count, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ void prog_publish_done(int *word) { prog_publish(word, TAIL_DONE); }
+__device__ __forceinline__ int prog_wait_past(const int *word, int e)
+{
+    int pg;
+    while ((pg = __hip_atomic_load(word, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) <= e) __builtin_amdgcn_s_sleep(1);
+    return pg;
+}
+// bracket discovery, lanes e and 32 + e: the value at the bracket's other end, and whether the two ends agree on one
+template <class T> __device__ __forceinline__ T pair_other(T v, int lane) { return __shfl(v, lane ^ 32, 64); }
+__device__ __forceinline__ bool pair_same(int v, int lane) { return v == pair_other(v, lane); }
 // the general walkers for a period the shaped steps decline (a tie in the top binade, a phase next to zero, ...):
 // out of line, with tables of their own (the workgroup's shared tables stay read-only)
 template <class Emit>
@@ -341,7 +363,36 @@ __device__ __attribute__((noinline)) double tail_code_slow(double ci, double rem
     const double cend = gc_fast_code_walk(f, gc_code_start(remcode, smax, ci, clen), clen, nt, emit);
     return gc_code_rem(cend, smax, ci);
 }
-
+// The ladder's lower rungs, for the chains (GcNoEmit) and the table tasks (Lds*Table): the certified period step, else
+// the emitter forgets the attempt and the walkers above take the period.  (gc_*_period_any of gnsscorr_nco.h walk inline
+// on the plan's tables: the kernel sits at its register cap, and S.PK.f has no reciprocals for the carrier walker.)
+template <class Emit>
+__device__ __forceinline__ double tail_code_period(const GcCodePlan &PC, const GcChan &c, double ci, double remcode, int nt, int lane, Emit &emit)
+{
+    GcFillLanes fill{lane};
+    double r;
+    if (gc_code_period(PC, remcode, nt, fill, &r, emit)) return r;
+    emit.reset();
+    return tail_code_slow(ci, remcode, c.clen, c.smax, nt, emit);
+}
+template <class Emit>
+__device__ __forceinline__ double tail_carrier_period(const GcCarPlan &PK, double ps, double remcarr, int n, int lane, Emit &emit)
+{
+    GcFillLanes fill{lane};
+    double r;
+    if (gc_carrier_period(PK, remcarr, n, fill, &r, emit)) return r;
+    emit.reset();
+    return tail_carrier_slow(ps, remcarr, n, emit);
+}
+// gc_code_claims_step of the channel's tail class tcls (gc_tail_class: how many positions the tail's instance holds)
+template <int IT, bool PERLANE>
+__device__ __forceinline__ bool tail_code_claims_step(int tcls, const GcCodePlan &PC, const GcCodeStepC<IT> &SC, double remcode, int nt,
+                                                      GcCodeClaims &cl, double *out)
+{
+    if (tcls == 0) return gc_code_claims_step<IT, gc_tail_max(0), false, PERLANE>(PC, SC, remcode, nt, cl, out);
+    if (tcls == 1) return gc_code_claims_step<IT, gc_tail_max(1), false, PERLANE>(PC, SC, remcode, nt, cl, out);
+    return gc_code_claims_step<IT, gc_tail_max(2), false, PERLANE>(PC, SC, remcode, nt, cl, out);
+}
 // the step WITH its checks, for a period whose start lies outside the bracket its claims were proved for (rare): out
 // of line, so that the chains' loops carry the value form only.  PC / PK / cl: the workgroup's tables and rows (LDS).
 template <int IT>
@@ -351,10 +402,7 @@ __device__ __attribute__((noinline)) bool tail_code_checked(const GcCodePlan *PC
     gc_code_stepc_init(SC, *PC);
     GcCodeClaims c2 = *cl;
     double r;
-    bool ok;
-    if (tcls == 0) ok = gc_code_claims_step<IT, gc_tail_max(0), false, true>(*PC, SC, remcode, nt, c2, &r);
-    else if (tcls == 1) ok = gc_code_claims_step<IT, gc_tail_max(1), false, true>(*PC, SC, remcode, nt, c2, &r);
-    else ok = gc_code_claims_step<IT, gc_tail_max(2), false, true>(*PC, SC, remcode, nt, c2, &r);
+    const bool ok = tail_code_claims_step<IT, true>(tcls, *PC, SC, remcode, nt, c2, &r);
     if (ok) *out = r;
     return ok;
 }
@@ -368,7 +416,6 @@ __device__ __attribute__((noinline)) bool tail_carrier_checked(const GcCarPlan *
     if (ok) *out = r;
     return ok;
 }
-
 #define GC_TAIL_NW 8            // wavefronts of the tail workgroup
 struct TailShared {
     gnsscorr_loop_t lp;
@@ -389,505 +436,359 @@ struct TailShared {
     GcCarSeg car[GC_STEP_KMAX][GC_NCAR];
     GcCodeSeg code[GC_STEP_KMAX][GC_NCODE];
 };
-
-__device__ __forceinline__ void tail_wave_sync()
+// ---- the tail's phases, in the kernel's order.  A: the kernel's arguments and who this lane is; S: the LDS block ----
+struct TailArgs {
+    const GcChan *chan; GcTrkState *state; gnsscorr_loop_t *loop; GcStepMeta *meta; const uint64_t *wrpos; const int *partial;
+    GcTrkUnit *unit; GcUnitSegs *segs; GcRound *rounds; double *corrI, *corrQ; int *nsamp_out; gnsscorr_trklog_t *log;
+    int *ndone, *nco_overflow, *lapped; unsigned *hostflags;
+    int nper, nseg, ntap_stride, max_n, kcap, plan;
+    int ch, tid, lane, wave;        // who this lane is
+};
+struct TailSteps { double ci, ps, spc, dlen; bool shape_ok; };    // q, the next interval's NCO steps (shape_ok: the reference's one-subtraction code wrap is defined)
+__device__ __forceinline__ void tail_copy_loop(gnsscorr_loop_t *to, const gnsscorr_loop_t *from, int tid)
 {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const unsigned long long *src = reinterpret_cast<const unsigned long long *>(from);
+    unsigned long long *dst = reinterpret_cast<unsigned long long *>(to);
+    for (int i = tid; i < (int)(sizeof(gnsscorr_loop_t) / 8); i += 64 * GC_TAIL_NW) dst[i] = src[i];
 }
-
-// One workgroup (GC_TAIL_NW wavefronts) per channel.
-//   close     wavefront 0: the interval the previous correlator launch produced -- per period the sums, sdrnavigation's
-//             bit sync / bit decision, cumsumcorr, the filters where due, the log row;
-//   plan      how many periods the next interval has (nav_interval, the run's end, what the ring holds); the step tables
-//             of its frequencies (one lane per binade); for more than one period the chain of period starts -- code on
-//             wavefront 1, carrier on wavefront 0 one step behind (it needs the period lengths), nothing emitted;
-//   tables    every (period, NCO) is a task of its own: the period step again, from its known start, with the piece
-//             table emitted into LDS -- all wavefronts side by side (a one-period interval skips the chain: these steps
-//             are the chain);
-//   out       per period: fixed-point / reciprocal forms (lane-parallel), the tables' invariants, the rounds, and the
-//             copy to the correlator's buffers.
-__global__ __launch_bounds__(64 * GC_TAIL_NW) void trk_step_tail_kernel(
-    const GcChan *__restrict__ chan, GcTrkState *__restrict__ state, gnsscorr_loop_t *__restrict__ loop,
-    GcStepMeta *__restrict__ meta, const uint64_t *__restrict__ wrpos, const int *__restrict__ partial,
-    GcTrkUnit *__restrict__ unit, GcUnitSegs *__restrict__ segs, GcRound *__restrict__ rounds, double *__restrict__ corrI,
-    double *__restrict__ corrQ, int *__restrict__ nsamp_out, gnsscorr_trklog_t *__restrict__ log, int *__restrict__ ndone,
-    int *__restrict__ nco_overflow, int *__restrict__ lapped, unsigned *__restrict__ hostflags, int nch, int nper, int nseg,
-    int ntap_stride, int max_n, int kcap, int plan)
+// state in -- all wavefronts.  Writes S.lp, S.st, S.navdone; returns the channel's meta.  A barrier follows.
+__device__ __forceinline__ GcStepMeta tail_state_in(const TailArgs &A, TailShared &S)
 {
-    __shared__ __attribute__((aligned(16))) TailShared S;
-    const int ch = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (ch >= nch) return;
-#ifdef GC_TAIL_PROF
-    unsigned long long tprev_ = __builtin_readcyclecounter();
-#endif
-    const GcChan &c = chan[ch];
-    const int ntap = c.ntap, dtype = c.dtype;
-    {
-        const unsigned long long *src = reinterpret_cast<const unsigned long long *>(loop + ch);
-        unsigned long long *dst = reinterpret_cast<unsigned long long *>(&S.lp);
-        for (int i = tid; i < (int)(sizeof(gnsscorr_loop_t) / 8); i += 64 * GC_TAIL_NW) dst[i] = src[i];
-    }
-    GcStepMeta m = meta[ch];
-    if (tid == 0) { S.st = state[ch]; S.navdone = 0; }
-    __syncthreads();
-    gnsscorr_loop_t *lp = &S.lp;
-    const double II0_before = S.lp.II[0];               // trk.II[0] of the last period closed (wavefront 0 overwrites it below)
-    const bool was_finished = m.finished != 0;
-    GC_TSTAMP(0);       // state in
-
-    // ---- close the interval the correlator launch before this one produced (wavefront 0) -----------------------
-    // the interval's correlator sums: every (period, tap, rail) of it at once
-    for (int x = tid; x < m.k * 2 * ntap; x += 64 * GC_TAIL_NW) {
+    tail_copy_loop(&S.lp, A.loop + A.ch, A.tid);
+    const GcStepMeta m = A.meta[A.ch];
+    if (A.tid == 0) { S.st = A.state[A.ch]; S.navdone = 0; }
+    return m;
+}
+// sums -- all wavefronts.  The closing interval's (period, tap, rail) sums: partial -> S.psum; a barrier hands them on.
+__device__ __forceinline__ void tail_sums(const TailArgs &A, TailShared &S, const GcStepMeta &m, int ntap)
+{
+    for (int x = A.tid; x < m.k * 2 * ntap; x += 64 * GC_TAIL_NW) {
         const int e = x / (2 * ntap), r = x - e * 2 * ntap;            // r: tap (I rail), ntap + tap (Q rail)
-        const int col = r < ntap ? r : ntap_stride + (r - ntap);
-        const int *pp = partial + ((size_t)ch * m.kcap + e) * nseg * 2 * ntap_stride + col;
+        const int col = r < ntap ? r : A.ntap_stride + (r - ntap);
+        const int *pp = A.partial + ((size_t)A.ch * m.kcap + e) * A.nseg * 2 * A.ntap_stride + col;
         int sum = 0;
-        for (int sg = 0; sg < nseg; sg++) sum += pp[(size_t)sg * 2 * ntap_stride];
+        for (int sg = 0; sg < A.nseg; sg++) sum += pp[(size_t)sg * 2 * A.ntap_stride];
         S.psum[e][r] = sum;
     }
-    __syncthreads();
-    GC_TSTAMP(1);       // sums
-    // sdrnavigation()'s bit synchronisation / bit decision for every period of the interval (ref src/sdrnav.c:18-36): it
-    // only looks at the prompt sums trk.II[0] / trk.oldI[0] and its own state, so wavefront 1 runs it for all periods
-    // while wavefront 0 accumulates; the filters (wavefront 0, below) then find each period's flags in LDS.
-    if (wave == 1 && lane == 0 && m.k > 0) {
+}
+// nav -- wavefront 1, lane 0, beside close.  sdrnavigation()'s bit sync / bit decision per closing period (ref
+// src/sdrnav.c:18-36): it only looks at the prompt sums (S.psum; II0_before: trk.II[0] of the period before, which close
+// overwrites) and its own fields of S.lp.  Writes S.nflagsync / nswloop / nbit; S.navdone tells close how far it is.
+__device__ __forceinline__ void tail_nav(const TailArgs &A, TailShared &S, int k, int ntap, double II0_before)
+{
+    gnsscorr_loop_t *lp = &S.lp;
+    if (A.lane == 0 && k > 0) {
         const double late_after = __ddiv_rn(2000.0, __dmul_rn(lp->ctime, 1000.0));
-        double prevII0 = II0_before;                    // trk.II[0] of the period before (what memcpy leaves in oldI[0]: ntap >= 3)
-        for (int e = 0; e < m.k; e++) {
+        double prevII0 = II0_before;                    // (what memcpy leaves in oldI[0]: ntap >= 3)
+        for (int e = 0; e < k; e++) {
             const double II0 = (double)S.psum[e][ntap] * (1.0 / 32.0);      // trk.II[0] = the correlator's QQ[0] (ref src/sdrtrk.c:42)
             nav_step_io(lp, late_after, II0, prevII0);
-            S.nflagsync[e] = lp->flagsync;
-            S.nswloop[e] = lp->swloop;
+            S.nflagsync[e] = lp->flagsync; S.nswloop[e] = lp->swloop;
             S.nbit[e] = (lp->flagsync && lp->swsync) ? lp->bit : 0;
             lp->cnt = lp->cnt + 1;
             prevII0 = II0;
-            __hip_atomic_store(&S.navdone, e + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            prog_publish(&S.navdone, e + 1);
         }
     }
-    if (wave == 0) {
-        GcTrkState st = S.st;
-        for (int e = 0; e < m.k; e++) {
-            const int p = m.pbase + e;
-            if (lane < ntap) {
-                const int sI = S.psum[e][lane], sQ = S.psum[e][ntap + lane];
-                const double cI = (double)sI * (1.0 / 32.0), cQ = (double)sQ * (1.0 / 32.0);     // correlator's II, QQ (ref src/sdrcmn.c:716-719)
-                corrI[((size_t)ch * nper + p) * ntap + lane] = cI;
-                corrQ[((size_t)ch * nper + p) * ntap + lane] = cQ;
-                // memcpy(oldI, II, 1 + 2*corrn*sizeof(double)): the last tap only gets its lowest byte (ref src/sdrtrk.c:35-36)
-                const double pII = lp->II[lane], pQQ = lp->QQ[lane];
-                double oI = pII, oQ = pQQ;
-                if (lane == ntap - 1) {
-                    oI = gc_u2d((gc_d2u(lp->oldI[lane]) & ~0xFFull) | (gc_d2u(pII) & 0xFFull));
-                    oQ = gc_u2d((gc_d2u(lp->oldQ[lane]) & ~0xFFull) | (gc_d2u(pQQ) & 0xFFull));
-                }
-                lp->oldI[lane] = oI;
-                lp->oldQ[lane] = oQ;
-                // correlator(..., trk.QQ, trk.II, ...): trk.II <- sum dataQ*code, trk.QQ <- sum dataI*code (ref src/sdrtrk.c:42)
-                lp->II[lane] = cQ;
-                lp->QQ[lane] = cI;
-                // cumsumcorr, polarity +1: the overlay code is all ones (ref src/sdrtrk.c:64-76, src/sdrmain.c:269)
-                lp->oldsumI[lane] = __dadd_rn(lp->oldsumI[lane], oI);
-                lp->oldsumQ[lane] = __dadd_rn(lp->oldsumQ[lane], oQ);
-                lp->sumI[lane] = __dadd_rn(lp->sumI[lane], cQ);
-                lp->sumQ[lane] = __dadd_rn(lp->sumQ[lane], cI);
+}
+// close -- wavefront 0.  Per closing period: II/QQ out, cumsumcorr (lane = tap), the filters where nav's flags (behind
+// S.navdone) say so, the log row, m.early; then S.want, the chains' start values (entry 0), the frequencies in S.st and
+// the progress words at zero.  Reads S.psum.  A barrier hands all of that to the planning phases.
+__device__ __forceinline__ void tail_close(const TailArgs &A, TailShared &S, GcStepMeta &m, int ntap)
+{
+    gnsscorr_loop_t *lp = &S.lp;
+    const int ch = A.ch, lane = A.lane;
+    GcTrkState st = S.st;
+    for (int e = 0; e < m.k; e++) {
+        const int p = m.pbase + e;
+        if (lane < ntap) {
+            const int sI = S.psum[e][lane], sQ = S.psum[e][ntap + lane];
+            const double cI = (double)sI * (1.0 / 32.0), cQ = (double)sQ * (1.0 / 32.0);     // correlator's II, QQ (ref src/sdrcmn.c:716-719)
+            A.corrI[((size_t)ch * A.nper + p) * ntap + lane] = cI;
+            A.corrQ[((size_t)ch * A.nper + p) * ntap + lane] = cQ;
+            // memcpy(oldI, II, 1 + 2*corrn*sizeof(double)): the last tap only gets its lowest byte (ref src/sdrtrk.c:35-36)
+            const double pII = lp->II[lane], pQQ = lp->QQ[lane];
+            double oI = pII, oQ = pQQ;
+            if (lane == ntap - 1) {
+                oI = gc_u2d((gc_d2u(lp->oldI[lane]) & ~0xFFull) | (gc_d2u(pII) & 0xFFull));
+                oQ = gc_u2d((gc_d2u(lp->oldQ[lane]) & ~0xFFull) | (gc_d2u(pQQ) & 0xFFull));
             }
-            tail_wave_sync();
-            // (this period's nav flags: wavefront 1 is usually ahead)
-            while (__hip_atomic_load(&S.navdone, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= e) __builtin_amdgcn_s_sleep(1);
-            int flag = 0;
-            if (lane == 0) {
-                if (!S.nflagsync[e]) {
-                    loop_pll(lp, st, 0, lp->ctime);
-                    loop_dll(lp, st, 0, lp->ctime);
-                    flag = 1;
-                } else if (S.nswloop[e]) {
-                    loop_pll(lp, st, 1, (double)lp->loopms / 1000);
-                    loop_dll(lp, st, 1, (double)lp->loopms / 1000);
-                    flag = 2;
-                }
-                gnsscorr_trklog_t *lg = log + (size_t)ch * nper + p;
-                lg->carrfreq = st.carrfreq;
-                lg->codefreq = st.codefreq;
-                lg->carrErr = lp->carrErr;
-                lg->codeErr = lp->codeErr;
-                lg->carrNco = lp->carrNco;
-                lg->codeNco = lp->codeNco;
-                lg->freqErr = lp->freqErr;
-                lg->flagloopfilter = flag;
-                lg->flagsync = S.nflagsync[e];
-                lg->navbit = S.nbit[e];
-                if (flag && e + 1 < m.k) m.early = 1;   // the plan held the frequencies beyond a filter update: must not happen
-            }
-            flag = __builtin_amdgcn_readfirstlane(flag);
-            st.carrfreq = gc_u2d(((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(gc_d2u(st.carrfreq) >> 32)) << 32) |
-                                 (unsigned)__builtin_amdgcn_readfirstlane((int)gc_d2u(st.carrfreq)));
-            st.codefreq = gc_u2d(((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(gc_d2u(st.codefreq) >> 32)) << 32) |
-                                 (unsigned)__builtin_amdgcn_readfirstlane((int)gc_d2u(st.codefreq)));
-            m.early = __builtin_amdgcn_readfirstlane(m.early);
-            if (flag && lane < ntap) {      // clearcumsumcorr (ref src/sdrtrk.c:77-86)
-                lp->oldsumI[lane] = 0.0;
-                lp->oldsumQ[lane] = 0.0;
-                lp->sumI[lane] = 0.0;
-                lp->sumQ[lane] = 0.0;
-            }
-            tail_wave_sync();
-            GC_TSTAMP(2);   // nav + filters + log
+            lp->oldI[lane] = oI; lp->oldQ[lane] = oQ;
+            // correlator(..., trk.QQ, trk.II, ...): trk.II <- sum dataQ*code, trk.QQ <- sum dataI*code (ref src/sdrtrk.c:42)
+            lp->II[lane] = cQ; lp->QQ[lane] = cI;
+            // cumsumcorr, polarity +1: the overlay code is all ones (ref src/sdrtrk.c:64-76, src/sdrmain.c:269)
+            lp->oldsumI[lane] = __dadd_rn(lp->oldsumI[lane], oI);
+            lp->oldsumQ[lane] = __dadd_rn(lp->oldsumQ[lane], oQ);
+            lp->sumI[lane] = __dadd_rn(lp->sumI[lane], cQ);
+            lp->sumQ[lane] = __dadd_rn(lp->sumQ[lane], cI);
         }
-        // the next interval: up to the next filter update, the end of the run, the step's capacity
-        int want = 0;
-        if (plan && m.done < nper) {
-            want = nav_interval(lp, kcap);
-            if (want > nper - m.done) want = nper - m.done;
-        }
+        tail_wave_sync();
+        (void)prog_wait_past(&S.navdone, e);            // (this period's nav flags: wavefront 1 is usually ahead)
+        int flag = 0;
         if (lane == 0) {
-            S.st.carrfreq = st.carrfreq;
-            S.st.codefreq = st.codefreq;
-            S.want = want;
-            S.k = 0;
-            S.prog = 0;
-            S.progc = 0;
-            S.nexttask = 0;
-            S.starved = 0;
-            S.remcode[0] = st.remcode;
-            S.remcarr[0] = st.remcarr;
-            S.buffloc[0] = st.buffloc;
+            if (!S.nflagsync[e]) {
+                loop_pll(lp, st, 0, lp->ctime);
+                loop_dll(lp, st, 0, lp->ctime);
+                flag = 1;
+            } else if (S.nswloop[e]) {
+                loop_pll(lp, st, 1, (double)lp->loopms / 1000);
+                loop_dll(lp, st, 1, (double)lp->loopms / 1000);
+                flag = 2;
+            }
+            gnsscorr_trklog_t *lg = A.log + (size_t)ch * A.nper + p;
+            lg->carrfreq = st.carrfreq; lg->codefreq = st.codefreq;
+            lg->carrErr = lp->carrErr; lg->codeErr = lp->codeErr; lg->freqErr = lp->freqErr;
+            lg->carrNco = lp->carrNco; lg->codeNco = lp->codeNco;
+            lg->flagloopfilter = flag; lg->flagsync = S.nflagsync[e]; lg->navbit = S.nbit[e];
+            if (flag && e + 1 < m.k) m.early = 1;   // the plan held the frequencies beyond a filter update: must not happen
         }
+        flag = __builtin_amdgcn_readfirstlane(flag);
+        st.carrfreq = gc_u2d(((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(gc_d2u(st.carrfreq) >> 32)) << 32) |
+                             (unsigned)__builtin_amdgcn_readfirstlane((int)gc_d2u(st.carrfreq)));
+        st.codefreq = gc_u2d(((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(gc_d2u(st.codefreq) >> 32)) << 32) |
+                             (unsigned)__builtin_amdgcn_readfirstlane((int)gc_d2u(st.codefreq)));
+        m.early = __builtin_amdgcn_readfirstlane(m.early);
+        if (flag && lane < ntap) {      // clearcumsumcorr (ref src/sdrtrk.c:77-86)
+            lp->oldsumI[lane] = lp->oldsumQ[lane] = lp->sumI[lane] = lp->sumQ[lane] = 0.0;
+        }
+        tail_wave_sync();
+        GC_TSTAMP(2);   // nav + filters + log
     }
-    __syncthreads();
-    m.consumed += m.k;
-    m.k = 0;
-
-    // ---- plan the next interval --------------------------------------------------------------------------------
-    const int want = S.want;
-    const double carrfreq = S.st.carrfreq, codefreq = S.st.codefreq;
-    const double dlen = (double)c.clen;
-    const double ci = __dmul_rn(c.ti, codefreq), ps = gc_carrier_ps(carrfreq, c.ti);
-    const double spc = __ddiv_rn(codefreq, c.f_sf);
-    const bool shape_ok = ci > 0.0 && ci < dlen;
-    GcFillLanes fill{lane};
-    if (want > 0) {
-        // step tables of the interval's two frequencies, one lane per binade
-        if (wave == 0) {
-            fast_init_lanes(S.PK.f, ps, false, lane);
-            if (lane == 0) S.PK.ydpi = __ddiv_rn(1.0, GC_NCO_DPI);
-        } else if (wave == 1) {
-            code_plan_init_lanes(S.PC, ci, c.clen, c.smax, lane);
-        } else if (wave == 2) {
-            fast_init_lanes(S.PK.fprem, -GC_NCO_DPI, true, lane);
-        }
+    // the next interval: up to the next filter update, the end of the run, the step's capacity
+    int want = 0;
+    if (A.plan && m.done < A.nper) want = min(nav_interval(lp, A.kcap), A.nper - m.done);
+    if (lane == 0) {
+        S.st.carrfreq = st.carrfreq; S.st.codefreq = st.codefreq;
+        S.want = want;
+        S.k = S.prog = S.progc = S.nexttask = S.starved = 0;
+        S.remcode[0] = st.remcode; S.remcarr[0] = st.remcarr; S.buffloc[0] = st.buffloc;
     }
-    __syncthreads();
-    GC_TSTAMP(3);       // step tables
-    if (want > 1) {
-        // The structure of the interval's periods from their closed-form starts (gc_spec_start), proved for a bracket
-        // around each start as the batch planner's discovery does (gnsscorr_plan.hip): lane e discovers the claims of
-        // period e from the bracket's lower end, lane 32 + e from its upper end; where both ends pass their checks with
-        // the same claims and the same sample count, every start in between does (every operation of the step is
-        // monotone in the start), and the chain below evaluates such a period without the checks.  The closed form
-        // reaches at most GC_STEP_KMAX periods from the interval's exact start: +-2^-25 holds what its missing rounding
-        // adds up to (< 1e-8).  A period without a bracket takes the step with its checks, then the certified step.
-        const double W = 2.98023223876953125e-8;         // 2^-25
-        const bool mine = lane < want || (lane >= 32 && lane - 32 < want);
-        const int pe = lane & 31;
-        const bool hiend = lane >= 32;
-        if (wave == 2 && mine) {
-            GcCodeClaims cc;
-            cc.tag = 0;
-            cc.n = cc.pad = 0;
-            cc.lo = cc.hi = 0.0;
-            bool ok = false;
-            int n = 0, side = 0;
-            double end = 0.0;
-            if (shape_ok && spc > 1e-300 && spc < 1e300) {
-                double rc, rk, dummy;
-                int nhat;
-                gc_spec_start(S.remcode[0], S.remcarr[0], ci, spc, ps, dlen, pe, &rc, &rk, &nhat);
-                end = hiend ? rc + W : rc - W;
-                n = gc_period_nsamp(dlen, end, spc);
-                side = end - S.PC.smaxci < 0.0 ? 1 : 0;                          // (ref src/sdrcmn.c:614: one branch for the whole bracket)
-                if (n > 0 && n <= (1 << 24)) ok = gc_code_claims<true>(S.PC, end, n + 2 * c.smax, cc, &dummy);
-            }
-            bool same = ok && __shfl(ok ? 1 : 0, lane ^ 32, 64) != 0;
-            same = same && n == __shfl(n, lane ^ 32, 64) && side == __shfl(side, lane ^ 32, 64);
-            same = same && cc.i0 == __shfl(cc.i0, lane ^ 32, 64) && cc.q == __shfl(cc.q, lane ^ 32, 64) &&
-                   cc.nl == __shfl(cc.nl, lane ^ 32, 64) && cc.jsum == __shfl(cc.jsum, lane ^ 32, 64);
-#pragma unroll
-            for (int i = 0; i < 13; i++) same = same && cc.dm[i] == __shfl(cc.dm[i], lane ^ 32, 64);
-            const double other = __shfl(end, lane ^ 32, 64);
-            if (!hiend) {
-                // (the discovering step allows the widest tail; the chain's instance may be narrower)
-                cc.tag = (same && n + 2 * c.smax - cc.jsum <= gc_tail_max(gc_tail_class(c.smax))) ? 1 : 0;
-                cc.n = n;
-                cc.lo = end;
-                cc.hi = other;
-                S.ccl[pe] = cc;
-            }
-        }
-        if (wave == 3 && mine) {
-            GcCarClaims ck;
-            ck.tag = 0;
-            ck.nl = ck.i0 = ck.nseg = ck.kprem = 0;
-            ck.pad[0] = ck.pad[1] = 0;
-            ck.lo = ck.hi = 0.0;
-#pragma unroll
-            for (int i = 0; i < GC_CLAIM_CSEG; i++) ck.dm[i] = 0;
-            bool ok = false;
-            int n = 0;
-            double end = 0.0;
-            if (shape_ok && spc > 1e-300 && spc < 1e300) {
-                double rc, rk, dummy;
-                gc_spec_start(S.remcode[0], S.remcarr[0], ci, spc, ps, dlen, pe, &rc, &rk, &n);
-                end = hiend ? rk + W : rk - W;
-                if (n > 0 && n <= (1 << 24)) {
-                    GcCarStepC CK;
-                    gc_car_stepc_init(CK, S.PK, c.nsamp + 16);
-                    ok = gc_carrier_claims_step<true>(S.PK, CK, end, n, ck, &dummy);
-                }
-            }
-            bool same = ok && __shfl(ok ? 1 : 0, lane ^ 32, 64) != 0;
-            same = same && ck.tag == __shfl(ck.tag, lane ^ 32, 64) && ck.nl == __shfl(ck.nl, lane ^ 32, 64) &&
-                   ck.i0 == __shfl(ck.i0, lane ^ 32, 64) && ck.nseg == __shfl(ck.nseg, lane ^ 32, 64) &&
-                   ck.kprem == __shfl(ck.kprem, lane ^ 32, 64);
-#pragma unroll
-            for (int i = 0; i < GC_CLAIM_CSEG; i++) same = same && ck.dm[i] == __shfl(ck.dm[i], lane ^ 32, 64);
-            const double other = __shfl(end, lane ^ 32, 64);
-            if (!hiend) {
-                // (tag 2, a period inside one binade, carries its own conditions and is judged by them: it needs no bracket)
-                ck.tag = same ? ck.tag : (ok && ck.tag == 2 ? 2 : 0);
-                ck.nl = n;
-                ck.lo = end;
-                ck.hi = other;
-                S.kcl[pe] = ck;
-            }
-        }
-        __syncthreads();
+}
+// q from the frequencies close left in S.st (every lane, after the barrier)
+__device__ __forceinline__ TailSteps tail_steps(const TailShared &S, const GcChan &c)
+{
+    const double codefreq = S.st.codefreq, dlen = (double)c.clen, ci = __dmul_rn(c.ti, codefreq);
+    return TailSteps{ci, gc_carrier_ps(S.st.carrfreq, c.ti), __ddiv_rn(codefreq, c.f_sf), dlen, ci > 0.0 && ci < dlen};
+}
+// step tables -- wavefronts 0, 1, 2, one lane per binade: S.PK.f, S.PC (shaped), S.PK.fprem.  Read-only after the barrier.
+__device__ __forceinline__ void tail_step_tables(const TailArgs &A, TailShared &S, const GcChan &c, const TailSteps &q)
+{
+    if (A.wave == 0) {
+        fast_init_lanes(S.PK.f, q.ps, false, A.lane);
+        if (A.lane == 0) S.PK.ydpi = __ddiv_rn(1.0, GC_NCO_DPI);
+    } else if (A.wave == 1) {
+        code_plan_init_lanes(S.PC, q.ci, c.clen, c.smax, A.lane);
+    } else if (A.wave == 2) {
+        fast_init_lanes(S.PK.fprem, -GC_NCO_DPI, true, A.lane);
     }
-    GC_TSTAMP(8);       // claims
-    if (want > 0) {
-        const uint64_t wp = wrpos[ch];
-        const bool have_data = wp >= (uint64_t)c.nsamp;
-        const uint64_t bufflocnow = wp - (uint64_t)c.nsamp;
-        if (wave == 1) {
-            // period starts: is the period there yet (ref src/sdrtrk.c:26-30), its length (:31-32), and -- for an interval of
-            // several periods -- the code chain (nothing emitted).  One instance per shape of the code step (the table binade
-            // that holds the code length), so that the step's constants stay in registers over the interval.
-            auto code_chain = [&](auto itop_tag) {
-                constexpr int ITOP = decltype(itop_tag)::value;       // (0: no instance: the certified step serves the channel)
-                constexpr int IT = ITOP ? ITOP : 7;
-                GcCodeStepC<IT> SC;
-                const bool inst = ITOP != 0 && S.PC.ok;
-                if (inst) gc_code_stepc_init(SC, S.PC);
-                const int tcls = gc_tail_class(c.smax);
-                double remcode = S.remcode[0];
-                uint64_t buffloc = S.buffloc[0];
-                GcNoEmit ne;
-                int k = 0;
-                const double yspc = __ddiv_rn(1.0, spc);
-                const bool fastdiv = spc > 1e-300 && spc < 1e300 && yspc < 1e300;
-                for (int e = 0; e < want; e++) {
-                    if (!(have_data && bufflocnow > buffloc)) { if (lane == 0) S.starved = 1; break; }
-                    // a period whose first samples the writer has overwritten since (more than a ring behind it): run as the
-                    // reference's sdrtracking() runs it, and counted (gnsscorr_trk_loop_lapped)
-                    if (lane == 0 && wp > c.ringlen && buffloc < wp - c.ringlen) atomicAdd(lapped, 1);
-                    // (dlen - remcode) / (codefreq / f_sf), ref src/sdrtrk.c:31-32: correctly rounded through the reciprocal
-                    // (gc_div_y) where that is safe, as the batch planner divides
-                    const double num = __dsub_rn(dlen, remcode);
-                    const double q = fastdiv ? gc_div_y(num, spc, yspc) : __ddiv_rn(num, spc);
-                    const int n = (q > -2147483648.0 && q < 2147483648.0) ? (int)q : 0;
-                    const bool valid = n > 0 && n <= max_n && shape_ok;
-                    if (lane == 0) {
-                        S.n[e] = n;
-                        S.valid[e] = valid ? 1 : 0;
-                        S.remcode[e] = remcode;
-                        S.buffloc[e] = buffloc;
-                    }
-                    k = e + 1;
-                    if (want > 1) {
-                        tail_wave_sync();
-                        if (lane == 0) __hip_atomic_store(&S.prog, k, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        if (valid) {
-                            double r = remcode;
-                            GcCodeClaims cl = S.ccl[e];
-                            const int nt = n + 2 * c.smax;
-                            // the exact start inside the bracket the claims were proved for: the values alone (the step's
-                            // verdict is unused, the compiler drops the checks); else the step with its checks
-                            const bool inside = __builtin_amdgcn_readfirstlane((inst && cl.tag == 1 && remcode >= cl.lo && remcode <= cl.hi && n == cl.n) ? 1 : 0) != 0;
-                            bool ok = inside;
-                            if (inside) {
-                                if (tcls == 0) (void)gc_code_claims_step<IT, gc_tail_max(0), false>(S.PC, SC, remcode, nt, cl, &r);
-                                else if (tcls == 1) (void)gc_code_claims_step<IT, gc_tail_max(1), false>(S.PC, SC, remcode, nt, cl, &r);
-                                else (void)gc_code_claims_step<IT, gc_tail_max(2), false>(S.PC, SC, remcode, nt, cl, &r);
-                            } else if (inst && cl.tag == 1) {
-                                double r2;
-                                ok = tail_code_checked<IT>(&S.PC, remcode, nt, tcls, &S.ccl[e], &r2);
-                                if (ok) r = r2;
-                            }
-                            if (ok) remcode = r;
-                            else if (gc_code_period(S.PC, remcode, nt, fill, &r, ne)) remcode = r;
-                            else remcode = tail_code_slow(ci, remcode, c.clen, c.smax, nt, ne);
-                        }
-                    }
-                    buffloc += (uint64_t)(int64_t)n;
-                    if (lane == 0) { S.remcode[e + 1] = remcode; S.buffloc[e + 1] = buffloc; }
-                }
-                tail_wave_sync();
-                if (lane == 0) {
-                    S.k = k;
-                    __hip_atomic_store(&S.prog, 0x7fffffff, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-            };
-            switch ((want > 1 && S.PC.ok) ? S.PC.itop : 0) {
-            case 7:  code_chain(std::integral_constant<int, 7>{}); break;
-            case 8:  code_chain(std::integral_constant<int, 8>{}); break;
-            case 9:  code_chain(std::integral_constant<int, 9>{}); break;
-            case 10: code_chain(std::integral_constant<int, 10>{}); break;
-            case 11: code_chain(std::integral_constant<int, 11>{}); break;
-            case 12: code_chain(std::integral_constant<int, 12>{}); break;
-            default: code_chain(std::integral_constant<int, 0>{}); break;
-            }
-        } else if (wave == 0 && want > 1) {
-            // the carrier chain, one step behind
-            double remcarr = S.remcarr[0];
-            GcNoEmit ne;
-            GcCarStepC CK;
-            gc_car_stepc_init(CK, S.PK, c.nsamp + 16);
-            for (int e = 0; e < want; e++) {
-                int pg;
-                while ((pg = __hip_atomic_load(&S.prog, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) <= e) __builtin_amdgcn_s_sleep(1);
-                if (pg == 0x7fffffff && e >= S.k) break;
-                const int n = S.n[e];
-                if (S.valid[e]) {
-                    double r = remcarr;
-                    GcCarClaims cl = S.kcl[e];
-                    const int tagu = __builtin_amdgcn_readfirstlane(cl.tag);
-                    const bool inside = __builtin_amdgcn_readfirstlane((tagu == 1 && remcarr >= cl.lo && remcarr <= cl.hi && n == cl.nl) ? 1 : 0) != 0;
-                    bool ok = inside;
-                    if (inside) {
-                        (void)gc_carrier_claims_step<false, false, 1>(S.PK, CK, remcarr, n, cl, &r);      // the values alone: the bracket is the proof
-                    } else if (tagu == 2) {
-                        double r2 = remcarr;
-                        ok = gc_carrier_claims_step<false, false, 2>(S.PK, CK, remcarr, n, cl, &r2);       // (its own conditions, checked)
-                        if (ok) r = r2;
-                    } else if (tagu == 1) {
-                        double r2;
-                        ok = tail_carrier_checked(&S.PK, c.nsamp, remcarr, n, &S.kcl[e], &r2);
-                        if (ok) r = r2;
-                    }
-                    if (ok) remcarr = r;
-                    else if (gc_carrier_period(S.PK, remcarr, n, fill, &r, ne)) remcarr = r;
-                    else remcarr = tail_carrier_slow(ps, remcarr, n, ne);
-                }
-                if (lane == 0) S.remcarr[e + 1] = remcarr;
-                tail_wave_sync();
-                if (lane == 0) __hip_atomic_store(&S.progc, e + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            if (lane == 0) __hip_atomic_store(&S.progc, 0x7fffffff, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
+}
+// discover (in the kernel's body, see there) -- code brackets on wavefront 2 (-> S.ccl), carrier brackets on wavefront 3
+// (-> S.kcl); a barrier hands the rows to the chains.  Each period's structure from its closed-form start (gc_spec_start
+// from entry 0), proved for a bracket around it as the batch planner's discovery does (gnsscorr_plan.hip): lane e discovers
+// period e's claims from the lower end, lane 32 + e from the upper end; where both pass their checks with the same claims
+// and sample count, every start in between does (every operation of the step is monotone in the start), and the chain
+// evaluates the period unchecked.  +-2^-25 holds what the closed form's missing rounding adds up to over GC_STEP_KMAX periods.
+constexpr double TAIL_BRACKET_W = 2.98023223876953125e-8;       // 2^-25
+// One period of a chain, the ladder from the top: the exact start inside the bracket the claims were proved for -> the
+// values alone (the verdict is unused, the compiler drops the checks); claims but no bracket around this start -> the step
+// with its checks, out of line; else, or where that declines, the lower rungs.  inst: SC holds the channel's instance.
+// (remcode by reference: returned by value, the code chain spills vector registers.)
+template <int IT>
+__device__ __forceinline__ void tail_code_step(const TailArgs &A, TailShared &S, const GcChan &c, const TailSteps &q, const GcCodeStepC<IT> &SC,
+                                                 bool inst, int tcls, int e, double &remcode, int n)
+{
+    double r = remcode;
+    GcCodeClaims cl = S.ccl[e];
+    const int nt = n + 2 * c.smax;
+    const bool inside = __builtin_amdgcn_readfirstlane((inst && cl.tag == 1 && remcode >= cl.lo && remcode <= cl.hi && n == cl.n) ? 1 : 0) != 0;
+    bool ok = inside;
+    if (inside) {
+        (void)tail_code_claims_step<IT, false>(tcls, S.PC, SC, remcode, nt, cl, &r);
+    } else if (inst && cl.tag == 1) {
+        double r2;
+        ok = tail_code_checked<IT>(&S.PC, remcode, nt, tcls, &S.ccl[e], &r2);
+        if (ok) r = r2;
     }
-    GC_TSTAMP(4);       // chain
-    // ---- tables: task t = (period t/2, carrier | code), taken from a queue in order -- a wavefront that has no chain
-    // to run starts on period 0 as soon as the chain has published its start, the chain's wavefronts join when done ----
+    GcNoEmit ne;
+    if (ok) remcode = r;
+    else remcode = tail_code_period(S.PC, c, q.ci, remcode, nt, A.lane, ne);
+}
+__device__ __forceinline__ double tail_carrier_step(const TailArgs &A, TailShared &S, const GcChan &c, const TailSteps &q, const GcCarStepC &CK,
+                                                    int e, double remcarr, int n)
+{
+    double r = remcarr;
+    GcCarClaims cl = S.kcl[e];
+    const int tagu = __builtin_amdgcn_readfirstlane(cl.tag);
+    const bool inside = __builtin_amdgcn_readfirstlane((tagu == 1 && remcarr >= cl.lo && remcarr <= cl.hi && n == cl.nl) ? 1 : 0) != 0;
+    bool ok = inside;
+    if (inside) {
+        (void)gc_carrier_claims_step<false, false, 1>(S.PK, CK, remcarr, n, cl, &r);      // the values alone: the bracket is the proof
+    } else if (tagu == 2) {
+        double r2 = remcarr;
+        ok = gc_carrier_claims_step<false, false, 2>(S.PK, CK, remcarr, n, cl, &r2);       // (its own conditions, checked)
+        if (ok) r = r2;
+    } else if (tagu == 1) {
+        double r2;
+        ok = tail_carrier_checked(&S.PK, c.nsamp, remcarr, n, &S.kcl[e], &r2);
+        if (ok) r = r2;
+    }
+    if (ok) return r;
+    GcNoEmit ne;
+    return tail_carrier_period(S.PK, q.ps, remcarr, n, A.lane, ne);
+}
+// code chain -- wavefront 1, every interval.  Per period: is it there yet (ref src/sdrtrk.c:26-30; else S.starved), its
+// length (:31-32) and, in an interval of several periods, the code step.  Reads S.ccl, S.PC; writes S.n / valid / remcode /
+// buffloc [e], publishes e on S.prog (the carrier chain and the table tasks wait there), steps to entry e + 1; at the end
+// S.k and done.  One instance per shape of the step (ITOP: the table binade that holds the code length; 0: none, the
+// certified step serves), so that its constants stay in registers over the interval.
+template <int ITOP>
+__device__ __forceinline__ void tail_code_chain(const TailArgs &A, TailShared &S, const GcChan &c, const TailSteps &q, int want)
+{
+    constexpr int IT = ITOP ? ITOP : 7;
+    const int lane = A.lane;
+    const uint64_t wp = A.wrpos[A.ch];
+    const bool have_data = wp >= (uint64_t)c.nsamp;
+    const uint64_t bufflocnow = wp - (uint64_t)c.nsamp;
+    GcCodeStepC<IT> SC;
+    const bool inst = ITOP != 0 && S.PC.ok;
+    if (inst) gc_code_stepc_init(SC, S.PC);
+    const int tcls = gc_tail_class(c.smax);
+    double remcode = S.remcode[0];
+    uint64_t buffloc = S.buffloc[0];
+    int k = 0;
+    const double yspc = __ddiv_rn(1.0, q.spc);
+    const bool fastdiv = q.spc > 1e-300 && q.spc < 1e300 && yspc < 1e300;
+    for (int e = 0; e < want; e++) {
+        if (!(have_data && bufflocnow > buffloc)) { if (lane == 0) S.starved = 1; break; }
+        // first samples overwritten since (more than a ring behind the writer): run as sdrtracking() runs it, and counted
+        if (lane == 0 && wp > c.ringlen && buffloc < wp - c.ringlen) atomicAdd(A.lapped, 1);
+        // (dlen - remcode) / (codefreq / f_sf), ref src/sdrtrk.c:31-32: through the reciprocal (gc_div_y) where that is safe
+        const double num = __dsub_rn(q.dlen, remcode);
+        const double qq = fastdiv ? gc_div_y(num, q.spc, yspc) : __ddiv_rn(num, q.spc);
+        const int n = (qq > -2147483648.0 && qq < 2147483648.0) ? (int)qq : 0;
+        const bool valid = n > 0 && n <= A.max_n && q.shape_ok;
+        if (lane == 0) { S.n[e] = n; S.valid[e] = valid ? 1 : 0; S.remcode[e] = remcode; S.buffloc[e] = buffloc; }
+        k = e + 1;
+        if (want > 1) {
+            tail_wave_sync();
+            if (lane == 0) prog_publish(&S.prog, k);
+            if (valid) tail_code_step<IT>(A, S, c, q, SC, inst, tcls, e, remcode, n);
+        }
+        buffloc += (uint64_t)(int64_t)n;
+        if (lane == 0) { S.remcode[e + 1] = remcode; S.buffloc[e + 1] = buffloc; }
+    }
+    tail_wave_sync();
+    if (lane == 0) { S.k = k; prog_publish_done(&S.prog); }
+}
+__device__ __forceinline__ void tail_code_chain_any(const TailArgs &A, TailShared &S, const GcChan &c, const TailSteps &q, int want)
+{
+    switch ((want > 1 && S.PC.ok) ? S.PC.itop : 0) {
+    case 7:  tail_code_chain<7>(A, S, c, q, want); break;
+    case 8:  tail_code_chain<8>(A, S, c, q, want); break;
+    case 9:  tail_code_chain<9>(A, S, c, q, want); break;
+    case 10: tail_code_chain<10>(A, S, c, q, want); break;
+    case 11: tail_code_chain<11>(A, S, c, q, want); break;
+    case 12: tail_code_chain<12>(A, S, c, q, want); break;
+    default: tail_code_chain<0>(A, S, c, q, want); break;
+    }
+}
+// carrier chain -- wavefront 0, intervals of several periods, one step behind the code chain: waits on S.prog for period
+// e's length, steps (S.kcl, S.PK), stores S.remcarr[e + 1], publishes on S.progc for the carrier table tasks; done at the end.
+__device__ __forceinline__ void tail_carrier_chain(const TailArgs &A, TailShared &S, const GcChan &c, const TailSteps &q, int want)
+{
+    double remcarr = S.remcarr[0];
+    GcCarStepC CK;
+    gc_car_stepc_init(CK, S.PK, c.nsamp + 16);
+    for (int e = 0; e < want; e++) {
+        if (prog_wait_past(&S.prog, e) == TAIL_DONE && e >= S.k) break;
+        if (S.valid[e]) remcarr = tail_carrier_step(A, S, c, q, CK, e, remcarr, S.n[e]);
+        if (A.lane == 0) S.remcarr[e + 1] = remcarr;
+        tail_wave_sync();
+        if (A.lane == 0) prog_publish(&S.progc, e + 1);
+    }
+    if (A.lane == 0) prog_publish_done(&S.progc);
+}
+// table tasks -- all wavefronts.  Task x = (period x/2, carrier | code), from a queue (S.nexttask) in order: the period
+// step again from its known start, its piece table emitted into LDS (S.k0 / S.car / S.code [e]) and finished by the lanes;
+// S.ncar / S.ncode [e].  A wavefront without a chain starts as soon as the period is published (S.prog; carrier tasks also
+// S.progc), the chains' wavefronts join when done.  A one-period interval has no chain: these steps are it and store
+// entry 1.  A barrier hands the tables to out.
+__device__ __forceinline__ void tail_table_tasks(const TailArgs &A, TailShared &S, const GcChan &c, const TailSteps &q, int want)
+{
+    const int lane = A.lane;
     for (;;) {
-        int t = 0;
-        if (lane == 0) t = __hip_atomic_fetch_add(&S.nexttask, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        t = __builtin_amdgcn_readfirstlane(t);
-        if (t >= 2 * want) break;
-        const int e = t >> 1;
-        // the period's start: code side from the code chain (prog), carrier side from the carrier chain (progc)
-        int pg;
-        while ((pg = __hip_atomic_load(&S.prog, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) <= e) __builtin_amdgcn_s_sleep(1);
-        if (pg == 0x7fffffff && e >= S.k) break;            // the ring holds fewer periods than wanted
-        if (!(t & 1) && want > 1)
-            while (__hip_atomic_load(&S.progc, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < e) __builtin_amdgcn_s_sleep(1);
-        const int k = want;                                 // (k == 1 below: the one-period interval, whose steps are the chain)
+        int x = 0;
+        if (lane == 0) x = __hip_atomic_fetch_add(&S.nexttask, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        x = __builtin_amdgcn_readfirstlane(x);
+        if (x >= 2 * want) break;
+        const int e = x >> 1;
+        if (prog_wait_past(&S.prog, e) == TAIL_DONE && e >= S.k) break;     // the ring holds fewer periods than wanted
+        if (!(x & 1) && want > 1) (void)prog_wait_past(&S.progc, e - 1);
         if (!S.valid[e]) {
-            if (lane == 0) { if (t & 1) S.ncode[e] = 0; else S.ncar[e] = 0; S.bad[e] = 0; }
-            if (k == 1 && lane == 0) { if (t & 1) S.remcode[1] = S.remcode[0]; else S.remcarr[1] = S.remcarr[0]; }
+            if (lane == 0) { if (x & 1) S.ncode[e] = 0; else S.ncar[e] = 0; S.bad[e] = 0; }
+            if (want == 1 && lane == 0) { if (x & 1) S.remcode[1] = S.remcode[0]; else S.remcarr[1] = S.remcarr[0]; }
             continue;
         }
         const int n = S.n[e];
-        if (t & 1) {
+        if (x & 1) {
             LdsCodeTable dt{(gc_lds_code)S.code[e], GC_NCODE, 0, 0, 0, 0, 0.0, 0.0};
-            const double remcode = S.remcode[e];
-            double r;
-            if (!gc_code_period(S.PC, remcode, n + 2 * c.smax, fill, &r, dt)) {
-                dt.reset();
-                r = tail_code_slow(ci, remcode, c.clen, c.smax, n + 2 * c.smax, dt);
-            }
+            const double r = tail_code_period(S.PC, c, q.ci, S.remcode[e], n + 2 * c.smax, lane, dt);
             tail_wave_sync();
             lds_code_finish((gc_lds_code)S.code[e], dt.n, lane);
-            if (lane == 0) {
-                S.ncode[e] = dt.overflow ? -1 : dt.n;
-                if (k == 1) S.remcode[1] = r;           // (one period: this step is the chain)
-            }
+            if (lane == 0) { S.ncode[e] = dt.overflow ? -1 : dt.n; if (want == 1) S.remcode[1] = r; }
         } else {
             LdsCarTable ct{(gc_lds_int)S.k0[e], (gc_lds_car)S.car[e], 0, 0, false};
-            const double remcarr = S.remcarr[e];
-            double r;
-            if (!gc_carrier_period(S.PK, remcarr, n, fill, &r, ct)) {
-                ct.reset();
-                r = tail_carrier_slow(ps, remcarr, n, ct);
-            }
+            const double r = tail_carrier_period(S.PK, q.ps, S.remcarr[e], n, lane, ct);
             tail_wave_sync();
             lds_car_finish((gc_lds_car)S.car[e], ct.n, lane);
-            if (lane == 0) {
-                S.ncar[e] = ct.overflow ? -1 : ct.n;
-                if (k == 1) S.remcarr[1] = r;
-            }
+            if (lane == 0) { S.ncar[e] = ct.overflow ? -1 : ct.n; if (want == 1) S.remcarr[1] = r; }
         }
     }
-    __syncthreads();
-    GC_TSTAMP(5);       // tables
-    // ---- out: per period the invariants, the rounds, the copy to the correlator's buffers ---------------------------
-    const int k = S.k;
+}
+// out -- period e on wavefront e mod GC_TAIL_NW.  Reads the chains' entries and the tables; checks what the correlator's
+// scans rely on (else nco_overflow, nothing correlated), copies the tables to segs, builds the rounds, writes unit and log.
+__device__ __forceinline__ void tail_out(const TailArgs &A, TailShared &S, const GcChan &c, int done, int k)
+{
+    const int ch = A.ch, lane = A.lane, dtype = c.dtype, nseg = A.nseg;
     const int nit = trk_ps_nit(dtype, 2), rgrp = GC_PS_WLANES * nit, rsamp = rgrp * (16 / dtype);     // a round: one wavefront's share (gnsscorr_ps.h)
-    for (int e = wave; e < k; e += GC_TAIL_NW) {
-        const int n = S.n[e], nt = n + 2 * c.smax;
-        const int p = m.done + e;
-        const size_t ui = (size_t)ch * kcap + e;
+    for (int e = A.wave; e < k; e += GC_TAIL_NW) {
+        const int n = S.n[e];
+        const int p = done + e;
+        const size_t ui = (size_t)ch * A.kcap + e;
         const uint64_t buffloc = S.buffloc[e];
         gc_lds_int sk0 = (gc_lds_int)S.k0[e];
         gc_lds_car scar = (gc_lds_car)S.car[e];
         gc_lds_code scode = (gc_lds_code)S.code[e];
         GcTrkUnit u;
-        const uint64_t a0 = (buffloc % c.ringlen) * (uint64_t)dtype;
-        u.a_al = a0 & ~(uint64_t)15;
-        u.head = (int)(a0 - u.a_al);
+        gc_unit_geometry(u, c, buffloc, n);
         u.n = S.valid[e] ? n : 0;
-        u.G = (u.head + n * dtype + 15) >> 4;
-        u.nt = nt;
         u.ncar = S.ncar[e];
         u.ncode = S.ncode[e];
         u.eq0 = u.eq1 = -1;                             // no edge table: the correlator finds the edges' start samples itself
         if (u.n > 0) {
-            // what the correlator's scans rely on: carrier pieces start at sample 0 and at increasing samples, code pieces
-            // are non-empty, contiguous and cover the nt replica positions
+            // carrier pieces start at sample 0 and at increasing samples; code pieces are non-empty, contiguous, cover nt
             bool bad = u.ncar < 1 || u.ncode < 1;
             if (!bad) {
                 if (lane == 0) bad = sk0[0] != 0;
                 if (lane + 1 < u.ncar) bad = bad || !(sk0[lane] < sk0[lane + 1]);
                 if (lane < u.ncode) {
                     const int je = scode[lane].j0 + scode[lane].cnt;
-                    bad = bad || scode[lane].cnt <= 0 || je != (lane + 1 < u.ncode ? scode[lane + 1].j0 : nt);
+                    bad = bad || scode[lane].cnt <= 0 || je != (lane + 1 < u.ncode ? scode[lane + 1].j0 : u.nt);
                 }
             }
             if (__any(bad)) {
-                if (lane == 0) atomicAdd(nco_overflow, 1);
-                u.n = 0;
-                u.ncar = u.ncode = 0;
+                if (lane == 0) atomicAdd(A.nco_overflow, 1);
+                u.n = u.ncar = u.ncode = 0;
             }
         } else {
             u.ncar = u.ncode = 0;
         }
         if (u.n > 0) {
-            GcUnitSegs *gs = segs + ui;
+            GcUnitSegs *gs = A.segs + ui;
             if (lane < u.ncar) {
                 gs->carK0[lane] = sk0[lane];
                 GcCarSeg cs;
-                cs.fx = scar[lane].fx;
-                cs.dfx = scar[lane].dfx;
+                cs.fx = scar[lane].fx; cs.dfx = scar[lane].dfx;
                 gs->car[lane] = cs;
             }
             if (lane < u.ncode) {
@@ -899,59 +800,158 @@ __global__ __launch_bounds__(64 * GC_TAIL_NW) void trk_step_tail_kernel(
             // rounds: four per correlator workgroup, one per wavefront (lane = round)
             const int g0 = lane * rgrp;
             if (lane < 4 * nseg && g0 < u.G) {
-                const unsigned short *rank = (const unsigned short *)(c.code + 1024);
-                const int kl = (g0 * 16 - u.head) / dtype;
-                const int kfirst = kl > 0 ? kl : 0;
-                const int kend = (kl + rsamp < n ? kl + rsamp : n);
-                int wa = 0, wb = 0, hint = 0;
-                const int ma = lds_code_chip_at(scode, u.ncode, kfirst, &wa, &hint);
-                const int mb = lds_code_chip_at(scode, u.ncode, kend - 1 + 2 * c.smax, &wb, nullptr);
-                GcRound ro;
-                ro.q0 = wa * c.nedge + (int)rank[ma];
-                ro.q1 = wb * c.nedge + (int)rank[mb];
-                ro.clast = (short)c.code[mb];
-                ro.w0 = (short)wa;
-                ro.hint = hint;
-                rounds[ui * nseg * 4 + lane] = ro;
+                int jfirst, jlast, wa = 0, wb = 0, hint = 0;
+                gc_round_span((g0 * 16 - u.head) / dtype, rsamp, n, c.smax, &jfirst, &jlast);
+                const int ma = lds_code_chip_at(scode, u.ncode, jfirst, &wa, &hint);
+                const int mb = lds_code_chip_at(scode, u.ncode, jlast, &wb, nullptr);
+                A.rounds[ui * nseg * 4 + lane] = gc_round_make(c.code, c.nedge, ma, wa, mb, wb, hint);
             }
         }
         if (lane == 0) {
-            unit[ui] = u;
-            gnsscorr_trklog_t *lg = log + (size_t)ch * nper + p;
-            lg->buffloc = buffloc;
-            lg->currnsamp = n;
-            lg->remcode = S.remcode[e + 1];
-            lg->remcarr = S.remcarr[e + 1];
-            nsamp_out[(size_t)ch * nper + p] = n;
+            A.unit[ui] = u;
+            gnsscorr_trklog_t *lg = A.log + (size_t)ch * A.nper + p;
+            lg->buffloc = buffloc; lg->currnsamp = n;
+            lg->remcode = S.remcode[e + 1]; lg->remcarr = S.remcarr[e + 1];
+            A.nsamp_out[(size_t)ch * A.nper + p] = n;
         }
     }
-    GC_TSTAMP(6);       // checks, tables out, rounds
-    if (want > 0) {
-        m.k = k;
-        m.kcap = kcap;
-        m.pbase = m.done;
-        m.done += k;
+}
+// state out -- thread 0: the state behind the k planned periods, meta, ndone, the host's flags; all wavefronts: S.lp back.
+__device__ __forceinline__ void tail_state_out(const TailArgs &A, TailShared &S, const GcStepMeta &m, int k, bool was_finished)
+{
+    const int ch = A.ch;
+    if (A.tid == 0) {
+        GcTrkState st = S.st;
+        st.remcode = S.remcode[k]; st.remcarr = S.remcarr[k]; st.buffloc = S.buffloc[k];
+        A.state[ch] = st;
+        A.meta[ch] = m;
+        A.ndone[ch] = m.consumed;
+        if (A.hostflags) {
+            if (m.finished && !was_finished) __hip_atomic_fetch_add(&A.hostflags[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (S.lp.flagsync) __hip_atomic_store(&A.hostflags[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
     }
+    tail_copy_loop(A.loop + ch, &S.lp, A.tid);
+}
+// One workgroup (GC_TAIL_NW wavefronts) per channel: the phases above.  Up to close they end the interval the previous
+// correlator launch produced; from the step tables on they plan the next one.
+__global__ __launch_bounds__(64 * GC_TAIL_NW) void trk_step_tail_kernel(
+    const GcChan *__restrict__ chan, GcTrkState *__restrict__ state, gnsscorr_loop_t *__restrict__ loop,
+    GcStepMeta *__restrict__ meta, const uint64_t *__restrict__ wrpos, const int *__restrict__ partial,
+    GcTrkUnit *__restrict__ unit, GcUnitSegs *__restrict__ segs, GcRound *__restrict__ rounds, double *__restrict__ corrI,
+    double *__restrict__ corrQ, int *__restrict__ nsamp_out, gnsscorr_trklog_t *__restrict__ log, int *__restrict__ ndone,
+    int *__restrict__ nco_overflow, int *__restrict__ lapped, unsigned *__restrict__ hostflags, int nch, int nper, int nseg,
+    int ntap_stride, int max_n, int kcap, int plan)
+{
+    __shared__ __attribute__((aligned(16))) TailShared S;
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= nch) return;
+    GC_TSTART();
+    const TailArgs A{chan, state, loop, meta, wrpos, partial, unit, segs, rounds, corrI, corrQ, nsamp_out, log, ndone, nco_overflow,
+                     lapped, hostflags, nper, nseg, ntap_stride, max_n, kcap, plan, (int)blockIdx.x, tid, tid & 63, tid >> 6};
+    const GcChan &c = chan[A.ch];
+    const int ntap = c.ntap;
+    GcStepMeta m = tail_state_in(A, S);
+    __syncthreads();
+    const double II0_before = S.lp.II[0];
+    const bool was_finished = m.finished != 0;
+    GC_TSTAMP(0);       // state in
+    tail_sums(A, S, m, ntap);
+    __syncthreads();
+    GC_TSTAMP(1);       // sums
+    if (A.wave == 1) tail_nav(A, S, m.k, ntap, II0_before);
+    if (A.wave == 0) tail_close(A, S, m, ntap);      // (GC_TSTAMP(2) after each period)
+    __syncthreads();
+    m.consumed += m.k; m.k = 0;
+    const int want = S.want;
+    const TailSteps q = tail_steps(S, c);
+    if (want > 0) tail_step_tables(A, S, c, q);
+    __syncthreads();
+    GC_TSTAMP(3);       // step tables
+    if (want > 1) {
+        // discover, left inline: as a function (one per wavefront, one for both, or out of line) the same statements cost a
+        // ten-period interval 2 000 to 3 500 clocks more, and loop-10 0.28 us per period in the bench
+        if (A.wave == 2) {       // code brackets -> S.ccl
+            const int lane = A.lane, pe = lane & 31;
+            const bool hiend = lane >= 32;
+            if (pe < want) {
+                GcCodeClaims cc;
+                cc.tag = cc.n = cc.pad = 0;
+                cc.lo = cc.hi = 0.0;
+                double end = 0.0;       // this lane's end of the bracket; the samples, wrap branch and verdict there
+                int n = 0, side = 0;
+                bool ok = false;
+                if (q.shape_ok && q.spc > 1e-300 && q.spc < 1e300) {
+                    double rc, rk, dummy;
+                    int nhat;
+                    gc_spec_start(S.remcode[0], S.remcarr[0], q.ci, q.spc, q.ps, q.dlen, pe, &rc, &rk, &nhat);
+                    end = hiend ? rc + TAIL_BRACKET_W : rc - TAIL_BRACKET_W;
+                    n = gc_period_nsamp(q.dlen, end, q.spc);
+                    side = end - S.PC.smaxci < 0.0 ? 1 : 0;                          // (ref src/sdrcmn.c:614: one branch for the whole bracket)
+                    if (n > 0 && n <= (1 << 24)) ok = gc_code_claims<true>(S.PC, end, n + 2 * c.smax, cc, &dummy);
+                }
+                bool same = ok && pair_other(ok ? 1 : 0, lane) != 0 && pair_same(n, lane) && pair_same(side, lane);
+                same = same && pair_same(cc.i0, lane) && pair_same(cc.q, lane) && pair_same(cc.nl, lane) && pair_same(cc.jsum, lane);
+#pragma unroll
+                for (int i = 0; i < 13; i++) same = same && pair_same(cc.dm[i], lane);
+                const double other = pair_other(end, lane);
+                if (!hiend) {
+                    // (the discovering step allows the widest tail; the chain's instance may be narrower)
+                    cc.tag = (same && n + 2 * c.smax - cc.jsum <= gc_tail_max(gc_tail_class(c.smax))) ? 1 : 0;
+                    cc.n = n; cc.lo = end; cc.hi = other;
+                    S.ccl[pe] = cc;
+                }
+            }
+        }
+        if (A.wave == 3) {       // carrier brackets -> S.kcl
+            const int lane = A.lane, pe = lane & 31;
+            const bool hiend = lane >= 32;
+            if (pe < want) {
+                GcCarClaims ck{};
+                double end = 0.0;
+                int n = 0;
+                bool ok = false;
+                if (q.shape_ok && q.spc > 1e-300 && q.spc < 1e300) {
+                    double rc, rk, dummy;
+                    gc_spec_start(S.remcode[0], S.remcarr[0], q.ci, q.spc, q.ps, q.dlen, pe, &rc, &rk, &n);
+                    end = hiend ? rk + TAIL_BRACKET_W : rk - TAIL_BRACKET_W;
+                    if (n > 0 && n <= (1 << 24)) {
+                        GcCarStepC CK;
+                        gc_car_stepc_init(CK, S.PK, c.nsamp + 16);
+                        ok = gc_carrier_claims_step<true>(S.PK, CK, end, n, ck, &dummy);
+                    }
+                }
+                bool same = ok && pair_other(ok ? 1 : 0, lane) != 0 && pair_same(ck.tag, lane) && pair_same(ck.nl, lane);
+                same = same && pair_same(ck.i0, lane) && pair_same(ck.nseg, lane) && pair_same(ck.kprem, lane);
+#pragma unroll
+                for (int i = 0; i < GC_CLAIM_CSEG; i++) same = same && pair_same(ck.dm[i], lane);
+                const double other = pair_other(end, lane);
+                if (!hiend) {
+                    // (tag 2, a period inside one binade, carries its own conditions and is judged by them: it needs no bracket)
+                    ck.tag = same ? ck.tag : (ok && ck.tag == 2 ? 2 : 0);
+                    ck.nl = n; ck.lo = end; ck.hi = other;
+                    S.kcl[pe] = ck;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    GC_TSTAMP(8);       // claims
+    if (want > 0) {
+        if (A.wave == 1) tail_code_chain_any(A, S, c, q, want);
+        else if (A.wave == 0 && want > 1) tail_carrier_chain(A, S, c, q, want);
+    }
+    GC_TSTAMP(4);       // chain
+    tail_table_tasks(A, S, c, q, want);
+    __syncthreads();
+    GC_TSTAMP(5);       // tables
+    const int k = S.k;
+    tail_out(A, S, c, m.done, k);
+    GC_TSTAMP(6);       // checks, tables out, rounds
+    if (want > 0) { m.k = k; m.kcap = kcap; m.pbase = m.done; m.done += k; }
     // the run is over for this channel once nothing is planned and nothing waits to be closed
     if (m.k == 0 && (m.done >= nper || S.starved || !plan)) m.finished = 1;
-    if (tid == 0) {
-        GcTrkState st = S.st;
-        st.remcode = S.remcode[k];
-        st.remcarr = S.remcarr[k];
-        st.buffloc = S.buffloc[k];
-        state[ch] = st;
-        meta[ch] = m;
-        ndone[ch] = m.consumed;
-        if (hostflags) {
-            if (m.finished && !was_finished) __hip_atomic_fetch_add(&hostflags[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            if (lp->flagsync) __hip_atomic_store(&hostflags[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-    {
-        unsigned long long *dst = reinterpret_cast<unsigned long long *>(loop + ch);
-        const unsigned long long *src = reinterpret_cast<const unsigned long long *>(&S.lp);
-        for (int i = tid; i < (int)(sizeof(gnsscorr_loop_t) / 8); i += 64 * GC_TAIL_NW) dst[i] = src[i];
-    }
+    tail_state_out(A, S, m, k, was_finished);
     GC_TSTAMP(7);       // state out
 }
 

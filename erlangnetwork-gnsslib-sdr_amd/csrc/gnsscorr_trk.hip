@@ -146,12 +146,8 @@ __global__ __launch_bounds__(GC_EXP_LANES) void trk_expand_kernel(const GcChan *
     const GcTrkPlan p = plan[i];
     GcUnitSegs *sg = segs + i;
     GcTrkUnit u;
-    const uint64_t a0 = (p.buffloc % c.ringlen) * (uint64_t)c.dtype;
-    u.a_al = a0 & ~(uint64_t)15;
-    u.head = (int)(a0 - u.a_al);
+    gc_unit_geometry(u, c, p.buffloc, p.n);
     u.n = p.n;
-    u.G = (u.head + p.n * c.dtype + 15) >> 4;
-    u.nt = p.n + 2 * c.smax;
     u.ncar = 0;
     u.ncode = 0;
     u.eq0 = -1;
@@ -194,25 +190,18 @@ __global__ __launch_bounds__(GC_EXP_LANES) void trk_expand_kernel(const GcChan *
     if (!rounds) { unit[i] = u; return; }
     const int nitc = trk_ps_nit(c.dtype, nit), rgrp = GC_PS_WLANES * nitc, rsamp = rgrp * (16 / c.dtype);
     const int rpw = trk_ps_rounds(c.dtype, max_n, nitc);
-    const unsigned short *rank = (const unsigned short *)(c.code + 1024);
+    const int8_t *code = c.code;
     int eq0 = 0x7fffffff, eq1 = -1;
     for (int seg = 0; seg < nseg; seg++) {
         const int g0 = seg * rgrp * rpw;
         if (g0 >= u.G) break;
         const int klo = (g0 * 16 - u.head) / c.dtype;
         for (int r = 0; r < rpw && g0 + r * rgrp < u.G; r++) {
-            const int kl = klo + r * rsamp;
-            const int kfirst = kl > 0 ? kl : 0;
-            const int kend = (kl + rsamp < p.n ? kl + rsamp : p.n);
-            int wa = 0, wb = 0, hint = 0;
-            const int ma = dt.chip_at(kfirst, &wa, &hint);
-            const int mb = dt.chip_at(kend - 1 + 2 * c.smax, &wb, nullptr);
-            GcRound ro;
-            ro.q0 = wa * c.nedge + (int)rank[ma];
-            ro.q1 = wb * c.nedge + (int)rank[mb];
-            ro.clast = (short)c.code[mb];
-            ro.w0 = (short)wa;
-            ro.hint = hint;
+            int jfirst, jlast, wa = 0, wb = 0, hint = 0;
+            gc_round_span(klo + r * rsamp, rsamp, p.n, c.smax, &jfirst, &jlast);
+            const int ma = dt.chip_at(jfirst, &wa, &hint);
+            const int mb = dt.chip_at(jlast, &wb, nullptr);
+            const GcRound ro = gc_round_make(code, c.nedge, ma, wa, mb, wb, hint);
             rounds[((size_t)i * nseg + seg) * GC_MAXR + r] = ro;
             eq0 = ro.q0 < eq0 ? ro.q0 : eq0;
             eq1 = ro.q1 > eq1 ? ro.q1 : eq1;
