@@ -124,12 +124,31 @@ extern "C" int gnsscorr_ring_create(gnsscorr_ctx *ctx, int ftype, int dtype, uin
         return gc_fail(GNSSCORR_EINVAL, "ring_create: dtype*ringlen must be a positive multiple of 16");
     if (devmem && ((uintptr_t)devmem & 15))
         return gc_fail(GNSSCORR_EINVAL, "ring_create: device buffer must be 16-byte aligned");
+    // The channels that read this ring keep their rows, which index it by their own dtype and nsamp: the new ring must
+    // be one gnsscorr_set_channels would have accepted for them (validated first: nothing is touched on failure)
+    bool referenced = false;
+    for (int i = 0; i < ctx->nch; i++) {
+        const gnsscorr_chan_t &c = ctx->hdesc[i];
+        if (c.ftype != ftype) continue;
+        referenced = true;
+        if (c.dtype != dtype)
+            return gc_fail(GNSSCORR_EINVAL, "ring_create: channel %d: dtype %d but ring %d would hold dtype %d "
+                           "(gnsscorr_set_channels comes first)", i, c.dtype, ftype, dtype);
+        if (ringlen < (uint64_t)c.nsamp + 100 + 32 / c.dtype)
+            return gc_fail(GNSSCORR_EINVAL, "ring_create: channel %d: ring %d (%llu samples) would be shorter than a code period (%d + 100 + %d)",
+                           i, ftype, (unsigned long long)ringlen, c.nsamp, 32 / c.dtype);
+    }
     GC_HIP(hipSetDevice(ctx->device));
     {
         std::lock_guard<std::mutex> lk(ctx->mtx);
-        // transfers into the old ring (ingest stream) and kernels reading it (compute stream) are over before it goes
-        if (ctx->in.stream) GC_HIP(hipStreamSynchronize(ctx->in.stream));
-        GC_HIP(hipStreamSynchronize(ctx->stream));
+        // Transfers into the old ring (ingest stream) and kernels reading it (compute stream) are over before it goes.
+        // Only the compute stream reads samples, but with channels the call also rewrites their device rows, which the
+        // planner, discovery and tables streams read (a look-ahead plan may still be running), and that plan was made
+        // for positions of the old stream: quiesce like gnsscorr_set_channels does, which drops it.
+        GC_TRY(gc_quiesce(ctx, true));
+        // a running schedule holds sample positions of the old stream (next_try, acq_wrpos, the TRACK channels'
+        // buffloc): it is off until the next gnsscorr_rx_start
+        if (referenced) ctx->rx.on = false;
         r->own.reset();
         r->mem = nullptr;
         if (devmem) {

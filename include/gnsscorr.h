@@ -62,7 +62,31 @@ int  gnsscorr_sync(gnsscorr_ctx *ctx);
  * sdrstat.fendbuffsize*sdrstat.buffcnt.
  * devmem == NULL allocates dtype*ringlen bytes with hipMalloc; otherwise the
  * caller's device buffer is used (e.g. the tensor an RCCL broadcast lands
- * in).  dtype*ringlen must be a multiple of 16. */
+ * in).  dtype*ringlen must be a multiple of 16.
+ * On a context that has channels (a front end switched under a live receiver)
+ * the call re-creates the ring under them.  The channels of that ring keep
+ * their device rows, which index the ring by the channel's own dtype and
+ * nsamp, so the new ring must be one gnsscorr_set_channels would accept for
+ * them: GNSSCORR_EINVAL naming the channel, with nothing touched -- the old
+ * ring, its write position and its contents (gnsscorr_ring_read) stay -- when
+ * a channel with this ftype has another dtype, or ringlen < nsamp + 100 +
+ * 32/dtype for it.  To change the dtype, call gnsscorr_set_channels with
+ * channels of another ring (or destroy the context) first.  Otherwise the call
+ * waits until nothing of the context is in flight (every stream, the ingest
+ * included; a look-ahead tracking plan is dropped), the write position becomes
+ * 0, an owned ring is zero filled, and the channels read the new ring from the
+ * next call on.  Everything else stays: the channel set and its acquisition
+ * settings, the prepared acquisition work and the last search's results, the
+ * tracking and loop states (their buffloc are positions of the old stream:
+ * gnsscorr_trk_set_state or a hand-over from a new search comes next), the
+ * IF monitor's last run.  A search needs (intg + 1) * nsamp new samples first
+ * (GNSSCORR_ESTATE until then).
+ * A running schedule (gnsscorr_rx_start done) holds positions of the old
+ * stream in next_try, acq_wrpos and the TRACK channels' buffloc: re-creating a
+ * ring that a channel reads switches the schedule off, and gnsscorr_rx_step,
+ * gnsscorr_rx_set, gnsscorr_rx_status, gnsscorr_rx_lock_set and
+ * gnsscorr_rx_lock_status return GNSSCORR_ESTATE until the next
+ * gnsscorr_rx_start.  A ring no channel reads leaves the schedule alone. */
 int  gnsscorr_ring_create(gnsscorr_ctx *ctx, int ftype, int dtype,
                           uint64_t ringlen, void *devmem);
 /* append nsamp samples from host memory (what file_pushtomembuf's fread
@@ -110,6 +134,17 @@ typedef struct {
     const int *corrp;           /* ref sdrtrk_t.corrp                        */
 } gnsscorr_chan_t;
 
+/* Replaces the context's channel set; may be called again on a live context
+ * (the satellite list changed).  Validates first (GNSSCORR_EINVAL /
+ * GNSSCORR_ESTATE naming the channel, nothing touched), waits until nothing of
+ * the context is in flight, and then starts the new set from nothing: tracking
+ * and loop states zero, no loop constants (gnsscorr_loop_set), the acquisition
+ * settings back at ncoh 1 / estep 0 / nref 0, no search results, the schedule
+ * and the lock monitor off (GNSSCORR_ESTATE until gnsscorr_rx_start), and the
+ * IF monitor's last run gone: gnsscorr_spec_fetch returns GNSSCORR_ESTATE
+ * until the next gnsscorr_spec_run.  The rings, their contents and write
+ * positions stay.  A new set computes bit for bit what it computes on a fresh
+ * context over the same ring contents. */
 int  gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch,
                            const gnsscorr_chan_t *ch);
 int  gnsscorr_num_channels(gnsscorr_ctx *ctx);
@@ -508,7 +543,12 @@ typedef struct {
 
 /* Every channel -> SEARCH, first due at (intg + 1) * nsamp samples, the first moment sdracquisition()'s look-back
  * fits (ref src/sdracq.c:24-26).  retry_ms <= 0: ACQSLEEP (2000).  Needs the channels set and gnsscorr_loop_set done
- * for every one of them (the constants the hand-over keeps); otherwise GNSSCORR_ESTATE. */
+ * for every one of them (the constants the hand-over keeps); otherwise GNSSCORR_ESTATE.
+ * May be called again on the same channels (after gnsscorr_ring_create it must be): the schedule starts over -- states,
+ * attempts, losses, the monitor off, the verdicts of a pending monitor launch dropped -- while the device's tracking and
+ * loop states are not touched.  A channel that is acquired again is handed over like any other and from then on is bit for
+ * bit a channel of a fresh context; until then its gnsscorr_rxstat_t.cnt keeps the count of its last run (the next
+ * hand-over restarts it at 0), and gnsscorr_loop_get shows the loop state that run left. */
 int  gnsscorr_rx_start(gnsscorr_ctx *ctx, int retry_ms);
 /* Park a channel (GNSSCORR_CH_IDLE: its tracking and loop state freeze) or re-arm it (GNSSCORR_CH_SEARCH: due at its
  * ring's current write position).  GNSSCORR_CH_TRACK is reached through acquisition only: GNSSCORR_EINVAL. */

@@ -490,7 +490,15 @@ def test_batch_outside_the_ring_is_refused(gc, orc, engine):
     engine.trk_run(1)
     with pytest.raises(gc.GnsscorrError, match="outside what the IF ring holds"):
         engine.trk_fetch()
-    # a ring shorter than a code period is refused when the channels are set
-    engine.ring_create(1, 2, 8192)
+    # a ring shorter than a code period is refused: under the channels that read it by the re-create itself (the old
+    # ring stays), on a context without channels when the channels are set
     with pytest.raises(gc.GnsscorrError, match="shorter than a code period"):
-        engine.set_channels([gc.Channel(3, dtype=2, f_if=0.0)])
+        engine.ring_create(1, 2, 8192)
+    assert engine.ring_wrpos(1) == 4 * ringlen
+    other = gc.Engine(0)
+    try:
+        other.ring_create(1, 2, 8192)
+        with pytest.raises(gc.GnsscorrError, match="shorter than a code period"):
+            other.set_channels([gc.Channel(3, dtype=2, f_if=0.0)])
+    finally:
+        other.close()
