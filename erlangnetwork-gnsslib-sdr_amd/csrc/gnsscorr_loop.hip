@@ -797,14 +797,15 @@ __device__ __forceinline__ void tail_out(const TailArgs &A, TailShared &S, const
                 sg.j0 = scode[lane].j0; sg.cnt = scode[lane].cnt; sg.w = scode[lane].w; sg.pad = 0;
                 gs->code[lane] = sg;
             }
-            // rounds: four per correlator workgroup, one per wavefront (lane = round)
-            const int g0 = lane * rgrp;
-            if (lane < 4 * nseg && g0 < u.G) {
+            // rounds: four per correlator workgroup, one per wavefront; a lane takes every 64th round (periods of more
+            // than 64 rounds, 65536 samples, have more rounds than the wavefront has lanes)
+            for (int r = lane; r < 4 * nseg && r * rgrp < u.G; r += 64) {
+                const int g0 = r * rgrp;
                 int jfirst, jlast, wa = 0, wb = 0, hint = 0;
                 gc_round_span((g0 * 16 - u.head) / dtype, rsamp, n, c.smax, &jfirst, &jlast);
                 const int ma = lds_code_chip_at(scode, u.ncode, jfirst, &wa, &hint);
                 const int mb = lds_code_chip_at(scode, u.ncode, jlast, &wb, nullptr);
-                A.rounds[ui * nseg * 4 + lane] = gc_round_make(c.code, c.nedge, ma, wa, mb, wb, hint);
+                A.rounds[ui * nseg * 4 + r] = gc_round_make(c.code, c.nedge, ma, wa, mb, wb, hint);
             }
         }
         if (lane == 0) {
@@ -1090,7 +1091,11 @@ static int ensure_step_buffers(gnsscorr_ctx *ctx)
         const int s = step_nseg(ctx->hchan[i].dtype, ctx->max_n);
         if (s > nseg) nseg = s;
     }
-    if (nseg > 64) return gc_fail(GNSSCORR_EINVAL, "trk_run_loop: period of %d samples too long (%d rounds, 64 at most)", ctx->max_n, nseg);
+    // (gnsscorr_set_channels accepts periods of up to 262144 samples: 65 workgroups of four rounds for either sample type)
+    const int most = step_nseg(2, 262144 + 100);
+    if (nseg > most)
+        return gc_fail(GNSSCORR_EINVAL, "trk_run_loop: period of %d samples too long (%d workgroups of four rounds, %d at most)",
+                       ctx->max_n, nseg, most);
     const size_t units = (size_t)ctx->nch * GC_STEP_KMAX;
     GC_RESERVE(ctx, L.dstep_unit, units);
     GC_RESERVE(ctx, L.dstep_segs, units);

@@ -264,14 +264,15 @@ def test_closed_loop_random_states_across_front_ends(gc, orc, engine, seed, dtyp
 
 
 def _random_states_case(gc, orc, engine, seed, dtype, f_if, f_sf, taps, flagsync, ctype=1, nper=130, nch=12,
-                        chunks=(97, 33)):
+                        chunks=(97, 33), ring_granule=1):
     """test_closed_loop_random_states_across_front_ends for one front end / tap set: nch channels from random start
-    states on noise, nper periods in len(chunks) runs, every period against orc_sdrthread_step."""
+    states on noise, nper periods in len(chunks) runs, every period against orc_sdrthread_step.  ring_granule: the
+    ring's length is rounded up to a multiple of it (a period length that is no multiple of the ring's 16 bytes)."""
     corrn, corrd, corrp = taps
     assert sum(chunks) == nper
     nsamp = int(f_sf * 1e-3)
     rng = np.random.default_rng(seed)
-    nsamples = nsamp * (nper + 4)
+    nsamples = -(-nsamp * (nper + 4) // ring_granule) * ring_granule
     data = rng.integers(-60, 61, size=(nsamples, 2) if dtype == 2 else (nsamples,), dtype=np.int8)
     engine.ring_create(1, dtype, nsamples)
     engine.ring_push_raw(1, data, nsamples)

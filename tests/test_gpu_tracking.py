@@ -16,17 +16,22 @@ F_SF = 16.368e6
 
 
 def _setup(gc, orc, engine, dtype, f_if, corrn, corrd, corrp, prns, nsamples, seed, buffloc0, ringlen=None,
-           amp=60):
+           amp=60, f_sf=F_SF, ftype=1, apply=True):
+    """apply=False: the samples, channels, start states and oracle channels only -- nothing goes to the engine (which
+    may be None): the caller creates the ring `ftype`, pushes, sets the channels and the states itself."""
     rng = np.random.default_rng(seed)
     shape = (nsamples, 2) if dtype == 2 else (nsamples,)
     data = rng.integers(-amp, amp + 1, size=shape, dtype=np.int8)
     # include the int8 extremes
     data.reshape(-1)[:4] = [-128, 127, -128, 127]
     ringlen = ringlen or nsamples
-    engine.ring_create(1, dtype, ringlen)
-    engine.ring_push_raw(1, data, nsamples)
-    chans = [gc.Channel(p, dtype=dtype, f_if=f_if, corrn=corrn, corrd=corrd, corrp=corrp) for p in prns]
-    engine.set_channels(chans)
+    if apply:
+        engine.ring_create(ftype, dtype, ringlen)
+        engine.ring_push_raw(ftype, data, nsamples)
+    chans = [gc.Channel(p, dtype=dtype, ftype=ftype, f_sf=f_sf, f_if=f_if, corrn=corrn, corrd=corrd, corrp=corrp)
+             for p in prns]
+    if apply:
+        engine.set_channels(chans)
     states, ochs = [], []
     for i, c in enumerate(chans):
         # channel 0 starts like a channel fresh out of acquisition (remcode = remcarr = 0, carrfreq on
@@ -38,9 +43,10 @@ def _setup(gc, orc, engine, dtype, f_if, corrn, corrd, corrp, prns, nsamples, se
                   remcode=(rng.uniform(0.01, 0.99) if i > 1 else 0.0), remcarr=rng.uniform(0, 6.2) if i else 0.0,
                   buffloc=buffloc0 + 1000 * i + (i % 3))
         states.append(st)
-        o = orc.make_chan(c.prn, dtype=dtype, f_if=f_if, corrn=corrn, corrd=corrd, corrp=corrp)
+        o = orc.make_chan(c.prn, dtype=dtype, f_sf=f_sf, f_if=f_if, corrn=corrn, corrd=corrd, corrp=corrp)
         ochs.append(o)
-    engine.trk_set_state(states)
+    if apply:
+        engine.trk_set_state(states)
     return data, chans, states, ochs
 
 
