@@ -363,15 +363,23 @@ __device__ __attribute__((noinline)) double tail_code_slow(double ci, double rem
     const double cend = gc_fast_code_walk(f, gc_code_start(remcode, smax, ci, clen), clen, nt, emit);
     return gc_code_rem(cend, smax, ci);
 }
+// whether an attempt ran out of table room (the chains' GcNoEmit holds no table)
+__device__ __forceinline__ bool tail_emit_over(const GcNoEmit &) { return false; }
+template <class Emit> __device__ __forceinline__ bool tail_emit_over(const Emit &emit) { return emit.overflow != 0; }
 // The ladder's lower rungs, for the chains (GcNoEmit) and the table tasks (Lds*Table): the certified period step, else
-// the emitter forgets the attempt and the walkers above take the period.  (gc_*_period_any of gnsscorr_nco.h walk inline
-// on the plan's tables: the kernel sits at its register cap, and S.PK.f has no reciprocals for the carrier walker.)
+// the emitter forgets the attempt and the walkers above take the period.  A step whose pieces did not fit the table is
+// such an attempt too: the code step spells out every replica position behind the second wrap as a piece of its own
+// (gc_code_period_body's tail, about 13 + smax - samples per chip pieces), the walker merges them by binade and stays at
+// at most 20 pieces for every span set_channels accepts.  The carrier step has no such rule: its pieces are the walker's,
+// one per binade visited (counted on the host, tests/test_tap_spans_host.py), so a table it overflows the walker
+// overflows too.  (gc_*_period_any of gnsscorr_nco.h walk inline on the plan's
+// tables: the kernel sits at its register cap, and S.PK.f has no reciprocals for the carrier walker.)
 template <class Emit>
 __device__ __forceinline__ double tail_code_period(const GcCodePlan &PC, const GcChan &c, double ci, double remcode, int nt, int lane, Emit &emit)
 {
     GcFillLanes fill{lane};
     double r;
-    if (gc_code_period(PC, remcode, nt, fill, &r, emit)) return r;
+    if (gc_code_period(PC, remcode, nt, fill, &r, emit) && !tail_emit_over(emit)) return r;
     emit.reset();
     return tail_code_slow(ci, remcode, c.clen, c.smax, nt, emit);
 }

@@ -384,7 +384,9 @@ int  gnsscorr_sbasframe_replay(gnsscorr_ctx *ctx, gnsscorr_sbasframe_t *st, cons
  * (II/QQ per period, periods not run are zero with nsamp_out 0) and
  * gnsscorr_trk_fetch_log.  A period that starts more than ringlen samples behind
  * the write position reads samples the writer has overwritten since: it is run,
- * as sdrtracking() runs it, and counted (gnsscorr_trk_loop_lapped). */
+ * as sdrtracking() runs it, and counted (gnsscorr_trk_loop_lapped).  Every tap set
+ * gnsscorr_set_channels accepts is served, outermost taps of 64 samples included,
+ * at any sample rate: no run depends on a channel's code phase for that. */
 int  gnsscorr_trk_run_loop(gnsscorr_ctx *ctx, int nperiod);
 /* *nlapped = periods of the last gnsscorr_trk_run_loop that read overwritten
  * samples (0: every period read what the ring holds); synchronises */

@@ -155,6 +155,84 @@ int nco_period_tables(double ti, double freq, double remcarr, double codefreq, i
     return r;
 }
 
+// Pieces the shape-specialised period steps emit into tables with room to spare (what a table of the closed loop's tail
+// would have to hold for the step to serve the period): -1 where the step declines.
+int nco_code_period_pieces(double ti, double codefreq, int len, double remcode, int smax, int nt, double *rem)
+{
+    static GcCodeSeg seg[1024];
+    GcCodeTable dt{seg, 1024, 0, 0};
+    GcCodePlan P;
+    gc_code_plan_init(P, ti * codefreq, len, smax);
+    GcFillLoop fill;
+    if (!gc_code_period(P, remcode, nt, fill, rem, dt) || dt.overflow) return -1;
+    return dt.n;
+}
+
+int nco_carrier_period_pieces(double ti, double freq, double remcarr, int n, double *prem)
+{
+    static int k0[1024];
+    static GcCarSeg seg[1024];
+    GcCarTable ct{k0, seg, 1024, 0, 0};
+    GcCarPlan P;
+    gc_car_plan_init(P, gc_carrier_ps(freq, ti));
+    GcFillLoop fill;
+    if (!gc_carrier_period(P, remcarr, n, fill, prem, ct) || ct.overflow) return -1;
+    return ct.n;
+}
+
+// The ladder of the closed loop's table tasks (gnsscorr_loop.hip: tail_code_period / tail_carrier_period) with tables of
+// `cap` pieces -- the caller hands in GC_NCODE / GC_NCAR as gnsscorr_internal.h states them: the shaped step; where it
+// declines, or (code, give_up_on_overflow) where its pieces do not fit the table, the attempt is forgotten and the fast
+// walker takes the period.  give_up_on_overflow = 0 is the ladder as it was before overflow became a reason to step down.
+// *rung: 0 the step served, 1 the walker.  Returns the pieces, -1 when the rung that served overflowed the table.
+int nco_tail_code_ladder(double ti, double codefreq, int len, double remcode, int smax, int nt, int cap, int give_up_on_overflow,
+                         int *chip, double *rem, int *rung)
+{
+    GcCodeSeg seg[256];
+    if (cap > 256) cap = 256;
+    GcCodeTable dt{seg, cap, 0, 0};
+    const double ci = ti * codefreq;
+    GcCodePlan P;
+    gc_code_plan_init(P, ci, len, smax);
+    GcFillLoop fill;
+    *rung = 0;
+    if (!(gc_code_period(P, remcode, nt, fill, rem, dt) && !(give_up_on_overflow && dt.overflow))) {
+        dt.reset();
+        *rung = 1;
+        GcNcoFast f;
+        gc_fast_init(f, ci);
+        *rem = gc_code_rem(gc_fast_code_walk(f, gc_code_start(remcode, smax, ci, len), len, nt, dt), smax, ci);
+    }
+    if (dt.overflow) return -1;
+    for (int j = 0; j < nt; j++) chip[j] = gc_code_chip_at(seg, dt.n, j, nullptr);
+    return dt.n;
+}
+
+// (the carrier ladder has no overflow rule: the step's pieces are the walker's, one per binade visited)
+int nco_tail_carrier_ladder(double ti, double freq, double remcarr, int n, int cap, int *idx, double *prem, int *rung)
+{
+    int k0[256];
+    GcCarSeg seg[256];
+    if (cap > 256) cap = 256;
+    GcCarTable ct{k0, seg, cap, 0, 0};
+    const double ps = gc_carrier_ps(freq, ti);
+    GcCarPlan P;
+    gc_car_plan_init(P, ps, false);                 // (the tail's carrier table has no reciprocals)
+    GcFillLoop fill;
+    *rung = 0;
+    if (!gc_carrier_period(P, remcarr, n, fill, prem, ct)) {
+        ct.reset();
+        *rung = 1;
+        GcNcoFast f, fp;
+        gc_fast_init(f, ps);
+        gc_fast_init(fp, -GC_NCO_DPI);
+        *prem = gc_fast_prem(fp, gc_fast_carrier_walk(f, gc_carrier_phis(remcarr), n, ct));
+    }
+    if (ct.overflow) return -1;
+    for (int k = 0; k < n; k++) idx[k] = gc_carrier_idx_at(k0, seg, ct.n, k);
+    return ct.n;
+}
+
 // The batch planner's steps on claims (gnsscorr_plan.hip: trk_spec_kernel discovers, trk_plan2_kernel evaluates): state after every
 // period; hits[0]/[1]: periods the code / carrier evaluation served, the rest go down the planner's ladder
 // (gc_*_period_any): the certified steps ([2]/[3]), else stretches and walkers ([4]/[5]).  shift_*: added to the

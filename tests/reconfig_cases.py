@@ -79,8 +79,7 @@ def differ(a, b, where=""):
 
 # ---- channels --------------------------------------------------------------------------------------------------------
 # Tap spacing (samples) by tap pairs: the outermost tap stays within 6 samples, 1.5 chips at the four samples per chip of
-# these inputs -- the reach of the shipped layout (18 samples at 16 per chip).  The closed loop declines taps that reach
-# 4.5 chips at this rate ("found on the way").
+# these inputs -- the reach of the shipped layout (18 samples at 16 per chip).
 CORRD = {1: 3, 2: 3, 3: 2, 6: 1}
 
 

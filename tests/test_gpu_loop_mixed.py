@@ -1,7 +1,7 @@
 """The closed loop (gnsscorr_trk_run_loop) as a receiver runs it, against the oracle (parity tests proper, -m gpu):
 one engine that mixes front ends, code types, tap spans and nav-sync states; a ring of a few code periods fed chunk
-by chunk while the loop runs; a channel the writer has lapped; and the widest tap span the loop serves, with the
-report one sample beyond it.
+by chunk while the loop runs; a channel the writer has lapped; and the tap spans on either side of the one at which, at
+16.368 Msps, the code step's pieces stop fitting the tail's table (tests/test_gpu_tap_spans.py has every front end).
 
 Bar: the one tests/test_gpu_loop.py sets -- sums, samples per period, remainders, filter-update flags, flagsync and
 decided bits bit for bit, filter outputs to 1e-12 with teacher forcing (_adopt), final state equal to the oracle's."""
@@ -226,17 +226,19 @@ def test_closed_loop_lapped_channel_is_counted(gc, orc, engine):
 
 @pytest.mark.parametrize("flagsync", [0, 1])
 def test_closed_loop_outermost_tap_28(gc, orc, engine, flagsync):
-    """One tap pair at 28 samples (corrn 1, corrd 28), the widest span the loop serves, before and after nav bit
-    sync: 4 channels x 60 periods in two runs against the oracle, as test_closed_loop_9_and_33_taps."""
+    """One tap pair at 28 samples (corrn 1, corrd 28), the widest span whose code table the step itself fills at this
+    rate (24 pieces, all the table holds), before and after nav bit sync: 4 channels x 60 periods in two runs against
+    the oracle, as test_closed_loop_9_and_33_taps."""
     _random_states_case(gc, orc, engine, 2800 + flagsync, 2, 0.0, F_SF, (1, 28, 28), flagsync, nper=60, nch=4,
                         chunks=(37, 23))
 
 
 @pytest.mark.parametrize("flagsync", [0, 1])
 @pytest.mark.parametrize("span", [29, 30])
-def test_closed_loop_outermost_tap_29_and_30_are_reported(gc, orc, engine, span, flagsync):
-    """From 29 samples on the loop does not serve the span yet: the run completes and the
-    fetch says so instead of handing out its zero sums."""
+def test_closed_loop_outermost_tap_29_and_30_match_the_oracle(gc, orc, engine, span, flagsync):
+    """From 29 samples on at this rate the code step's pieces do not fit the tail's table and the walker serves
+    (the loop used to report such runs as needing more NCO pieces than the tables hold): the same
+    four channels and eight periods, now against the oracle, and the fetch is clean."""
     n = 16368 * 12
     rng = np.random.default_rng(span + flagsync)
     data = rng.integers(-60, 61, size=(n, 2), dtype=np.int8)
@@ -244,10 +246,18 @@ def test_closed_loop_outermost_tap_29_and_30_are_reported(gc, orc, engine, span,
     engine.ring_push_raw(1, data, n)
     chans = [gc.Channel(p, dtype=2, f_if=0.0, corrn=1, corrd=span, corrp=span) for p in (1, 8, 15, 26)]
     engine.set_channels(chans)
-    engine.trk_set_state([dict(carrfreq=float(rng.uniform(-5000, 5000)), codefreq=c.crate + float(rng.uniform(-3, 3)),
-                               remcode=float(rng.uniform(0, 1)), remcarr=float(rng.uniform(0, 6)), buffloc=100 + 999 * i)
-                          for i, c in enumerate(chans)])
+    states = [dict(carrfreq=float(rng.uniform(-5000, 5000)), codefreq=c.crate + float(rng.uniform(-3, 3)),
+                   remcode=float(rng.uniform(0, 1)), remcarr=float(rng.uniform(0, 6)), buffloc=100 + 999 * i)
+              for i, c in enumerate(chans)]
+    engine.trk_set_state(states)
     engine.loop_set([engine.loop_state(i, 0.0, flagsync=flagsync, synci=3 * i, cnt=2001) for i in range(4)])
-    engine.trk_run_loop(8)
-    with pytest.raises(gc.GnsscorrError, match="more NCO pieces"):
-        engine.trk_fetch_log()
+    ochs = []
+    for i, (c, st) in enumerate(zip(chans, states)):
+        o = orc.make_chan(c.prn, dtype=2, f_if=0.0, corrn=1, corrd=span, corrp=span)
+        o.acq.acqfreq = 0.0
+        o.carrfreq, o.codefreq, o.remcode, o.remcarr = st["carrfreq"], st["codefreq"], st["remcode"], st["remcarr"]
+        o.flagsync, o.synci, o.cnt = flagsync, 3 * i, 2001
+        ochs.append(o)
+    bufflocs = [C.c_uint64(st["buffloc"]) for st in states]
+    _check_against_oracle(orc, engine, ochs, orc.make_ring(data, n, n), bufflocs, 8, 3, tol=1e-12)
+    _check_final(engine, ochs, bufflocs, 3)

@@ -194,10 +194,8 @@ def test_full_scale_samples_33_taps_26msps(gc, orc, engine, dtype):
 ])
 def test_closed_loop_9_and_33_taps(gc, orc, engine, taps, flagsync):
     """Closed loop (trk_run_loop) from random start states, teacher-forced as in tests/test_gpu_loop.py: 8 channels x
-    100 periods in two runs, int8 IQ at 16.368 Msps, outermost taps at 8 and 16 samples.  (trk_run_loop does not serve
-    outermost taps of 29 samples and more yet: the run completes, but its sums come back zero and the fetch reports
-    the run as needing more NCO pieces than the tables hold.  The batched trk_run above
-    serves the whole 64-sample range.  DESIGN.md section 8.)"""
+    100 periods in two runs, int8 IQ at 16.368 Msps, outermost taps at 8 and 16 samples.  (The closed loop at wider
+    spans, up to the 64 samples set_channels accepts, on every front end: tests/test_gpu_tap_spans.py.)"""
     corrn, corrd, corrp = taps
     if corrp % corrd:
         c = gc.Channel(1, corrn=corrn, corrd=corrd, corrp=corrp)
