@@ -51,8 +51,15 @@ SEED1, SEED2 = 31, 32
 ABSENT1 = 20
 
 
-def chan(key, ring, taps, prn, ctype=CTYPE_L1CA):
-    return dict(key=key, ring=ring, taps=taps, prn=prn, ctype=ctype)
+def chan(key, ring, taps, prn, ctype=CTYPE_L1CA, f_sf=None, f_if=None):
+    """A channel of the receiver; f_sf / f_if: its own sample rate and IF (tests/symbol_rate_cases.py: the ring does not
+    know a rate, initsdrch()'s f_sf gives a struct its nsamp), by default the recordings'."""
+    c = dict(key=key, ring=ring, taps=taps, prn=prn, ctype=ctype)
+    if f_sf is not None:
+        c["f_sf"] = f_sf
+    if f_if is not None:
+        c["f_if"] = f_if
+    return c
 
 
 # the mixed receiver: (dtype, corrn) groups of 6, 2, 6 and 3 members; taps A and B share corrn 2 and differ in smax
@@ -93,7 +100,12 @@ WRAP_NPER = 8
 
 
 def ringcfg(c):
-    return IF1 if c["ring"] == 1 else IF2
+    cfg = IF1 if c["ring"] == 1 else IF2
+    return dict(cfg, f_if=c["f_if"]) if "f_if" in c else cfg
+
+
+def rate_of(c):
+    return c.get("f_sf", F_SF)
 
 
 def codes(gc):
@@ -140,7 +152,7 @@ def start_state(c, fpos0, salt=0):
 
 def oracle_chan(orc, c):
     corrn, corrd, corrp = TAPS[c["taps"]]
-    return orc.make_chan(c["prn"], ctype=c["ctype"], f_sf=F_SF, corrn=corrn, corrd=corrd, corrp=corrp, **ringcfg(c), **LOOPB)
+    return orc.make_chan(c["prn"], ctype=c["ctype"], f_sf=rate_of(c), corrn=corrn, corrd=corrd, corrp=corrp, **ringcfg(c), **LOOPB)
 
 
 def set_ini(gc, taps="A"):
@@ -159,7 +171,7 @@ def init_sdr(gc, c, sdr=None, chno=1):
     sdr = gc.SdrCh() if sdr is None else sdr
     cfg = ringcfg(c)
     sys_ = SYS_GLO if c["ctype"] == CTYPE_G1 else SYS_GPS
-    assert gc.lib().initsdrch(chno, sys_, c["prn"], c["ctype"], cfg["dtype"], c["ring"], F_CF, F_SF, cfg["f_if"], C.byref(sdr)) == 0
+    assert gc.lib().initsdrch(chno, sys_, c["prn"], c["ctype"], cfg["dtype"], c["ring"], F_CF, rate_of(c), cfg["f_if"], C.byref(sdr)) == 0
     return sdr
 
 
