@@ -144,6 +144,86 @@ def g1frame_replay(state, log_rows, cnt0=0):
         raise RuntimeError("gnsscorr_g1frame_replay: error %d" % rc)
 
 
+OBSHIST, PTIMING, SYNCQCAP = 80, 68.802, 4096  # GNSSCORR_OBSHIST, GNSSCORR_PTIMING (ms), GNSSCORR_SYNCQCAP
+EINVAL, ESTATE = -1, -3
+
+
+class SyncFrame(C.Structure):
+    """gnsscorr_syncframe_t: what a frame replay found, and the week, for the rows of one push."""
+    _fields_ = [("flagdec", C.c_int), ("week", C.c_int), ("firstsf", C.c_uint64), ("firstsfcnt", C.c_uint64)]
+
+
+class EpochObs(C.Structure):
+    """gnsscorr_epochobs_t: one satellite's row of an observation epoch."""
+    _fields_ = ([("ch", C.c_int), ("week", C.c_int)] + [(n, C.c_double) for n in ("tow", "P", "L", "D", "S")] +
+                [("sampref", C.c_uint64)])
+
+
+class Sync:
+    """gnsscorr_sync_t: observation epochs from the rows of several channels (ref src/sdrsync.c:49-121; DESIGN.md
+    section 3.8).  Host code only.  A refused call raises GnsscorrError with the code in `.code`."""
+
+    def __init__(self, nch, outms):
+        L = self._L = lib()
+        L.gnsscorr_sync_last_error.restype = C.c_char_p
+        L.gnsscorr_sync_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int]
+        L.gnsscorr_sync_destroy.argtypes = [C.c_void_p]
+        L.gnsscorr_sync_destroy.restype = None
+        L.gnsscorr_sync_channel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]
+        L.gnsscorr_sync_push.argtypes = [C.c_void_p, C.c_int, C.POINTER(SyncFrame), C.c_void_p, C.c_int]
+        L.gnsscorr_sync_detach.argtypes = [C.c_void_p, C.c_int]
+        L.gnsscorr_sync_flush.argtypes = [C.c_void_p]
+        L.gnsscorr_sync_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        self.h = C.c_void_p()
+        self.nch = int(nch)
+        self._ok(L.gnsscorr_sync_create(C.byref(self.h), int(nch), int(outms)))
+
+    def _ok(self, rc):
+        if rc < 0:
+            e = GnsscorrError(self._L.gnsscorr_sync_last_error().decode())
+            e.code = rc
+            raise e
+        return rc
+
+    def close(self):
+        if self.h:
+            self._L.gnsscorr_sync_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def channel(self, ch, nsamp, ctime, ti):
+        self._ok(self._L.gnsscorr_sync_channel(self.h, int(ch), int(nsamp), float(ctime), float(ti)))
+
+    def push(self, ch, frame, rows):
+        """rows: numpy array of ObsRow (obs_replay's); frame: SyncFrame, or a frame state plus week as (state, week)."""
+        if isinstance(frame, tuple):
+            frame = SyncFrame(int(frame[0].flagdec), int(frame[1]), int(frame[0].firstsf), int(frame[0].firstsfcnt))
+        rows = np.ascontiguousarray(rows, dtype=np.dtype(ObsRow))
+        self._ok(self._L.gnsscorr_sync_push(self.h, int(ch), C.byref(frame), rows.ctypes.data, int(rows.shape[0])))
+
+    def detach(self, ch):
+        self._ok(self._L.gnsscorr_sync_detach(self.h, int(ch)))
+
+    def flush(self):
+        self._ok(self._L.gnsscorr_sync_flush(self.h))
+
+    def fetch(self, max_out=None):
+        """The rows of the epochs made so far (numpy array of EpochObs); all of them without max_out."""
+        parts = []
+        while True:
+            want = 1024 if max_out is None else max_out - sum(len(p) for p in parts)
+            out = np.zeros(max(want, 1), dtype=np.dtype(EpochObs))
+            k = self._ok(self._L.gnsscorr_sync_fetch(self.h, out.ctypes.data, want))
+            parts.append(out[:k])
+            if k < want or max_out is not None:
+                return np.concatenate(parts)
+
+
 class SbasFrameState(C.Structure):
     """gnsscorr_sbasframe_t: frame synchronisation of SBAS L1 on the decided symbols (ref src/sdrnav.c:40-82)."""
     _fields_ = ([("fbits", C.c_int * 1512)] +
@@ -284,7 +364,9 @@ EXPORTS_GNSSCORR = [
     "gnsscorr_lock_run", "gnsscorr_rx_lock_set", "gnsscorr_rx_lock_status",
     "gnsscorr_acq_set_coherent", "gnsscorr_acq_get_coherent", "gnsscorr_g1frame_replay",
     "gnsscorr_acq_set_bitedge", "gnsscorr_acq_get_bitedge", "gnsscorr_acq_fetch_edge",
-    "gnsscorr_acq_set_refine", "gnsscorr_acq_get_refine", "gnsscorr_acq_fetch_fine"]
+    "gnsscorr_acq_set_refine", "gnsscorr_acq_get_refine", "gnsscorr_acq_fetch_fine",
+    "gnsscorr_sync_create", "gnsscorr_sync_destroy", "gnsscorr_sync_channel", "gnsscorr_sync_push",
+    "gnsscorr_sync_detach", "gnsscorr_sync_flush", "gnsscorr_sync_fetch", "gnsscorr_sync_last_error"]
 EXPORTS_SDR = [
     "sdracquisition", "checkacquisition", "sdrtracking", "cumsumcorr", "clearcumsumcorr", "pll", "dll",
     "readinifile", "chk_initvalue", "initacqstruct", "inittrkprmstruct", "inittrkstruct", "initsdrch",

@@ -38,6 +38,7 @@ extern "C" {
 #define GNSSCORR_EINVAL    -1   /* bad argument / unsupported shape          */
 #define GNSSCORR_EHIP      -2   /* HIP runtime error (no device, OOM, ...)   */
 #define GNSSCORR_ESTATE    -3   /* call order (no ring, no channels, ...)    */
+#define GNSSCORR_ENOMEM    -4   /* host memory (gnsscorr_sync_* only)        */
 
 #define GNSSCORR_MAXTAPS   33   /* 1 + 2*corrn, corrn <= 16                  */
 #define GNSSCORR_MAXFREQ   1024 /* Doppler bins per channel                  */
@@ -328,6 +329,78 @@ typedef struct {
 /* log[nper]: one channel's rows; cnt0: sdrthread's cnt at log[0].  The caller zero-initialises st; a log may be replayed
  * in pieces of any length.  Returns 0, or GNSSCORR_EINVAL (a NULL pointer, nper < 0) with nothing touched. */
 int  gnsscorr_g1frame_replay(gnsscorr_g1frame_t *st, const gnsscorr_trklog_t *log, int nper, uint64_t cnt0);
+
+/* ---- observation epochs: pseudorange, carrier phase and Doppler across channels ----
+ * The body of syncthread()'s loop (ref src/sdrsync.c:49-121, with interp1() and uint64todouble(), ref
+ * src/sdrcmn.c:505-565) replayed over the rows gnsscorr_obs_replay gives each channel: one pseudorange per satellite at
+ * a common epoch, carrier phase and Doppler interpolated to that epoch.  The RINEX / RTCM writers behind it are not part
+ * of this library.  Plain host code without the device: csrc/sdr_sync.c links alone.  DESIGN.md section 3.8 states the
+ * semantics in full, the reference's quirks that are kept (lettered (a)..(e) there) and the one conversion C leaves
+ * undefined.
+ *
+ * History.  Per channel tow, codei, cntout, remcout, L, D hold GNSSCORR_OBSHIST elements, zero at creation, and S0 = 0.
+ * Consuming a row shifts them by one and puts the row at [0], as setobsdata() does (ref src/sdrtrk.c:163-173); a row with
+ * snr != 0 also sets S0 = S.
+ *
+ * Order of consumption.  The reference polls while the channel threads append rows in real time; here pushed rows wait
+ * in a queue per channel, and the waiting row with the smallest codei (the lower channel on ties) is consumed as soon as
+ * every attached channel has a row waiting.  gnsscorr_sync_channel attaches a channel; gnsscorr_sync_detach drops its
+ * queue, zeroes its history and its eligibility and stops it from holding the others back; it attaches again with its
+ * next push.  Detach a channel that leaves TRACK or that will deliver nothing for a while.  So what is consumed, and
+ * every epoch, depends neither on how a channel's rows are cut into pushes nor on the order of pushes between channels.
+ * The frame fields given with a push belong to every row of that push.  codei values are sample indices of one stream
+ * origin and rate, as in the reference, whose two Stereo rings run at one rate.
+ *
+ * Poll.  After every consumed row one pass of ref src/sdrsync.c:53-121 runs over the histories.  Eligible are the
+ * channels whose last consumed row had flagdec && week != 0 && cntout >= firstsfcnt, in channel order.  reftow is the
+ * smallest tow[0] among them, starting from 3600*24*7.  No epoch when none is eligible, when reftow equals the pass
+ * before's, when (int)(reftow*1000) % outms != 0, or when reftow*1000 lies below the range of int.  Otherwise ind (per
+ * position in the eligible list, kept from pass to pass, set where a history element lies within 1e-4 of reftow), the
+ * nearest channel refi (smallest codei[ind]), diffcnt = cntout[ind] - firstsfcnt of refi, sampref = firstsf +
+ * nsamp*(-PTIMING/(1000*ctime) + diffcnt) -- the product converted to int64 towards zero (0x8000000000000000 where it
+ * does not fit) and added modulo 2^64 --, sampbase = codei[79] - 10*nsamp of refi, samprefd = (double)(sampref -
+ * sampbase); and per eligible channel
+ *     P = CLIGHT * ti * ((double)(codei[ind] - sampref) - remcout[ind])        metres, CLIGHT = 299792458
+ *     L, D = interp1 over (double)(codei[k] - sampbase), k = 0..79, at samprefd
+ *     S = S0, week = the channel's, tow = reftow + PTIMING/1000.
+ * All differences of sample counts are uint64 and wrap. */
+#define GNSSCORR_OBSHIST   80           /* ref OBSINTERPN, src/sdr.h:197 */
+#define GNSSCORR_PTIMING   68.802       /* ref PTIMING, ms, src/sdr.h:196 */
+#define GNSSCORR_SYNCQCAP  4096         /* rows that may wait per channel */
+typedef struct gnsscorr_sync gnsscorr_sync_t;
+/* what the frame decoder found (gnsscorr_frame_t / gnsscorr_sbasframe_t / gnsscorr_g1frame_t: flagdec, firstsf,
+ * firstsfcnt) and the week: from the caller's ephemeris decoder for L1 C/A, from the state for G1 and SBAS */
+typedef struct {
+    int    flagdec, week;
+    uint64_t firstsf, firstsfcnt;
+} gnsscorr_syncframe_t;
+typedef struct {
+    int    ch, week;
+    double tow, P, L, D, S;
+    uint64_t sampref;                   /* the sample the epoch's pseudoranges count from */
+} gnsscorr_epochobs_t;
+
+/* outms: ref sdrini.outms, the epoch grid in ms.  GNSSCORR_EINVAL: NULL, nch <= 0, outms <= 0.  Any of the calls may
+ * answer GNSSCORR_ENOMEM; rows that wait then stay where they are.  One thread at a time per gnsscorr_sync_t. */
+int  gnsscorr_sync_create(gnsscorr_sync_t **st, int nch, int outms);
+void gnsscorr_sync_destroy(gnsscorr_sync_t *st);
+/* The constants of channel ch (ref sdrch_t.nsamp / .ctime / .ti); empties and attaches it.  GNSSCORR_EINVAL, nothing
+ * touched: NULL, ch out of range, a value that is not positive and finite, a ti that differs from another channel's. */
+int  gnsscorr_sync_channel(gnsscorr_sync_t *st, int ch, int nsamp, double ctime, double ti);
+/* rows[n] of channel ch, in order, with the frame fields that hold for them; consumes what can be consumed.
+ * GNSSCORR_EINVAL, nothing touched: NULL, ch out of range, a push before gnsscorr_sync_channel, a row whose codei is
+ * not above the channel's last (since it was last emptied).  GNSSCORR_ESTATE, nothing touched: more than
+ * GNSSCORR_SYNCQCAP rows would wait; the message names the channel that holds the others back. */
+int  gnsscorr_sync_push(gnsscorr_sync_t *st, int ch, const gnsscorr_syncframe_t *fr, const gnsscorr_obsrow_t *rows, int n);
+int  gnsscorr_sync_detach(gnsscorr_sync_t *st, int ch);
+/* consumes every row that waits, in the same order, whether or not every attached channel has one */
+int  gnsscorr_sync_flush(gnsscorr_sync_t *st);
+/* Takes up to max_out rows of the epochs made so far, oldest first, and returns their number: an epoch is nsat
+ * consecutive rows with one tow, in channel order. */
+int  gnsscorr_sync_fetch(gnsscorr_sync_t *st, gnsscorr_epochobs_t *out, int max_out);
+/* the message of the last failed gnsscorr_sync_* call of this thread (csrc/sdr_sync.c links without the rest of the
+ * library, so it keeps its own) */
+const char *gnsscorr_sync_last_error(void);
 
 /* ---- FEC: sliding-window Viterbi decoder (K = 7, rate 1/2) on the device ------
  * predecodefec() for CTYPE_L1SBAS (ref src/sdrnav.c:302-318): init_viterbi27(.., 0), update_blk over win/2 symbol
