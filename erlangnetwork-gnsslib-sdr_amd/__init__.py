@@ -235,6 +235,124 @@ class SbasFrameState(C.Structure):
 V27POLYA, V27POLYB = 0x6d, 0x4f              # libfec's fec.h (ref src/sdrinit.c:502)
 
 
+class RxNavCh(C.Structure):
+    """gnsscorr_rxnavch_t: the constants of one channel of an RxNav."""
+    _fields_ = ([(n, C.c_int) for n in ("ctype", "nsamp", "loopms", "pad")] +
+                [(n, C.c_double) for n in ("f_sf", "f_if", "foffset", "ctime", "ti", "oldremcode")])
+
+
+class RxNavStat(C.Structure):
+    """gnsscorr_rxnavstat_t: one channel's nav state in short."""
+    _fields_ = ([(n, C.c_int) for n in ("ctype", "attached", "flagsyncf", "flagdec", "polarity", "week", "id", "resets")] +
+                [(n, C.c_uint64) for n in ("cnt", "firstsf", "firstsfcnt", "nrows")] +
+                [("firstsftow", C.c_double), ("tow", C.c_double)])
+
+
+class RxNav:
+    """gnsscorr_rxnav_t: frames, observables and epochs behind every step.  RxNav(channels, outms,
+    hold_steps) creates one from RxNavCh's (or dicts of their fields); Engine.rx_nav() wraps the context's, which the
+    context owns.  A refused call raises GnsscorrError with the code in `.code`."""
+
+    def __init__(self, channels=None, outms=10, hold_steps=0, handle=None):
+        L = self._L = lib()
+        _bind_rxnav(L)
+        self.own = handle is None
+        if handle is not None:
+            self.h = C.c_void_p(handle)
+            return
+        chans = [c if isinstance(c, RxNavCh) else RxNavCh(**c) for c in channels]
+        arr = (RxNavCh * max(len(chans), 1))(*chans)
+        self.h = C.c_void_p()
+        self._ok(L.gnsscorr_rxnav_create(C.byref(self.h), len(chans), arr, int(outms), int(hold_steps)))
+
+    def _ok(self, rc):
+        if rc < 0:
+            e = GnsscorrError(self._L.gnsscorr_rxnav_last_error().decode())
+            e.code = rc
+            raise e
+        return rc
+
+    def close(self):
+        if self.h and self.own:
+            self._L.gnsscorr_rxnav_destroy(self.h)
+        self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def week(self, ch, week):
+        self._ok(self._L.gnsscorr_rxnav_week(self.h, int(ch), int(week)))
+
+    def feed(self, log, II0, ndone, cnt_after, tracking, ctx=None):
+        """log [nch][stride] of TrkLog, II0 [nch][stride], ndone / cnt_after / tracking [nch]; ctx: an Engine, for SBAS."""
+        log = np.ascontiguousarray(log, dtype=np.dtype(TrkLog))
+        II0 = np.ascontiguousarray(II0, dtype=np.float64)
+        if log.ndim != 2 or II0.shape != log.shape:
+            raise ValueError("RxNav.feed: log and II0 are [nch][stride]")
+        ndone = np.ascontiguousarray(ndone, dtype=np.int32)
+        cnt_after = np.ascontiguousarray(cnt_after, dtype=np.uint64)
+        tracking = np.ascontiguousarray(tracking, dtype=np.int32)
+        if not ndone.shape == cnt_after.shape == tracking.shape == (log.shape[0],):
+            raise ValueError("RxNav.feed: ndone, cnt_after and tracking are [nch]")
+        self._ok(self._L.gnsscorr_rxnav_feed(self.h, ctx.h if ctx is not None else None, log.ctypes.data, II0.ctypes.data,
+                                             int(log.shape[1]), ndone.ctypes.data, cnt_after.ctypes.data, tracking.ctypes.data))
+
+    def flush(self):
+        self._ok(self._L.gnsscorr_rxnav_flush(self.h))
+
+    def fetch(self, max_out=None):
+        """The rows of the epochs made so far (numpy array of EpochObs); all of them without max_out."""
+        parts = []
+        while True:
+            want = 1024 if max_out is None else max_out - sum(len(p) for p in parts)
+            out = np.zeros(max(want, 1), dtype=np.dtype(EpochObs))
+            k = self._ok(self._L.gnsscorr_rxnav_fetch(self.h, out.ctypes.data, want))
+            parts.append(out[:k])
+            if k < want or max_out is not None:
+                return np.concatenate(parts)
+
+    def status(self, nch):
+        """numpy array [nch] of RxNavStat."""
+        st = np.zeros(nch, dtype=np.dtype(RxNavStat))
+        self._ok(self._L.gnsscorr_rxnav_status(self.h, st.ctypes.data))
+        return st
+
+    def frame(self, ch, ctype):
+        """A copy of channel ch's frame state: FrameState, SbasFrameState or G1FrameState by `ctype`."""
+        st = {CTYPE_L1CA: FrameState, CTYPE_L1SBAS: SbasFrameState, CTYPE_G1: G1FrameState}[ctype]()
+        self._ok(self._L.gnsscorr_rxnav_frame(self.h, int(ch), C.byref(st), C.sizeof(st)))
+        return st
+
+    def rows(self, ch, max_rows=4096):
+        """The rows of observables the last feed made for channel ch (numpy array of ObsRow)."""
+        out = np.zeros(max(max_rows, 1), dtype=np.dtype(ObsRow))
+        k = self._ok(self._L.gnsscorr_rxnav_rows(self.h, int(ch), out.ctypes.data, int(max_rows)))
+        return out[:k]
+
+
+def _bind_rxnav(L):
+    L.gnsscorr_rxnav_last_error.restype = C.c_char_p
+    L.gnsscorr_rxnav_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(RxNavCh), C.c_int, C.c_int]
+    L.gnsscorr_rxnav_destroy.argtypes = [C.c_void_p]
+    L.gnsscorr_rxnav_destroy.restype = None
+    L.gnsscorr_rxnav_week.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.gnsscorr_rxnav_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gnsscorr_rxnav_flush.argtypes = [C.c_void_p]
+    L.gnsscorr_rxnav_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.gnsscorr_rxnav_status.argtypes = [C.c_void_p, C.c_void_p]
+    L.gnsscorr_rxnav_frame.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+    L.gnsscorr_rxnav_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.gnsscorr_rx_nav_start.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.gnsscorr_rx_nav_step.argtypes = [C.c_void_p, C.c_int]
+    L.gnsscorr_rx_nav_stop.argtypes = [C.c_void_p]
+    L.gnsscorr_rx_nav.argtypes = [C.c_void_p]
+    L.gnsscorr_rx_nav.restype = C.c_void_p
+    L.gnsscorr_trk_fetch_prompt.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+
+
 class SpecParams(C.Structure):
     """gnsscorr_spec_t: one IF-monitor configuration (include/gnsscorr.h)."""
     _fields_ = [("ftype", C.c_int), ("nfft", C.c_int), ("nloop", C.c_int), ("n", C.c_int), ("f_sf", C.c_double)]
@@ -366,7 +484,11 @@ EXPORTS_GNSSCORR = [
     "gnsscorr_acq_set_bitedge", "gnsscorr_acq_get_bitedge", "gnsscorr_acq_fetch_edge",
     "gnsscorr_acq_set_refine", "gnsscorr_acq_get_refine", "gnsscorr_acq_fetch_fine",
     "gnsscorr_sync_create", "gnsscorr_sync_destroy", "gnsscorr_sync_channel", "gnsscorr_sync_push",
-    "gnsscorr_sync_detach", "gnsscorr_sync_flush", "gnsscorr_sync_fetch", "gnsscorr_sync_last_error"]
+    "gnsscorr_sync_detach", "gnsscorr_sync_flush", "gnsscorr_sync_fetch", "gnsscorr_sync_last_error",
+    "gnsscorr_trk_fetch_prompt", "gnsscorr_rxnav_create", "gnsscorr_rxnav_destroy", "gnsscorr_rxnav_week",
+    "gnsscorr_rxnav_feed", "gnsscorr_rxnav_flush", "gnsscorr_rxnav_fetch", "gnsscorr_rxnav_status", "gnsscorr_rxnav_frame",
+    "gnsscorr_rxnav_rows", "gnsscorr_rxnav_last_error", "gnsscorr_rx_nav_start", "gnsscorr_rx_nav_step", "gnsscorr_rx_nav",
+    "gnsscorr_rx_nav_stop"]
 EXPORTS_SDR = [
     "sdracquisition", "checkacquisition", "sdrtracking", "cumsumcorr", "clearcumsumcorr", "pll", "dll",
     "readinifile", "chk_initvalue", "initacqstruct", "inittrkprmstruct", "inittrkstruct", "initsdrch",
@@ -437,6 +559,8 @@ def lib():
         L.gnsscorr_acq_set_refine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.gnsscorr_acq_get_refine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.gnsscorr_acq_fetch_fine.argtypes = [C.c_void_p, C.POINTER(AcqFine), C.c_void_p]
+    if hasattr(L, "gnsscorr_rxnav_create"):         # (likewise: tools/rx_nav_time.py)
+        _bind_rxnav(L)
     L.gnsscorr_fft16k.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     L.gnsscorr_pspec.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.gnsscorr_timing_enable.argtypes = [C.c_void_p, C.c_int]
@@ -901,6 +1025,34 @@ class Engine:
                      acq=dict(acqcodei=a.acq.acqcodei, freqi=a.acq.freqi, acqfreq=a.acq.acqfreq, cn0=a.acq.cn0,
                               peakr=a.acq.peakr, flagacq=a.acq.flagacq, iters=a.acq.iters, buffloc=a.acq.buffloc))
                 for a in arr]
+
+    # -- frames, observables and epochs behind every step
+    def rx_nav_start(self, outms, hold_steps=0):
+        """Switches the nav driver on (gnsscorr_rx_nav_start): with the schedule, before its first step."""
+        _check(self._L.gnsscorr_rx_nav_start(self.h, int(outms), int(hold_steps)))
+
+    def rx_nav_step(self, max_periods):
+        """rx_step (schedule on) or trk_run_loop (off) of max_periods, and the feed of its rows; the plain fetches stay
+        valid behind it."""
+        _check(self._L.gnsscorr_rx_nav_step(self.h, int(max_periods)))
+        self._nepoch = max_periods
+
+    def rx_nav(self):
+        """The context's RxNav (week, fetch, flush, status, frame, rows), or None while the driver is off.  The context
+        owns it: the wrapper is good until the driver is switched off."""
+        h = self._L.gnsscorr_rx_nav(self.h)
+        return RxNav(handle=h) if h else None
+
+    def rx_nav_stop(self):
+        _check(self._L.gnsscorr_rx_nav_stop(self.h))
+
+    def trk_fetch_prompt(self):
+        """(II0, QQ0) [nch][nperiod]: tap 0 of trk_fetch's II and QQ, gathered on the device."""
+        nch, ne = len(self.channels), self._nepoch
+        II0 = np.empty((nch, ne), np.float64)
+        QQ0 = np.empty((nch, ne), np.float64)
+        _check(self._L.gnsscorr_trk_fetch_prompt(self.h, II0.ctypes.data, QQ0.ctypes.data))
+        return II0, QQ0
 
     # -- lock monitor
     def rx_lock_set(self, prm=None, ch0=0, nch=None):

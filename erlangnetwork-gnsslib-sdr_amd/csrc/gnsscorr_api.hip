@@ -82,6 +82,7 @@ static void drop_channel_buffers(gnsscorr_ctx *ctx)
     ctx->out = GcTrkOut();
     ctx->loop = GcLoop();
     ctx->rx = GcRx();
+    ctx->nav.off();
     ctx->lock_pending = false;
 }
 
@@ -148,7 +149,10 @@ extern "C" int gnsscorr_ring_create(gnsscorr_ctx *ctx, int ftype, int dtype, uin
         GC_TRY(gc_quiesce(ctx, true));
         // a running schedule holds sample positions of the old stream (next_try, acq_wrpos, the TRACK channels'
         // buffloc): it is off until the next gnsscorr_rx_start
-        if (referenced) ctx->rx.on = false;
+        if (referenced) {
+            ctx->rx.on = false;
+            ctx->nav.off();             // its counters and frame positions are the old stream's, too
+        }
         r->own.reset();
         r->mem = nullptr;
         if (devmem) {

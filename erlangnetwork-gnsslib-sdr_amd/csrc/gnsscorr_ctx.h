@@ -194,7 +194,8 @@ struct GcTrkOut {
     GcDevBuf<double> dcorrI, dcorrQ;               // [unit][ntap]
     GcDevBuf<double> dsumI, dsumQ;                 // [nch][ntap] batch sums
     GcDevBuf<int> nsamp;                           // [unit]
-    GcDevBuf<int> dnco_overflow;                   // units whose NCO tables overflowed since the last fetch
+    GcDevBuf<double> dprompt;                      // [2][unit] tap 0 of dcorrQ, dcorrI (gnsscorr_trk_fetch_prompt; made on first use)
+    GcDevBuf<int> dnco_overflow;                  // units whose NCO tables overflowed since the last fetch
     GcDevBuf<int> dring_viol;                      // planned periods outside what the ring holds, since the last fetch
     size_t units = 0;                              // (channel, period) units the per-unit buffers are sized for
     int last_nepoch = 0;                           // periods per channel of the last completed run (0: none yet)
@@ -270,6 +271,27 @@ struct GcRx {
     GcDevBuf<gnsscorr_lock_t> dlock;               // [nch] the detector's state
     GcPinBuf<int> lock_list;                       // mapped: [nch] the channels of a launch (host writes, kernel reads)
     GcPinBuf<unsigned> lock_lost;                  // mapped: [nch] 1: the launch declared the channel lost (kernel writes)
+};
+
+// Frames, observables and epochs behind every step (gnsscorr_rx_nav_*, gnsscorr_rx.hip): the core object of
+// csrc/sdr_rxnav.c, owned, and the host arrays a step's fetches land in.  off() is what gnsscorr_set_channels,
+// gnsscorr_rx_start and a gnsscorr_ring_create under the channels do to it.
+struct GcNav {
+    gnsscorr_rxnav_t *nv = nullptr;                // nullptr: the driver is off
+    std::vector<gnsscorr_trklog_t> log;            // [nch][max_periods]
+    std::vector<double> ii0;                       // [nch][max_periods]
+    std::vector<int> ndone, tracking;              // [nch]
+    std::vector<uint64_t> cnt;                     // [nch]
+    std::vector<gnsscorr_rxstat_t> st;             // [nch] (schedule on)
+    GcNav() = default;
+    GcNav(const GcNav &) = delete;
+    GcNav &operator=(const GcNav &) = delete;
+    ~GcNav() { off(); }
+    void off()
+    {
+        if (nv) gnsscorr_rxnav_destroy(nv);
+        nv = nullptr;
+    }
 };
 
 // The FFT twiddle tables (gc_acq_twiddles, gnsscorr_acq.hip), made once per context on first use: they depend on nothing
@@ -418,6 +440,7 @@ struct gnsscorr_ctx {
     GcRx rx;
     GcEvent ev_lock;                               // end of the last lock monitor launch (made on first use)
     bool lock_pending = false;                     // ev_lock is recorded and rx.lock_lost not read yet
+    GcNav nav;
 
     // FFT tables (context lifetime); acquisition and the IF monitor (replaced whole per channel set, acquisition also
     // per coherent setting)

@@ -26,6 +26,7 @@ extern "C" int gnsscorr_rx_start(gnsscorr_ctx *ctx, int retry_ms)
         if (!ctx->loop.isset[i])
             return gc_fail(GNSSCORR_ESTATE, "rx_start: channel %d has no loop constants (gnsscorr_loop_set)", i);
     GcRx &rx = ctx->rx;
+    ctx->nav.off();             // the nav driver's states belong to the schedule that ends here (gnsscorr_rx_nav_start comes after)
     rx.retry_ms = retry_ms > 0 ? retry_ms : GC_ACQSLEEP;
     gnsscorr_rxstat_t z;
     memset(&z, 0, sizeof(z));
@@ -141,4 +142,92 @@ extern "C" int gnsscorr_rx_status(gnsscorr_ctx *ctx, gnsscorr_rxstat_t *st)
         st[i].cnt = cnt[i];
     }
     return GNSSCORR_OK;
+}
+
+// ---- frames, observables and epochs behind every step: the context's driver of csrc/sdr_rxnav.c -----------------------
+static int nav_fail(int rc) { return gc_fail(rc, "%s", gnsscorr_rxnav_last_error()); }
+
+extern "C" int gnsscorr_rx_nav_start(gnsscorr_ctx *ctx, int outms, int hold_steps)
+{
+    if (!ctx) return gc_fail(GNSSCORR_EINVAL, "null context");
+    if (!ctx->nch) return gc_fail(GNSSCORR_ESTATE, "rx_nav_start: no channels set");
+    const int nch = ctx->nch;
+    for (int i = 0; i < nch; i++)
+        if (!ctx->loop.isset[i])
+            return gc_fail(GNSSCORR_ESTATE, "rx_nav_start: channel %d has no loop constants (gnsscorr_loop_set)", i);
+    if (ctx->rx.on)
+        for (int i = 0; i < nch; i++)
+            if (ctx->rx.st[i].attempts > 0)
+                return gc_fail(GNSSCORR_ESTATE, "rx_nav_start: the schedule has stepped (channel %d was searched): start the "
+                               "nav driver before the first gnsscorr_rx_step", i);
+    // the constants: the channel table, loopms of the loop constants, the remcode the first row's oldremcode is
+    std::vector<gnsscorr_loop_t> lp(nch);
+    std::vector<gnsscorr_trkstate_t> ts(nch);
+    GC_TRY(gnsscorr_loop_get(ctx, 0, nch, lp.data()));
+    GC_TRY(gnsscorr_trk_get_state(ctx, 0, nch, ts.data()));
+    std::vector<gnsscorr_rxnavch_t> ch(nch);
+    for (int i = 0; i < nch; i++) {
+        const gnsscorr_chan_t &c = ctx->hdesc[i];
+        memset(&ch[i], 0, sizeof(ch[i]));
+        ch[i].ctype = c.ctype;
+        ch[i].nsamp = c.nsamp;
+        ch[i].loopms = lp[i].loopms;
+        ch[i].f_sf = c.f_sf;
+        ch[i].f_if = c.f_if;
+        ch[i].foffset = c.foffset;
+        ch[i].ctime = c.ctime;
+        ch[i].ti = c.ti;
+        ch[i].oldremcode = ts[i].remcode;
+    }
+    gnsscorr_rxnav_t *nv = nullptr;
+    const int rc = gnsscorr_rxnav_create(&nv, nch, ch.data(), outms, hold_steps);
+    if (rc) return nav_fail(rc);            // (a driver that was running stays)
+    ctx->nav.off();
+    ctx->nav.nv = nv;
+    return GNSSCORR_OK;
+}
+
+extern "C" int gnsscorr_rx_nav_stop(gnsscorr_ctx *ctx)
+{
+    if (!ctx) return gc_fail(GNSSCORR_EINVAL, "null context");
+    if (!ctx->nav.nv) return gc_fail(GNSSCORR_ESTATE, "rx_nav_stop: no gnsscorr_rx_nav_start yet");
+    ctx->nav.off();
+    return GNSSCORR_OK;
+}
+
+extern "C" gnsscorr_rxnav_t *gnsscorr_rx_nav(gnsscorr_ctx *ctx) { return ctx ? ctx->nav.nv : nullptr; }
+
+extern "C" int gnsscorr_rx_nav_step(gnsscorr_ctx *ctx, int max_periods)
+{
+    if (!ctx || !ctx->nav.nv) return gc_fail(GNSSCORR_ESTATE, "rx_nav_step: no gnsscorr_rx_nav_start yet");
+    GC_TRY(ctx->rx.on ? gnsscorr_rx_step(ctx, max_periods) : gnsscorr_trk_run_loop(ctx, max_periods));
+    GcNav &nav = ctx->nav;
+    const int nch = ctx->nch;
+    const size_t units = (size_t)nch * max_periods;
+    if (nav.log.size() < units) {
+        nav.log.resize(units);
+        nav.ii0.resize(units);
+    }
+    nav.ndone.resize(nch);
+    nav.tracking.resize(nch);
+    nav.cnt.resize(nch);
+    // the step's rows and the prompt column; sdrthread's cnt and the state behind the step
+    GC_TRY(gnsscorr_trk_fetch_log(ctx, nav.log.data(), nav.ndone.data()));
+    GC_TRY(gnsscorr_trk_fetch_prompt(ctx, nav.ii0.data(), nullptr));
+    if (ctx->rx.on) {
+        nav.st.resize(nch);
+        GC_TRY(gnsscorr_rx_status(ctx, nav.st.data()));
+        for (int i = 0; i < nch; i++) {
+            nav.cnt[i] = nav.st[i].cnt;
+            nav.tracking[i] = nav.st[i].state == GNSSCORR_CH_TRACK;
+        }
+    } else {
+        GC_HIP(hipMemcpy2DAsync(nav.cnt.data(), sizeof(uint64_t), (const char *)ctx->loop.dloop.p + offsetof(gnsscorr_loop_t, cnt),
+                                sizeof(gnsscorr_loop_t), sizeof(uint64_t), nch, hipMemcpyDeviceToHost, ctx->stream));
+        GC_HIP(hipStreamSynchronize(ctx->stream));
+        for (int i = 0; i < nch; i++) nav.tracking[i] = 1;
+    }
+    const int rc = gnsscorr_rxnav_feed(nav.nv, ctx, nav.log.data(), nav.ii0.data(), max_periods, nav.ndone.data(), nav.cnt.data(),
+                                       nav.tracking.data());
+    return rc ? nav_fail(rc) : GNSSCORR_OK;
 }

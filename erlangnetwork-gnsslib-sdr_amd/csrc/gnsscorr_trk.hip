@@ -1079,6 +1079,39 @@ extern "C" int gnsscorr_trk_fetch(gnsscorr_ctx *ctx, double *trkII, double *trkQ
     return gc_nco_check(ctx);
 }
 
+// Tap 0 of every (channel, period) unit of both result arrays, gathered into out[2][units]: [0] from corrQ (trk.II),
+// [1] from corrI (trk.QQ).  One thread per unit; the reads are ntap doubles apart, the writes contiguous.
+__global__ void trk_prompt_kernel(const double *__restrict__ corrQ, const double *__restrict__ corrI, double *__restrict__ out,
+                                  unsigned units, int ntap)
+{
+    const unsigned u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= units) return;
+    out[u] = corrQ[(size_t)u * ntap];
+    out[(size_t)units + u] = corrI[(size_t)u * ntap];
+}
+
+extern "C" int gnsscorr_trk_fetch_prompt(gnsscorr_ctx *ctx, double *II0, double *QQ0)
+{
+    if (!ctx || !ctx->out.last_nepoch) return gc_fail(GNSSCORR_ESTATE, "trk_fetch_prompt: no completed trk_run");
+    GC_HIP(hipSetDevice(ctx->device));
+    GcTrkOut &o = ctx->out;
+    const size_t units = (size_t)ctx->nch * o.last_nepoch;
+    if (units > 0x7fffffffu) return gc_fail(GNSSCORR_EINVAL, "trk_fetch_prompt: %zu (channel, period) units", units);
+    if (II0 || QQ0) {
+        GC_RESERVE(ctx, o.dprompt, 2 * units);
+        {
+            GcTimed t(ctx, "trk_prompt");
+            hipLaunchKernelGGL(trk_prompt_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, ctx->stream, o.dcorrQ.p, o.dcorrI.p,
+                               o.dprompt.p, (unsigned)units, ctx->ntap);
+            GC_HIP(hipGetLastError());
+        }
+        if (II0) GC_HIP(hipMemcpyAsync(II0, o.dprompt.p, sizeof(double) * units, hipMemcpyDeviceToHost, ctx->stream));
+        if (QQ0) GC_HIP(hipMemcpyAsync(QQ0, o.dprompt.p + units, sizeof(double) * units, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    GC_HIP(hipStreamSynchronize(ctx->stream));
+    return gc_nco_check(ctx);
+}
+
 extern "C" int gnsscorr_trk_fetch_sums(gnsscorr_ctx *ctx, double *sumI, double *sumQ)
 {
     if (!ctx || !ctx->out.last_nepoch) return gc_fail(GNSSCORR_ESTATE, "trk_fetch_sums: no completed trk_run");

@@ -466,6 +466,11 @@ int  gnsscorr_trk_run_loop(gnsscorr_ctx *ctx, int nperiod);
 int  gnsscorr_trk_loop_lapped(gnsscorr_ctx *ctx, int *nlapped);
 /* log[nch][nperiod] of the last gnsscorr_trk_run_loop; ndone[nch] = periods run */
 int  gnsscorr_trk_fetch_log(gnsscorr_ctx *ctx, gnsscorr_trklog_t *log, int *ndone);
+/* Tap 0 of gnsscorr_trk_fetch's II / QQ alone, [nch][nperiod] of the last run of either kind, bit for bit; either
+ * pointer may be NULL.  The prompt column is gathered on the device (kernel "trk_prompt") into a compact buffer, so the
+ * call moves nch*nperiod doubles per array where gnsscorr_trk_fetch moves nch*nperiod*ntap.  Synchronises the stream
+ * and reports what gnsscorr_trk_fetch reports. */
+int  gnsscorr_trk_fetch_prompt(gnsscorr_ctx *ctx, double *II0, double *QQ0);
 
 /* ---- acquisition: parallel code phase search --------------------------------
  * For every channel: up to `intg` iterations of pcorrelator() (ref
@@ -678,6 +683,84 @@ int  gnsscorr_rx_lock_set(gnsscorr_ctx *ctx, int ch0, int nch, const gnsscorr_lo
  * has sent each channel back to SEARCH.  Either may be NULL.  Synchronises. */
 int  gnsscorr_rx_lock_status(gnsscorr_ctx *ctx, gnsscorr_lock_t *st, int *losses);
 
+/* ---- frames, observables and epochs behind every step ------------------------
+ * The loop a caller writes around a step's rows, as a library object: one nav state per
+ * channel -- the frame state of its code type and the observables' state -- plus one gnsscorr_sync_t.  Plain host code
+ * (csrc/sdr_rxnav.c): the only device work is what gnsscorr_sbasframe_replay does for an SBAS channel.  DESIGN.md
+ * section 3.9 states the rules of a feed; in short, after validation, per channel in ascending order:
+ *   1. reset: the frame state, the running part of the observables' state (constants kept, oldremcode 0) and nrows are
+ *      zeroed and the channel is detached from the epochs when tracking[k] == 0, or when ndone[k] > 0, cnt0 == 0 and the
+ *      channel was fed rows since its last reset (a hand-over restarted cnt); resets counts those that zeroed something;
+ *   2. with ndone[k] > 0 and tracking[k], the rows go through the frame replay of the code type (gnsscorr_frame_replay,
+ *      gnsscorr_g1frame_replay, gnsscorr_sbasframe_replay without time aid) with cnt0 = cnt_after[k] - ndone[k];
+ *   3. if the frame state has flagdec: flagsyncf, polarity, firstsftow and firstsfcnt go into the observables' state;
+ *   4. gnsscorr_obs_replay over the same rows, II0 and cnt0;
+ *   5. gnsscorr_sync_push of those rows with {flagdec, week, firstsf, firstsfcnt}: the state's week for G1 and SBAS, what
+ *      gnsscorr_rxnav_week last set for L1 C/A (the caller's ephemeris decoder; 0: none yet).  No rows, no push;
+ *   6. a channel that is attached, has tracking[k], and had ndone[k] == 0 in hold_steps consecutive feeds in each of
+ *      which some other channel had rows, is detached; its nav state stays.  hold_steps 0: never.
+ * Nothing is flushed.  The one dependence on how a channel's rows are cut into feeds is the documented loop's: the row
+ * in which the observables learn of the frame is the first row of the piece that raised flagdec, not the row that
+ * decided the frame's last symbol (an inverted frame's half cycle enters the carrier phase there).  Everything else is
+ * independent of the cut.
+ * Errors.  GNSSCORR_EINVAL, nothing touched: a NULL pointer, ndone[k] < 0, stride < ndone[k], cnt_after[k] < ndone[k],
+ * an SBAS channel with ctx == NULL.  GNSSCORR_ESTATE, nothing touched, the channel named: ndone[k] > 0, the channel was
+ * fed before, and cnt0 is neither 0 nor the cnt_after[k] of the feed before (a step's rows were skipped).  An error of a
+ * replay or of the push (GNSSCORR_ESTATE for a full queue) is returned with the channel named; the channels before it
+ * have been fed.  One thread at a time per object. */
+typedef struct {                    /* constants of one channel */
+    int    ctype, nsamp, loopms, pad;               /* CTYPE_L1CA (1) / CTYPE_L1SBAS (27) / CTYPE_G1 (20) */
+    double f_sf, f_if, foffset, ctime, ti;
+    double oldremcode;              /* gnsscorr_obs_t.oldremcode for the channel's very first row; 0 after every reset */
+} gnsscorr_rxnavch_t;
+typedef struct {
+    int      ctype, attached;       /* attached: has pushed rows to the epochs since it was last detached */
+    int      flagsyncf, flagdec, polarity, week, id;   /* id: sfid / string number / message type decoded last */
+    int      resets;                /* how often a non-empty state of this channel was zeroed */
+    uint64_t cnt;                   /* sdrthread's cnt behind the last feed */
+    uint64_t firstsf, firstsfcnt, nrows;            /* nrows: rows of observables since the last reset */
+    double   firstsftow, tow;       /* tow of the last row of observables, 0: none yet */
+} gnsscorr_rxnavstat_t;
+typedef struct gnsscorr_rxnav gnsscorr_rxnav_t;
+
+/* GNSSCORR_EINVAL: NULL, nch <= 0, hold_steps < 0, a code type outside the three.  What gnsscorr_sync_create and
+ * gnsscorr_sync_channel refuse is passed through with their message (outms <= 0, a ti that differs between channels).
+ * Every channel starts declared and detached. */
+int  gnsscorr_rxnav_create(gnsscorr_rxnav_t **nv, int nch, const gnsscorr_rxnavch_t *ch, int outms, int hold_steps);
+void gnsscorr_rxnav_destroy(gnsscorr_rxnav_t *nv);
+int  gnsscorr_rxnav_week(gnsscorr_rxnav_t *nv, int ch, int week);       /* L1 C/A: the caller's decoder; 0: none yet */
+/* log[nch][stride] and II0[nch][stride]: a step's gnsscorr_trk_fetch_log rows and tap 0 of II (gnsscorr_trk_fetch_prompt);
+ * ndone[k]: the rows of channel k that count; cnt_after[k]: sdrthread's cnt of channel k behind the step; tracking[k]:
+ * channel k is in TRACK behind the step.  ctx may be NULL when no channel is CTYPE_L1SBAS. */
+int  gnsscorr_rxnav_feed(gnsscorr_rxnav_t *nv, gnsscorr_ctx *ctx, const gnsscorr_trklog_t *log, const double *II0,
+                         int stride, const int *ndone, const uint64_t *cnt_after, const int *tracking);
+int  gnsscorr_rxnav_flush(gnsscorr_rxnav_t *nv);                                        /* gnsscorr_sync_flush */
+int  gnsscorr_rxnav_fetch(gnsscorr_rxnav_t *nv, gnsscorr_epochobs_t *out, int max_out); /* gnsscorr_sync_fetch */
+int  gnsscorr_rxnav_status(gnsscorr_rxnav_t *nv, gnsscorr_rxnavstat_t *st);             /* st[nch] */
+int  gnsscorr_rxnav_frame(gnsscorr_rxnav_t *nv, int ch, void *state, size_t size);      /* copy of the channel's
+                                    gnsscorr_frame_t / _sbasframe_t / _g1frame_t; size must be that struct's */
+int  gnsscorr_rxnav_rows(gnsscorr_rxnav_t *nv, int ch, gnsscorr_obsrow_t *rows, int max_rows);  /* rows the last feed made;
+                                    returns their number, at most max_rows */
+/* the message of the last failed gnsscorr_rxnav_* call of this thread (csrc/sdr_rxnav.c links without the device code,
+ * so it keeps its own; the context's calls below copy it into gnsscorr_last_error) */
+const char *gnsscorr_rxnav_last_error(void);
+
+/* The context's driver: a step of the receiver and the feed of its rows in one call.
+ * gnsscorr_rx_nav_start needs the channels and gnsscorr_loop_set for every one of them (GNSSCORR_ESTATE otherwise).  It
+ * fills gnsscorr_rxnavch_t from the channel table and the loop constants and takes oldremcode from the tracking state.
+ * With the schedule on (gnsscorr_rx_start done) it must come before the first step: GNSSCORR_ESTATE if any channel has
+ * attempts > 0.  Without the schedule every channel counts as tracking.  Calling it again starts over.
+ * gnsscorr_rx_nav_step runs gnsscorr_rx_step(max_periods) with the schedule on, gnsscorr_trk_run_loop(max_periods)
+ * without (their error comes first), fetches the log, ndone, the prompt column and the counters (gnsscorr_rxstat_t.cnt
+ * and state == GNSSCORR_CH_TRACK, or gnsscorr_loop_t.cnt) and feeds the core.  The plain fetches stay valid behind it.
+ * gnsscorr_set_channels, a later gnsscorr_rx_start and a gnsscorr_ring_create of a ring that a channel reads switch the
+ * driver off: its calls return GNSSCORR_ESTATE (gnsscorr_rx_nav: NULL) until the next start.  gnsscorr_destroy frees it. */
+int  gnsscorr_rx_nav_start(gnsscorr_ctx *ctx, int outms, int hold_steps);
+int  gnsscorr_rx_nav_step(gnsscorr_ctx *ctx, int max_periods);
+gnsscorr_rxnav_t *gnsscorr_rx_nav(gnsscorr_ctx *ctx);   /* the context's core object, NULL when off: week, fetch, flush,
+                                                           status, frame, rows go through it */
+int  gnsscorr_rx_nav_stop(gnsscorr_ctx *ctx);
+
 /* ---- op-level device entry points (used by the per-call symbols and tests) --
  * 16384-point complex FFT batches on device memory, unnormalised, sign -1
  * forward / +1 backward; in/out are device pointers to float2[batch][16384] */
@@ -723,7 +806,7 @@ int  gnsscorr_spec_fetch(gnsscorr_ctx *ctx, double *s, size_t s_cap,
 /* per-kernel launch timing: enable, run, then read the accumulated HIP-event
  * time of the named kernel ("trk_corr", "trk_plan", "trk_spec", "trk_expand",
  * "trk_finish", "acq_fwd", "acq_corr", "acq_code", "acq_final", "spec_psd",
- * "spec_sum", "spec_hist", "fec_viterbi27", "rx_lock").
+ * "spec_sum", "spec_hist", "fec_viterbi27", "rx_lock", "trk_prompt").
  * on = 1: every kernel; on = 2: only the two correlator kernels ("trk_corr",
  * "acq_corr"), leaving the planner and tables streams free of events; 0: off */
 int  gnsscorr_timing_enable(gnsscorr_ctx *ctx, int on);
