@@ -870,6 +870,14 @@ class Engine:
         _check(self._L.gnsscorr_trk_fetch_sums(self.h, sI.ctypes.data, sQ.ctypes.data))
         return sI, sQ
 
+    def trk_devptrs(self):
+        """(II, QQ) device addresses of the last run's result arrays as integers, laid out as trk_fetch returns them
+        (gnsscorr_trk_devptrs): work queued on the context's stream after this call sees every trk_run issued before
+        it.  The addresses change when a longer batch makes the arrays grow."""
+        II, QQ = C.c_void_p(), C.c_void_p()
+        _check(self._L.gnsscorr_trk_devptrs(self.h, C.byref(II), C.byref(QQ)))
+        return int(II.value or 0), int(QQ.value or 0)
+
     # -- closed loop
     def loop_state(self, ch, acqfreq, dllb=(5.0, 1.0), pllb=(30.0, 10.0), fllb=(200.0, 50.0), flagsync=0, synci=0,
                    cnt=0, loop=None):

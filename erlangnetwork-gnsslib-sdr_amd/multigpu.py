@@ -73,7 +73,12 @@ class ShardedEngine:
     RCCL broadcast) and read on the engine's stream (the correlator kernels).  When those are two streams -- an
     Engine created with its own -- feed() first makes torch's stream wait for the engine's last launch (the slot it
     is about to overwrite may still be read by the batch in flight) and wait() makes the engine's stream wait for
-    the broadcast before the write position moves.  With the engine on torch's current stream both are no-ops.
+    the broadcast before the write position moves.  With the engine created on the torch stream that is current
+    (Engine(device, torch.cuda.Stream().cuda_stream) under torch.cuda.stream(...)) both waits are on that one stream and
+    order nothing it does not order already: stream order alone carries a caller's write to the correlator
+    (tests/test_gpu_device_seam.py).  torch's *default* stream is not such a stream: its handle is null, which
+    gnsscorr_create answers with a private stream, so an Engine made from torch.cuda.current_stream().cuda_stream
+    outside any stream context is one with its own stream, and the two waits are what orders it.
     """
 
     SLOTS = 4

@@ -48,6 +48,55 @@ def test_stereo_packed_bytes_feed_both_rings(gc, orc, engine):
     assert np.array_equal(engine.ring_read(2, start, ringlen, 2), e2[start:])
 
 
+def _stereo(orc, seed, n):
+    """n packed NSL Stereo bytes, every byte value among them, and the oracle's expansion for front end 1 and 2."""
+    rng = np.random.default_rng(seed)
+    packed = rng.integers(0, 256, size=n, dtype=np.uint8)
+    packed[:256] = np.arange(256, dtype=np.uint8)
+    e1 = np.zeros(n, np.int8)
+    e2 = np.zeros((n, 2), np.int8)
+    orc.lib().orc_stereo_exp(packed.ctypes.data, n, 1, e1.ctypes.data)
+    orc.lib().orc_stereo_exp(packed.ctypes.data, n, 2, e2.ctypes.data)
+    return packed, e1, e2
+
+
+@pytest.mark.parametrize("ftype", [1, 2])
+def test_stereo_packed_bytes_feed_the_one_ring_that_exists(gc, orc, engine, ftype):
+    """Only front end 1's ring, or only front end 2's: the unpack kernel's branch for the ring that is not there."""
+    n, ringlen = 100001, 1 << 16                             # the stream laps the ring
+    packed, e1, e2 = _stereo(orc, 20 + ftype, n)
+    engine.ring_create(ftype, ftype, ringlen)                # front end 1 is real (dtype 1), front end 2 IQ (dtype 2)
+    engine.ring_push_packed(gc.FMT_STEREO, packed[:60001], 60001)
+    engine.ring_push_packed(gc.FMT_STEREO, packed[60001:], n - 60001)
+    assert engine.ring_wrpos(ftype) == n and engine.ring_wrpos(3 - ftype) == 0
+    assert engine.ring_devptr(3 - ftype) is None
+    want = (e1, e2)[ftype - 1]
+    assert np.array_equal(engine.ring_read(ftype, n - ringlen, ringlen, ftype), want[n - ringlen:])
+
+
+def test_stereo_packed_bytes_into_rings_of_different_lengths_and_positions(gc, orc, engine):
+    """Rings of 2^15 and 3 * 2^14 samples, ring 2 advanced beforehand by a raw push so that the two write positions
+    differ: 100 001 packed bytes lap both rings at different places.  A push may not exceed a ring (include/gnsscorr.h),
+    so the bytes go in four pushes of at most 2^15; the two-push split is refused, with nothing written."""
+    n, len1, len2, ahead = 100001, 1 << 15, 3 << 14, 1237
+    packed, e1, e2 = _stereo(orc, 23, n)
+    raw = np.random.default_rng(24).integers(-128, 128, size=(ahead, 2), dtype=np.int8)
+    engine.ring_create(1, 1, len1)
+    engine.ring_create(2, 2, len2)
+    engine.ring_push_raw(2, raw, ahead)
+    with pytest.raises(gc.GnsscorrError, match="larger than the ring"):
+        engine.ring_push_packed(gc.FMT_STEREO, packed[:50001], 50001)
+    assert engine.ring_wrpos(1) == 0 and engine.ring_wrpos(2) == ahead
+    cuts = [0, 30001, 50001, 80001, n]
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        engine.ring_push_packed(gc.FMT_STEREO, packed[a:b], b - a)
+    assert engine.ring_wrpos(1) == n and engine.ring_wrpos(2) == ahead + n
+    assert n % len1 != (ahead + n) % len2 and n // len1 == 3 and (ahead + n) // len2 == 2
+    assert np.array_equal(engine.ring_read(1, n - len1, len1, 1), e1[n - len1:])
+    s2 = np.concatenate([raw, e2])
+    assert np.array_equal(engine.ring_read(2, ahead + n - len2, len2, 2), s2[ahead + n - len2:])
+
+
 def test_rtlsdr_unsigned_bytes(gc, orc, engine):
     rng = np.random.default_rng(3)
     n = 200000
