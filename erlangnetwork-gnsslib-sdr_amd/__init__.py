@@ -483,6 +483,7 @@ EXPORTS_GNSSCORR = [
     "gnsscorr_acq_set_coherent", "gnsscorr_acq_get_coherent", "gnsscorr_g1frame_replay",
     "gnsscorr_acq_set_bitedge", "gnsscorr_acq_get_bitedge", "gnsscorr_acq_fetch_edge",
     "gnsscorr_acq_set_refine", "gnsscorr_acq_get_refine", "gnsscorr_acq_fetch_fine",
+    "gnsscorr_acq_set_codedoppler", "gnsscorr_acq_get_codedoppler", "gnsscorr_acq_fetch_shifts",
     "gnsscorr_sync_create", "gnsscorr_sync_destroy", "gnsscorr_sync_channel", "gnsscorr_sync_push",
     "gnsscorr_sync_detach", "gnsscorr_sync_flush", "gnsscorr_sync_fetch", "gnsscorr_sync_last_error",
     "gnsscorr_trk_fetch_prompt", "gnsscorr_rxnav_create", "gnsscorr_rxnav_destroy", "gnsscorr_rxnav_week",
@@ -559,6 +560,10 @@ def lib():
         L.gnsscorr_acq_set_refine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.gnsscorr_acq_get_refine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.gnsscorr_acq_fetch_fine.argtypes = [C.c_void_p, C.POINTER(AcqFine), C.c_void_p]
+    if hasattr(L, "gnsscorr_acq_set_codedoppler"):  # (likewise: tools/acq_slip_time.py)
+        L.gnsscorr_acq_set_codedoppler.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
+        L.gnsscorr_acq_get_codedoppler.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
+        L.gnsscorr_acq_fetch_shifts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
     if hasattr(L, "gnsscorr_rxnav_create"):         # (likewise: tools/rx_nav_time.py)
         _bind_rxnav(L)
     L.gnsscorr_fft16k.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
@@ -696,12 +701,13 @@ class Channel:
     ncoh: code periods the search integrates coherently per group (gnsscorr_acq_set_coherent; 1: the reference's
     integration); estep: step of the bit-edge hypotheses of a group (gnsscorr_acq_set_bitedge; 0: none, otherwise
     1 .. ncoh-1 with ncoh >= 2); nref: code periods an acquired channel's carrier frequency is refined over
-    (gnsscorr_acq_set_refine; 0: none, otherwise 2 .. min(intg, MAXCOH)); Engine.set_channels applies them, in that
-    order."""
+    (gnsscorr_acq_set_refine; 0: none, otherwise 2 .. min(intg, MAXCOH)); cdop: the search compensates code Doppler
+    across its groups with the channel's own f_cf (gnsscorr_acq_set_codedoppler; for G1 the slot's carrier);
+    Engine.set_channels applies them, in that order."""
 
     def __init__(self, prn, ctype=CTYPE_L1CA, dtype=DTYPEIQ, ftype=FTYPE1, f_cf=1575.42e6,
                  f_sf=16.368e6, f_if=0.0, corrn=2, corrd=3, corrp=3, hband=7000, step=200, intg=10,
-                 fend=FEND_FILE, ppmerr=0, ncoh=1, estep=0, nref=0):
+                 fend=FEND_FILE, ppmerr=0, ncoh=1, estep=0, nref=0, cdop=False):
         self.prn, self.ctype, self.dtype, self.ftype = prn, ctype, dtype, ftype
         self.code, self.crate = gencode(prn, ctype)
         self.clen = len(self.code)
@@ -722,6 +728,7 @@ class Channel:
         self.ncoh = ncoh
         self.estep = estep
         self.nref = nref
+        self.cdop = bool(cdop)
         self.nfreq = 2 * (hband // step) + 1
         self.nfft = 2 * self.nsamp
         self.freq = np.array([f_if + ((i - (self.nfreq - 1) // 2) * float(step)) + self.foffset
@@ -835,6 +842,8 @@ class Engine:
         nref = [getattr(c, "nref", 0) for c in channels]
         if any(k != 0 for k in nref):
             self.acq_set_refine(nref)
+        if any(getattr(c, "cdop", False) for c in channels):
+            self.acq_set_codedoppler([c.f_cf if getattr(c, "cdop", False) else 0.0 for c in channels])
 
     # -- tracking
     def trk_set_state(self, states, ch0=0):
@@ -968,6 +977,28 @@ class Engine:
         arr = (C.c_int * len(self.channels))()
         _check(self._L.gnsscorr_acq_fetch_edge(self.h, arr))
         return list(arr)
+
+    def acq_set_codedoppler(self, f_cf, ch0=0):
+        """RF carrier (Hz) channels ch0 .. ch0+len(f_cf)-1 compensate code Doppler with across the groups of a search
+        (gnsscorr_acq_set_codedoppler; 0: off, what set_channels resets to before it applies Channel.cdop)."""
+        arr = (C.c_double * len(f_cf))(*[float(v) for v in f_cf])
+        _check(self._L.gnsscorr_acq_set_codedoppler(self.h, ch0, len(f_cf), arr))
+
+    def acq_get_codedoppler(self, ch0=0, nch=None):
+        nch = len(self.channels) - ch0 if nch is None else nch
+        arr = (C.c_double * nch)()
+        _check(self._L.gnsscorr_acq_get_codedoppler(self.h, ch0, nch, arr))
+        return list(arr)
+
+    def acq_fetch_shifts(self, ch):
+        """(s, back) of channel ch as the last prepare built them (gnsscorr_acq_fetch_shifts): s an int32 array
+        [nfreq][groups], back the samples the search looks back beyond (intg + 1) * nsamp."""
+        c = self.channels[ch]
+        ncoh = self.acq_get_coherent(ch, 1)[0]
+        s = np.zeros((c.nfreq, c.intg // ncoh), np.int32)
+        back = C.c_int(0)
+        _check(self._L.gnsscorr_acq_fetch_shifts(self.h, ch, s.ctypes.data, C.byref(back)))
+        return s, back.value
 
     def acq_set_refine(self, nref, ch0=0):
         """Code periods channels ch0 .. ch0+len(nref)-1 refine their carrier frequency over after a search acquires

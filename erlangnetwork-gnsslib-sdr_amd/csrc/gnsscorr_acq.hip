@@ -44,6 +44,12 @@
 // line search over their squares (acq_fine); both hand-overs then start from that frequency.  No result row is
 // written, and a search without such a channel queues none of the three.
 //
+// Code-Doppler compensation (gnsscorr_acq_set_codedoppler): a channel with a carrier f_cf reads group g
+// of bin b s(b, g) samples later (gc_acq_shifts: a host table per grid), so that every group of a bin sees the code at
+// the lag it had in group 0; the search is the search at write position wrpos - back, which is what the kernels are
+// handed.  acq_fwd's CDOP instances add the table entry to the window origin; nothing behind them knows.  Not included:
+// drift inside a group, a codefreq preset at hand-over, the drop-in sdracquisition(), the sharded engine.
+//
 // Every run works on a channel list (gnsscorr_acq_run_subset; gnsscorr_acq_run is the list 0..nch-1): the
 // per-channel kernels take their channel from a compacted device list, acq_fwd its frequency grid from the
 // list of grids that have a listed channel, so grid sizes follow the list.  Everything a channel owns (code
@@ -55,6 +61,7 @@
 // row, an X slot, a code spectrum, a prompt pair and the sections of d_list and arrive are (GcAcqDims, GcAcq:
 // gnsscorr_ctx.h).  A search is gc_acq_run_list: its plan, the upload, the search's queue and the refinement's.
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdlib>
 #include <type_traits>
@@ -254,16 +261,19 @@ __global__ void acq_nco_kernel(const GcChan *__restrict__ chan, const int *__res
 // some listed grid integrates coherently, and the sample functor adds the group's ncoh windows (for a grid with ncoh = 1
 // that is the same integer, so the same float); the instance without COH is free of the loop.  EDGE (with COH): some
 // listed grid has bit-edge hypotheses; slot = iteration * H + hypothesis index, and the functor subtracts the windows
-// j >= h of hypothesis h > 0 (a grid without hypotheses has H = 1, h = 0: the same integers again).
-template <bool COH, bool EDGE = false>
+// j >= h of hypothesis h > 0 (a grid without hypotheses has H = 1, h = 0: the same integers again).  CDOP (with COH;
+// DESIGN.md 3.2f): some channel compensates code Doppler; the window of (bin, iteration) starts shifts[grid][bin][iteration]
+// samples later, one scalar load (a grid without compensation has a row of zeros: the same samples again).
+template <bool COH, bool EDGE = false, bool CDOP = false>
 __global__ __launch_bounds__(GC_FFT_THREADS) void acq_fwd_kernel(
     const GcChan *__restrict__ chan, const int *__restrict__ grid_chan, const int *__restrict__ glist,
     const GcAcqCar *__restrict__ car,
     const uint64_t *__restrict__ grid_wrpos, const float2 *__restrict__ tw16k,
     const float2 *__restrict__ tw32p, const float2 *__restrict__ tw64p1, const float2 *__restrict__ tw64p3,
-    float2 *__restrict__ X, int maxfreq, int maxslot, int L)
+    float2 *__restrict__ X, int maxfreq, int maxslot, int L, const int32_t *__restrict__ shifts, int maxintg)
 {
     static_assert(COH || !EDGE, "hypotheses belong to coherent groups");
+    static_assert(COH || !CDOP, "compensated grids run the coherent instances");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2 *lds = reinterpret_cast<float2 *>(smem);
     const GcAcqDims d = {maxfreq, 0, maxslot, L};       // (scalar arguments, as acq_corr; no rows here)
@@ -280,7 +290,9 @@ __global__ __launch_bounds__(GC_FFT_THREADS) void acq_fwd_kernel(
     if (bin >= c.nfreq || it >= (COH ? acq_groups(c) : c.intg)) return;
     const int n = c.nsamp, n2 = 2 * n, dtype = c.dtype;
     // window of iteration `it`: ref src/sdracq.c:24-32; a group starts ncoh windows after the one before
-    const uint64_t buffloc = grid_wrpos[g] - (uint64_t)(c.intg + 1) * n + (uint64_t)it * ((uint64_t)ncoh * n);
+    uint64_t buffloc = grid_wrpos[g] - (uint64_t)(c.intg + 1) * n + (uint64_t)it * ((uint64_t)ncoh * n);
+    // (grid_wrpos is `back` short of the write position, and s(b, 0) = 0: the sum stays inside what the ring holds)
+    if constexpr (CDOP) buffloc += (uint64_t)(int64_t)shifts[((size_t)g * maxfreq + bin) * maxintg + it];
     const uint64_t base = buffloc % c.ringlen;
     const gc_gptr_i8 ring = (gc_gptr_i8)c.ring;
     const uint64_t ringlen = c.ringlen;
@@ -1077,12 +1089,39 @@ int gc_acq_twiddles(gnsscorr_ctx *ctx)
     const int lds = GC_FFT_LDS + 256, fwd = lds + GC_ACQ_CARLDS, corr = GC_ACQ_CORR_LDS;
     const struct { const void *kernel; int lds; } dyn[] = {
         {(const void *)acq_fwd_kernel<false>, fwd}, {(const void *)acq_fwd_kernel<true>, fwd},
-        {(const void *)acq_fwd_kernel<true, true>, fwd}, {(const void *)acq_code_kernel, lds},
+        {(const void *)acq_fwd_kernel<true, true>, fwd}, {(const void *)acq_fwd_kernel<true, false, true>, fwd},
+        {(const void *)acq_fwd_kernel<true, true, true>, fwd}, {(const void *)acq_code_kernel, lds},
         {(const void *)acq_corr_kernel<512>, corr}, {(const void *)acq_corr_kernel<1024>, corr},
         {(const void *)acq_corr_kernel<512, true>, corr}, {(const void *)acq_corr64_kernel, corr},
         {(const void *)fft16k_kernel<-1>, lds}, {(const void *)fft16k_kernel<+1>, lds}, {(const void *)pspec_kernel, lds}};
     for (const auto &k : dyn) GC_HIP(hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds));
     f.ready = true;
+    return GNSSCORR_OK;
+}
+
+// Code-Doppler compensation (include/gnsscorr.h): group g of bin b starts s(b, g) samples later, in fp64
+// and in this order:  dop = (freq[b] - f_if) - foffset;  x = (dop / f_cf) * (double)(g * ncoh * n);  s = -rint(x).
+int gc_acq_shifts(const gnsscorr_ctx *ctx, int ch, std::vector<int32_t> &s, int *back)
+{
+    const GcChan &c = ctx->hchan[ch];
+    const gnsscorr_chan_t &d = ctx->hdesc[ch];
+    const int G = acq_groups(c);
+    const double f_cf = ctx->hfcf[ch];
+    s.assign((size_t)c.nfreq * G, 0);
+    *back = 0;
+    if (f_cf == 0.0) return GNSSCORR_OK;
+    for (int b = 0; b < c.nfreq; b++)
+        for (int g = 0; g < G; g++) {
+            const double dop = (d.freq[b] - d.f_if) - d.foffset;
+            const double x = (dop / f_cf) * (double)((int64_t)g * c.ncoh * c.nsamp);
+            const double r = rint(x);           // round-half-even
+            if (!(fabs(r) <= (double)c.nsamp))
+                return gc_fail(GNSSCORR_EINVAL, "acquisition: channel %d: code-Doppler shift of %.0f samples in group %d of bin %d "
+                               "(more than a code period of %d)", ch, -r, g, b, c.nsamp);
+            const int32_t v = -(int32_t)r;
+            s[(size_t)b * G + g] = v;
+            if (v > *back) *back = v;
+        }
     return GNSSCORR_OK;
 }
 
@@ -1113,6 +1152,24 @@ static int acq_prepare(gnsscorr_ctx *ctx)
     if (d.L == 2 * GC_L && d.maxslot != d.maxintg)
         return gc_fail(GNSSCORR_ESTATE, "acquisition: bit-edge hypotheses on the 65536-point transform");
     w->dims = d;
+    // the grids' shift tables, from each grid's first channel (the channels of a grid agree on them: assign_acq_grids)
+    w->cdop = false;
+    w->shifts.assign((size_t)w->ngrid * d.maxfreq * d.maxintg, 0);
+    w->back.assign(w->ngrid, 0);
+    for (int g = 0; g < w->ngrid; g++) {
+        const int ch = w->grid_chan[g], G = acq_groups(ctx->hchan[ch]);
+        std::vector<int32_t> s;
+        GC_TRY(gc_acq_shifts(ctx, ch, s, &w->back[g]));
+        for (int b = 0; b < ctx->hchan[ch].nfreq; b++)
+            std::copy(s.begin() + (size_t)b * G, s.begin() + (size_t)(b + 1) * G,
+                      w->shifts.begin() + ((size_t)g * d.maxfreq + b) * d.maxintg);
+        w->cdop = w->cdop || ctx->hfcf[ch] != 0.0;
+    }
+    if (w->cdop) {
+        GC_RESERVE(ctx, w->d_shifts, w->shifts.size());
+        GC_HIP(hipMemcpyAsync(w->d_shifts, w->shifts.data(), sizeof(int32_t) * w->shifts.size(), hipMemcpyHostToDevice,
+                              ctx->stream));
+    }
     GC_RESERVE(ctx, w->X, (size_t)w->ngrid * d.maxslot * d.maxfreq * d.L);
     GC_RESERVE(ctx, w->rows, (size_t)nch * d.maxintg * d.maxfreq);
     GC_RESERVE(ctx, w->arrive, w->arrive_ints());
@@ -1193,6 +1250,7 @@ int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chl
     std::vector<int> part;          // acq_corr's order of the list: the nplain channels without bit-edge hypotheses,
     int nplain = 0;                 // then those with (a launch each)
     bool coh = false, edge = false; // a listed grid integrates coherently / has bit-edge hypotheses
+    bool cdop = false;              // a listed grid compensates code Doppler
     int maxref = 0;                 // the longest refine span of a listed channel, 0: no refinement
     // The caller's list and wp_ring into the plan above.  A valid list prepares the channel set and fences the rings'
     // transfers: the grids are acq_prepare's, a ring's write position the fence's.
@@ -1222,15 +1280,18 @@ int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chl
             const GcChan &c = ctx->hchan[w->grid_chan[g]];
             const int ft = ctx->hdesc[w->grid_chan[g]].ftype;
             const uint64_t wp = wp_ring[ft - 1] ? wp_ring[ft - 1] : ctx->ring[ft - 1].wrpos;
-            if (wp < (uint64_t)(c.intg + 1) * c.nsamp)
+            // a compensated grid's search is the search at wp - back
+            const uint64_t look = (uint64_t)(c.intg + 1) * c.nsamp + (uint64_t)w->back[g];
+            if (wp < look)
                 return gc_fail(GNSSCORR_ESTATE, "acq_run: ring %d holds %llu samples, %llu needed", ft,
-                               (unsigned long long)wp, (unsigned long long)((uint64_t)(c.intg + 1) * c.nsamp));
-            if (c.ringlen < (uint64_t)(c.intg + 1) * c.nsamp)
-                return gc_fail(GNSSCORR_EINVAL, "acq_run: ring %d (%llu samples) is shorter than the %d code periods the search looks back",
-                               ft, (unsigned long long)c.ringlen, c.intg + 1);
-            gw[g] = wp;
+                               (unsigned long long)wp, (unsigned long long)look);
+            if (c.ringlen < look)
+                return gc_fail(GNSSCORR_EINVAL, "acq_run: ring %d (%llu samples) is shorter than the %d code periods%s the search looks back",
+                               ft, (unsigned long long)c.ringlen, c.intg + 1, w->back[g] ? " and the code-Doppler shift" : "");
+            gw[g] = wp - (uint64_t)w->back[g];
             coh = coh || c.ncoh > 1;
             edge = edge || c.estep > 0;
+            cdop = cdop || ctx->hfcf[w->grid_chan[g]] != 0.0;
         }
         part = list;
         nplain = (int)(std::stable_partition(part.begin(), part.end(), [&](int ch) { return ctx->hchan[ch].estep <= 0; }) -
@@ -1260,11 +1321,12 @@ int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chl
         const GcAcqDims &d = w->dims;
         {
             GcTimed t(ctx, "acq_fwd");
-            auto fwd = edge ? acq_fwd_kernel<true, true> : coh ? acq_fwd_kernel<true> : acq_fwd_kernel<false>;
+            auto fwd = cdop ? (edge ? acq_fwd_kernel<true, true, true> : acq_fwd_kernel<true, false, true>)
+                     : edge ? acq_fwd_kernel<true, true> : coh ? acq_fwd_kernel<true> : acq_fwd_kernel<false>;
             hipLaunchKernelGGL(fwd, dim3(d.maxfreq, d.maxslot, glist.size()), dim3(GC_FFT_THREADS),
                                GC_FFT_LDS + 256 + GC_ACQ_CARLDS, ctx->stream, ctx->dchan, w->d_grid_chan, w->d_grids(),
                                w->car, w->d_grid_wrpos, f.tw16k, f.tw32p, f.tw64p1, f.tw64p3, w->X, d.maxfreq, d.maxslot,
-                               d.L);
+                               d.L, (const int32_t *)w->d_shifts.p, d.maxintg);
         }
         GC_HIP(hipGetLastError());
         // channels that are not listed: no iterations, a zero result row
@@ -1363,6 +1425,21 @@ extern "C" int gnsscorr_acq_fetch_edge(gnsscorr_ctx *ctx, int *edge)
     if (!ctx || !edge) return gc_fail(GNSSCORR_EINVAL, "acq_fetch_edge: null context or result array");
     if (!ctx->acq.ran) return gc_fail(GNSSCORR_ESTATE, "acq_fetch_edge: no acq_run yet");
     return acq_copy_out(ctx, edge, ctx->acq.edge, sizeof(int) * ctx->nch);
+}
+
+// The channel's copy of its grid's shift table as the last prepare built it, [nfreq][groups], and the grid's look-back
+extern "C" int gnsscorr_acq_fetch_shifts(gnsscorr_ctx *ctx, int ch, int32_t *s, int *back)
+{
+    if (!ctx || !s || !back) return gc_fail(GNSSCORR_EINVAL, "acq_fetch_shifts: null context or result");
+    if (ch < 0 || ch >= ctx->nch) return gc_fail(GNSSCORR_EINVAL, "acq_fetch_shifts: channel %d of %d", ch, ctx->nch);
+    const GcAcq &w = ctx->acq;
+    if (!w.prepared) return gc_fail(GNSSCORR_ESTATE, "acq_fetch_shifts: no search has prepared the channel set yet");
+    const GcChan &c = ctx->hchan[ch];
+    const int G = acq_groups(c);
+    for (int b = 0; b < c.nfreq; b++)
+        for (int g = 0; g < G; g++) s[(size_t)b * G + g] = w.shifts[((size_t)c.grid * w.dims.maxfreq + b) * w.dims.maxintg + g];
+    *back = w.back[c.grid];
+    return GNSSCORR_OK;
 }
 
 // The refinement of the last search (include/gnsscorr.h).  A search that queued none (no listed channel with nref > 0)

@@ -5,6 +5,7 @@
 // (The batched tracker's entry points live in gnsscorr_trk.hip, acquisition's in
 // gnsscorr_acq.hip, the closed loop's in gnsscorr_loop.hip, the reference-named
 // per-call symbols in gnsscorr_compat.hip.)
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -404,8 +405,10 @@ static void retarget_rings(gnsscorr_ctx *ctx)
     upload_channels(ctx);
 }
 
-// acquisition grid = channels that share ring, sample grid, Doppler bins, coherent integration and bit-edge step: they
-// share the forward spectra.  Grids are numbered in the order of their first channel.
+// acquisition grid = channels that share ring, sample grid, Doppler bins, coherent integration, bit-edge step and
+// code-Doppler shifts (the same f_cf, and where it is not 0 the same f_if and foffset: with the rest of the key their
+// shift tables agree, gc_acq_shifts): they share the forward spectra.  Grids are numbered in the order of their first
+// channel.
 static void assign_acq_grids(gnsscorr_ctx *ctx)
 {
     int ngrid = 0;
@@ -417,7 +420,8 @@ static void assign_acq_grids(gnsscorr_ctx *ctx)
             const gnsscorr_chan_t &o = ctx->hdesc[j];
             if (o.ftype == d.ftype && o.dtype == d.dtype && o.nsamp == d.nsamp && o.nfreq == d.nfreq &&
                 o.intg == d.intg && o.ti == d.ti && o.nfft == d.nfft && ctx->hchan[j].ncoh == g.ncoh &&
-                ctx->hchan[j].estep == g.estep &&
+                ctx->hchan[j].estep == g.estep && ctx->hfcf[j] == ctx->hfcf[i] &&
+                (ctx->hfcf[i] == 0.0 || (o.f_if == d.f_if && o.foffset == d.foffset)) &&
                 !memcmp(o.freq, d.freq, sizeof(double) * d.nfreq))
                 g.grid = ctx->hchan[j].grid;
         }
@@ -472,6 +476,7 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
     ctx->hfreq.resize(nch);
     ctx->hcorrp.resize(nch);
     ctx->hchan.assign(nch, GcChan());
+    ctx->hfcf.assign(nch, 0.0);
     std::vector<int8_t> codes((size_t)nch * GC_CODEBLOCK, 0);
     std::vector<double> freqs;
     ctx->ntap = 1 + 2 * ch[0].corrn;
@@ -601,6 +606,28 @@ extern "C" int gnsscorr_acq_get_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, int
 {
     GC_TRY(acq_setting_range("acq_get_bitedge", ctx, ch0, nch, estep));
     for (int i = 0; i < nch; i++) estep[i] = ctx->hchan[ch0 + i].estep;
+    return GNSSCORR_OK;
+}
+
+// Code-Doppler compensation per channel (include/gnsscorr.h); the shift tables are acq_prepare's
+extern "C" int gnsscorr_acq_set_codedoppler(gnsscorr_ctx *ctx, int ch0, int nch, const double *f_cf)
+{
+    if (!ctx || !f_cf || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
+        return gc_fail(GNSSCORR_EINVAL, "acq_set_codedoppler: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    for (int i = 0; i < nch; i++)
+        if (!std::isfinite(f_cf[i]) || f_cf[i] < 0.0)
+            return gc_fail(GNSSCORR_EINVAL, "acq_set_codedoppler: channel %d: f_cf %g (0 for off, or a finite carrier in Hz)",
+                           ch0 + i, f_cf[i]);
+    return acq_change_grids(ctx, [&] {
+        for (int i = 0; i < nch; i++) ctx->hfcf[ch0 + i] = f_cf[i];
+    });
+}
+
+extern "C" int gnsscorr_acq_get_codedoppler(gnsscorr_ctx *ctx, int ch0, int nch, double *f_cf)
+{
+    if (!ctx || !f_cf || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
+        return gc_fail(GNSSCORR_EINVAL, "acq_get_codedoppler: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    for (int i = 0; i < nch; i++) f_cf[i] = ctx->hfcf[ch0 + i];
     return GNSSCORR_OK;
 }
 

@@ -360,6 +360,11 @@ struct GcAcq {
     GcDevBuf<int> iters;        // [ch] iteration limit for acq_corr
     GcDevBuf<gnsscorr_acqres_t> res;    // [ch]
     GcDevBuf<int> edge;         // [ch] bit edge of the deciding group's best row (gnsscorr_acq_fetch_edge), -1: none
+    // code-Doppler compensation (gnsscorr_acq_set_codedoppler): acq_prepare builds the tables on the host
+    bool cdop = false;                  // some channel compensates: acq_fwd runs its CDOP instances, d_shifts is made
+    std::vector<int32_t> shifts;        // [grid][bin][iter] (stride maxfreq, maxintg): s(b, g), zero for a grid without
+    std::vector<int> back;              // [grid] the grid's look-back beyond (intg + 1)*nsamp: max(0, max s)
+    GcDevBuf<int32_t> d_shifts;         // device copy of shifts (cdop only)
     GcDevBuf<double> P;         // one channel's power array (on demand)
     // carrier refinement (gnsscorr_acq_set_refine; made by the first search that lists a channel with nref > 0)
     GcDevBuf<GcAcqCar> fcar;    // [ch] carrier table of the refine span: res[ch].acqfreq over nref*nsamp samples (n 0: none)
@@ -412,6 +417,7 @@ struct gnsscorr_ctx {
     int nch = 0;
     std::vector<GcChan> hchan;
     std::vector<gnsscorr_chan_t> hdesc;         // host copies (code/freq/corrp pointers re-targeted)
+    std::vector<double> hfcf;                   // [nch] gnsscorr_acq_set_codedoppler's f_cf, 0: no compensation
     std::vector<std::vector<short>> hcode;
     std::vector<std::vector<double>> hfreq;
     std::vector<std::vector<int>> hcorrp;
@@ -504,6 +510,9 @@ int gc_loop_take_state(gnsscorr_ctx *ctx);
 // gnsscorr_acq.hip: one search over a channel list; the device hand-over of its acquired channels into the closed loop
 int gc_acq_run_list(gnsscorr_ctx *ctx, const uint64_t wp_ring[2], const int *chlist, int n);
 int gc_acq_handover(gnsscorr_ctx *ctx, bool quiesce);
+// the code-Doppler shifts s(b, g) of a channel ([bin][iter], stride groups) and its look-back `back`; EINVAL for a shift
+// beyond a code period.  A channel without compensation has zeros
+int gc_acq_shifts(const gnsscorr_ctx *ctx, int ch, std::vector<int32_t> &s, int *back);
 // gnsscorr_loop.hip: gnsscorr_trk_run_loop with per-channel write positions
 int gc_trk_run_loop(gnsscorr_ctx *ctx, int nperiod, const uint64_t *wp_ch);
 // gnsscorr_lock.hip: the lock monitor over the periods the last gc_trk_run_loop tracked, for the TRACK channels that have

@@ -16,7 +16,16 @@
 
 #define GC_ACQSLEEP 2000        // ms, ref src/sdr.h (ACQSLEEP)
 
-static uint64_t rx_first_try(const GcChan &c) { return (uint64_t)(c.intg + 1) * (uint64_t)c.nsamp; }   // ref src/sdracq.c:24-26
+// ref src/sdracq.c:24-26; a channel that compensates code Doppler looks `back` samples further (shifts
+// beyond a code period are the search's to refuse)
+static uint64_t rx_first_try(const gnsscorr_ctx *ctx, int ch)
+{
+    const GcChan &c = ctx->hchan[ch];
+    std::vector<int32_t> s;
+    int back = 0;
+    if (ctx->hfcf[ch] != 0.0 && gc_acq_shifts(ctx, ch, s, &back) != GNSSCORR_OK) back = 0;
+    return (uint64_t)(c.intg + 1) * (uint64_t)c.nsamp + (uint64_t)back;
+}
 
 extern "C" int gnsscorr_rx_start(gnsscorr_ctx *ctx, int retry_ms)
 {
@@ -41,7 +50,7 @@ extern "C" int gnsscorr_rx_start(gnsscorr_ctx *ctx, int retry_ms)
     rx.lock_listed.clear();
     for (int i = 0; i < ctx->nch; i++) {
         rx.st[i].state = GNSSCORR_CH_SEARCH;
-        rx.st[i].next_try = rx_first_try(ctx->hchan[i]);
+        rx.st[i].next_try = rx_first_try(ctx, i);
     }
     rx.on = true;
     return GNSSCORR_OK;
@@ -94,7 +103,7 @@ extern "C" int gnsscorr_rx_step(gnsscorr_ctx *ctx, int max_periods)
     std::vector<int> due;
     for (int i = 0; i < nch; i++) {
         const uint64_t wp = wpr[ctx->hdesc[i].ftype - 1];
-        if (rx.st[i].state == GNSSCORR_CH_SEARCH && wp >= rx.st[i].next_try && wp >= rx_first_try(ctx->hchan[i])) due.push_back(i);
+        if (rx.st[i].state == GNSSCORR_CH_SEARCH && wp >= rx.st[i].next_try && wp >= rx_first_try(ctx, i)) due.push_back(i);
     }
     if (!due.empty()) {
         int rc = gc_acq_run_list(ctx, wpr, due.data(), (int)due.size());

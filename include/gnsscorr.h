@@ -556,8 +556,8 @@ int  gnsscorr_acq_get_coherent(gnsscorr_ctx *ctx, int ch0, int nch, int *ncoh);
  * context's: GNSSCORR_EINVAL when any channel of the context has nsamp > 16384.  Also GNSSCORR_EINVAL, nothing touched
  * and the channel named: a range outside the channel table, estep < 0, estep >= 1 on a channel with ncoh < 2, estep >=
  * ncoh.  Quiesces and drops the prepared acquisition work; channels share forward spectra only when their estep agree
- * as well.  Not included: data wipe-off, code-Doppler compensation, a bit-synchronisation preset from the edge; the
- * drop-in sdracquisition() is untouched. */
+ * as well.  Not included: data wipe-off, a bit-synchronisation preset from the edge; the drop-in sdracquisition() is
+ * untouched.  (Code-Doppler compensation: gnsscorr_acq_set_codedoppler, below.) */
 int  gnsscorr_acq_set_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, const int *estep);
 int  gnsscorr_acq_get_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, int *estep);
 /* edge[nch] of the last search (above); synchronises.  GNSSCORR_ESTATE before a search. */
@@ -590,7 +590,7 @@ int  gnsscorr_acq_fetch_edge(gnsscorr_ctx *ctx, int *edge);
  * table, nref < 0, nref == 1, nref > min(intg, GNSSCORR_MAXCOH).  Quiesces and uploads the channel table; the prepared
  * acquisition work and the last search's results stay.  A search without a listed channel with nref > 0 queues exactly
  * the launches it queued before.  Not included: interpolation between the estimator's bins, code-Doppler
- * compensation, data wipe-off; the drop-in sdracquisition() is untouched. */
+ * compensation inside the refine span (rule 3), data wipe-off; the drop-in sdracquisition() is untouched. */
 #define GNSSCORR_FINE_BINS 256
 typedef struct {
     double finefreq, quality;
@@ -601,6 +601,39 @@ int  gnsscorr_acq_get_refine(gnsscorr_ctx *ctx, int ch0, int nch, int *nref);
 /* fine[nch] of the last search; prompt may be NULL, else nch * GNSSCORR_MAXCOH * 2 int32 (I, Q of P_m, zero beyond
  * nref); synchronises.  GNSSCORR_ESTATE before a search. */
 int  gnsscorr_acq_fetch_fine(gnsscorr_ctx *ctx, gnsscorr_acqfine_t *fine, int32_t *prompt);
+/* Code-Doppler compensation across the groups of a search (opt-in per channel).  A satellite at Doppler
+ * fd has its code compressed by fd / f_cf, so over a long span the correlation peak walks from group to group (5 kHz on
+ * L1: 0.65 chip over 200 ms) and the non-coherent sum smears it.  f_cf[i] is the RF carrier of channel ch0 + i in Hz
+ * (the reference's sdrch_t.f_cf); 0 switches the compensation off, is the default and what gnsscorr_set_channels resets
+ * to; gnsscorr_acq_set_coherent and gnsscorr_acq_set_bitedge keep it.  A channel with G = intg / ncoh groups, n = nsamp
+ * and bins freq[b] reads group g of bin b s(b, g) samples later, in fp64 and in exactly this order:
+ *     dop    = (freq[b] - f_if) - foffset
+ *     x      = (dop / f_cf) * (double)((int64_t)g * ncoh * n)
+ *     s(b,g) = -(int32_t)rint(x)               round-half-even; s(b, 0) = 0
+ *     back   = max(0, max over b, g of s(b,g))
+ *     b0     = wrpos - back - (intg + 1) * n
+ * Group g of bin b covers the (ncoh + 1) * n ring samples from b0 + g * ncoh * n + s(b,g) on: a positive Doppler starts
+ * later groups earlier (s < 0), a negative one later, and `back` keeps the last window inside wrpos.  Everything else is
+ * the coherent search's: wipe-off phase 0 at the span's first sample, the windows summed as integers, checkacquisition()'s
+ * rules after every group, the first passing group wins, iters = (g + 1) * ncoh, cn0 over ncoh * ctime, buffloc = b0 +
+ * acqcodei when acquired and b0 + intg * n when not.  The lag is the lag in group 0's frame: tracking starts from the
+ * right samples and no hand-over changes.  The search is, in every respect, the search at write position wrpos - back:
+ * the look-back checks of gnsscorr_acq_run (GNSSCORR_ESTATE / GNSSCORR_EINVAL with the sample counts) and the
+ * receiver schedule's first search add `back`; gnsscorr_acq_power re-runs with the same shifts; bit-edge hypotheses,
+ * the refinement and the 65536-point path combine with it.  With f_cf = 0 for every channel, results, rows and power
+ * arrays are bit for bit those of a search without this call.
+ * The tables are built on the host when a search prepares the channel set (at most nfreq * G int32 per grid), and that
+ * search returns GNSSCORR_EINVAL when some |s(b,g)| > n: more than a code period has no meaning.  Channels share
+ * forward spectra only when their shift tables agree as well.
+ * gnsscorr_acq_set_codedoppler: GNSSCORR_EINVAL, nothing touched and the channel named, for a range outside the
+ * channel table and an f_cf that is negative or not finite.  Quiesces and drops the prepared acquisition work.
+ * gnsscorr_acq_fetch_shifts: the channel's s[nfreq][G] and back, as the last prepare built them; GNSSCORR_ESTATE before
+ * the first search has prepared.
+ * Not included: drift inside a group (at most 0.065 chip in 20 ms on L1), a codefreq preset at hand-over, the drop-in
+ * sdracquisition(), the sharded engine. */
+int  gnsscorr_acq_set_codedoppler(gnsscorr_ctx *ctx, int ch0, int nch, const double *f_cf);
+int  gnsscorr_acq_get_codedoppler(gnsscorr_ctx *ctx, int ch0, int nch, double *f_cf);
+int  gnsscorr_acq_fetch_shifts(gnsscorr_ctx *ctx, int ch, int32_t *s /* [nfreq][groups] */, int *back);
 
 /* ---- receiver schedule: acquire, hand over and track each channel by state ----
  * sdrthread()'s state machine (ref src/sdrmain.c:247-316) for every channel of the context: a channel calls
