@@ -465,8 +465,7 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
             return gc_fail(GNSSCORR_EINVAL, "channel %d: ring %d (%llu samples) is shorter than a code period (%d + 100 + %d)",
                            i, c.ftype, (unsigned long long)r.ringlen, c.nsamp, 32 / c.dtype);
     }
-    int rc = gc_quiesce(ctx);
-    if (rc) return rc;
+    GC_TRY(gc_quiesce(ctx));
     drop_channel_buffers(ctx);
 
     ctx->nch = nch;
@@ -495,10 +494,7 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
         gc_build_codeblock(d.code, d.clen, codes.data() + (size_t)i * GC_CODEBLOCK, &g.nedge, &g.pm1);
         ctx->have_dtype[d.dtype] = true;
         g.dtype = d.dtype; g.clen = d.clen; g.nsamp = d.nsamp; g.nsampchip = d.nsampchip;
-        g.ntap = 1 + 2 * d.corrn;
-        g.smax = d.corrp[d.corrn - 1];
-        g.tapoff[0] = 0;
-        for (int k = 0; k < d.corrn; k++) { g.tapoff[1 + 2 * k] = -d.corrp[k]; g.tapoff[2 + 2 * k] = d.corrp[k]; }
+        gc_chan_set_taps(g, d.corrp, d.corrn);
         g.ti = d.ti; g.f_sf = d.f_sf; g.crate = d.crate; g.ctime = d.ctime;
         g.nfreq = d.nfreq; g.intg = d.intg; g.nfft = d.nfft;
         g.freq_off = (int)freqs.size();
@@ -534,13 +530,7 @@ extern "C" int gnsscorr_set_channels(gnsscorr_ctx *ctx, int nch, const gnsscorr_
     return upload_channels(ctx);
 }
 
-// The per-channel acquisition settings below take a channel range [ch0, ch0 + nch) and an array of nch values
-static int acq_setting_range(const char *fn, gnsscorr_ctx *ctx, int ch0, int nch, const int *values)
-{
-    if (!ctx || !values || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
-        return gc_fail(GNSSCORR_EINVAL, "%s: channel range [%d,%d) of %d", fn, ch0, ch0 + nch, ctx ? ctx->nch : 0);
-    return GNSSCORR_OK;
-}
+// The per-channel acquisition settings below take a channel range and its values (gc_chan_range, gnsscorr_ctx.h)
 
 // A setting the forward spectra depend on: once nothing is in flight, write() changes the host channel table, the grids
 // are numbered again, the table goes up, and what acquisition had prepared for the old setting (code spectra, carrier
@@ -549,8 +539,7 @@ template <class Write>
 static int acq_change_grids(gnsscorr_ctx *ctx, Write write)
 {
     GC_HIP(hipSetDevice(ctx->device));
-    int rc = gc_quiesce(ctx);
-    if (rc) return rc;
+    GC_TRY(gc_quiesce(ctx));
     write();
     assign_acq_grids(ctx);
     ctx->acq = GcAcq();
@@ -560,7 +549,7 @@ static int acq_change_grids(gnsscorr_ctx *ctx, Write write)
 // Coherent integration per channel (include/gnsscorr.h)
 extern "C" int gnsscorr_acq_set_coherent(gnsscorr_ctx *ctx, int ch0, int nch, const int *ncoh)
 {
-    GC_TRY(acq_setting_range("acq_set_coherent", ctx, ch0, nch, ncoh));
+    GC_TRY(gc_chan_range("acq_set_coherent", ctx, ch0, nch, ncoh));
     for (int i = 0; i < nch; i++) {
         const int intg = ctx->hchan[ch0 + i].intg;
         if (ncoh[i] < 1 || ncoh[i] > GNSSCORR_MAXCOH || intg % ncoh[i] != 0)
@@ -577,7 +566,7 @@ extern "C" int gnsscorr_acq_set_coherent(gnsscorr_ctx *ctx, int ch0, int nch, co
 
 extern "C" int gnsscorr_acq_get_coherent(gnsscorr_ctx *ctx, int ch0, int nch, int *ncoh)
 {
-    GC_TRY(acq_setting_range("acq_get_coherent", ctx, ch0, nch, ncoh));
+    GC_TRY(gc_chan_range("acq_get_coherent", ctx, ch0, nch, ncoh));
     for (int i = 0; i < nch; i++) ncoh[i] = ctx->hchan[ch0 + i].ncoh;
     return GNSSCORR_OK;
 }
@@ -585,7 +574,7 @@ extern "C" int gnsscorr_acq_get_coherent(gnsscorr_ctx *ctx, int ch0, int nch, in
 // Bit-edge hypotheses per channel (include/gnsscorr.h)
 extern "C" int gnsscorr_acq_set_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, const int *estep)
 {
-    GC_TRY(acq_setting_range("acq_set_bitedge", ctx, ch0, nch, estep));
+    GC_TRY(gc_chan_range("acq_set_bitedge", ctx, ch0, nch, estep));
     // the hypotheses are served by the 32768-point transform only, and the transform length is the context's
     for (int i = 0; i < ctx->nch; i++)
         if (ctx->hchan[i].nsamp > 16384)
@@ -604,7 +593,7 @@ extern "C" int gnsscorr_acq_set_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, con
 
 extern "C" int gnsscorr_acq_get_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, int *estep)
 {
-    GC_TRY(acq_setting_range("acq_get_bitedge", ctx, ch0, nch, estep));
+    GC_TRY(gc_chan_range("acq_get_bitedge", ctx, ch0, nch, estep));
     for (int i = 0; i < nch; i++) estep[i] = ctx->hchan[ch0 + i].estep;
     return GNSSCORR_OK;
 }
@@ -612,8 +601,7 @@ extern "C" int gnsscorr_acq_get_bitedge(gnsscorr_ctx *ctx, int ch0, int nch, int
 // Code-Doppler compensation per channel (include/gnsscorr.h); the shift tables are acq_prepare's
 extern "C" int gnsscorr_acq_set_codedoppler(gnsscorr_ctx *ctx, int ch0, int nch, const double *f_cf)
 {
-    if (!ctx || !f_cf || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
-        return gc_fail(GNSSCORR_EINVAL, "acq_set_codedoppler: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    GC_TRY(gc_chan_range("acq_set_codedoppler", ctx, ch0, nch, f_cf));
     for (int i = 0; i < nch; i++)
         if (!std::isfinite(f_cf[i]) || f_cf[i] < 0.0)
             return gc_fail(GNSSCORR_EINVAL, "acq_set_codedoppler: channel %d: f_cf %g (0 for off, or a finite carrier in Hz)",
@@ -625,8 +613,7 @@ extern "C" int gnsscorr_acq_set_codedoppler(gnsscorr_ctx *ctx, int ch0, int nch,
 
 extern "C" int gnsscorr_acq_get_codedoppler(gnsscorr_ctx *ctx, int ch0, int nch, double *f_cf)
 {
-    if (!ctx || !f_cf || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
-        return gc_fail(GNSSCORR_EINVAL, "acq_get_codedoppler: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    GC_TRY(gc_chan_range("acq_get_codedoppler", ctx, ch0, nch, f_cf));
     for (int i = 0; i < nch; i++) f_cf[i] = ctx->hfcf[ch0 + i];
     return GNSSCORR_OK;
 }
@@ -635,7 +622,7 @@ extern "C" int gnsscorr_acq_get_codedoppler(gnsscorr_ctx *ctx, int ch0, int nch,
 // numbers, and what acquisition has prepared and the last search's results stay.
 extern "C" int gnsscorr_acq_set_refine(gnsscorr_ctx *ctx, int ch0, int nch, const int *nref)
 {
-    GC_TRY(acq_setting_range("acq_set_refine", ctx, ch0, nch, nref));
+    GC_TRY(gc_chan_range("acq_set_refine", ctx, ch0, nch, nref));
     for (int i = 0; i < nch; i++) {
         const int intg = ctx->hchan[ch0 + i].intg, top = intg < GNSSCORR_MAXCOH ? intg : GNSSCORR_MAXCOH;
         if (nref[i] < 0 || nref[i] == 1 || nref[i] > top)
@@ -643,15 +630,14 @@ extern "C" int gnsscorr_acq_set_refine(gnsscorr_ctx *ctx, int ch0, int nch, cons
                            nref[i], top, intg, GNSSCORR_MAXCOH);
     }
     GC_HIP(hipSetDevice(ctx->device));
-    int rc = gc_quiesce(ctx);
-    if (rc) return rc;
+    GC_TRY(gc_quiesce(ctx));
     for (int i = 0; i < nch; i++) ctx->hchan[ch0 + i].nref = nref[i];
     return upload_channels(ctx);
 }
 
 extern "C" int gnsscorr_acq_get_refine(gnsscorr_ctx *ctx, int ch0, int nch, int *nref)
 {
-    GC_TRY(acq_setting_range("acq_get_refine", ctx, ch0, nch, nref));
+    GC_TRY(gc_chan_range("acq_get_refine", ctx, ch0, nch, nref));
     for (int i = 0; i < nch; i++) nref[i] = ctx->hchan[ch0 + i].nref;
     return GNSSCORR_OK;
 }

@@ -23,12 +23,9 @@ struct GcOnce {
     GcDevBuf<int8_t> code;                           // one code block
     GcDevBuf<GcChan> chan;
     GcDevBuf<GcTrkPlan> plan;
-    GcDevBuf<GcTrkUnit> unit;
-    GcDevBuf<GcUnitSegs> segs;
+    GcUnitBufs bufs;                                 // one unit of the call's nseg workgroups (corr_unit)
     GcDevBuf<int> overflow;
     GcDevBuf<double> out;                            // 4*GNSSCORR_MAXTAPS: corrI, corrQ, sumI, sumQ
-    GcDevBuf<int> partial;                           // nseg*2*ntap
-    GcDevBuf<GcRound> rounds;                        // nseg*GC_MAXR
     GcDevBuf<unsigned long long> finish;             // GC_FINISH_SCRATCH words, zero between launches
 };
 static GcOnce &g_once = *new GcOnce();
@@ -39,8 +36,6 @@ static int once_init(gnsscorr_ctx *ctx)
     GC_HIP(hipSetDevice(ctx->device));
     GC_RESERVE(ctx, g_once.code, GC_CODEBLOCK);
     GC_RESERVE(ctx, g_once.plan, 1);
-    GC_RESERVE(ctx, g_once.unit, 1);
-    GC_RESERVE(ctx, g_once.segs, 1);
     GC_RESERVE(ctx, g_once.overflow, 1);
     GC_HIP(hipMemsetAsync(g_once.overflow, 0, sizeof(int), ctx->stream));
     GC_RESERVE(ctx, g_once.out, 4 * GNSSCORR_MAXTAPS);
@@ -73,6 +68,18 @@ static void host_rems(double phi0, double freq, double ti, int n, double coff, i
     }
 }
 
+// The channel record of one call: what the tracking kernels read of a channel, the rest zero
+static GcChan once_chan(const int8_t *ring, uint64_t ringlen, const int8_t *code, int dtype, int clen, int n, const int *corrp,
+                        int corrn, double ti, int nedge, int pm1)
+{
+    GcChan c;
+    memset(&c, 0, sizeof(c));
+    c.ring = ring; c.ringlen = ringlen; c.code = code;
+    c.dtype = dtype; c.clen = clen; c.nsamp = n; c.ti = ti; c.nedge = nedge; c.pm1 = pm1;
+    gc_chan_set_taps(c, corrp, corrn);
+    return c;
+}
+
 // One (channel, period) unit on samples that already sit in a device ring.
 static int corr_unit(gnsscorr_ctx *ctx, const int8_t *ring, uint64_t ringlen, int dtype, double ti,
                      int n, double freq, double phi0, double crate, double coff, const int *s, int ns,
@@ -81,36 +88,25 @@ static int corr_unit(gnsscorr_ctx *ctx, const int8_t *ring, uint64_t ringlen, in
     if (ns < 1 || 1 + 2 * ns > GNSSCORR_MAXTAPS) return gc_fail(GNSSCORR_EINVAL, "correlator: ns %d", ns);
     if (coden < 1 || coden > 1023) return gc_fail(GNSSCORR_EINVAL, "correlator: code length %d", coden);
     if (n < 1) return gc_fail(GNSSCORR_EINVAL, "correlator: n %d", n);
-    int rc = once_init(ctx);
-    if (rc) return rc;
-    GcChan c;
-    memset(&c, 0, sizeof(c));
-    c.ring = ring; c.ringlen = ringlen; c.code = g_once.code;
-    c.dtype = dtype; c.clen = coden; c.nsamp = n; c.ntap = 1 + 2 * ns; c.smax = s[ns - 1];
-    c.tapoff[0] = 0;
-    for (int k = 0; k < ns; k++) { c.tapoff[1 + 2 * k] = -s[k]; c.tapoff[2 + 2 * k] = s[k]; }
-    c.ti = ti;
+    GC_TRY(once_init(ctx));
+    static int8_t block[GC_CODEBLOCK];     // guarded by ctx->mtx; every call ends with a stream sync
+    int nedge, pm1;
+    gc_build_codeblock(codein, coden, block, &nedge, &pm1);
+    const GcChan c = once_chan(ring, ringlen, g_once.code, dtype, coden, n, s, ns, ti, nedge, pm1);
     GcTrkPlan p;
     memset(&p, 0, sizeof(p));
     p.buffloc = buffloc; p.coff = coff; p.phi0 = phi0; p.carrfreq = freq; p.codefreq = crate; p.n = n;
-    static int8_t block[GC_CODEBLOCK];     // guarded by ctx->mtx; every call ends with a stream sync
-    gc_build_codeblock(codein, coden, block, &c.nedge, &c.pm1);
     GC_HIP(hipMemcpyAsync(g_once.code, block, GC_CODEBLOCK, hipMemcpyHostToDevice, ctx->stream));
     GC_HIP(hipMemcpyAsync(g_once.chan, &c, sizeof(c), hipMemcpyHostToDevice, ctx->stream));
     GC_HIP(hipMemcpyAsync(g_once.plan, &p, sizeof(p), hipMemcpyHostToDevice, ctx->stream));
-    const int nseg = gc_trk_nseg(dtype, n);
-    GC_RESERVE(ctx, g_once.partial, (size_t)nseg * 2 * c.ntap);
-    GC_RESERVE(ctx, g_once.rounds, (size_t)nseg * GC_MAXR);
-    rc = gc_launch_trk_expand(ctx->stream, g_once.chan, g_once.plan, g_once.unit, g_once.segs, nullptr, 1, 1, g_once.rounds,
-                              nseg, n, g_once.overflow);
-    if (rc) return rc;
-    rc = gc_launch_trk_corr(ctx->stream, g_once.chan, g_once.unit, g_once.segs, g_once.rounds, g_once.partial, 1, 1, nseg,
-                            c.ntap, dtype, c.ntap, n, c.smax, nullptr);
-    if (rc) return rc;
-    rc = gc_launch_trk_finish(ctx->stream, g_once.partial, g_once.out, g_once.out + GNSSCORR_MAXTAPS,
-                              g_once.out + 2 * GNSSCORR_MAXTAPS, g_once.out + 3 * GNSSCORR_MAXTAPS, g_once.finish, 1, 1, nseg,
-                              c.ntap);
-    if (rc) return rc;
+    GcTrkLaunch a;             // (no edge table, no sample counts)
+    a.st = ctx->stream; a.chan = g_once.chan; a.plan = g_once.plan; a.bufs = &g_once.bufs;
+    a.nch = 1; a.nepoch = 1; a.nseg = gc_trk_nseg(dtype, n); a.ntap = c.ntap; a.max_n = n; a.smax_max = c.smax;
+    a.nco_overflow = g_once.overflow; a.scratch = g_once.finish;
+    a.corrI = g_once.out; a.corrQ = g_once.out + GNSSCORR_MAXTAPS;
+    a.sumI = g_once.out + 2 * GNSSCORR_MAXTAPS; a.sumQ = g_once.out + 3 * GNSSCORR_MAXTAPS;
+    GC_TRY(g_once.bufs.reserve(ctx, 1, a.nseg, GC_MAXR, c.ntap));
+    GC_TRY(gc_launch_trk_chain(a, dtype));
     double host[2 * GNSSCORR_MAXTAPS];
     int over = 0;
     GC_HIP(hipMemcpyAsync(host, g_once.out, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
@@ -202,11 +198,8 @@ struct TrkCombiner {
     int cap = 0, nseg_cap = 0;
     GcDevBuf<char> dstage;
     GcPinBuf<char> hstage;
-    GcDevBuf<GcTrkUnit> dunit;
-    GcDevBuf<GcUnitSegs> dsegs;
-    GcDevBuf<GcRound> drounds;
-    GcDevBuf<int> dpartial;
-    GcDevBuf<double> dsum;                              // sumI[cap][ntap], sumQ[cap][ntap] (device; unused by sdrtracking)
+    GcUnitBufs bufs;                                    // cap units of nseg_cap workgroups, GNSSCORR_MAXTAPS taps
+    GcDevBuf<double> dsum;                             // sumI[cap][ntap], sumQ[cap][ntap] (device; unused by sdrtracking)
     GcPinBuf<double> hres;                              // corrI[cap][ntap], corrQ[cap][ntap] (mapped, written by the device)
     GcPinBuf<int> hover;                                // NCO piece-table overflow (mapped)
     GcDevBuf<unsigned long long> dfinish;
@@ -240,17 +233,13 @@ int cmb_reserve(gnsscorr_ctx *ctx, int k, int nseg)
     q.cap = q.nseg_cap = 0;            // (until every buffer below is there)
     const size_t stage = (sizeof(GcChan) + sizeof(GcTrkPlan)) * cap + 64;
     GC_RESERVE(ctx, q.dstage, stage);
-    GC_RESERVE(ctx, q.dunit, cap);
-    GC_RESERVE(ctx, q.dsegs, cap);
-    GC_RESERVE(ctx, q.drounds, (size_t)cap * ns * GC_MAXR);
-    GC_RESERVE(ctx, q.dpartial, (size_t)cap * ns * 2 * nt);
+    GC_TRY(q.bufs.reserve(ctx, cap, ns, GC_MAXR, nt));
     GC_RESERVE(ctx, q.dsum, (size_t)cap * 2 * nt);
     GC_RESERVE(ctx, q.dfinish, (size_t)cap * GC_FINISH_SCRATCH);
     GC_HIP(hipMemsetAsync(q.dfinish, 0, sizeof(unsigned long long) * cap * GC_FINISH_SCRATCH, ctx->stream));
-    int rc = q.hstage.reserve(stage);
-    if (!rc) rc = q.hres.reserve((size_t)cap * 2 * nt, hipHostMallocMapped);
-    if (!rc) rc = q.hover.reserve(16, hipHostMallocMapped);
-    if (rc) return rc;
+    GC_TRY(q.hstage.reserve(stage));
+    GC_TRY(q.hres.reserve((size_t)cap * 2 * nt, hipHostMallocMapped));
+    GC_TRY(q.hover.reserve(16, hipHostMallocMapped));
     *q.hover = 0;
     q.cap = cap; q.nseg_cap = ns;
     return 0;
@@ -287,8 +276,7 @@ int cmb_run_group(gnsscorr_ctx *ctx, std::vector<TrkReq *> &grp)
         if (sm > smax_max) smax_max = sm;
     }
     const int nseg = gc_trk_nseg(dtype, max_n);
-    int rc = cmb_reserve(ctx, k, nseg);
-    if (rc) return rc;
+    GC_TRY(cmb_reserve(ctx, k, nseg));
     const double tp0 = g_cprof.on ? CmbProf::now() : 0.0;
     const size_t plan_off = (sizeof(GcChan) * (size_t)k + 63) & ~(size_t)63;
     GcChan *hchan = reinterpret_cast<GcChan *>(q.hstage.p), *dchan = reinterpret_cast<GcChan *>(q.dstage.p);
@@ -297,17 +285,9 @@ int cmb_run_group(gnsscorr_ctx *ctx, std::vector<TrkReq *> &grp)
         sdrch_t *sdr = grp[i]->sdr;
         const GcRing &ring = ctx->ring[sdr->ftype == FTYPE2 ? 1 : 0];
         CodeSlot *cs;
-        rc = cmb_code(ctx, sdr, grp[i]->codesum, &cs);
-        if (rc) return rc;
-        GcChan &c = hchan[i];
-        memset(&c, 0, sizeof(c));
-        c.ring = ring.mem; c.ringlen = ring.ringlen; c.code = cs->dcode;
-        c.dtype = dtype; c.clen = sdr->clen; c.nsamp = grp[i]->n; c.ntap = ntap;
-        c.smax = sdr->trk.corrp[sdr->trk.corrn - 1];
-        c.tapoff[0] = 0;
-        for (int t = 0; t < sdr->trk.corrn; t++) { c.tapoff[1 + 2 * t] = -sdr->trk.corrp[t]; c.tapoff[2 + 2 * t] = sdr->trk.corrp[t]; }
-        c.ti = sdr->ti;
-        c.nedge = cs->nedge; c.pm1 = cs->pm1;
+        GC_TRY(cmb_code(ctx, sdr, grp[i]->codesum, &cs));
+        hchan[i] = once_chan(ring.mem, ring.ringlen, cs->dcode, dtype, sdr->clen, grp[i]->n, sdr->trk.corrp, sdr->trk.corrn,
+                             sdr->ti, cs->nedge, cs->pm1);
         GcTrkPlan &p = hplan[i];
         memset(&p, 0, sizeof(p));
         p.buffloc = grp[i]->buffloc; p.coff = sdr->trk.oldremcode; p.phi0 = sdr->trk.oldremcarr;
@@ -316,14 +296,14 @@ int cmb_run_group(gnsscorr_ctx *ctx, std::vector<TrkReq *> &grp)
     hipStream_t st = ctx->stream;
     const double tp1 = g_cprof.on ? CmbProf::now() : 0.0;
     GC_HIP(hipMemcpyAsync(q.dstage, q.hstage, plan_off + sizeof(GcTrkPlan) * k, hipMemcpyHostToDevice, st));
-    rc = gc_launch_trk_expand(st, dchan, dplan, q.dunit, q.dsegs, nullptr, k, 1, q.drounds, nseg, max_n, q.hover.dev);
-    if (rc) return rc;
-    rc = gc_launch_trk_corr(st, dchan, q.dunit, q.dsegs, q.drounds, q.dpartial, k, 1, nseg, ntap, dtype, ntap, max_n, smax_max, nullptr);
-    if (rc) return rc;
+    GcTrkLaunch a;             // (no edge table, no sample counts)
+    a.st = st; a.chan = dchan; a.plan = dplan; a.bufs = &q.bufs;
+    a.nch = k; a.nepoch = 1; a.nseg = nseg; a.ntap = ntap; a.max_n = max_n; a.smax_max = smax_max;
+    a.nco_overflow = q.hover.dev; a.scratch = q.dfinish;
     // (the period's sums straight into pinned host memory: no copy back)
-    double *cI = q.hres.dev, *cQ = q.hres.dev + (size_t)q.cap * ntap, *sI = q.dsum, *sQ = q.dsum + (size_t)q.cap * ntap;
-    rc = gc_launch_trk_finish(st, q.dpartial, cI, cQ, sI, sQ, q.dfinish, k, 1, nseg, ntap);
-    if (rc) return rc;
+    a.corrI = q.hres.dev; a.corrQ = q.hres.dev + (size_t)q.cap * ntap;
+    a.sumI = q.dsum; a.sumQ = q.dsum + (size_t)q.cap * ntap;
+    GC_TRY(gc_launch_trk_chain(a, dtype));
     const double tp2 = g_cprof.on ? CmbProf::now() : 0.0;
     GC_HIP(hipStreamSynchronize(st));
     const double tp3 = g_cprof.on ? CmbProf::now() : 0.0;

@@ -1,5 +1,6 @@
 // gnsscorr_ctx.h -- host-side context object behind the opaque gnsscorr_ctx, and the move-only types it owns its
 // resources by: GcDevBuf / GcPinBuf (memory), GcEvent / GcStream (handles).  Deleting the context releases all of them.
+// Also the correlator launches' buffer set (GcUnitBufs), the tracking launchers' argument block (GcTrkLaunch), gc_chan_range.
 #pragma once
 
 #include <map>
@@ -202,15 +203,55 @@ struct GcTrkOut {
     bool fin_pending = false;                      // a batched run was issued and the streams have not been drained since
 };
 
+// What a correlator launch reads its (channel, period) units from and writes its sums to.  The batch's plan slots, the
+// closed loop's step buffers and the two scratch sets of the drop-in symbols (gnsscorr_compat.hip) each own one.
+struct GcUnitBufs {
+    GcDevBuf<GcTrkUnit> unit;      // [unit] per-unit constants
+    GcDevBuf<GcUnitSegs> segs;     // [unit]: the unit's carrier / code NCO piece tables
+    GcDevBuf<GcRound> rounds;      // [unit][nseg][rounds per workgroup]: GC_MAXR; 4 in the closed loop, one per wavefront
+    GcDevBuf<int> partial;         // [unit][nseg][2*ntap] int32 partial sums
+    int reserve(gnsscorr_ctx *ctx, size_t units, int nseg, int rounds_per_workgroup, int ntap)
+    {
+        GC_RESERVE(ctx, unit, units);
+        GC_RESERVE(ctx, segs, units);
+        GC_RESERVE(ctx, rounds, units * nseg * rounds_per_workgroup);
+        GC_RESERVE(ctx, partial, units * nseg * 2 * ntap);
+        return 0;
+    }
+};
+
 // One plan slot: the planner stream expands batch k+1 into one slot while batch k is correlated from the other
 struct GcPlanSlot {
     GcDevBuf<GcTrkPlan> plan;      // [unit]
-    GcDevBuf<GcTrkUnit> unit;      // [unit] per-unit constants
-    GcDevBuf<GcRound> rounds;      // [unit][nseg][GC_MAXR]
-    GcDevBuf<GcUnitSegs> segs;     // [unit]: the unit's carrier / code NCO piece tables
-    GcDevBuf<int> partial;         // [ch][epoch][segment][2*ntap] int32 partial sums
+    GcUnitBufs bufs;               // rounds: GC_MAXR per workgroup
     GcDevBuf<unsigned short> etab; // [unit][GC_EDGTAB] start samples of the batch's chip edges (trk_edges -> trk_corr)
 };
+
+// The argument block of the tracking launchers (gnsscorr_trk.hip): a plain host struct, never a kernel argument
+struct GcTrkLaunch {
+    hipStream_t st;
+    const GcChan *chan;            // device channel table, [nch]
+    const GcTrkPlan *plan;         // [nch][nepoch]
+    const GcUnitBufs *bufs;
+    int nch, nepoch, nseg, max_n, smax_max;
+    int ntap;                      // taps per channel, and the stride of the partial sums
+    unsigned short *etab = nullptr;    // edge table (GcPlanSlot::etab), or null: the correlator finds the edges itself
+    int *nsamp_out = nullptr;      // [nch][nepoch] samples per period, or null
+    int *nco_overflow;             // device counter of units whose NCO tables did not fit (their outputs are zero)
+    double *corrI, *corrQ, *sumI, *sumQ;   // trk_finish: [unit][ntap] correlator outputs, [nch][ntap] batch sums
+    unsigned long long *scratch;   // GC_FINISH_SCRATCH words per channel, zero before the first launch and after every one
+};
+int gc_launch_trk_expand(const GcTrkLaunch &a);
+// one launch serves every channel of that dtype; callers invoke it once per dtype present in the channel set
+int gc_launch_trk_corr(const GcTrkLaunch &a, int dtype);
+int gc_launch_trk_finish(const GcTrkLaunch &a);
+// the three back to back on a.st, for a channel set of one dtype (the drop-in symbols)
+static inline int gc_launch_trk_chain(const GcTrkLaunch &a, int dtype)
+{
+    GC_TRY(gc_launch_trk_expand(a));
+    GC_TRY(gc_launch_trk_corr(a, dtype));
+    return gc_launch_trk_finish(a);
+}
 
 // The batched tracker (gnsscorr_trk.hip): what gnsscorr_trk_run owns, per channel set.  The planner (a short sequential
 // NCO chain per channel) runs one batch ahead on its own stream: plan entries and the chained state are double buffered,
@@ -241,10 +282,7 @@ struct GcLoop {
     GcDevBuf<gnsscorr_loop_t> dloop;               // [nch] the channels' loop states
     std::vector<char> isset;                       // [nch] the channel's loop constants have been set (gnsscorr_loop_set)
     GcDevBuf<GcStepMeta> dstep_meta;               // [nch]
-    GcDevBuf<GcTrkUnit> dstep_unit;                // [nch][GC_STEP_KMAX]
-    GcDevBuf<GcUnitSegs> dstep_segs;
-    GcDevBuf<GcRound> dstep_rounds;                // [nch][GC_STEP_KMAX][step_nseg][4]
-    GcDevBuf<int> dstep_partial;                   // [nch][GC_STEP_KMAX][step_nseg][2*ntap]
+    GcUnitBufs step;                               // [nch][GC_STEP_KMAX] units, step_nseg workgroups of four rounds each
     int step_nseg = 0;
     GcPinBuf<unsigned> hostflags;                  // mapped: [0] channels whose run is over, [1] some channel has its nav bit synchronised
     int kmax = 1;                                  // largest loopms among the channels' loop states (gnsscorr_loop_set)
@@ -490,6 +528,15 @@ struct GcTimed {
         ctx->timers[name].pending.emplace_back(std::move(a), std::move(b));
     }
 };
+
+// The per-channel setters and getters take a channel range [ch0, ch0 + nch) and an array of nch values: EINVAL unless
+// both are there and the range lies inside the channel set (compared without forming ch0 + nch, which can overflow)
+static inline int gc_chan_range(const char *fn, const gnsscorr_ctx *ctx, int ch0, int nch, const void *values)
+{
+    if (!ctx || !values || ch0 < 0 || nch <= 0 || ch0 > ctx->nch - nch)
+        return gc_fail(GNSSCORR_EINVAL, "%s: channel range [%d,%d) of %d", fn, ch0, (int)((unsigned)ch0 + nch), ctx ? ctx->nch : 0);
+    return GNSSCORR_OK;
+}
 
 // gnsscorr_trk.hip.  gc_drain: the planner, tables, discovery and main streams are idle afterwards.  gc_quiesce: that
 // (and the ingest stream when `ingest`), then drops the look-ahead plan and marks the state touched

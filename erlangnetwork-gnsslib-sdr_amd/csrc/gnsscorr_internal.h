@@ -43,6 +43,15 @@ struct GcChan {
 static_assert(offsetof(GcChan, estep) + 2 * sizeof(short) == offsetof(GcChan, ti) && sizeof(GcChan) == 248,
               "estep and nref sit in the hole behind tapoff");
 
+// The channel's taps from the corrn offsets corrp[] (samples, positive and increasing) of its early/late pairs
+static inline void gc_chan_set_taps(GcChan &c, const int *corrp, int corrn)
+{
+    c.ntap = 1 + 2 * corrn;
+    c.smax = corrp[corrn - 1];
+    c.tapoff[0] = 0;
+    for (int k = 0; k < corrn; k++) { c.tapoff[1 + 2 * k] = -corrp[k]; c.tapoff[2 + 2 * k] = corrp[k]; }
+}
+
 // Code block = GC_CODEBLOCK bytes per channel:
 //   [0, 1024)     int8 chips (clen of them, zero padded)
 //   [1024, 3072)  uint16 rank[x], x < clen: number of chip edges at chip indices <= x
@@ -174,23 +183,13 @@ __device__ __forceinline__ GcRound gc_round_make(const int8_t *code, int nedge, 
     return ro;
 }
 
-// kernel launchers (definitions in gnsscorr_trk.hip / gnsscorr_plan.hip / gnsscorr_acq.hip)
+// kernel launchers (definitions in gnsscorr_plan.hip; trk_expand's, trk_corr's and trk_finish's, on one argument block: gnsscorr_ctx.h)
 size_t gc_trk_spec_ints(size_t units);
 int gc_launch_trk_spec(hipStream_t st, const GcChan *chan, const GcTrkState *state_in, int nch, int nepoch, int *claims,
                        int e_off);
 int gc_launch_trk_plan(hipStream_t st, const GcChan *chan, const GcTrkState *state_in, GcTrkState *state_out,
                        GcTrkPlan *plan, int nch, int nepoch, int *claims);
-// nco_overflow: device counter of units whose NCO tables did not fit (their outputs are zero)
-int gc_launch_trk_expand(hipStream_t st, const GcChan *chan, const GcTrkPlan *plan, GcTrkUnit *unit, GcUnitSegs *segs,
-                         int *nsamp_out, int nch, int nepoch, GcRound *rounds, int nseg, int max_n, int *nco_overflow);
-int gc_launch_trk_corr(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit, const GcUnitSegs *segs,
-                       const GcRound *rounds, int *partial, int nch,
-                       int nepoch, int nseg, int ntap_stride, int dtype, int ntap, int max_n, int smax_max,
-                       const unsigned short *etab);
-// scratch: GC_FINISH_SCRATCH 64-bit words per channel, zero before the first launch (the kernel leaves them zero)
-#define GC_FINISH_SCRATCH (2 * GNSSCORR_MAXTAPS + 1)
-int gc_launch_trk_finish(hipStream_t st, const int *partial, double *corrI, double *corrQ, double *sumI,
-                         double *sumQ, unsigned long long *scratch, int nch, int nepoch, int nseg, int ntap);
+#define GC_FINISH_SCRATCH (2 * GNSSCORR_MAXTAPS + 1)   // trk_finish's scratch, 64-bit words per channel
 int gc_trk_nseg(int dtype, int max_n);
 
 // ---- closed loop in steps (gnsscorr_loop.hip) ---------------------------------------------------------------

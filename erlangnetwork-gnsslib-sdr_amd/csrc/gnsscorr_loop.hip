@@ -966,7 +966,7 @@ __global__ __launch_bounds__(64 * GC_TAIL_NW) void trk_step_tail_kernel(
 
 // (channel, period of its interval, quarter) -> one workgroup: ps_unit on four rounds of the period, one per wavefront
 template <int DTYPE, int NTAP, int NIT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NTAP <= 7 ? 4 : (NTAP <= 13 ? 3 : (NTAP <= 21 ? 2 : 1)), 8)))
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(trk_tap_waves_per_eu(NTAP), 8)))
 void trk_step_corr_kernel(const GcChan *__restrict__ chan, const GcStepMeta *__restrict__ meta, const GcTrkUnit *__restrict__ unit,
                           const GcUnitSegs *__restrict__ segs, const GcRound *__restrict__ rounds, int *__restrict__ partial,
                           int nch, int kcap, int nseg, int ntap_stride, int max_n)
@@ -994,19 +994,15 @@ int launch_step_corr(gnsscorr_ctx *ctx, int kcap)
     if (ctx->smax_max > 64) return gc_fail(GNSSCORR_EINVAL, "trk_step: tap offset %d samples (<= 64 supported)", ctx->smax_max);
     constexpr int NIT = DTYPE == 1 ? 1 : 2;
     const GcLoop &lp = ctx->loop;
-    const int nch = ctx->nch, ntap = ctx->ntap;
-    const unsigned grid = (unsigned)(nch * lp.step_nseg * kcap);
-#define GC_SC(N) do { hipLaunchKernelGGL((trk_step_corr_kernel<DTYPE, N, NIT>), dim3(grid), dim3(256), 0, ctx->stream, ctx->dchan.p, \
-                                         lp.dstep_meta.p, lp.dstep_unit.p, lp.dstep_segs.p, lp.dstep_rounds.p, lp.dstep_partial.p, nch, \
-                                         kcap, lp.step_nseg, ntap, ctx->max_n); \
-                      GC_HIP(hipGetLastError()); return 0; } while (0)
-    if (ntap <= 3) GC_SC(3);
-    if (ntap <= 5) GC_SC(5);
-    if (ntap <= 7) GC_SC(7);
-    if (ntap <= 13) GC_SC(13);
-    if (ntap <= 21) GC_SC(21);
-    GC_SC(33);
-#undef GC_SC
+    const unsigned grid = (unsigned)(ctx->nch * lp.step_nseg * kcap);
+    // (the channels of a set share their tap count, so an instance needs no lower bound)
+    return trk_with_tap_bucket(ctx->ntap, [&](auto N, int) {
+        hipLaunchKernelGGL((trk_step_corr_kernel<DTYPE, decltype(N)::value, NIT>), dim3(grid), dim3(256), 0, ctx->stream,
+                           ctx->dchan.p, lp.dstep_meta.p, lp.step.unit.p, lp.step.segs.p, lp.step.rounds.p, lp.step.partial.p, ctx->nch,
+                           kcap, lp.step_nseg, ctx->ntap, ctx->max_n);
+        GC_HIP(hipGetLastError());
+        return 0;
+    });
 }
 
 // workgroups per period in step mode: four rounds (one per wavefront) each
@@ -1023,8 +1019,8 @@ int launch_step_tail(gnsscorr_ctx *ctx, int kcap, int plan)
     if (kcap < 1 || kcap > GC_STEP_KMAX) return gc_fail(GNSSCORR_EINVAL, "trk_step: %d periods per step (1..%d)", kcap, GC_STEP_KMAX);
     GcLoop &lp = ctx->loop;
     hipLaunchKernelGGL(trk_step_tail_kernel, dim3(ctx->nch), dim3(64 * GC_TAIL_NW), 0, ctx->stream, ctx->dchan.p,
-                       ctx->state.cur(), lp.dloop.p, lp.dstep_meta.p, lp.dwrpos.p, lp.dstep_partial.p, lp.dstep_unit.p,
-                       lp.dstep_segs.p, lp.dstep_rounds.p, ctx->out.dcorrI.p, ctx->out.dcorrQ.p, ctx->out.nsamp.p, lp.dlog.p, lp.ddone.p,
+                       ctx->state.cur(), lp.dloop.p, lp.dstep_meta.p, lp.dwrpos.p, lp.step.partial.p, lp.step.unit.p,
+                       lp.step.segs.p, lp.step.rounds.p, ctx->out.dcorrI.p, ctx->out.dcorrQ.p, ctx->out.nsamp.p, lp.dlog.p, lp.ddone.p,
                        ctx->out.dnco_overflow.p, lp.dlapped.p, lp.hostflags.dev, ctx->nch, lp.run_nper, lp.step_nseg, ctx->ntap, ctx->max_n,
                        kcap, plan);
     GC_HIP(hipGetLastError());
@@ -1038,14 +1034,12 @@ int loop_step(gnsscorr_ctx *ctx, int kcap, int plan)
     if (!plan) return launch_step_tail(ctx, kcap, 0);
     {
         GcTimed t(ctx, "trk_step_tail");
-        int rc = launch_step_tail(ctx, kcap, 1);
-        if (rc) return rc;
+        GC_TRY(launch_step_tail(ctx, kcap, 1));
     }
     for (int dtype = 1; dtype <= 2; dtype++) {
         if (!ctx->have_dtype[dtype]) continue;
         GcTimed t(ctx, "trk_step_corr");
-        int rc = dtype == 2 ? launch_step_corr<2>(ctx, kcap) : launch_step_corr<1>(ctx, kcap);
-        if (rc) return rc;
+        GC_TRY(dtype == 2 ? launch_step_corr<2>(ctx, kcap) : launch_step_corr<1>(ctx, kcap));
     }
     return GNSSCORR_OK;
 }
@@ -1055,8 +1049,7 @@ int loop_step(gnsscorr_ctx *ctx, int kcap, int plan)
 // ---- the host driver --------------------------------------------------------------------------------------
 extern "C" int gnsscorr_loop_set(gnsscorr_ctx *ctx, int ch0, int nch, const gnsscorr_loop_t *lp)
 {
-    if (!ctx || !lp || ch0 < 0 || nch <= 0 || ch0 + nch > ctx->nch)
-        return gc_fail(GNSSCORR_EINVAL, "loop_set: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    GC_TRY(gc_chan_range("loop_set", ctx, ch0, nch, lp));
     for (int i = 0; i < nch; i++) {
         const gnsscorr_loop_t &l = lp[i];
         const int ntap = ctx->hchan[ch0 + i].ntap;
@@ -1066,7 +1059,7 @@ extern "C" int gnsscorr_loop_set(gnsscorr_ctx *ctx, int ch0, int nch, const gnss
             return gc_fail(GNSSCORR_EINVAL, "loop_set: channel %d: loopms %d, rate %d (rate 1..20)", ch0 + i, l.loopms, l.rate);
     }
     GC_HIP(hipSetDevice(ctx->device));
-    { int rc = gc_quiesce(ctx); if (rc) return rc; }
+    GC_TRY(gc_quiesce(ctx));
     GcLoop &L = ctx->loop;
     GC_HIP(hipMemcpyAsync(L.dloop + ch0, lp, sizeof(gnsscorr_loop_t) * nch, hipMemcpyHostToDevice, ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
@@ -1080,10 +1073,9 @@ extern "C" int gnsscorr_loop_set(gnsscorr_ctx *ctx, int ch0, int nch, const gnss
 
 extern "C" int gnsscorr_loop_get(gnsscorr_ctx *ctx, int ch0, int nch, gnsscorr_loop_t *lp)
 {
-    if (!ctx || !lp || ch0 < 0 || nch <= 0 || ch0 + nch > ctx->nch)
-        return gc_fail(GNSSCORR_EINVAL, "loop_get: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    GC_TRY(gc_chan_range("loop_get", ctx, ch0, nch, lp));
     GC_HIP(hipSetDevice(ctx->device));
-    { int rc = gc_quiesce(ctx); if (rc) return rc; }
+    GC_TRY(gc_quiesce(ctx));
     GC_HIP(hipMemcpyAsync(lp, ctx->loop.dloop + ch0, sizeof(gnsscorr_loop_t) * nch, hipMemcpyDeviceToHost, ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
     return GNSSCORR_OK;
@@ -1104,14 +1096,9 @@ static int ensure_step_buffers(gnsscorr_ctx *ctx)
     if (nseg > most)
         return gc_fail(GNSSCORR_EINVAL, "trk_run_loop: period of %d samples too long (%d workgroups of four rounds, %d at most)",
                        ctx->max_n, nseg, most);
-    const size_t units = (size_t)ctx->nch * GC_STEP_KMAX;
-    GC_RESERVE(ctx, L.dstep_unit, units);
-    GC_RESERVE(ctx, L.dstep_segs, units);
-    GC_RESERVE(ctx, L.dstep_rounds, units * nseg * 4);        // four rounds (one per wavefront) per workgroup
-    GC_RESERVE(ctx, L.dstep_partial, units * nseg * 2 * ctx->ntap);
+    GC_TRY(L.step.reserve(ctx, (size_t)ctx->nch * GC_STEP_KMAX, nseg, 4, ctx->ntap));   // four rounds (one per wavefront) per workgroup
     GC_RESERVE(ctx, L.dlapped, 1);
-    int rc = L.hostflags.reserve(16, hipHostMallocMapped);
-    if (rc) return rc;
+    GC_TRY(L.hostflags.reserve(16, hipHostMallocMapped));
     GC_RESERVE(ctx, L.dstep_meta, ctx->nch);
     L.step_nseg = nseg;
     return GNSSCORR_OK;

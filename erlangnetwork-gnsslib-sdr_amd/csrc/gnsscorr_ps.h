@@ -1,6 +1,7 @@
 // gnsscorr_ps.h -- the prefix-sum E/P/L correlator of one (channel, code period) on one 256-lane workgroup
 // (ps_unit), shared by the batch kernel (gnsscorr_trk.hip) and the closed-loop step kernels (gnsscorr_loop.hip).
-// gfx950 only.  Replaces correlator() = mixcarr + rescode + dot_22/dot_23 (ref src/sdrcmn.c:608-722).
+// gfx950 only.  Replaces correlator() = mixcarr + rescode + dot_22/dot_23 (ref src/sdrcmn.c:608-722).  In front of it
+// what both launch sites size and pick their instances by: rounds, groups per lane, the tap buckets.
 #pragma once
 
 #include <type_traits>
@@ -33,7 +34,20 @@ __host__ __device__ inline int trk_ps_rounds(int dtype, int max_n, int nit)
 // groups per lane and round: real (1-byte) samples carry 16 running sums per group, one group keeps
 // the LDS image small
 __host__ __device__ inline int trk_ps_nit(int dtype, int nit) { return dtype == 1 ? 1 : nit; }
-
+// The tap buckets: the correlator kernels are compiled for NTAP = 3, 5, 7, 13, 21 and 33 accumulators; an instance serves
+// the tap counts (lower bound, NTAP].  Calls f(NTAP as a std::integral_constant, lower bound) for the smallest that holds ntap.
+template <class F>
+inline int trk_with_tap_bucket(int ntap, F &&f)
+{
+    if (ntap <= 3)  return f(std::integral_constant<int, 3>{}, 0);
+    if (ntap <= 5)  return f(std::integral_constant<int, 5>{}, 3);
+    if (ntap <= 7)  return f(std::integral_constant<int, 7>{}, 5);
+    if (ntap <= 13) return f(std::integral_constant<int, 13>{}, 7);
+    if (ntap <= 21) return f(std::integral_constant<int, 21>{}, 13);
+    return f(std::integral_constant<int, 33>{}, 21);
+}
+// waves per EU the prefix-sum kernels of a bucket are compiled for (amdgpu_waves_per_eu's lower bound)
+constexpr int trk_tap_waves_per_eu(int ntap) { return ntap <= 7 ? 4 : (ntap <= 13 ? 3 : (ntap <= 21 ? 2 : 1)); }
 
 // sum over the wavefront, valid in lane 63 (row scans, then row broadcasts)
 template <int CTRL, int ROWMASK>

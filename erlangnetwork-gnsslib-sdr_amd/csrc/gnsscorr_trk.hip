@@ -18,19 +18,18 @@
 //              across the wavefront and the workgroup.  All sums are exact
 //              integers (|sum| < 2^31), scaled by 1/32 at the end like the
 //              reference's CSCALE.
-//   Below the kernels, the host driver of the batched tracker: gnsscorr_trk_run on its four streams, the buffers
-//   it and the closed loop reserve (GcBatch, GcTrkOut in gnsscorr_ctx.h), gc_drain / gc_quiesce, the fetch calls
-//   and trk_set/get_state.
+//   Below the kernels, the launchers (gc_launch_trk_expand / _corr / _finish on one argument block, GcTrkLaunch; the
+//   run-time switches, trk_switches) and the host driver of the batched tracker: gnsscorr_trk_run on its four streams,
+//   the buffers it and the closed loop reserve (GcBatch, GcTrkOut in gnsscorr_ctx.h), gc_drain / gc_quiesce, the fetch
+//   calls and trk_set/get_state.
 #include <cstdlib>
 #include <type_traits>
-
 
 #include "gnsscorr_ctx.h"        // the host driver below the kernels
 #include "gnsscorr_lut.h"        // the carrier LUT (trk_corr builds its dot-product operands from it)
 #include "gnsscorr_ps.h"
 
 namespace {
-
 
 // ---------------------------------------------------------------------------
 // per-unit constants and NCO tables
@@ -550,7 +549,7 @@ __global__ __launch_bounds__(256) void trk_edges_kernel(const GcChan *__restrict
 }
 
 template <int DTYPE, int NTAP, int NIT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NTAP <= 7 ? 4 : (NTAP <= 13 ? 3 : (NTAP <= 21 ? 2 : 1)), 8))) void trk_corr_ps_kernel(const GcChan *__restrict__ chan,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(trk_tap_waves_per_eu(NTAP), 8))) void trk_corr_ps_kernel(const GcChan *__restrict__ chan,
                                                           const GcTrkUnit *__restrict__ unit,
                                                           const GcUnitSegs *__restrict__ segs,
                                                           const GcRound *__restrict__ rounds,
@@ -630,143 +629,129 @@ __global__ __launch_bounds__(256) void trk_finish_kernel(const int *__restrict__
     if (tid == 0) __hip_atomic_store(&sc[SS - 1], 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-int g_trk_nit = 0;      // groups per lane per segment workgroup (1, 2, 4 or 8); 0 = not yet chosen
-int g_trk_algo = 0;     // 1 = prefix-sum form (default), 2 = replica form (GNSSCORR_TRK_ALGO=replica)
+// The run-time switches of the tracking path, read once per process (trk_switches)
+struct TrkSwitches {
+    int algo;       // 1 = prefix-sum form (default), 2 = replica form (GNSSCORR_TRK_ALGO=replica)
+    int nit;        // GNSSCORR_TRK_NIT, groups per lane: prefix-sum form 1 or 2, replica form 2, 4 or 8; anything else: 2
+    int ablate;     // GNSSCORR_TRK_ABLATE: phases the correlator leaves out (measurements only), 0: none
+    bool noetab;    // GNSSCORR_TRK_NOEDGETAB: no edge table, the correlator finds the chip edges itself
+    TrkSwitches()
+    {
+        const char *a = getenv("GNSSCORR_TRK_ALGO"), *e = getenv("GNSSCORR_TRK_NIT"), *ab = getenv("GNSSCORR_TRK_ABLATE");
+        algo = (a && a[0] == 'r') ? 2 : 1;
+        nit = e ? atoi(e) : 2;
+        if (algo == 1 ? (nit != 1 && nit != 2) : (nit != 2 && nit != 4 && nit != 8)) nit = 2;
+        ablate = ab ? atoi(ab) : 0;
+        noetab = getenv("GNSSCORR_TRK_NOEDGETAB") != nullptr;
+    }
+};
+const TrkSwitches &trk_switches() { static const TrkSwitches sw; return sw; }
 
+// the correlator's grid: workgroups (segment, epoch, channel), the epochs rounded up to the 8 slots of the workgroup order
+int corr_grid(const GcTrkLaunch &a, unsigned *grid)
+{
+    const long long total = 8LL * ((a.nepoch + 7) / 8) * a.nch * a.nseg;
+    if (total > 0x7fffffffLL) return gc_fail(GNSSCORR_EINVAL, "trk_corr: batch too large (%lld workgroups)", total);
+    *grid = (unsigned)total;
+    return 0;
+}
+
+// The instance <DTYPE, NTAP, NIT> serves the channels of that dtype with ntap in (ntap_lo, NTAP]
 template <int DTYPE, int NTAP, int NIT>
-int launch_corr_ps(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit, const GcUnitSegs *segs, const GcRound *rounds, int *partial,
-                   int nch, int nepoch, int nseg, int ntap_stride, int ntap_lo, int max_n, const unsigned short *etab)
+int launch_corr_ps(const GcTrkLaunch &a, int ntap_lo)
 {
     static_assert(PsLayout<DTYPE, NIT>::bytes(NTAP) <= 64 * 1024, "static LDS image");
-    const int rpw = trk_ps_rounds(DTYPE, max_n, NIT);
-    static const int ablate = getenv("GNSSCORR_TRK_ABLATE") ? atoi(getenv("GNSSCORR_TRK_ABLATE")) : 0;
-    const long long total = 8LL * ((nepoch + 7) / 8) * nch * nseg;
-    if (total > 0x7fffffffLL) return gc_fail(GNSSCORR_EINVAL, "trk_corr: batch too large (%lld workgroups)", total);
-    hipLaunchKernelGGL((trk_corr_ps_kernel<DTYPE, NTAP, NIT>), dim3((unsigned)total), dim3(256), 0, st, chan, unit,
-                       segs, rounds, partial, nch, nepoch, nseg, ntap_stride, ntap_lo, max_n, rpw, ablate, etab);
+    const TrkSwitches &sw = trk_switches();
+    const int rpw = trk_ps_rounds(DTYPE, a.max_n, NIT);
+    const unsigned short *etab = sw.noetab ? nullptr : a.etab;
+    unsigned grid;
+    GC_TRY(corr_grid(a, &grid));
+    hipLaunchKernelGGL((trk_corr_ps_kernel<DTYPE, NTAP, NIT>), dim3(grid), dim3(256), 0, a.st, a.chan, a.bufs->unit.p,
+                       a.bufs->segs.p, a.bufs->rounds.p, a.bufs->partial.p, a.nch, a.nepoch, a.nseg, a.ntap, ntap_lo, a.max_n,
+                       rpw, sw.ablate, etab);
     GC_HIP(hipGetLastError());
     return 0;
 }
 
 template <int DTYPE, int NTAP, int NIT>
-int launch_corr(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit, const GcUnitSegs *segs, int *partial, int nch, int nepoch,
-                int nseg, int ntap_stride, int ntap_lo, int max_n, int smax_max)
+int launch_corr(const GcTrkLaunch &a, int ntap_lo)
 {
     constexpr int RED_BYTES = ((4 * 2 * NTAP * 4) + 15) & ~15;
     constexpr int SEGS = 256 * NIT * (16 / DTYPE);
     constexpr int RS = SEGS / 8 + 64;
     const int lds = (int)((DTYPE == 2 ? 512 : 1024) + RED_BYTES + 8 * RS * 4 + ((GC_NCAR + 4) & ~3) * 4 +
                           GC_NCAR * sizeof(GcCarSeg) + GC_NCODE * sizeof(GcCodeSeg));
-    static const int ablate = getenv("GNSSCORR_TRK_ABLATE") ? atoi(getenv("GNSSCORR_TRK_ABLATE")) : 0;
     if (lds > 64 * 1024)
         GC_HIP(hipFuncSetAttribute((const void *)trk_corr_kernel<DTYPE, NTAP, NIT>,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    const long long total = 8LL * ((nepoch + 7) / 8) * nch * nseg;
-    if (total > 0x7fffffffLL) return gc_fail(GNSSCORR_EINVAL, "trk_corr: batch too large (%lld workgroups)", total);
-    dim3 grid((unsigned)total), block(256);
-    hipLaunchKernelGGL((trk_corr_kernel<DTYPE, NTAP, NIT>), grid, block, lds, st, chan, unit, segs, partial, nch, nepoch,
-                       nseg, ntap_stride, ntap_lo, max_n, ablate);
+    unsigned grid;
+    GC_TRY(corr_grid(a, &grid));
+    hipLaunchKernelGGL((trk_corr_kernel<DTYPE, NTAP, NIT>), dim3(grid), dim3(256), lds, a.st, a.chan, a.bufs->unit.p,
+                       a.bufs->segs.p, a.bufs->partial.p, a.nch, a.nepoch, a.nseg, a.ntap, ntap_lo, a.max_n,
+                       trk_switches().ablate);
     GC_HIP(hipGetLastError());
     return 0;
 }
 
 template <int DTYPE, int NTAP>
-int launch_corr_nit(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit, const GcUnitSegs *segs, const GcRound *rounds, int *partial, int nch, int nepoch,
-                    int nseg, int ntap_stride, int ntap_lo, int max_n, int smax_max, const unsigned short *etab)
+int launch_corr_nit(const GcTrkLaunch &a, int ntap_lo)
 {
-    if (g_trk_algo == 1) {
-        if (g_trk_nit == 1 || DTYPE == 1)
-            return launch_corr_ps<DTYPE, NTAP, 1>(st, chan, unit, segs, rounds, partial, nch, nepoch, nseg, ntap_stride, ntap_lo, max_n, etab);
-        return launch_corr_ps<DTYPE, NTAP, DTYPE == 1 ? 1 : 2>(st, chan, unit, segs, rounds, partial, nch, nepoch, nseg, ntap_stride, ntap_lo, max_n, etab);
+    const TrkSwitches &sw = trk_switches();
+    if (sw.algo == 1) {
+        if (sw.nit == 1 || DTYPE == 1) return launch_corr_ps<DTYPE, NTAP, 1>(a, ntap_lo);
+        return launch_corr_ps<DTYPE, NTAP, DTYPE == 1 ? 1 : 2>(a, ntap_lo);
     }
-    switch (g_trk_nit) {
-    default: return launch_corr<DTYPE, NTAP, 2>(st, chan, unit, segs, partial, nch, nepoch, nseg, ntap_stride, ntap_lo, max_n, smax_max);
-    case 8: return launch_corr<DTYPE, NTAP, 8>(st, chan, unit, segs, partial, nch, nepoch, nseg, ntap_stride, ntap_lo, max_n, smax_max);
-    case 4: return launch_corr<DTYPE, NTAP, 4>(st, chan, unit, segs, partial, nch, nepoch, nseg, ntap_stride, ntap_lo, max_n, smax_max);
+    switch (sw.nit) {
+    default: return launch_corr<DTYPE, NTAP, 2>(a, ntap_lo);
+    case 8: return launch_corr<DTYPE, NTAP, 8>(a, ntap_lo);
+    case 4: return launch_corr<DTYPE, NTAP, 4>(a, ntap_lo);
     }
 }
 
+// the smallest instance that holds a.ntap accumulators
 template <int DTYPE>
-int launch_corr_taps(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit, const GcUnitSegs *segs, const GcRound *rounds, int *partial, int nch, int nepoch,
-                     int nseg, int ntap_stride, int ntap, int max_n, int smax_max, const unsigned short *etab)
+int launch_corr_taps(const GcTrkLaunch &a)
 {
-    // smallest instantiation that holds ntap accumulators; it serves (lo, NTAP]
-#define GC_LC(N, LO) return launch_corr_nit<DTYPE, N>(st, chan, unit, segs, rounds, partial, nch, nepoch, nseg, ntap_stride, LO, max_n, smax_max, etab)
-    if (ntap <= 3)  GC_LC(3, 0);
-    if (ntap <= 5)  GC_LC(5, 3);
-    if (ntap <= 7)  GC_LC(7, 5);
-    if (ntap <= 13) GC_LC(13, 7);
-    if (ntap <= 21) GC_LC(21, 13);
-    GC_LC(33, 21);
-#undef GC_LC
-}
-
-void trk_pick_nit()
-{
-    if (g_trk_nit) return;
-    const char *a = getenv("GNSSCORR_TRK_ALGO");
-    g_trk_algo = (a && a[0] == 'r') ? 2 : 1;
-    const char *e = getenv("GNSSCORR_TRK_NIT");
-    g_trk_nit = e ? atoi(e) : 2;
-    if (g_trk_algo == 1) {
-        if (g_trk_nit != 1 && g_trk_nit != 2) g_trk_nit = 2;
-    } else {
-        if (g_trk_nit != 2 && g_trk_nit != 4 && g_trk_nit != 8) g_trk_nit = 2;
-    }
+    return trk_with_tap_bucket(a.ntap, [&](auto N, int lo) { return launch_corr_nit<DTYPE, decltype(N)::value>(a, lo); });
 }
 
 }  // namespace
 
 int gc_trk_nseg(int dtype, int max_n)
 {
-    trk_pick_nit();
+    const TrkSwitches &sw = trk_switches();
     const int groups = (15 + max_n * dtype + 15) / 16 + 1;
     // real (1-byte) samples carry 16 running sums per group: one group per lane keeps the LDS image small
-    const int nit = g_trk_algo == 1 ? trk_ps_nit(dtype, g_trk_nit) : g_trk_nit;
-    if (g_trk_algo == 1) {          // prefix-sum form: rounds of one wavefront each, GC_MAXR per workgroup
-        const int rounds = (groups + GC_PS_WLANES * nit - 1) / (GC_PS_WLANES * nit);
-        return (rounds + GC_MAXR - 1) / GC_MAXR;
-    }
-    return (groups + 256 * nit - 1) / (256 * nit);
+    const int nit = sw.algo == 1 ? trk_ps_nit(dtype, sw.nit) : sw.nit;
+    // prefix-sum form: rounds of one wavefront each, GC_MAXR per workgroup; replica form: 256 lanes of nit groups
+    const int per_wg = sw.algo == 1 ? GC_PS_WLANES * nit * GC_MAXR : 256 * nit;
+    return (groups + per_wg - 1) / per_wg;
 }
 
-int gc_launch_trk_expand(hipStream_t st, const GcChan *chan, const GcTrkPlan *plan, GcTrkUnit *unit, GcUnitSegs *segs,
-                         int *nsamp_out, int nch, int nepoch, GcRound *rounds, int nseg, int max_n, int *nco_overflow)
+int gc_launch_trk_expand(const GcTrkLaunch &a)
 {
-    trk_pick_nit();
-    const int total = nch * nepoch;
-    hipLaunchKernelGGL(trk_expand_kernel, dim3((total + 63) / 64), dim3(64), 0, st, chan, plan, unit, segs, nsamp_out,
-                       nch, nepoch, g_trk_algo == 1 ? rounds : (GcRound *)nullptr, nseg, max_n, g_trk_nit, nco_overflow);
+    const TrkSwitches &sw = trk_switches();
+    const int total = a.nch * a.nepoch;
+    hipLaunchKernelGGL(trk_expand_kernel, dim3((total + 63) / 64), dim3(64), 0, a.st, a.chan, a.plan, a.bufs->unit.p,
+                       a.bufs->segs.p, a.nsamp_out, a.nch, a.nepoch, sw.algo == 1 ? a.bufs->rounds.p : (GcRound *)nullptr, a.nseg,
+                       a.max_n, sw.nit, a.nco_overflow);
     GC_HIP(hipGetLastError());
     return 0;
 }
 
-// One launch serves every channel whose (dtype, tap bucket) matches; callers
-// invoke it once per distinct dtype present in the channel set.
-// etab: the start samples of the periods' chip edges (launch_trk_edges on the same stream before this), or null
-int gc_launch_trk_corr(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit, const GcUnitSegs *segs,
-                       const GcRound *rounds, int *partial, int nch,
-                       int nepoch, int nseg, int ntap_stride, int dtype, int ntap, int max_n, int smax_max,
-                       const unsigned short *etab)
+int gc_launch_trk_corr(const GcTrkLaunch &a, int dtype)
 {
-    trk_pick_nit();
-    if (smax_max > 64) return gc_fail(GNSSCORR_EINVAL, "trk_corr: tap offset %d samples (<= 64 supported)", smax_max);
-    static const bool noetab = getenv("GNSSCORR_TRK_NOEDGETAB") != nullptr;
-    if (g_trk_algo != 1 || noetab) etab = nullptr;
-    if (dtype == 2)
-        return launch_corr_taps<2>(st, chan, unit, segs, rounds, partial, nch, nepoch, nseg, ntap_stride, ntap, max_n, smax_max, etab);
-    if (dtype == 1)
-        return launch_corr_taps<1>(st, chan, unit, segs, rounds, partial, nch, nepoch, nseg, ntap_stride, ntap, max_n, smax_max, etab);
+    if (a.smax_max > 64) return gc_fail(GNSSCORR_EINVAL, "trk_corr: tap offset %d samples (<= 64 supported)", a.smax_max);
+    if (dtype == 2) return launch_corr_taps<2>(a);
+    if (dtype == 1) return launch_corr_taps<1>(a);
     return gc_fail(GNSSCORR_EINVAL, "trk_corr: dtype %d not 1 or 2", dtype);
 }
 
-static int launch_trk_edges(hipStream_t st, const GcChan *chan, const GcTrkUnit *unit, const GcUnitSegs *segs, unsigned short *etab,
-                        int nch, int nepoch)
+static int launch_trk_edges(const GcTrkLaunch &a)
 {
-    static const bool noetab = getenv("GNSSCORR_TRK_NOEDGETAB") != nullptr;
-    trk_pick_nit();
-    if (!etab || noetab || g_trk_algo != 1) return 0;
-    hipLaunchKernelGGL(trk_edges_kernel, dim3(nch * nepoch), dim3(256), 0, st, chan, unit, segs, etab, nch, nepoch);
+    if (!a.etab || trk_switches().noetab || trk_switches().algo != 1) return 0;
+    hipLaunchKernelGGL(trk_edges_kernel, dim3(a.nch * a.nepoch), dim3(256), 0, a.st, a.chan, a.bufs->unit.p, a.bufs->segs.p,
+                       a.etab, a.nch, a.nepoch);
     GC_HIP(hipGetLastError());
     return 0;
 }
@@ -787,21 +772,19 @@ __global__ void trk_ringcheck_kernel(const GcChan *__restrict__ chan, const GcTr
     if (p.buffloc + (uint64_t)p.n > wp || (wp > rl && p.buffloc < wp - rl)) atomicAdd(viol, 1);
 }
 
-static int launch_trk_ringcheck(hipStream_t st, const GcChan *chan, const GcTrkPlan *plan, const int8_t *ring0, uint64_t wrpos0,
-                            uint64_t wrpos1, int nch, int nepoch, int *viol)
+static int launch_trk_ringcheck(const GcTrkLaunch &a, const int8_t *ring0, const uint64_t wr[2], int *viol)
 {
-    const int total = nch * nepoch;
-    hipLaunchKernelGGL(trk_ringcheck_kernel, dim3((total + 255) / 256), dim3(256), 0, st, chan, plan, ring0, wrpos0, wrpos1,
-                       nch, nepoch, viol);
+    const int total = a.nch * a.nepoch;
+    hipLaunchKernelGGL(trk_ringcheck_kernel, dim3((total + 255) / 256), dim3(256), 0, a.st, a.chan, a.plan, ring0, wr[0], wr[1],
+                       a.nch, a.nepoch, viol);
     GC_HIP(hipGetLastError());
     return 0;
 }
 
-int gc_launch_trk_finish(hipStream_t st, const int *partial, double *corrI, double *corrQ, double *sumI,
-                         double *sumQ, unsigned long long *scratch, int nch, int nepoch, int nseg, int ntap)
+int gc_launch_trk_finish(const GcTrkLaunch &a)
 {
-    hipLaunchKernelGGL(trk_finish_kernel, dim3(nch, (nepoch + 255) / 256), dim3(256), 0, st, partial, corrI, corrQ,
-                       sumI, sumQ, scratch, nepoch, nseg, ntap);
+    hipLaunchKernelGGL(trk_finish_kernel, dim3(a.nch, (a.nepoch + 255) / 256), dim3(256), 0, a.st, a.bufs->partial.p, a.corrI,
+                       a.corrQ, a.sumI, a.sumQ, a.scratch, a.nepoch, a.nseg, a.ntap);
     GC_HIP(hipGetLastError());
     return 0;
 }
@@ -874,10 +857,7 @@ static int ensure_batch_buffers(gnsscorr_ctx *ctx, int nepoch)
     }
     for (GcPlanSlot &s : b.slot) {
         GC_RESERVE(ctx, s.plan, units);
-        GC_RESERVE(ctx, s.partial, units * b.nseg * 2 * ctx->ntap);
-        GC_RESERVE(ctx, s.unit, units);
-        GC_RESERVE(ctx, s.rounds, units * b.nseg * GC_MAXR);
-        GC_RESERVE(ctx, s.segs, units);
+        GC_TRY(s.bufs.reserve(ctx, units, b.nseg, GC_MAXR, ctx->ntap));
         GC_RESERVE(ctx, s.etab, units * GC_EDGTAB);
     }
     for (int i = 0; i < 2; i++) GC_RESERVE(ctx, b.dspec2[i], gc_trk_spec_ints(units));
@@ -942,16 +922,28 @@ static int plan_into(gnsscorr_ctx *ctx, int s, int nepoch, hipEvent_t gate)
     return GNSSCORR_OK;
 }
 
+// the launchers' arguments for the batch of nepoch periods planned into slot s, on stream st
+static GcTrkLaunch slot_launch(gnsscorr_ctx *ctx, int s, int nepoch, hipStream_t st)
+{
+    const GcBatch &b = ctx->batch;
+    const GcTrkOut &o = ctx->out;
+    GcTrkLaunch a;
+    a.st = st; a.chan = ctx->dchan; a.plan = b.slot[s].plan; a.bufs = &b.slot[s].bufs; a.etab = b.slot[s].etab;
+    a.nch = ctx->nch; a.nepoch = nepoch; a.nseg = b.nseg; a.ntap = ctx->ntap; a.max_n = ctx->max_n; a.smax_max = ctx->smax_max;
+    a.nsamp_out = o.nsamp; a.nco_overflow = o.dnco_overflow; a.scratch = b.dfinish;
+    a.corrI = o.dcorrI; a.corrQ = o.dcorrQ; a.sumI = o.dsumI; a.sumQ = o.dsumQ;
+    return a;
+}
+
 // A batch planned into slot s.  Its table kernels -- expand, ring check (wr: what it may take as written), edges -- go
 // to the tables stream, behind the slot's plan and behind the correlator that last read the slot's tables (two
 // batches ago) -- and, for now, behind the previous batch's correlator (below) -- off the main stream, beside the next
-// chain and the previous batch's finish; the slot's ev_tab marks them built.  The main stream carries one correlator launch per dtype, behind ev_tab; the slot's ev_corr marks the
-// tables consumed.
+// chain and the previous batch's finish; the slot's ev_tab marks them built.  The main stream carries one correlator
+// launch per dtype, behind ev_tab; the slot's ev_corr marks the tables consumed.
 static int correlate_slot(gnsscorr_ctx *ctx, int s, int nepoch, const uint64_t wr[2])
 {
-    GcBatch &b = ctx->batch;
-    GcPlanSlot &sl = b.slot[s];
     hipStream_t ts = ctx->stream_tables;
+    const GcTrkLaunch tab = slot_launch(ctx, s, nepoch, ts), cor = slot_launch(ctx, s, nepoch, ctx->stream);
     GC_HIP(hipStreamWaitEvent(ts, ctx->ev_plan[s], 0));
     GC_HIP(hipStreamWaitEvent(ts, ctx->ev_corr[s], 0));        // (never recorded, or drained since: no wait)
     // Not a data dependency: the tables also start behind the previous batch's correlator.  While the chain bounds the
@@ -963,25 +955,22 @@ static int correlate_slot(gnsscorr_ctx *ctx, int s, int nepoch, const uint64_t w
     // the per-unit constants and NCO tables of the planned periods
     {
         GcTimed t(ctx, "trk_expand", ts);
-        GC_TRY(gc_launch_trk_expand(ts, ctx->dchan, sl.plan, sl.unit, sl.segs, ctx->out.nsamp, ctx->nch, nepoch,
-                                    sl.rounds, b.nseg, ctx->max_n, ctx->out.dnco_overflow));
+        GC_TRY(gc_launch_trk_expand(tab));
     }
     // the planned periods against what the rings hold now
     // (the write positions travel as kernel arguments: no copy, no host synchronisation per batch)
-    GC_TRY(launch_trk_ringcheck(ts, ctx->dchan, sl.plan, (const int8_t *)ctx->ring[0].mem, wr[0], wr[1], ctx->nch,
-                                nepoch, ctx->out.dring_viol));
+    GC_TRY(launch_trk_ringcheck(tab, (const int8_t *)ctx->ring[0].mem, wr, ctx->out.dring_viol));
     {
         // start samples of the periods' chip edges, for the correlator's look-up phase
         GcTimed t(ctx, "trk_edges", ts);
-        GC_TRY(launch_trk_edges(ts, ctx->dchan, sl.unit, sl.segs, sl.etab, ctx->nch, nepoch));
+        GC_TRY(launch_trk_edges(tab));
     }
     GC_HIP(hipEventRecord(ctx->ev_tab[s], ts));                // tables built, plan entries consumed
     GC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_tab[s], 0));
     for (int dtype = 1; dtype <= 2; dtype++) {
         if (!ctx->have_dtype[dtype]) continue;
         GcTimed t(ctx, "trk_corr");
-        GC_TRY(gc_launch_trk_corr(ctx->stream, ctx->dchan, sl.unit, sl.segs, sl.rounds, sl.partial, ctx->nch, nepoch, b.nseg,
-                                  ctx->ntap, dtype, ctx->ntap, ctx->max_n, ctx->smax_max, sl.etab));
+        GC_TRY(gc_launch_trk_corr(cor, dtype));
     }
     GC_HIP(hipEventRecord(ctx->ev_corr[s], ctx->stream));     // the slot's tables are consumed
     return GNSSCORR_OK;
@@ -993,12 +982,9 @@ static int correlate_slot(gnsscorr_ctx *ctx, int s, int nepoch, const uint64_t w
 // trk_run sees the outputs.
 static int finish_slot(gnsscorr_ctx *ctx, int s, int nepoch)
 {
-    GcBatch &b = ctx->batch;
-    GcTrkOut &o = ctx->out;
     GcTimed t(ctx, "trk_finish");
-    GC_TRY(gc_launch_trk_finish(ctx->stream, b.slot[s].partial, o.dcorrI, o.dcorrQ, o.dsumI, o.dsumQ, b.dfinish, ctx->nch,
-                                nepoch, b.nseg, ctx->ntap));
-    o.fin_pending = true;
+    GC_TRY(gc_launch_trk_finish(slot_launch(ctx, s, nepoch, ctx->stream)));
+    ctx->out.fin_pending = true;
     return GNSSCORR_OK;
 }
 
@@ -1135,8 +1121,7 @@ extern "C" int gnsscorr_trk_devptrs(gnsscorr_ctx *ctx, void **trkII, void **trkQ
 
 extern "C" int gnsscorr_trk_set_state(gnsscorr_ctx *ctx, int ch0, int nch, const gnsscorr_trkstate_t *st)
 {
-    if (!ctx || !st || ch0 < 0 || nch <= 0 || ch0 + nch > ctx->nch)
-        return gc_fail(GNSSCORR_EINVAL, "trk_set_state: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    GC_TRY(gc_chan_range("trk_set_state", ctx, ch0, nch, st));
     static_assert(sizeof(gnsscorr_trkstate_t) == sizeof(GcTrkState), "state layout");
     GC_HIP(hipSetDevice(ctx->device));
     GC_TRY(gc_quiesce(ctx));
@@ -1147,8 +1132,7 @@ extern "C" int gnsscorr_trk_set_state(gnsscorr_ctx *ctx, int ch0, int nch, const
 
 extern "C" int gnsscorr_trk_get_state(gnsscorr_ctx *ctx, int ch0, int nch, gnsscorr_trkstate_t *st)
 {
-    if (!ctx || !st || ch0 < 0 || nch <= 0 || ch0 + nch > ctx->nch)
-        return gc_fail(GNSSCORR_EINVAL, "trk_get_state: channel range [%d,%d) of %d", ch0, ch0 + nch, ctx ? ctx->nch : 0);
+    GC_TRY(gc_chan_range("trk_get_state", ctx, ch0, nch, st));
     GC_HIP(hipSetDevice(ctx->device));
     // leaves the look-ahead plan valid: reading the committed state changes nothing
     GC_TRY(gc_drain(ctx));

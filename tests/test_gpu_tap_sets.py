@@ -4,7 +4,8 @@ The tracking correlator is compiled once per tap bucket, NTAP = 3, 5, 7, 13, 21 
 gnsscorr_trk.hip); each instantiation serves the tap counts (lo, NTAP] and masks the accumulator slots it does not
 use.  These tests run the lowest and the highest member of every bucket, outermost taps up to the 64 samples
 set_channels accepts, every correlator form at 33 taps, full-scale samples at the longest period, the closed loop at
-9 and 33 taps and the reference-named correlator() with 16 tap pairs.
+3, 7, 9, 13, 21 and 33 taps (every bucket; 5 taps is what the rest of the suite runs it at) and the reference-named
+correlator() with 16 tap pairs.
 
 Bar: bit-exact sums, samples per period, remainders and filter-update flags (tests/test_gpu_tracking.py,
 tests/test_gpu_loop.py)."""
@@ -202,6 +203,22 @@ def test_closed_loop_9_and_33_taps(gc, orc, engine, taps, flagsync):
         assert c.ne == c.nl == 0 and orc.make_chan(1, corrn=corrn, corrd=corrd, corrp=corrp).ne == 0
     _random_states_case(gc, orc, engine, 900 + 10 * corrn + corrp + flagsync, 2, 0.0, F_SF, taps, flagsync, nper=100,
                         nch=8, chunks=(61, 39))
+
+
+@pytest.mark.parametrize("taps,flagsync", [
+    ((1, 3, 3), 0),             # 3 taps: the bucket of 3
+    ((3, 2, 2), 1),             # 7 taps: the bucket of 7
+    ((6, 3, 3), 0),             # 13 taps: the bucket of 13
+    ((10, 2, 2), 1),            # 21 taps: the bucket of 21
+], ids=lambda p: f"{1 + 2 * p[0]}taps" if isinstance(p, tuple) else f"sync{p}")
+def test_closed_loop_remaining_tap_buckets(gc, orc, engine, taps, flagsync):
+    """The closed loop's correlator instances come off the same tap-bucket ladder as the batch's (trk_with_tap_bucket,
+    gnsscorr_ps.h); the cases above and the rest of the suite run it at 5, 9 and 33 taps.  Here 3, 7, 13 and 21 taps,
+    the top of the other four buckets: 2 channels x 40 periods in two runs, int8 IQ at 16.368 Msps, before and after
+    nav bit synchronisation in turn, bit for bit as above."""
+    corrn, corrd, corrp = taps
+    _random_states_case(gc, orc, engine, 900 + 10 * corrn + corrp + flagsync, 2, 0.0, F_SF, taps, flagsync, nper=40,
+                        nch=2, chunks=(23, 17))
 
 
 @pytest.mark.parametrize("dtype,freq", [(2, -3456.5), (1, 4.092e6 + 1500.25)])
