@@ -394,6 +394,24 @@ class LockState(C.Structure):
                 [(n, C.c_int) for n in ("open", "n", "k", "nbad", "lost", "reason", "windows", "pad")])
 
 
+class BsyncPrm(C.Structure):
+    """gnsscorr_bsyncprm_t: the parameters of bit synchronisation by symbol energy (nsym 0: off).  Tests of the best
+    alignment against the one half a symbol away come every nsym whole symbols from start_cnt on, up to nsym_max; a
+    test passes when E[best] >= gate * E[half]."""
+    _fields_ = [("start_cnt", C.c_int), ("nsym", C.c_int), ("nsym_max", C.c_int), ("pad", C.c_int), ("gate", C.c_double)]
+
+
+class BsyncState(C.Structure):
+    """gnsscorr_bsync_t: the bit-synchronisation detector's state of one channel.  Per offset o (a
+    symbol begins on the periods with cnt mod rate == o): E the energy of the whole symbols so far, sI / sQ / fill the
+    open symbol.  a0: cnt of the first counted row (armed); n: whole symbols per offset; done: 0 running, 1 decided
+    (best, synci = the biti of a symbol's last period, decided_cnt, ratio_last), 2 given up at nsym_max, 3 the loop
+    synchronised first."""
+    _fields_ = ([("E", C.c_double * 20), ("sI", C.c_double * 20), ("sQ", C.c_double * 20), ("ratio_last", C.c_double),
+                 ("a0", C.c_uint64), ("decided_cnt", C.c_uint64), ("fill", C.c_int * 20)] +
+                [(n, C.c_int) for n in ("armed", "n", "tests", "done", "best", "synci")])
+
+
 def mu_from_cn0(cn0_dbhz, rate, ctime):
     """The mean narrow-band / wide-band power ratio of a nav bit of `rate` periods of `ctime` seconds at that C/N0:
     (1 + rate*x) / (1 + x) with x = 10^(cn0/10) * ctime, the inverse of C/N0 = (mu - 1) / ((rate - mu) * ctime).  For
@@ -480,6 +498,7 @@ EXPORTS_GNSSCORR = [
     "gnsscorr_acq_run_subset", "gnsscorr_loop_start_from_acq", "gnsscorr_rx_start", "gnsscorr_rx_set",
     "gnsscorr_rx_step", "gnsscorr_rx_status", "gnsscorr_fec_run", "gnsscorr_sbasframe_replay",
     "gnsscorr_lock_run", "gnsscorr_rx_lock_set", "gnsscorr_rx_lock_status",
+    "gnsscorr_bsync_run", "gnsscorr_rx_bsync_set", "gnsscorr_rx_bsync_status",
     "gnsscorr_acq_set_coherent", "gnsscorr_acq_get_coherent", "gnsscorr_g1frame_replay",
     "gnsscorr_acq_set_bitedge", "gnsscorr_acq_get_bitedge", "gnsscorr_acq_fetch_edge",
     "gnsscorr_acq_set_refine", "gnsscorr_acq_get_refine", "gnsscorr_acq_fetch_fine",
@@ -580,6 +599,9 @@ def lib():
     L.gnsscorr_lock_run.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int, C.c_int]
     L.gnsscorr_rx_lock_set.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(LockPrm)]
     L.gnsscorr_rx_lock_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gnsscorr_bsync_run.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int, C.c_int]
+    L.gnsscorr_rx_bsync_set.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(BsyncPrm)]
+    L.gnsscorr_rx_bsync_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.gnsscorr_debug_fec_parts.argtypes = [C.c_void_p, C.c_int]   # (tools; not part of include/gnsscorr.h)
     L.gnsscorr_debug_poison.argtypes = [C.c_void_p, C.c_int]      # (tests; not part of include/gnsscorr.h)
     if hasattr(L, "gnsscorr_debug_cmb_stats"):                    # (tests; bound when present, like the symbols below)
@@ -1127,6 +1149,42 @@ class Engine:
             raise ValueError("lock_run: st must be a contiguous array of LockState")
         _check(self._L.gnsscorr_lock_run(self.h, prm.ctypes.data, rate.ctypes.data, st.ctypes.data, I.ctypes.data, Q.ctypes.data,
                                          log.ctypes.data, ndone.ctypes.data, cnt0.ctypes.data, nch, nper))
+        return st
+
+    # -- bit synchronisation by symbol energy
+    def rx_bsync_set(self, prm=None, ch0=0, nch=None):
+        """The bit-synchronisation detector's parameters for channels ch0 .. ch0+nch-1 (default: all from ch0 on): a
+        BsyncPrm, a dict of its fields, or None to switch it off."""
+        nch = len(self.channels) - ch0 if nch is None else nch
+        if isinstance(prm, dict):
+            prm = BsyncPrm(**prm)
+        _check(self._L.gnsscorr_rx_bsync_set(self.h, ch0, nch, C.byref(prm) if prm is not None else None))
+
+    def rx_bsync_status(self):
+        """(states, applied): numpy arrays [nch] of BsyncState and of int32 (gnsscorr_rx_bsync_status)."""
+        nch = len(self.channels)
+        st = np.zeros(nch, dtype=np.dtype(BsyncState))
+        applied = np.zeros(nch, np.int32)
+        _check(self._L.gnsscorr_rx_bsync_status(self.h, st.ctypes.data, applied.ctypes.data))
+        return st, applied
+
+    def bsync_run(self, prm, rate, st, I, Q, log, ndone, cnt0):
+        """gnsscorr_bsync_run: prm [nch] of BsyncPrm, rate [nch], st [nch] of BsyncState (updated in place), I / Q
+        [nch][nper], log [nch][nper] of TrkLog, ndone [nch], cnt0 [nch].  Returns st."""
+        I = np.ascontiguousarray(I, dtype=np.float64)
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        nch, nper = I.shape
+        prm = np.ascontiguousarray(prm, dtype=np.dtype(BsyncPrm))
+        rate = np.ascontiguousarray(rate, dtype=np.int32)
+        log = np.ascontiguousarray(log, dtype=np.dtype(TrkLog))
+        ndone = np.ascontiguousarray(ndone, dtype=np.int32)
+        cnt0 = np.ascontiguousarray(cnt0, dtype=np.uint64)
+        if not (Q.shape == log.shape == (nch, nper) and prm.shape == rate.shape == ndone.shape == cnt0.shape == st.shape == (nch,)):
+            raise ValueError("bsync_run: array shapes")
+        if st.dtype != np.dtype(BsyncState) or not st.flags.c_contiguous:
+            raise ValueError("bsync_run: st must be a contiguous array of BsyncState")
+        _check(self._L.gnsscorr_bsync_run(self.h, prm.ctypes.data, rate.ctypes.data, st.ctypes.data, I.ctypes.data, Q.ctypes.data,
+                                          log.ctypes.data, ndone.ctypes.data, cnt0.ctypes.data, nch, nper))
         return st
 
     # -- IF monitor

@@ -309,6 +309,13 @@ struct GcRx {
     GcDevBuf<gnsscorr_lock_t> dlock;               // [nch] the detector's state
     GcPinBuf<int> lock_list;                       // mapped: [nch] the channels of a launch (host writes, kernel reads)
     GcPinBuf<unsigned> lock_lost;                  // mapped: [nch] 1: the launch declared the channel lost (kernel writes)
+    // bit synchronisation by symbol energy (gnsscorr_bsync.hip), off until gnsscorr_rx_bsync_set
+    std::vector<gnsscorr_bsyncprm_t> bsyncprm;     // [nch]; nsym 0: the channel's detector is off
+    int bsync_on = 0;                              // channels whose detector is on
+    GcDevBuf<gnsscorr_bsyncprm_t> dbsyncprm;       // [nch]
+    GcDevBuf<gnsscorr_bsync_t> dbsync;             // [nch] the detector's state
+    GcDevBuf<int> dbsync_applied;                  // [nch] times the kernel preset the channel's loop state
+    GcPinBuf<int> bsync_list;                      // mapped: [nch] the channels of a launch (host writes, kernel reads)
 };
 
 // Frames, observables and epochs behind every step (gnsscorr_rx_nav_*, gnsscorr_rx.hip): the core object of
@@ -499,6 +506,8 @@ struct gnsscorr_ctx {
 
     // lock monitor (gnsscorr_lock.hip): staging of gnsscorr_lock_run's host arrays
     GcDevBuf<unsigned char> dlock_stage;
+    // bit synchronisation (gnsscorr_bsync.hip): staging of gnsscorr_bsync_run's host arrays
+    GcDevBuf<unsigned char> dbsync_stage;
 
     // timing
     int timing = 0;                                // 0: off, 1: every kernel, 2: only the two correlator kernels (trk_corr, acq_corr)
@@ -565,3 +574,6 @@ int gc_trk_run_loop(gnsscorr_ctx *ctx, int nperiod, const uint64_t *wp_ch);
 // gnsscorr_lock.hip: the lock monitor over the periods the last gc_trk_run_loop tracked, for the TRACK channels that have
 // it on; queues the launch and its event on the context's stream and does not wait
 int gc_rx_lock_launch(gnsscorr_ctx *ctx, int nperiod);
+// gnsscorr_bsync.hip: the bit-synchronisation detector over the same periods, for the TRACK channels that have it on;
+// queues the launch on the context's stream and does not wait
+int gc_rx_bsync_launch(gnsscorr_ctx *ctx, int nperiod);

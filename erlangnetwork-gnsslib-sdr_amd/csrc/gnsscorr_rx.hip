@@ -5,7 +5,8 @@
 // ones into the closed loop (acq_to_loop_kernel), and the closed loop itself, in which a channel that is not tracking
 // is handed a write position of 0 and so plans nothing (trk_step_tail_kernel, ref src/sdrtrk.c:26-30).  The way back,
 // TRACK -> SEARCH, which the reference lacks, is the lock monitor's (gnsscorr_lock.hip): it runs behind the closed loop
-// of a step, and the next step reads its verdicts.
+// of a step, and the next step reads its verdicts.  In front of it, bit synchronisation by symbol energy
+// (gnsscorr_bsync.hip) presets flagsync / synci of a tracking channel on the device, for the next step's first period.
 //
 // The reference sleeps ACQSLEEP = 2000 ms of wall time after a failed search (ref src/sdracq.c:57-60).  Here the pause
 // is counted on the sample clock -- retry_ms * 1e-3 * f_sf samples of the channel's ring from the write position of
@@ -48,6 +49,14 @@ extern "C" int gnsscorr_rx_start(gnsscorr_ctx *ctx, int retry_ms)
     rx.losses.assign(ctx->nch, 0);
     rx.lock_on = 0;
     rx.lock_listed.clear();
+    // so is the bit-synchronisation detector; the applied counts start over (behind a launch of an earlier schedule)
+    const gnsscorr_bsyncprm_t boff = {0, 0, 0, 0, 0.0};
+    rx.bsyncprm.assign(ctx->nch, boff);
+    rx.bsync_on = 0;
+    if (rx.dbsync_applied) {
+        GC_HIP(hipSetDevice(ctx->device));
+        GC_HIP(hipMemsetAsync(rx.dbsync_applied, 0, sizeof(int) * ctx->nch, ctx->stream));
+    }
     for (int i = 0; i < ctx->nch; i++) {
         rx.st[i].state = GNSSCORR_CH_SEARCH;
         rx.st[i].next_try = rx_first_try(ctx, i);
@@ -130,6 +139,9 @@ extern "C" int gnsscorr_rx_step(gnsscorr_ctx *ctx, int max_periods)
     std::vector<uint64_t> wp(nch);
     for (int i = 0; i < nch; i++) wp[i] = rx.st[i].state == GNSSCORR_CH_TRACK ? wpr[ctx->hdesc[i].ftype - 1] : 0;
     int rc = gc_trk_run_loop(ctx, max_periods, wp.data());
+    // 3b. bit synchronisation by symbol energy over the periods just tracked: a decision presets flagsync / synci in the
+    //     device's loop state, which the next step's first period sees; nothing waits for it here
+    if (!rc && rx.bsync_on) rc = gc_rx_bsync_launch(ctx, max_periods);
     if (rc || !rx.lock_on) return rc;
     // 4. the lock monitor over the periods just tracked, behind the loop's last tail; nothing waits for it here
     return gc_rx_lock_launch(ctx, max_periods);

@@ -85,8 +85,9 @@ int  gnsscorr_sync(gnsscorr_ctx *ctx);
  * A running schedule (gnsscorr_rx_start done) holds positions of the old
  * stream in next_try, acq_wrpos and the TRACK channels' buffloc: re-creating a
  * ring that a channel reads switches the schedule off, and gnsscorr_rx_step,
- * gnsscorr_rx_set, gnsscorr_rx_status, gnsscorr_rx_lock_set and
- * gnsscorr_rx_lock_status return GNSSCORR_ESTATE until the next
+ * gnsscorr_rx_set, gnsscorr_rx_status, gnsscorr_rx_lock_set,
+ * gnsscorr_rx_lock_status, gnsscorr_rx_bsync_set and gnsscorr_rx_bsync_status
+ * return GNSSCORR_ESTATE until the next
  * gnsscorr_rx_start.  A ring no channel reads leaves the schedule alone. */
 int  gnsscorr_ring_create(gnsscorr_ctx *ctx, int ftype, int dtype,
                           uint64_t ringlen, void *devmem);
@@ -141,7 +142,8 @@ typedef struct {
  * the context is in flight, and then starts the new set from nothing: tracking
  * and loop states zero, no loop constants (gnsscorr_loop_set), the acquisition
  * settings back at ncoh 1 / estep 0 / nref 0, no search results, the schedule
- * and the lock monitor off (GNSSCORR_ESTATE until gnsscorr_rx_start), and the
+ * the lock monitor and the bit-synchronisation detector off (GNSSCORR_ESTATE
+ * until gnsscorr_rx_start), and the
  * IF monitor's last run gone: gnsscorr_spec_fetch returns GNSSCORR_ESTATE
  * until the next gnsscorr_spec_run.  The rings, their contents and write
  * positions stay.  A new set computes bit for bit what it computes on a fresh
@@ -716,6 +718,56 @@ int  gnsscorr_rx_lock_set(gnsscorr_ctx *ctx, int ch0, int nch, const gnsscorr_lo
  * has sent each channel back to SEARCH.  Either may be NULL.  Synchronises. */
 int  gnsscorr_rx_lock_status(gnsscorr_ctx *ctx, gnsscorr_lock_t *st, int *losses);
 
+/* ---- bit synchronisation by symbol energy: preset flagsync / synci from the first tracked periods ----
+ * checksync() starts only after cnt > 2000, and its shift-register branch (PRN > 5) takes the first `rate` prompts of
+ * one sign for a symbol, wherever the true edge is.  The detector is the standard estimator instead: over the tracked
+ * periods from start_cnt on, the prompt sums are added coherently over one symbol at each of the `rate` alignments, and
+ * the alignment with the most energy wins when it beats the alignment half a symbol away by the factor `gate`.
+ * Opt-in per channel; with it off for every channel gnsscorr_rx_step launches nothing new.
+ * The detector (every arithmetic statement one IEEE double operation, no contraction), per channel over
+ * the rows e < ndone of one closed-loop run in period order, c = cnt0 + e, (I, Q) = tap 0 of the row's II / QQ,
+ * R = the channel's rate:
+ *   1. c == 0: the state is zeroed (the first period behind a hand-over).
+ *   2. done != 0: nothing more is read.
+ *   3. the row's flagsync != 0: done = 3 (the loop synchronised by its own rule, or was preset); stop.
+ *   4. c < start_cnt: the row does not count.
+ *   5. the first counted row: armed = 1, a0 = c.
+ *   6. for every offset o = 0 .. R-1 in ascending order: if fill[o] > 0 or c mod R == o: sI[o] += I, sQ[o] += Q,
+ *      fill[o]++; when fill[o] == R: E[o] = E[o] + (sI[o]*sI[o] + sQ[o]*sQ[o]), sI[o] = sQ[o] = 0, fill[o] = 0.
+ *      Offsets are in biti units: offset o means a symbol begins on the periods with cnt mod R == o.
+ *   7. with L = c - a0 + 1: when (L + 1) mod R == 0 every offset has completed exactly n = (L + 1)/R - 1 whole symbols.
+ *      If n >= 1 and n mod nsym == 0, a test: o* = the offset with the largest E (lowest index on ties),
+ *      h = (o* + R/2) mod R (integer division), tests++, ratio_last = E[o*]/E[h] when E[h] > 0, else 0.  Pass when
+ *      E[o*] > 0 and E[o*] >= gate*E[h] (the product, not the quotient): done = 1, best = o*,
+ *      synci = (o* + R - 1) mod R (the biti of a symbol's last period, what checkbit() expects), decided_cnt = c.
+ *      Otherwise, if n >= nsym_max: done = 2, the channel is given up and the reference's rule stays in charge.
+ * The state does not depend on how the stream is cut into runs. */
+typedef struct { int start_cnt, nsym, nsym_max, pad; double gate; } gnsscorr_bsyncprm_t;
+typedef struct { double E[20], sI[20], sQ[20]; double ratio_last; uint64_t a0, decided_cnt;
+                 int fill[20]; int armed, n, tests, done, best, synci; } gnsscorr_bsync_t;
+/* Op-level: the detector's kernel over host arrays, the twin of gnsscorr_lock_run.  prm[nch] (nsym 0: the channel's
+ * detector is off and its state stays), rate[nch] (2..20), st[nch] in-out, I / Q [nch][nper], log[nch][nper] (only
+ * flagsync is read), ndone[nch] (0..nper), cnt0[nch].  start_cnt >= 0, 1 <= nsym <= nsym_max <= 4096, gate >= 1:
+ * otherwise GNSSCORR_EINVAL naming the field, st untouched.  Writes no loop state.  Runs on the context's stream and
+ * synchronises it; timer name "rx_bsync". */
+int  gnsscorr_bsync_run(gnsscorr_ctx *ctx, const gnsscorr_bsyncprm_t *prm, const int *rate, gnsscorr_bsync_t *st,
+                        const double *I, const double *Q, const gnsscorr_trklog_t *log, const int *ndone,
+                        const uint64_t *cnt0, int nch, int nper);
+/* The detector's parameters for channels ch0 .. ch0+nch-1 of the schedule (one prm for all of them); prm == NULL or
+ * nsym == 0 switches it off for them.  Their detector state is zeroed.  gnsscorr_rx_start and gnsscorr_set_channels
+ * leave it off for all; without gnsscorr_rx_start GNSSCORR_ESTATE.  With the detector on, gnsscorr_rx_step
+ *   3b. behind the closed loop (and in front of the lock monitor) queues the kernel over the periods this step tracked
+ *       for the TRACK channels that have it on, without waiting for it.  A channel whose done became 1 in that launch
+ *       and whose device loop state (the state behind the step's last period) still has flagsync == 0 gets
+ *       flagsync = 1 and synci written into its gnsscorr_loop_t by the same kernel, and its applied count goes up;
+ *       navcnt, bitIP, biti and bitsync[] stay, as checksync()'s own success leaves them.
+ * A decision therefore takes effect with the first period of the next step: the moment depends on how the stream is
+ * cut into steps, as the lock monitor's verdicts do; the detector's state does not. */
+int  gnsscorr_rx_bsync_set(gnsscorr_ctx *ctx, int ch0, int nch, const gnsscorr_bsyncprm_t *prm);
+/* st[nch]: the detector states on the device, behind whatever the stream still runs; applied[nch]: how often the
+ * schedule preset each channel.  Either may be NULL.  Synchronises. */
+int  gnsscorr_rx_bsync_status(gnsscorr_ctx *ctx, gnsscorr_bsync_t *st, int *applied);
+
 /* ---- frames, observables and epochs behind every step ------------------------
  * The loop a caller writes around a step's rows, as a library object: one nav state per
  * channel -- the frame state of its code type and the observables' state -- plus one gnsscorr_sync_t.  Plain host code
@@ -839,7 +891,7 @@ int  gnsscorr_spec_fetch(gnsscorr_ctx *ctx, double *s, size_t s_cap,
 /* per-kernel launch timing: enable, run, then read the accumulated HIP-event
  * time of the named kernel ("trk_corr", "trk_plan", "trk_spec", "trk_expand",
  * "trk_finish", "acq_fwd", "acq_corr", "acq_code", "acq_final", "spec_psd",
- * "spec_sum", "spec_hist", "fec_viterbi27", "rx_lock", "trk_prompt").
+ * "spec_sum", "spec_hist", "fec_viterbi27", "rx_lock", "rx_bsync", "trk_prompt").
  * on = 1: every kernel; on = 2: only the two correlator kernels ("trk_corr",
  * "acq_corr"), leaving the planner and tables streams free of events; 0: off */
 int  gnsscorr_timing_enable(gnsscorr_ctx *ctx, int on);
