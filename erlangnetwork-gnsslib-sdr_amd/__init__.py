@@ -412,6 +412,34 @@ class BsyncState(C.Structure):
                 [(n, C.c_int) for n in ("armed", "n", "tests", "done", "best", "synci")])
 
 
+class CfmPrm(C.Structure):
+    """gnsscorr_cfmprm_t: the parameters of the correlation monitor (kbits 0: off).  Windows of kbits whole nav bits
+    behind the first skip_bits; a window is bad when its prompt sum is not positive or a pair j <= npair has
+    |delta - dref| > dtol or |ratio - rref| > rtol; nbad bad windows in a row raise the alarm."""
+    _fields_ = [("kbits", C.c_int), ("skip_bits", C.c_int), ("nbad", C.c_int), ("npair", C.c_int), ("dtol", C.c_double),
+                ("rtol", C.c_double), ("dref", C.c_double * 16), ("rref", C.c_double * 16)]
+
+
+class CfmState(C.Structure):
+    """gnsscorr_cfm_t: the correlation monitor's state of one channel.  Per tap t (P, E1, L1, E2, L2,
+    ...): sI / sQ the open bit, aI / aQ / aP the open window (data-wiped sums and power), cfI / cfQ / cfP the last
+    closed window; per pair j: delta[j-1], ratio[j-1] of that window.  win_cnt: cnt of the period that closed it; bits:
+    whole bits seen; nbad: bad windows in a row; alarm, alarms, windows, worst_pair (the first failing pair, 0 none)."""
+    _fields_ = ([(n, C.c_double * 33) for n in ("sI", "sQ", "aI", "aQ", "aP", "cfI", "cfQ", "cfP")] +
+                [("delta", C.c_double * 16), ("ratio", C.c_double * 16), ("win_cnt", C.c_uint64)] +
+                [(n, C.c_int) for n in ("open", "n", "k", "bits", "nbad", "alarm", "alarms", "windows", "worst_pair", "pad")])
+
+
+def cfm_prm(kbits=0, skip_bits=0, nbad=1, npair=1, dtol=0.0, rtol=0.0, dref=(), rref=()):
+    """A CfmPrm from plain values; dref / rref shorter than 16 are filled with 0."""
+    p = CfmPrm(kbits=kbits, skip_bits=skip_bits, nbad=nbad, npair=npair, dtol=dtol, rtol=rtol)
+    for j, v in enumerate(dref):
+        p.dref[j] = v
+    for j, v in enumerate(rref):
+        p.rref[j] = v
+    return p
+
+
 def mu_from_cn0(cn0_dbhz, rate, ctime):
     """The mean narrow-band / wide-band power ratio of a nav bit of `rate` periods of `ctime` seconds at that C/N0:
     (1 + rate*x) / (1 + x) with x = 10^(cn0/10) * ctime, the inverse of C/N0 = (mu - 1) / ((rate - mu) * ctime).  For
@@ -499,6 +527,7 @@ EXPORTS_GNSSCORR = [
     "gnsscorr_rx_step", "gnsscorr_rx_status", "gnsscorr_fec_run", "gnsscorr_sbasframe_replay",
     "gnsscorr_lock_run", "gnsscorr_rx_lock_set", "gnsscorr_rx_lock_status",
     "gnsscorr_bsync_run", "gnsscorr_rx_bsync_set", "gnsscorr_rx_bsync_status",
+    "gnsscorr_cfm_run", "gnsscorr_rx_cfm_set", "gnsscorr_rx_cfm_status",
     "gnsscorr_acq_set_coherent", "gnsscorr_acq_get_coherent", "gnsscorr_g1frame_replay",
     "gnsscorr_acq_set_bitedge", "gnsscorr_acq_get_bitedge", "gnsscorr_acq_fetch_edge",
     "gnsscorr_acq_set_refine", "gnsscorr_acq_get_refine", "gnsscorr_acq_fetch_fine",
@@ -602,6 +631,9 @@ def lib():
     L.gnsscorr_bsync_run.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int, C.c_int]
     L.gnsscorr_rx_bsync_set.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(BsyncPrm)]
     L.gnsscorr_rx_bsync_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gnsscorr_cfm_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int]
+    L.gnsscorr_rx_cfm_set.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(CfmPrm)]
+    L.gnsscorr_rx_cfm_status.argtypes = [C.c_void_p, C.c_void_p]
     L.gnsscorr_debug_fec_parts.argtypes = [C.c_void_p, C.c_int]   # (tools; not part of include/gnsscorr.h)
     L.gnsscorr_debug_poison.argtypes = [C.c_void_p, C.c_int]      # (tests; not part of include/gnsscorr.h)
     if hasattr(L, "gnsscorr_debug_cmb_stats"):                    # (tests; bound when present, like the symbols below)
@@ -1185,6 +1217,41 @@ class Engine:
             raise ValueError("bsync_run: st must be a contiguous array of BsyncState")
         _check(self._L.gnsscorr_bsync_run(self.h, prm.ctypes.data, rate.ctypes.data, st.ctypes.data, I.ctypes.data, Q.ctypes.data,
                                           log.ctypes.data, ndone.ctypes.data, cnt0.ctypes.data, nch, nper))
+        return st
+
+    # -- correlation monitor
+    def rx_cfm_set(self, prm=None, ch0=0, nch=None):
+        """The correlation monitor's parameters for channels ch0 .. ch0+nch-1 (default: all from ch0 on): a CfmPrm, a
+        dict of its fields (dref / rref: sequences of up to 16 values, the rest 0), or None to switch it off."""
+        nch = len(self.channels) - ch0 if nch is None else nch
+        if isinstance(prm, dict):
+            prm = cfm_prm(**prm)
+        _check(self._L.gnsscorr_rx_cfm_set(self.h, ch0, nch, C.byref(prm) if prm is not None else None))
+
+    def rx_cfm_status(self):
+        """numpy array [nch] of CfmState (gnsscorr_rx_cfm_status)."""
+        st = np.zeros(len(self.channels), dtype=np.dtype(CfmState))
+        _check(self._L.gnsscorr_rx_cfm_status(self.h, st.ctypes.data))
+        return st
+
+    def cfm_run(self, prm, rate, corrn, st, II, QQ, log, ndone, cnt0):
+        """gnsscorr_cfm_run: prm [nch] of CfmPrm, rate [nch], corrn, st [nch] of CfmState (updated in place), II / QQ
+        [nch][nper][1+2*corrn], log [nch][nper] of TrkLog, ndone [nch], cnt0 [nch].  Returns st."""
+        II = np.ascontiguousarray(II, dtype=np.float64)
+        QQ = np.ascontiguousarray(QQ, dtype=np.float64)
+        nch, nper, ntap = II.shape
+        prm = np.ascontiguousarray(prm, dtype=np.dtype(CfmPrm))
+        rate = np.ascontiguousarray(rate, dtype=np.int32)
+        log = np.ascontiguousarray(log, dtype=np.dtype(TrkLog))
+        ndone = np.ascontiguousarray(ndone, dtype=np.int32)
+        cnt0 = np.ascontiguousarray(cnt0, dtype=np.uint64)
+        if not (QQ.shape == II.shape and ntap == 1 + 2 * corrn and log.shape == (nch, nper) and
+                prm.shape == rate.shape == ndone.shape == cnt0.shape == st.shape == (nch,)):
+            raise ValueError("cfm_run: array shapes")
+        if st.dtype != np.dtype(CfmState) or not st.flags.c_contiguous:
+            raise ValueError("cfm_run: st must be a contiguous array of CfmState")
+        _check(self._L.gnsscorr_cfm_run(self.h, prm.ctypes.data, rate.ctypes.data, corrn, st.ctypes.data, II.ctypes.data,
+                                        QQ.ctypes.data, log.ctypes.data, ndone.ctypes.data, cnt0.ctypes.data, nch, nper))
         return st
 
     # -- IF monitor

@@ -316,6 +316,12 @@ struct GcRx {
     GcDevBuf<gnsscorr_bsync_t> dbsync;             // [nch] the detector's state
     GcDevBuf<int> dbsync_applied;                  // [nch] times the kernel preset the channel's loop state
     GcPinBuf<int> bsync_list;                      // mapped: [nch] the channels of a launch (host writes, kernel reads)
+    // the correlation monitor (gnsscorr_cfm.hip), off until gnsscorr_rx_cfm_set
+    std::vector<gnsscorr_cfmprm_t> cfmprm;         // [nch]; kbits 0: the channel's monitor is off
+    int cfm_on = 0;                                // channels whose monitor is on
+    GcDevBuf<gnsscorr_cfmprm_t> dcfmprm;           // [nch]
+    GcDevBuf<gnsscorr_cfm_t> dcfm;                 // [nch] the monitor's state
+    GcPinBuf<int> cfm_list;                        // mapped: [nch] the channels of a launch (host writes, kernel reads)
 };
 
 // Frames, observables and epochs behind every step (gnsscorr_rx_nav_*, gnsscorr_rx.hip): the core object of
@@ -508,6 +514,8 @@ struct gnsscorr_ctx {
     GcDevBuf<unsigned char> dlock_stage;
     // bit synchronisation (gnsscorr_bsync.hip): staging of gnsscorr_bsync_run's host arrays
     GcDevBuf<unsigned char> dbsync_stage;
+    // correlation monitor (gnsscorr_cfm.hip): staging of gnsscorr_cfm_run's host arrays
+    GcDevBuf<unsigned char> dcfm_stage;
 
     // timing
     int timing = 0;                                // 0: off, 1: every kernel, 2: only the two correlator kernels (trk_corr, acq_corr)
@@ -577,3 +585,6 @@ int gc_rx_lock_launch(gnsscorr_ctx *ctx, int nperiod);
 // gnsscorr_bsync.hip: the bit-synchronisation detector over the same periods, for the TRACK channels that have it on;
 // queues the launch on the context's stream and does not wait
 int gc_rx_bsync_launch(gnsscorr_ctx *ctx, int nperiod);
+// gnsscorr_cfm.hip: the correlation monitor over the same periods, for the TRACK channels that have it on; queues the
+// launch on the context's stream, waits for nothing and records no event
+int gc_rx_cfm_launch(gnsscorr_ctx *ctx, int nperiod);

@@ -7,6 +7,8 @@
 // TRACK -> SEARCH, which the reference lacks, is the lock monitor's (gnsscorr_lock.hip): it runs behind the closed loop
 // of a step, and the next step reads its verdicts.  In front of it, bit synchronisation by symbol energy
 // (gnsscorr_bsync.hip) presets flagsync / synci of a tracking channel on the device, for the next step's first period.
+// Behind both, the correlation monitor (gnsscorr_cfm.hip) sums every tap over whole nav bits and tests the shape of the
+// correlation function; it reports only.
 //
 // The reference sleeps ACQSLEEP = 2000 ms of wall time after a failed search (ref src/sdracq.c:57-60).  Here the pause
 // is counted on the sample clock -- retry_ms * 1e-3 * f_sf samples of the channel's ring from the write position of
@@ -56,6 +58,15 @@ extern "C" int gnsscorr_rx_start(gnsscorr_ctx *ctx, int retry_ms)
     if (rx.dbsync_applied) {
         GC_HIP(hipSetDevice(ctx->device));
         GC_HIP(hipMemsetAsync(rx.dbsync_applied, 0, sizeof(int) * ctx->nch, ctx->stream));
+    }
+    // and the correlation monitor; its states start over (behind a launch of an earlier schedule)
+    gnsscorr_cfmprm_t coff;
+    memset(&coff, 0, sizeof(coff));
+    rx.cfmprm.assign(ctx->nch, coff);
+    rx.cfm_on = 0;
+    if (rx.dcfm) {
+        GC_HIP(hipSetDevice(ctx->device));
+        GC_HIP(hipMemsetAsync(rx.dcfm, 0, sizeof(gnsscorr_cfm_t) * ctx->nch, ctx->stream));
     }
     for (int i = 0; i < ctx->nch; i++) {
         rx.st[i].state = GNSSCORR_CH_SEARCH;
@@ -142,9 +153,11 @@ extern "C" int gnsscorr_rx_step(gnsscorr_ctx *ctx, int max_periods)
     // 3b. bit synchronisation by symbol energy over the periods just tracked: a decision presets flagsync / synci in the
     //     device's loop state, which the next step's first period sees; nothing waits for it here
     if (!rc && rx.bsync_on) rc = gc_rx_bsync_launch(ctx, max_periods);
-    if (rc || !rx.lock_on) return rc;
     // 4. the lock monitor over the periods just tracked, behind the loop's last tail; nothing waits for it here
-    return gc_rx_lock_launch(ctx, max_periods);
+    if (!rc && rx.lock_on) rc = gc_rx_lock_launch(ctx, max_periods);
+    // 5. the correlation monitor over the same periods: it reports only (gnsscorr_rx_cfm_status), so no step reads it
+    if (!rc && rx.cfm_on) rc = gc_rx_cfm_launch(ctx, max_periods);
+    return rc;
 }
 
 extern "C" int gnsscorr_rx_status(gnsscorr_ctx *ctx, gnsscorr_rxstat_t *st)

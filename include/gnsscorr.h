@@ -86,7 +86,8 @@ int  gnsscorr_sync(gnsscorr_ctx *ctx);
  * stream in next_try, acq_wrpos and the TRACK channels' buffloc: re-creating a
  * ring that a channel reads switches the schedule off, and gnsscorr_rx_step,
  * gnsscorr_rx_set, gnsscorr_rx_status, gnsscorr_rx_lock_set,
- * gnsscorr_rx_lock_status, gnsscorr_rx_bsync_set and gnsscorr_rx_bsync_status
+ * gnsscorr_rx_lock_status, gnsscorr_rx_bsync_set, gnsscorr_rx_bsync_status,
+ * gnsscorr_rx_cfm_set and gnsscorr_rx_cfm_status
  * return GNSSCORR_ESTATE until the next
  * gnsscorr_rx_start.  A ring no channel reads leaves the schedule alone. */
 int  gnsscorr_ring_create(gnsscorr_ctx *ctx, int ftype, int dtype,
@@ -142,8 +143,9 @@ typedef struct {
  * the context is in flight, and then starts the new set from nothing: tracking
  * and loop states zero, no loop constants (gnsscorr_loop_set), the acquisition
  * settings back at ncoh 1 / estep 0 / nref 0, no search results, the schedule
- * the lock monitor and the bit-synchronisation detector off (GNSSCORR_ESTATE
- * until gnsscorr_rx_start), and the
+ * the lock monitor, the bit-synchronisation detector and the correlation
+ * monitor off (GNSSCORR_ESTATE until gnsscorr_rx_start, and then off for every
+ * channel until gnsscorr_rx_lock_set / _bsync_set / _cfm_set), and the
  * IF monitor's last run gone: gnsscorr_spec_fetch returns GNSSCORR_ESTATE
  * until the next gnsscorr_spec_run.  The rings, their contents and write
  * positions stay.  A new set computes bit for bit what it computes on a fresh
@@ -768,6 +770,65 @@ int  gnsscorr_rx_bsync_set(gnsscorr_ctx *ctx, int ch0, int nch, const gnsscorr_b
  * schedule preset each channel.  Either may be NULL.  Synchronises. */
 int  gnsscorr_rx_bsync_status(gnsscorr_ctx *ctx, gnsscorr_bsync_t *st, int *applied);
 
+/* ---- correlation monitor: data-wiped tap sums and signal quality tests on every tap ----
+ * The engine computes up to GNSSCORR_MAXTAPS correlator taps per channel and period, and the loops read the prompt and
+ * one early / late pair.  The monitor sums every tap over whole nav bits, wipes the data bit off, adds kbits bits up
+ * to a window -- the shape of the correlation function, which the tap sums of gnsscorr_trk_fetch_sums cannot give
+ * because the data flips cancel there -- and tests each window's early-minus-late (delta) and early-plus-late (ratio)
+ * metrics per tap pair against nominal values: multipath and spoofing detection (signal quality monitoring).  Opt-in
+ * per channel; it reports and never acts: it writes no loop, tracking or schedule state.
+ * The monitor (every arithmetic statement one IEEE double operation, no contraction, sums in period
+ * order, window sums in bit order), per channel with R = gnsscorr_loop_t.rate (2..20), T = 1 + 2*corrn taps in the
+ * order {P, E1, L1, E2, L2, ...}, I_t[e] / Q_t[e] = tap t of row e of gnsscorr_trk_fetch's II / QQ (II is the in-phase
+ * arm, the one pll() and checkbit() read), flagsync[e] / navbit[e] of the log row, c = cnt0 + e:
+ *   for e in 0 .. ndone-1:
+ *     if c == 0: st = all zero                          (first period behind a hand-over)
+ *     if flagsync[e] == 0: continue
+ *     if st.open: for t < T: sI[t] += I_t[e], sQ[t] += Q_t[e];  n += 1
+ *     if navbit[e] != 0:                                (checkbit() closed a bit in this period)
+ *       if st.open and n == R:                          (a whole bit; any other length is dropped)
+ *         bits += 1
+ *         if bits > skip_bits:
+ *           d = +1.0 if navbit[e] > 0 else -1.0
+ *           for t < T: aI[t] += d*sI[t], aQ[t] += d*sQ[t], aP[t] += (sI[t]*sI[t] + sQ[t]*sQ[t])
+ *           k += 1
+ *           if k == kbits:                              (a window closes)
+ *             cfI, cfQ, cfP = aI, aQ, aP;  win_cnt = c;  windows += 1;  P = cfI[0]
+ *             for j in 1 .. 16: if j <= corrn and P > 0: delta[j-1] = (cfI[2j-1] - cfI[2j]) / P,
+ *                                                        ratio[j-1] = (cfI[2j-1] + cfI[2j]) / P;  else both 0.0
+ *             bad = not (P > 0);  worst = 0
+ *             for j in 1 .. npair (ascending): if |delta[j-1] - dref[j-1]| > dtol or |ratio[j-1] - rref[j-1]| > rtol:
+ *               bad = true, and worst = j if worst == 0
+ *             worst_pair = worst;  nbad = nbad + 1 if bad else 0;  alarm = 1 if nbad >= prm.nbad else 0
+ *             alarms += alarm;  aI = aQ = aP = 0.0 for all t;  k = 0
+ *       open = 1;  n = 0;  sI[t] = sQ[t] = 0.0 for all t
+ * The state does not depend on how the stream is cut into runs.  The bits just behind bit synchronisation belong to
+ * skip_bits: the switch of the loop filters throws the code loop off for about 3.5 s. */
+typedef struct { int kbits, skip_bits, nbad, npair; double dtol, rtol, dref[16], rref[16]; } gnsscorr_cfmprm_t;
+typedef struct { double sI[33], sQ[33], aI[33], aQ[33], aP[33], cfI[33], cfQ[33], cfP[33], delta[16], ratio[16];
+                 uint64_t win_cnt; int open, n, k, bits, nbad, alarm, alarms, windows, worst_pair, pad; } gnsscorr_cfm_t;
+/* Op-level: the monitor's kernel over host arrays, the twin of gnsscorr_bsync_run.  prm[nch] (kbits 0: the channel's
+ * monitor is off and its state stays), rate[nch] (2..20), corrn (1..16, one for all channels), st[nch] in-out, II / QQ
+ * [nch][nper][1+2*corrn], log[nch][nper] (only flagsync and navbit are read), ndone[nch] (0..nper), cnt0[nch].
+ * kbits 1..4096, skip_bits >= 0, nbad >= 1, 1 <= npair <= corrn, dtol > 0, rtol > 0, dref / rref finite: otherwise
+ * GNSSCORR_EINVAL naming the channel and the field, st untouched.  One staged transfer, the kernel on the context's
+ * stream, one synchronisation; timer name "rx_cfm". */
+int  gnsscorr_cfm_run(gnsscorr_ctx *ctx, const gnsscorr_cfmprm_t *prm, const int *rate, int corrn, gnsscorr_cfm_t *st,
+                      const double *II, const double *QQ, const gnsscorr_trklog_t *log, const int *ndone,
+                      const uint64_t *cnt0, int nch, int nper);
+/* The monitor's parameters for channels ch0 .. ch0+nch-1 of the schedule (one prm for all of them); prm == NULL or
+ * kbits == 0 switches it off for them.  Their monitor state is zeroed.  gnsscorr_rx_start and gnsscorr_set_channels
+ * leave it off for all; without gnsscorr_rx_start GNSSCORR_ESTATE.  With the monitor on, gnsscorr_rx_step
+ *   5. behind the closed loop, the bit-synchronisation detector and the lock monitor's launch queues the kernel over
+ *      the periods this step tracked for the TRACK channels that have it on.  It reads the device's correlator outputs,
+ *      log, period counts and the loop states' rate / cnt in place, waits for nothing and records no event.
+ * With the monitor off for every channel a step issues exactly the launches and synchronisations it issues without it.
+ * A channel that is re-acquired restarts cnt at 0, which zeroes its monitor state. */
+int  gnsscorr_rx_cfm_set(gnsscorr_ctx *ctx, int ch0, int nch, const gnsscorr_cfmprm_t *prm);
+/* st[nch]: the monitor states on the device, behind whatever the stream still runs (zeros when the monitor has never
+ * been on).  Synchronises. */
+int  gnsscorr_rx_cfm_status(gnsscorr_ctx *ctx, gnsscorr_cfm_t *st);
+
 /* ---- frames, observables and epochs behind every step ------------------------
  * The loop a caller writes around a step's rows, as a library object: one nav state per
  * channel -- the frame state of its code type and the observables' state -- plus one gnsscorr_sync_t.  Plain host code
@@ -891,7 +952,8 @@ int  gnsscorr_spec_fetch(gnsscorr_ctx *ctx, double *s, size_t s_cap,
 /* per-kernel launch timing: enable, run, then read the accumulated HIP-event
  * time of the named kernel ("trk_corr", "trk_plan", "trk_spec", "trk_expand",
  * "trk_finish", "acq_fwd", "acq_corr", "acq_code", "acq_final", "spec_psd",
- * "spec_sum", "spec_hist", "fec_viterbi27", "rx_lock", "rx_bsync", "trk_prompt").
+ * "spec_sum", "spec_hist", "fec_viterbi27", "rx_lock", "rx_bsync", "rx_cfm",
+ * "trk_prompt").
  * on = 1: every kernel; on = 2: only the two correlator kernels ("trk_corr",
  * "acq_corr"), leaving the planner and tables streams free of events; 0: off */
 int  gnsscorr_timing_enable(gnsscorr_ctx *ctx, int on);
