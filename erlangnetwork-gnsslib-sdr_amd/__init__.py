@@ -1147,14 +1147,36 @@ class Engine:
         _check(self._L.gnsscorr_trk_fetch_prompt(self.h, II0.ctypes.data, QQ0.ctypes.data))
         return II0, QQ0
 
+    # -- the schedule's stages: what the three rx_*_set and the three *_run wrappers share
+    def _rx_stage_set(self, fn, make, prm, ch0, nch):
+        nch = len(self.channels) - ch0 if nch is None else nch
+        if isinstance(prm, dict):
+            prm = make(**prm)
+        _check(fn(self.h, ch0, nch, C.byref(prm) if prm is not None else None))
+
+    @staticmethod
+    def _stage_arrays(who, prm_t, st_t, prm, rate, st, I, Q, log, ndone, cnt0, taps=()):
+        """The *_run arguments as the library reads them, I / Q [nch][nper] + taps; shapes and st checked."""
+        I = np.ascontiguousarray(I, dtype=np.float64)
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        nch, nper = I.shape[:2]
+        prm = np.ascontiguousarray(prm, dtype=np.dtype(prm_t))
+        rate = np.ascontiguousarray(rate, dtype=np.int32)
+        log = np.ascontiguousarray(log, dtype=np.dtype(TrkLog))
+        ndone = np.ascontiguousarray(ndone, dtype=np.int32)
+        cnt0 = np.ascontiguousarray(cnt0, dtype=np.uint64)
+        if not (Q.shape == I.shape == (nch, nper) + taps and log.shape == (nch, nper) and
+                prm.shape == rate.shape == ndone.shape == cnt0.shape == st.shape == (nch,)):
+            raise ValueError("%s: array shapes" % who)
+        if st.dtype != np.dtype(st_t) or not st.flags.c_contiguous:
+            raise ValueError("%s: st must be a contiguous array of %s" % (who, st_t.__name__))
+        return prm, rate, I, Q, log, ndone, cnt0, nch, nper
+
     # -- lock monitor
     def rx_lock_set(self, prm=None, ch0=0, nch=None):
         """The lock monitor's parameters for channels ch0 .. ch0+nch-1 (default: all from ch0 on): a LockPrm, a dict of
         its fields, or None to switch it off."""
-        nch = len(self.channels) - ch0 if nch is None else nch
-        if isinstance(prm, dict):
-            prm = LockPrm(**prm)
-        _check(self._L.gnsscorr_rx_lock_set(self.h, ch0, nch, C.byref(prm) if prm is not None else None))
+        self._rx_stage_set(self._L.gnsscorr_rx_lock_set, LockPrm, prm, ch0, nch)
 
     def rx_lock_status(self):
         """(states, losses): numpy arrays [nch] of LockState and of int32 (gnsscorr_rx_lock_status)."""
@@ -1167,30 +1189,16 @@ class Engine:
     def lock_run(self, prm, rate, st, I, Q, log, ndone, cnt0):
         """gnsscorr_lock_run: prm [nch] of LockPrm, rate [nch], st [nch] of LockState (updated in place), I / Q
         [nch][nper], log [nch][nper] of TrkLog, ndone [nch], cnt0 [nch].  Returns st."""
-        I = np.ascontiguousarray(I, dtype=np.float64)
-        Q = np.ascontiguousarray(Q, dtype=np.float64)
-        nch, nper = I.shape
-        prm = np.ascontiguousarray(prm, dtype=np.dtype(LockPrm))
-        rate = np.ascontiguousarray(rate, dtype=np.int32)
-        log = np.ascontiguousarray(log, dtype=np.dtype(TrkLog))
-        ndone = np.ascontiguousarray(ndone, dtype=np.int32)
-        cnt0 = np.ascontiguousarray(cnt0, dtype=np.uint64)
-        if not (Q.shape == log.shape == (nch, nper) and prm.shape == rate.shape == ndone.shape == cnt0.shape == st.shape == (nch,)):
-            raise ValueError("lock_run: array shapes")
-        if st.dtype != np.dtype(LockState) or not st.flags.c_contiguous:
-            raise ValueError("lock_run: st must be a contiguous array of LockState")
+        prm, rate, I, Q, log, ndone, cnt0, nch, nper = self._stage_arrays("lock_run", LockPrm, LockState, prm, rate, st, I, Q, log, ndone, cnt0)
         _check(self._L.gnsscorr_lock_run(self.h, prm.ctypes.data, rate.ctypes.data, st.ctypes.data, I.ctypes.data, Q.ctypes.data,
-                                         log.ctypes.data, ndone.ctypes.data, cnt0.ctypes.data, nch, nper))
+               log.ctypes.data, ndone.ctypes.data, cnt0.ctypes.data, nch, nper))
         return st
 
     # -- bit synchronisation by symbol energy
     def rx_bsync_set(self, prm=None, ch0=0, nch=None):
         """The bit-synchronisation detector's parameters for channels ch0 .. ch0+nch-1 (default: all from ch0 on): a
         BsyncPrm, a dict of its fields, or None to switch it off."""
-        nch = len(self.channels) - ch0 if nch is None else nch
-        if isinstance(prm, dict):
-            prm = BsyncPrm(**prm)
-        _check(self._L.gnsscorr_rx_bsync_set(self.h, ch0, nch, C.byref(prm) if prm is not None else None))
+        self._rx_stage_set(self._L.gnsscorr_rx_bsync_set, BsyncPrm, prm, ch0, nch)
 
     def rx_bsync_status(self):
         """(states, applied): numpy arrays [nch] of BsyncState and of int32 (gnsscorr_rx_bsync_status)."""
@@ -1203,30 +1211,16 @@ class Engine:
     def bsync_run(self, prm, rate, st, I, Q, log, ndone, cnt0):
         """gnsscorr_bsync_run: prm [nch] of BsyncPrm, rate [nch], st [nch] of BsyncState (updated in place), I / Q
         [nch][nper], log [nch][nper] of TrkLog, ndone [nch], cnt0 [nch].  Returns st."""
-        I = np.ascontiguousarray(I, dtype=np.float64)
-        Q = np.ascontiguousarray(Q, dtype=np.float64)
-        nch, nper = I.shape
-        prm = np.ascontiguousarray(prm, dtype=np.dtype(BsyncPrm))
-        rate = np.ascontiguousarray(rate, dtype=np.int32)
-        log = np.ascontiguousarray(log, dtype=np.dtype(TrkLog))
-        ndone = np.ascontiguousarray(ndone, dtype=np.int32)
-        cnt0 = np.ascontiguousarray(cnt0, dtype=np.uint64)
-        if not (Q.shape == log.shape == (nch, nper) and prm.shape == rate.shape == ndone.shape == cnt0.shape == st.shape == (nch,)):
-            raise ValueError("bsync_run: array shapes")
-        if st.dtype != np.dtype(BsyncState) or not st.flags.c_contiguous:
-            raise ValueError("bsync_run: st must be a contiguous array of BsyncState")
+        prm, rate, I, Q, log, ndone, cnt0, nch, nper = self._stage_arrays("bsync_run", BsyncPrm, BsyncState, prm, rate, st, I, Q, log, ndone, cnt0)
         _check(self._L.gnsscorr_bsync_run(self.h, prm.ctypes.data, rate.ctypes.data, st.ctypes.data, I.ctypes.data, Q.ctypes.data,
-                                          log.ctypes.data, ndone.ctypes.data, cnt0.ctypes.data, nch, nper))
+               log.ctypes.data, ndone.ctypes.data, cnt0.ctypes.data, nch, nper))
         return st
 
     # -- correlation monitor
     def rx_cfm_set(self, prm=None, ch0=0, nch=None):
         """The correlation monitor's parameters for channels ch0 .. ch0+nch-1 (default: all from ch0 on): a CfmPrm, a
         dict of its fields (dref / rref: sequences of up to 16 values, the rest 0), or None to switch it off."""
-        nch = len(self.channels) - ch0 if nch is None else nch
-        if isinstance(prm, dict):
-            prm = cfm_prm(**prm)
-        _check(self._L.gnsscorr_rx_cfm_set(self.h, ch0, nch, C.byref(prm) if prm is not None else None))
+        self._rx_stage_set(self._L.gnsscorr_rx_cfm_set, cfm_prm, prm, ch0, nch)
 
     def rx_cfm_status(self):
         """numpy array [nch] of CfmState (gnsscorr_rx_cfm_status)."""
@@ -1237,21 +1231,10 @@ class Engine:
     def cfm_run(self, prm, rate, corrn, st, II, QQ, log, ndone, cnt0):
         """gnsscorr_cfm_run: prm [nch] of CfmPrm, rate [nch], corrn, st [nch] of CfmState (updated in place), II / QQ
         [nch][nper][1+2*corrn], log [nch][nper] of TrkLog, ndone [nch], cnt0 [nch].  Returns st."""
-        II = np.ascontiguousarray(II, dtype=np.float64)
-        QQ = np.ascontiguousarray(QQ, dtype=np.float64)
-        nch, nper, ntap = II.shape
-        prm = np.ascontiguousarray(prm, dtype=np.dtype(CfmPrm))
-        rate = np.ascontiguousarray(rate, dtype=np.int32)
-        log = np.ascontiguousarray(log, dtype=np.dtype(TrkLog))
-        ndone = np.ascontiguousarray(ndone, dtype=np.int32)
-        cnt0 = np.ascontiguousarray(cnt0, dtype=np.uint64)
-        if not (QQ.shape == II.shape and ntap == 1 + 2 * corrn and log.shape == (nch, nper) and
-                prm.shape == rate.shape == ndone.shape == cnt0.shape == st.shape == (nch,)):
-            raise ValueError("cfm_run: array shapes")
-        if st.dtype != np.dtype(CfmState) or not st.flags.c_contiguous:
-            raise ValueError("cfm_run: st must be a contiguous array of CfmState")
+        prm, rate, II, QQ, log, ndone, cnt0, nch, nper = self._stage_arrays("cfm_run", CfmPrm, CfmState, prm, rate, st, II, QQ, log, ndone, cnt0,
+                                                                             (1 + 2 * corrn,))
         _check(self._L.gnsscorr_cfm_run(self.h, prm.ctypes.data, rate.ctypes.data, corrn, st.ctypes.data, II.ctypes.data,
-                                        QQ.ctypes.data, log.ctypes.data, ndone.ctypes.data, cnt0.ctypes.data, nch, nper))
+               QQ.ctypes.data, log.ctypes.data, ndone.ctypes.data, cnt0.ctypes.data, nch, nper))
         return st
 
     # -- IF monitor

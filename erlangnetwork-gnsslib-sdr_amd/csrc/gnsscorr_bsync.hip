@@ -30,7 +30,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "gnsscorr_ctx.h"
+#include "gnsscorr_stage.h"
 
 #define GC_BSYNC_WAVES 4                        // channels per workgroup
 #define GC_BSYNC_MAXRATE 20                     // gnsscorr_bsync_t's arrays, gnsscorr_loop_t.bitsync[]
@@ -41,41 +41,31 @@ struct GcBsyncLds {
     double I[2][64], Q[2][64];                  // the chunk's prompt sums, two chunks deep
 };
 
-// chlist: the channels of the launch (nullptr: channel = list index), nlist of them.  I / Q: element
-// ch * ch_stride + e * row_stride is the prompt sum of row e.  rate / cnt: byte pointers to channel 0's value and the
-// byte stride to the next channel's; cnt_after: the value is the cnt behind the run (cnt0 = cnt - ndone), else cnt0.
-// loop: nullptr, or the loop states [channel]: a channel decided in this launch (done 0 -> 1) whose flagsync is still 0
-// gets flagsync = 1 and synci, and applied[channel] goes up by one.
+// v: the rows (GcRowsView, gnsscorr_stage.h).  loop: nullptr, or the loop states [channel]: a channel decided in this
+// launch (done 0 -> 1) whose flagsync is still 0 gets flagsync = 1 and synci, and applied[channel] goes up by one.
 // grid ceil(nlist / GC_BSYNC_WAVES), GC_BSYNC_WAVES * 64 lanes.
-__global__ __launch_bounds__(GC_BSYNC_WAVES * 64) void rx_bsync_kernel(
-    const int *__restrict__ chlist, int nlist, const gnsscorr_bsyncprm_t *__restrict__ prm, const char *__restrict__ rate,
-    size_t rate_stride, gnsscorr_bsync_t *__restrict__ st, const double *__restrict__ I, const double *__restrict__ Q,
-    size_t ch_stride, size_t row_stride, const gnsscorr_trklog_t *__restrict__ log, int nper,
-    const int *__restrict__ ndone, const char *__restrict__ cnt, size_t cnt_stride, int cnt_after,
-    gnsscorr_loop_t *loop, int *__restrict__ applied)
+__global__ __launch_bounds__(GC_BSYNC_WAVES * 64) void rx_bsync_kernel(const GcRowsView v, const gnsscorr_bsyncprm_t *__restrict__ prm,
+                                                                       gnsscorr_bsync_t *__restrict__ st, gnsscorr_loop_t *loop,
+                                                                       int *__restrict__ applied)
 {
     GC_FP_STRICT                                // plain operators below, one IEEE operation each: no product is fused into a sum
     __shared__ GcBsyncLds lds[GC_BSYNC_WAVES];
     __shared__ int rows_of[GC_BSYNC_WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     GcBsyncLds &L = lds[wave];
-    const int li = blockIdx.x * GC_BSYNC_WAVES + wave;
-    const bool have = li < nlist;
-    const int ch = have ? (chlist ? chlist[li] : li) : 0;
+    const GcRows r = gc_rows(v, blockIdx.x * GC_BSYNC_WAVES + wave);
+    const bool have = r.have;
+    const int ch = r.ch, rt = have ? r.rt : 2;  // (a wavefront without a channel still divides by its rate)
+    const unsigned long long cnt0 = r.cnt0;
     const bool own = lane < GC_BSYNC_MAXRATE;   // the lane holds an element of the state's arrays
     gnsscorr_bsyncprm_t p = {0, 0, 0, 0, 0.0};
-    int rt = 2, nd = 0;
-    unsigned long long cnt0 = 0;
+    int nd = r.nd;
     // the state: the arrays by lane, the rest wave-uniform
     double E = 0.0, sI = 0.0, sQ = 0.0, ratio_last = 0.0;
     unsigned long long a0 = 0, decided_cnt = 0;
     int fill = 0, armed = 0, n = 0, tests = 0, done = 0, best = 0, synci = 0;
     if (have) {
         p = prm[ch];
-        rt = *reinterpret_cast<const int *>(rate + (size_t)ch * rate_stride);
-        nd = min(max(ndone[ch], 0), nper);
-        cnt0 = *reinterpret_cast<const unsigned long long *>(cnt + (size_t)ch * cnt_stride);
-        if (cnt_after) cnt0 -= (unsigned long long)nd;
         if (p.nsym <= 0 || rt < 2 || rt > GC_BSYNC_MAXRATE) nd = 0;         // the channel's detector is off
         const gnsscorr_bsync_t &s = st[ch];
         if (own) {
@@ -104,8 +94,9 @@ __global__ __launch_bounds__(GC_BSYNC_WAVES * 64) void rx_bsync_kernel(
     bool live = nd > 0 && !done;                                            // rule 2
     int newly = 0;
     int phase = (int)(cnt0 % (unsigned long long)rt);                      // c mod R, carried from row to row
-    const double *pI = I + (size_t)ch * ch_stride, *pQ = Q + (size_t)ch * ch_stride;
-    const gnsscorr_trklog_t *plog = log + (size_t)ch * (size_t)nper;
+    const double *pI = r.pI, *pQ = r.pQ;
+    const gnsscorr_trklog_t *plog = r.plog;
+    const size_t row_stride = v.row_stride;
 
     for (int k = 0; k < nchunk; k++) {
         const int base = k << 6, e = base + lane, b = k & 1;
@@ -238,7 +229,13 @@ int bsync_check_prm(const char *who, const gnsscorr_bsyncprm_t &p, int rate, int
     return GNSSCORR_OK;
 }
 
-size_t bsync_align(size_t n) { return (n + 15) & ~(size_t)15; }
+void bsync_launch(gnsscorr_ctx *ctx, const GcRowsView &rows, const gnsscorr_bsyncprm_t *prm, gnsscorr_bsync_t *st, gnsscorr_loop_t *loop,
+                  int *applied)
+{
+    GcTimed t(ctx, "rx_bsync");
+    hipLaunchKernelGGL(rx_bsync_kernel, dim3((rows.nlist + GC_BSYNC_WAVES - 1) / GC_BSYNC_WAVES), dim3(GC_BSYNC_WAVES * 64), 0, ctx->stream,
+                       rows, prm, st, loop, applied);
+}
 
 }  // namespace
 
@@ -256,81 +253,28 @@ extern "C" int gnsscorr_bsync_run(gnsscorr_ctx *ctx, const gnsscorr_bsyncprm_t *
         if (ndone[i] < 0 || ndone[i] > nper) return gc_fail(GNSSCORR_EINVAL, "bsync_run: channel %d: ndone %d of %d rows", i, ndone[i], nper);
     }
     if (nch == 0) return GNSSCORR_OK;
-    std::lock_guard<std::mutex> lk(ctx->mtx);
-    GC_HIP(hipSetDevice(ctx->device));
-    // one staging buffer, one transfer: prm, rate, ndone, cnt0, st, I, Q, log
-    const size_t units = (size_t)nch * nper;
-    const size_t o_prm = 0, o_rate = bsync_align(o_prm + sizeof(gnsscorr_bsyncprm_t) * nch), o_nd = bsync_align(o_rate + sizeof(int) * nch),
-                 o_cnt = bsync_align(o_nd + sizeof(int) * nch), o_st = bsync_align(o_cnt + sizeof(uint64_t) * nch),
-                 o_I = bsync_align(o_st + sizeof(gnsscorr_bsync_t) * nch), o_Q = bsync_align(o_I + sizeof(double) * units),
-                 o_log = bsync_align(o_Q + sizeof(double) * units), total = bsync_align(o_log + sizeof(gnsscorr_trklog_t) * units);
-    std::vector<unsigned char> blob(total, 0);
-    memcpy(&blob[o_prm], prm, sizeof(gnsscorr_bsyncprm_t) * nch);
-    memcpy(&blob[o_rate], rate, sizeof(int) * nch);
-    memcpy(&blob[o_nd], ndone, sizeof(int) * nch);
-    memcpy(&blob[o_cnt], cnt0, sizeof(uint64_t) * nch);
-    memcpy(&blob[o_st], st, sizeof(gnsscorr_bsync_t) * nch);
-    memcpy(&blob[o_I], I, sizeof(double) * units);
-    memcpy(&blob[o_Q], Q, sizeof(double) * units);
-    memcpy(&blob[o_log], log, sizeof(gnsscorr_trklog_t) * units);
-    GC_RESERVE(ctx, ctx->dbsync_stage, total);
-    unsigned char *d = ctx->dbsync_stage;
-    GC_HIP(hipMemcpyAsync(d, blob.data(), total, hipMemcpyHostToDevice, ctx->stream));
-    {
-        GcTimed t(ctx, "rx_bsync");
-        hipLaunchKernelGGL(rx_bsync_kernel, dim3((nch + GC_BSYNC_WAVES - 1) / GC_BSYNC_WAVES), dim3(GC_BSYNC_WAVES * 64), 0, ctx->stream,
-                           (const int *)nullptr, nch, (const gnsscorr_bsyncprm_t *)(d + o_prm), (const char *)(d + o_rate), sizeof(int),
-                           (gnsscorr_bsync_t *)(d + o_st), (const double *)(d + o_I), (const double *)(d + o_Q), (size_t)nper, (size_t)1,
-                           (const gnsscorr_trklog_t *)(d + o_log), nper, (const int *)(d + o_nd), (const char *)(d + o_cnt),
-                           sizeof(uint64_t), 0, (gnsscorr_loop_t *)nullptr, (int *)nullptr);
-    }
-    GC_HIP(hipGetLastError());
-    std::vector<gnsscorr_bsync_t> out(nch);
-    GC_HIP(hipMemcpyAsync(out.data(), d + o_st, sizeof(gnsscorr_bsync_t) * nch, hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    memcpy(st, out.data(), sizeof(gnsscorr_bsync_t) * nch);
-    return GNSSCORR_OK;
+    return gc_stage_run(ctx, prm, rate, st, I, Q, log, ndone, cnt0, nch, nper, 1,
+                        [&](const GcRowsView &rows, const gnsscorr_bsyncprm_t *dprm, gnsscorr_bsync_t *dst) {
+                            bsync_launch(ctx, rows, dprm, dst, nullptr, nullptr);
+                        });
 }
 
 extern "C" int gnsscorr_rx_bsync_set(gnsscorr_ctx *ctx, int ch0, int nch, const gnsscorr_bsyncprm_t *prm)
 {
     if (!ctx || !ctx->rx.on) return gc_fail(GNSSCORR_ESTATE, "rx_bsync_set: no gnsscorr_rx_start yet");
-    if (ch0 < 0 || nch < 0 || ch0 > ctx->nch - nch) return gc_fail(GNSSCORR_EINVAL, "rx_bsync_set: channels %d..%d of %d", ch0, ch0 + nch - 1, ctx->nch);
-    if (nch == 0) return GNSSCORR_OK;
     GC_HIP(hipSetDevice(ctx->device));
     GcRx &rx = ctx->rx;
+    // the detector's own, before it can be on: the applied counts, which no kernel has seen when they are made
+    if (!rx.dbsync_applied) {
+        GC_RESERVE(ctx, rx.dbsync_applied, ctx->nch);
+        GC_HIP(hipMemset(rx.dbsync_applied.p, 0, sizeof(int) * ctx->nch));
+    }
     gnsscorr_bsyncprm_t p = {0, 0, 0, 0, 0.0};
     if (prm && prm->nsym != 0) {
         p = *prm;
         p.pad = 0;
-        // the channels' nav bit lengths: one column of the device's loop states
-        std::vector<int> rate(nch);
-        GC_HIP(hipMemcpy2DAsync(rate.data(), sizeof(int), (const char *)(ctx->loop.dloop.p + ch0) + offsetof(gnsscorr_loop_t, rate),
-                                sizeof(gnsscorr_loop_t), sizeof(int), nch, hipMemcpyDeviceToHost, ctx->stream));
-        GC_HIP(hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < nch; i++) {
-            int rc = bsync_check_prm("rx_bsync_set", p, rate[i], ch0 + i);
-            if (rc) return rc;
-        }
     }
-    const bool fresh = !rx.dbsync_applied;
-    GC_RESERVE(ctx, rx.dbsyncprm, ctx->nch);
-    GC_RESERVE(ctx, rx.dbsync, ctx->nch);
-    GC_RESERVE(ctx, rx.dbsync_applied, ctx->nch);
-    { int rc = rx.bsync_list.reserve(ctx->nch, hipHostMallocMapped); if (rc) return rc; }
-    for (int i = 0; i < nch; i++) rx.bsyncprm[ch0 + i] = p;
-    rx.bsync_on = 0;
-    for (int i = 0; i < ctx->nch; i++) rx.bsync_on += rx.bsyncprm[i].nsym != 0;
-    // behind whatever the stream still runs (a detector launch of the last step included)
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    GC_HIP(hipMemcpy(rx.dbsyncprm.p, rx.bsyncprm.data(), sizeof(gnsscorr_bsyncprm_t) * ctx->nch, hipMemcpyHostToDevice));
-    if (fresh) {
-        GC_HIP(hipMemset(rx.dbsync.p, 0, sizeof(gnsscorr_bsync_t) * ctx->nch));
-        GC_HIP(hipMemset(rx.dbsync_applied.p, 0, sizeof(int) * ctx->nch));
-    } else {
-        GC_HIP(hipMemset(rx.dbsync.p + ch0, 0, sizeof(gnsscorr_bsync_t) * nch));
-    }
-    return GNSSCORR_OK;
+    return rx.bsync.set(ctx, "rx_bsync_set", ch0, nch, p, bsync_check_prm);
 }
 
 extern "C" int gnsscorr_rx_bsync_status(gnsscorr_ctx *ctx, gnsscorr_bsync_t *st, int *applied)
@@ -338,14 +282,10 @@ extern "C" int gnsscorr_rx_bsync_status(gnsscorr_ctx *ctx, gnsscorr_bsync_t *st,
     if (!ctx || !ctx->rx.on) return gc_fail(GNSSCORR_ESTATE, "rx_bsync_status: no gnsscorr_rx_start yet");
     GC_HIP(hipSetDevice(ctx->device));
     const int nch = ctx->nch;
-    const bool made = (bool)ctx->rx.dbsync_applied;                         // else the detector has never been on
-    if (st) {
-        if (made) GC_HIP(hipMemcpyAsync(st, ctx->rx.dbsync, sizeof(gnsscorr_bsync_t) * nch, hipMemcpyDeviceToHost, ctx->stream));
-        else memset(st, 0, sizeof(gnsscorr_bsync_t) * nch);
-    }
+    if (st) GC_TRY(ctx->rx.bsync.status(ctx, st));
     if (applied) {
-        if (made) GC_HIP(hipMemcpyAsync(applied, ctx->rx.dbsync_applied, sizeof(int) * nch, hipMemcpyDeviceToHost, ctx->stream));
-        else memset(applied, 0, sizeof(int) * nch);
+        if (ctx->rx.dbsync_applied) GC_HIP(hipMemcpyAsync(applied, ctx->rx.dbsync_applied, sizeof(int) * nch, hipMemcpyDeviceToHost, ctx->stream));
+        else memset(applied, 0, sizeof(int) * nch);                         // the detector has never been on
     }
     GC_HIP(hipStreamSynchronize(ctx->stream));
     return GNSSCORR_OK;
@@ -354,22 +294,9 @@ extern "C" int gnsscorr_rx_bsync_status(gnsscorr_ctx *ctx, gnsscorr_bsync_t *st,
 int gc_rx_bsync_launch(gnsscorr_ctx *ctx, int nperiod)
 {
     GcRx &rx = ctx->rx;
-    // the closed loop of this step drained the stream before its first launch: the kernel that read the list last is over
-    int n = 0;
-    for (int i = 0; i < ctx->nch; i++)
-        if (rx.bsyncprm[i].nsym != 0 && rx.st[i].state == GNSSCORR_CH_TRACK) rx.bsync_list[n++] = i;
+    const int n = rx.bsync.fill(rx.st);
     if (!n) return GNSSCORR_OK;
-    {
-        GcTimed t(ctx, "rx_bsync");
-        // trk.II is the correlator's QQ (ref src/sdrtrk.c:42): gnsscorr_trk_fetch's II rows are dcorrQ
-        hipLaunchKernelGGL(rx_bsync_kernel, dim3((n + GC_BSYNC_WAVES - 1) / GC_BSYNC_WAVES), dim3(GC_BSYNC_WAVES * 64), 0, ctx->stream,
-                           (const int *)rx.bsync_list.dev, n, (const gnsscorr_bsyncprm_t *)rx.dbsyncprm.p,
-                           (const char *)ctx->loop.dloop.p + offsetof(gnsscorr_loop_t, rate), sizeof(gnsscorr_loop_t), rx.dbsync.p,
-                           (const double *)ctx->out.dcorrQ.p, (const double *)ctx->out.dcorrI.p, (size_t)nperiod * ctx->ntap, (size_t)ctx->ntap,
-                           (const gnsscorr_trklog_t *)ctx->loop.dlog.p, nperiod, (const int *)ctx->loop.ddone.p,
-                           (const char *)ctx->loop.dloop.p + offsetof(gnsscorr_loop_t, cnt), sizeof(gnsscorr_loop_t), 1,
-                           ctx->loop.dloop.p, rx.dbsync_applied.p);
-    }
+    bsync_launch(ctx, gc_rows_of_run(ctx, rx.bsync.list.dev, n, nperiod), rx.bsync.dprm, rx.bsync.dst, ctx->loop.dloop, rx.dbsync_applied);
     GC_HIP(hipGetLastError());
     return GNSSCORR_OK;
 }

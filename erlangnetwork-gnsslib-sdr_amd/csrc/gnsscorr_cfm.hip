@@ -35,7 +35,7 @@
 #include <cmath>
 #include <vector>
 
-#include "gnsscorr_ctx.h"
+#include "gnsscorr_stage.h"
 
 #define GC_CFM_WAVES 4                          // channels per workgroup
 #define GC_CFM_ROWS 8                           // data rows in flight (divides 64)
@@ -43,29 +43,20 @@
 
 namespace {
 
-// chlist: the channels of the launch (nullptr: channel = list index), nlist of them.  I / Q: element
-// ch * ch_stride + e * row_stride + t is tap t of row e; ntap = 1 + 2 corrn <= row_stride.  rate / cnt: byte pointers to
-// channel 0's value and the byte stride to the next channel's; cnt_after: the value is the cnt behind the run
-// (cnt0 = cnt - ndone), else cnt0.
+// v: the rows (GcRowsView, gnsscorr_stage.h), tap t of a row at + t; ntap = 1 + 2 corrn <= row_stride.
 // grid ceil(nlist / GC_CFM_WAVES), GC_CFM_WAVES * 64 lanes.
-__global__ __launch_bounds__(GC_CFM_WAVES * 64) void rx_cfm_kernel(
-    const int *__restrict__ chlist, int nlist, const gnsscorr_cfmprm_t *__restrict__ prm, const char *__restrict__ rate,
-    size_t rate_stride, gnsscorr_cfm_t *__restrict__ st, const double *__restrict__ I, const double *__restrict__ Q,
-    size_t ch_stride, size_t row_stride, int ntap, const gnsscorr_trklog_t *__restrict__ log, int nper,
-    const int *__restrict__ ndone, const char *__restrict__ cnt, size_t cnt_stride, int cnt_after)
+__global__ __launch_bounds__(GC_CFM_WAVES * 64) void rx_cfm_kernel(const GcRowsView v, const gnsscorr_cfmprm_t *__restrict__ prm,
+                                                                   gnsscorr_cfm_t *__restrict__ st, int ntap)
 {
     GC_FP_STRICT                                // plain operators below, one IEEE operation each: no product is fused into a sum
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = blockIdx.x * GC_CFM_WAVES + wave;
-    if (li >= nlist) return;                                                // (the kernel has no barrier)
-    const int ch = chlist ? chlist[li] : li;
+    const GcRows r = gc_rows(v, blockIdx.x * GC_CFM_WAVES + wave);
+    if (!r.have) return;                                                    // (the kernel has no barrier)
+    const int ch = r.ch, rt = r.rt, nd = r.nd;
+    const unsigned long long cnt0 = r.cnt0;
     const gnsscorr_cfmprm_t &p = prm[ch];
     const int kbits = p.kbits, skip_bits = p.skip_bits, nbad_max = p.nbad, npair = p.npair;
     const double dtol = p.dtol, rtol = p.rtol;
-    const int rt = *reinterpret_cast<const int *>(rate + (size_t)ch * rate_stride);
-    const int nd = min(max(ndone[ch], 0), nper);
-    unsigned long long cnt0 = *reinterpret_cast<const unsigned long long *>(cnt + (size_t)ch * cnt_stride);
-    if (cnt_after) cnt0 -= (unsigned long long)nd;
     if (nd <= 0 || kbits <= 0 || rt < 2 || ntap < 3 || ntap > GNSSCORR_MAXTAPS) return;    // nothing to read, or the monitor is off
     const int corrn = (ntap - 1) >> 1;
     const bool own = lane < GNSSCORR_MAXTAPS;   // the lane holds an element of the state's tap arrays
@@ -95,8 +86,9 @@ __global__ __launch_bounds__(GC_CFM_WAVES * 64) void rx_cfm_kernel(
         open = s.open; n = s.n; k = s.k; bits = s.bits; nbad = s.nbad; alarm = s.alarm; alarms = s.alarms;
         windows = s.windows; worst = s.worst_pair;
     }
-    const double *pI = I + (size_t)ch * ch_stride + lane, *pQ = Q + (size_t)ch * ch_stride + lane;
-    const gnsscorr_trklog_t *plog = log + (size_t)ch * (size_t)nper;
+    const double *pI = r.pI + lane, *pQ = r.pQ + lane;
+    const gnsscorr_trklog_t *plog = r.plog;
+    const size_t row_stride = v.row_stride;
 
     for (int base = 0; base < nd; base += 64) {
         const int e = base + lane;
@@ -211,7 +203,12 @@ int cfm_check_prm(const char *who, const gnsscorr_cfmprm_t &p, int rate, int cor
     return GNSSCORR_OK;
 }
 
-size_t cfm_align(size_t n) { return (n + 15) & ~(size_t)15; }
+void cfm_launch(gnsscorr_ctx *ctx, const GcRowsView &rows, const gnsscorr_cfmprm_t *prm, gnsscorr_cfm_t *st, int ntap)
+{
+    GcTimed t(ctx, "rx_cfm");
+    hipLaunchKernelGGL(rx_cfm_kernel, dim3((rows.nlist + GC_CFM_WAVES - 1) / GC_CFM_WAVES), dim3(GC_CFM_WAVES * 64), 0, ctx->stream,
+                       rows, prm, st, ntap);
+}
 
 }  // namespace
 
@@ -230,77 +227,21 @@ extern "C" int gnsscorr_cfm_run(gnsscorr_ctx *ctx, const gnsscorr_cfmprm_t *prm,
         if (ndone[i] < 0 || ndone[i] > nper) return gc_fail(GNSSCORR_EINVAL, "cfm_run: channel %d: ndone %d of %d rows", i, ndone[i], nper);
     }
     if (nch == 0) return GNSSCORR_OK;
-    std::lock_guard<std::mutex> lk(ctx->mtx);
-    GC_HIP(hipSetDevice(ctx->device));
-    // one staging buffer, one transfer: prm, rate, ndone, cnt0, st, II, QQ, log
     const int ntap = 1 + 2 * corrn;
-    const size_t units = (size_t)nch * nper, vals = units * ntap;
-    const size_t o_prm = 0, o_rate = cfm_align(o_prm + sizeof(gnsscorr_cfmprm_t) * nch), o_nd = cfm_align(o_rate + sizeof(int) * nch),
-                 o_cnt = cfm_align(o_nd + sizeof(int) * nch), o_st = cfm_align(o_cnt + sizeof(uint64_t) * nch),
-                 o_I = cfm_align(o_st + sizeof(gnsscorr_cfm_t) * nch), o_Q = cfm_align(o_I + sizeof(double) * vals),
-                 o_log = cfm_align(o_Q + sizeof(double) * vals), total = cfm_align(o_log + sizeof(gnsscorr_trklog_t) * units);
-    std::vector<unsigned char> blob(total, 0);
-    memcpy(&blob[o_prm], prm, sizeof(gnsscorr_cfmprm_t) * nch);
-    memcpy(&blob[o_rate], rate, sizeof(int) * nch);
-    memcpy(&blob[o_nd], ndone, sizeof(int) * nch);
-    memcpy(&blob[o_cnt], cnt0, sizeof(uint64_t) * nch);
-    memcpy(&blob[o_st], st, sizeof(gnsscorr_cfm_t) * nch);
-    memcpy(&blob[o_I], II, sizeof(double) * vals);
-    memcpy(&blob[o_Q], QQ, sizeof(double) * vals);
-    memcpy(&blob[o_log], log, sizeof(gnsscorr_trklog_t) * units);
-    GC_RESERVE(ctx, ctx->dcfm_stage, total);
-    unsigned char *d = ctx->dcfm_stage;
-    GC_HIP(hipMemcpyAsync(d, blob.data(), total, hipMemcpyHostToDevice, ctx->stream));
-    {
-        GcTimed t(ctx, "rx_cfm");
-        hipLaunchKernelGGL(rx_cfm_kernel, dim3((nch + GC_CFM_WAVES - 1) / GC_CFM_WAVES), dim3(GC_CFM_WAVES * 64), 0, ctx->stream,
-                           (const int *)nullptr, nch, (const gnsscorr_cfmprm_t *)(d + o_prm), (const char *)(d + o_rate), sizeof(int),
-                           (gnsscorr_cfm_t *)(d + o_st), (const double *)(d + o_I), (const double *)(d + o_Q), (size_t)nper * ntap,
-                           (size_t)ntap, ntap, (const gnsscorr_trklog_t *)(d + o_log), nper, (const int *)(d + o_nd),
-                           (const char *)(d + o_cnt), sizeof(uint64_t), 0);
-    }
-    GC_HIP(hipGetLastError());
-    std::vector<gnsscorr_cfm_t> out(nch);
-    GC_HIP(hipMemcpyAsync(out.data(), d + o_st, sizeof(gnsscorr_cfm_t) * nch, hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    memcpy(st, out.data(), sizeof(gnsscorr_cfm_t) * nch);
-    return GNSSCORR_OK;
+    return gc_stage_run(ctx, prm, rate, st, II, QQ, log, ndone, cnt0, nch, nper, ntap,
+                        [&](const GcRowsView &rows, const gnsscorr_cfmprm_t *dprm, gnsscorr_cfm_t *dst) { cfm_launch(ctx, rows, dprm, dst, ntap); });
 }
 
 extern "C" int gnsscorr_rx_cfm_set(gnsscorr_ctx *ctx, int ch0, int nch, const gnsscorr_cfmprm_t *prm)
 {
     if (!ctx || !ctx->rx.on) return gc_fail(GNSSCORR_ESTATE, "rx_cfm_set: no gnsscorr_rx_start yet");
-    if (ch0 < 0 || nch < 0 || ch0 > ctx->nch - nch) return gc_fail(GNSSCORR_EINVAL, "rx_cfm_set: channels %d..%d of %d", ch0, ch0 + nch - 1, ctx->nch);
-    if (nch == 0) return GNSSCORR_OK;
-    GC_HIP(hipSetDevice(ctx->device));
-    GcRx &rx = ctx->rx;
     gnsscorr_cfmprm_t p;
     memset(&p, 0, sizeof(p));
-    if (prm && prm->kbits != 0) {
-        p = *prm;
-        // the channels' nav bit lengths: one column of the device's loop states
-        std::vector<int> rate(nch);
-        GC_HIP(hipMemcpy2DAsync(rate.data(), sizeof(int), (const char *)(ctx->loop.dloop.p + ch0) + offsetof(gnsscorr_loop_t, rate),
-                                sizeof(gnsscorr_loop_t), sizeof(int), nch, hipMemcpyDeviceToHost, ctx->stream));
-        GC_HIP(hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < nch; i++) {
-            int rc = cfm_check_prm("rx_cfm_set", p, rate[i], (ctx->ntap - 1) / 2, ch0 + i);
-            if (rc) return rc;
-        }
-    }
-    const bool fresh = !rx.dcfm;
-    GC_RESERVE(ctx, rx.dcfmprm, ctx->nch);
-    GC_RESERVE(ctx, rx.dcfm, ctx->nch);
-    { int rc = rx.cfm_list.reserve(ctx->nch, hipHostMallocMapped); if (rc) return rc; }
-    for (int i = 0; i < nch; i++) rx.cfmprm[ch0 + i] = p;
-    rx.cfm_on = 0;
-    for (int i = 0; i < ctx->nch; i++) rx.cfm_on += rx.cfmprm[i].kbits != 0;
-    // behind whatever the stream still runs (a monitor launch of the last step included)
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    GC_HIP(hipMemcpy(rx.dcfmprm.p, rx.cfmprm.data(), sizeof(gnsscorr_cfmprm_t) * ctx->nch, hipMemcpyHostToDevice));
-    if (fresh) GC_HIP(hipMemset(rx.dcfm.p, 0, sizeof(gnsscorr_cfm_t) * ctx->nch));
-    else GC_HIP(hipMemset(rx.dcfm.p + ch0, 0, sizeof(gnsscorr_cfm_t) * nch));
-    return GNSSCORR_OK;
+    if (prm && prm->kbits != 0) p = *prm;
+    const int corrn = (ctx->ntap - 1) / 2;
+    return ctx->rx.cfm.set(ctx, "rx_cfm_set", ch0, nch, p, [corrn](const char *who, const gnsscorr_cfmprm_t &q, int rate, int ch) {
+        return cfm_check_prm(who, q, rate, corrn, ch);
+    });
 }
 
 extern "C" int gnsscorr_rx_cfm_status(gnsscorr_ctx *ctx, gnsscorr_cfm_t *st)
@@ -308,8 +249,7 @@ extern "C" int gnsscorr_rx_cfm_status(gnsscorr_ctx *ctx, gnsscorr_cfm_t *st)
     if (!ctx || !ctx->rx.on) return gc_fail(GNSSCORR_ESTATE, "rx_cfm_status: no gnsscorr_rx_start yet");
     if (!st) return gc_fail(GNSSCORR_EINVAL, "rx_cfm_status: null argument");
     GC_HIP(hipSetDevice(ctx->device));
-    if (ctx->rx.dcfm) GC_HIP(hipMemcpyAsync(st, ctx->rx.dcfm, sizeof(gnsscorr_cfm_t) * ctx->nch, hipMemcpyDeviceToHost, ctx->stream));
-    else memset(st, 0, sizeof(gnsscorr_cfm_t) * ctx->nch);                  // the monitor has never been on
+    GC_TRY(ctx->rx.cfm.status(ctx, st));
     GC_HIP(hipStreamSynchronize(ctx->stream));
     return GNSSCORR_OK;
 }
@@ -317,21 +257,9 @@ extern "C" int gnsscorr_rx_cfm_status(gnsscorr_ctx *ctx, gnsscorr_cfm_t *st)
 int gc_rx_cfm_launch(gnsscorr_ctx *ctx, int nperiod)
 {
     GcRx &rx = ctx->rx;
-    // the closed loop of this step drained the stream before its first launch: the kernel that read the list last is over
-    int n = 0;
-    for (int i = 0; i < ctx->nch; i++)
-        if (rx.cfmprm[i].kbits != 0 && rx.st[i].state == GNSSCORR_CH_TRACK) rx.cfm_list[n++] = i;
+    const int n = rx.cfm.fill(rx.st);
     if (!n) return GNSSCORR_OK;
-    {
-        GcTimed t(ctx, "rx_cfm");
-        // trk.II is the correlator's QQ (ref src/sdrtrk.c:42): gnsscorr_trk_fetch's II rows are dcorrQ
-        hipLaunchKernelGGL(rx_cfm_kernel, dim3((n + GC_CFM_WAVES - 1) / GC_CFM_WAVES), dim3(GC_CFM_WAVES * 64), 0, ctx->stream,
-                           (const int *)rx.cfm_list.dev, n, (const gnsscorr_cfmprm_t *)rx.dcfmprm.p,
-                           (const char *)ctx->loop.dloop.p + offsetof(gnsscorr_loop_t, rate), sizeof(gnsscorr_loop_t), rx.dcfm.p,
-                           (const double *)ctx->out.dcorrQ.p, (const double *)ctx->out.dcorrI.p, (size_t)nperiod * ctx->ntap, (size_t)ctx->ntap,
-                           ctx->ntap, (const gnsscorr_trklog_t *)ctx->loop.dlog.p, nperiod, (const int *)ctx->loop.ddone.p,
-                           (const char *)ctx->loop.dloop.p + offsetof(gnsscorr_loop_t, cnt), sizeof(gnsscorr_loop_t), 1);
-    }
+    cfm_launch(ctx, gc_rows_of_run(ctx, rx.cfm.list.dev, n, nperiod), rx.cfm.dprm, rx.cfm.dst, ctx->ntap);
     GC_HIP(hipGetLastError());
     return GNSSCORR_OK;
 }

@@ -1,6 +1,7 @@
 // gnsscorr_ctx.h -- host-side context object behind the opaque gnsscorr_ctx, and the move-only types it owns its
 // resources by: GcDevBuf / GcPinBuf (memory), GcEvent / GcStream (handles).  Deleting the context releases all of them.
-// Also the correlator launches' buffer set (GcUnitBufs), the tracking launchers' argument block (GcTrkLaunch), gc_chan_range.
+// Also the correlator launches' buffer set (GcUnitBufs), the tracking launchers' argument block (GcTrkLaunch), the record
+// of a schedule stage (GcStage), gc_chan_range.
 #pragma once
 
 #include <map>
@@ -295,33 +296,33 @@ struct GcLoop {
     int last_nper = 0;                             // > 0: the last run was a closed-loop one of that many periods
 };
 
+// One per-channel stage behind the closed loop of the schedule, off until its gnsscorr_rx_*_set; the operations are in
+// gnsscorr_stage.h
+template <class Prm, class St>
+struct GcStage {
+    std::vector<Prm> prm;                          // [nch]; all zero: the channel's stage is off
+    int on = 0;                                    // channels whose stage is on
+    GcDevBuf<Prm> dprm;                            // [nch]
+    GcDevBuf<St> dst;                              // [nch] the stage's state
+    GcPinBuf<int> list;                            // mapped: [nch] the channels of a launch (host writes, kernel reads)
+    template <class Check> int set(gnsscorr_ctx *ctx, const char *who, int ch0, int nch, const Prm &p, Check check);
+    int status(gnsscorr_ctx *ctx, St *out) const;
+    int start(gnsscorr_ctx *ctx);
+    int fill(const std::vector<gnsscorr_rxstat_t> &rxst);
+};
+
 // The receiver schedule (gnsscorr_rx.hip): sdrthread()'s per-channel state, kept by the host
 struct GcRx {
     bool on = false;
     int retry_ms = 0;                              // the reference's ACQSLEEP, counted on each channel's sample clock
     std::vector<gnsscorr_rxstat_t> st;             // [nch] (cnt is filled in by gnsscorr_rx_status)
-    // the lock monitor (gnsscorr_lock.hip), off until gnsscorr_rx_lock_set
-    std::vector<gnsscorr_lockprm_t> lockprm;       // [nch]; kbits 0: the channel's monitor is off
+    GcStage<gnsscorr_lockprm_t, gnsscorr_lock_t> lock;      // the lock monitor (gnsscorr_lock.hip)
     std::vector<int> losses;                       // [nch] times the channel was sent back to SEARCH
-    int lock_on = 0;                               // channels whose monitor is on
     std::vector<int> lock_listed;                  // the channels of the launch whose words are still to be read
-    GcDevBuf<gnsscorr_lockprm_t> dlockprm;         // [nch]
-    GcDevBuf<gnsscorr_lock_t> dlock;               // [nch] the detector's state
-    GcPinBuf<int> lock_list;                       // mapped: [nch] the channels of a launch (host writes, kernel reads)
     GcPinBuf<unsigned> lock_lost;                  // mapped: [nch] 1: the launch declared the channel lost (kernel writes)
-    // bit synchronisation by symbol energy (gnsscorr_bsync.hip), off until gnsscorr_rx_bsync_set
-    std::vector<gnsscorr_bsyncprm_t> bsyncprm;     // [nch]; nsym 0: the channel's detector is off
-    int bsync_on = 0;                              // channels whose detector is on
-    GcDevBuf<gnsscorr_bsyncprm_t> dbsyncprm;       // [nch]
-    GcDevBuf<gnsscorr_bsync_t> dbsync;             // [nch] the detector's state
+    GcStage<gnsscorr_bsyncprm_t, gnsscorr_bsync_t> bsync;   // bit synchronisation by symbol energy (gnsscorr_bsync.hip)
     GcDevBuf<int> dbsync_applied;                  // [nch] times the kernel preset the channel's loop state
-    GcPinBuf<int> bsync_list;                      // mapped: [nch] the channels of a launch (host writes, kernel reads)
-    // the correlation monitor (gnsscorr_cfm.hip), off until gnsscorr_rx_cfm_set
-    std::vector<gnsscorr_cfmprm_t> cfmprm;         // [nch]; kbits 0: the channel's monitor is off
-    int cfm_on = 0;                                // channels whose monitor is on
-    GcDevBuf<gnsscorr_cfmprm_t> dcfmprm;           // [nch]
-    GcDevBuf<gnsscorr_cfm_t> dcfm;                 // [nch] the monitor's state
-    GcPinBuf<int> cfm_list;                        // mapped: [nch] the channels of a launch (host writes, kernel reads)
+    GcStage<gnsscorr_cfmprm_t, gnsscorr_cfm_t> cfm;         // the correlation monitor (gnsscorr_cfm.hip)
 };
 
 // Frames, observables and epochs behind every step (gnsscorr_rx_nav_*, gnsscorr_rx.hip): the core object of
@@ -510,12 +511,8 @@ struct gnsscorr_ctx {
     GcDevBuf<unsigned char> dfec_out;              // [nch][npos][rowbytes]
     int fec_parts = 3;                             // (tools) 3: the decoder; 1 / 2: forward pass / chainback alone
 
-    // lock monitor (gnsscorr_lock.hip): staging of gnsscorr_lock_run's host arrays
-    GcDevBuf<unsigned char> dlock_stage;
-    // bit synchronisation (gnsscorr_bsync.hip): staging of gnsscorr_bsync_run's host arrays
-    GcDevBuf<unsigned char> dbsync_stage;
-    // correlation monitor (gnsscorr_cfm.hip): staging of gnsscorr_cfm_run's host arrays
-    GcDevBuf<unsigned char> dcfm_stage;
+    // staging of gnsscorr_{lock,bsync,cfm}_run's host arrays (gc_stage_run, gnsscorr_stage.h)
+    GcDevBuf<unsigned char> dstage;
 
     // timing
     int timing = 0;                                // 0: off, 1: every kernel, 2: only the two correlator kernels (trk_corr, acq_corr)

@@ -26,7 +26,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "gnsscorr_ctx.h"
+#include "gnsscorr_stage.h"
 
 #define GC_LOCK_WAVES 4                         // channels per workgroup
 
@@ -55,36 +55,25 @@ __device__ __forceinline__ void lock_sum(const double *li, const double *lq, uns
     }
 }
 
-// chlist: the channels of the launch (nullptr: channel = list index), nlist of them.  I / Q: element
-// ch * ch_stride + e * row_stride is the prompt sum of row e.  rate / cnt: byte pointers to channel 0's value and the
-// byte stride to the next channel's; cnt_after: the value is the cnt behind the run (cnt0 = cnt - ndone), else cnt0.
-// lostw: nullptr, or a word per channel: 1 when this launch declared the channel lost, else 0.
-// grid ceil(nlist / GC_LOCK_WAVES), GC_LOCK_WAVES * 64 lanes.
-__global__ __launch_bounds__(GC_LOCK_WAVES * 64) void rx_lock_kernel(
-    const int *__restrict__ chlist, int nlist, const gnsscorr_lockprm_t *__restrict__ prm, const char *__restrict__ rate,
-    size_t rate_stride, gnsscorr_lock_t *__restrict__ st, const double *__restrict__ I, const double *__restrict__ Q,
-    size_t ch_stride, size_t row_stride, const gnsscorr_trklog_t *__restrict__ log, int nper,
-    const int *__restrict__ ndone, const char *__restrict__ cnt, size_t cnt_stride, int cnt_after,
-    unsigned *__restrict__ lostw)
+// v: the rows (GcRowsView, gnsscorr_stage.h).  lostw: nullptr, or a word per channel: 1 when this launch declared the
+// channel lost, else 0.  grid ceil(nlist / GC_LOCK_WAVES), GC_LOCK_WAVES * 64 lanes.
+__global__ __launch_bounds__(GC_LOCK_WAVES * 64) void rx_lock_kernel(const GcRowsView v, const gnsscorr_lockprm_t *__restrict__ prm,
+                                                                     gnsscorr_lock_t *__restrict__ st, unsigned *__restrict__ lostw)
 {
     __shared__ GcLockLds lds[GC_LOCK_WAVES];
     __shared__ int rows_of[GC_LOCK_WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     GcLockLds &L = lds[wave];
-    const int li = blockIdx.x * GC_LOCK_WAVES + wave;
-    const bool have = li < nlist;
-    const int ch = have ? (chlist ? chlist[li] : li) : 0;
+    const GcRows r = gc_rows(v, blockIdx.x * GC_LOCK_WAVES + wave);
+    const bool have = r.have;
+    const int ch = r.ch, rt = r.rt;
+    const unsigned long long cnt0 = r.cnt0;
     gnsscorr_lockprm_t p = {0, 0, 0, 0, 0.0};
     gnsscorr_lock_t s = {0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int rt = 0, nd = 0;
-    unsigned long long cnt0 = 0;
+    int nd = r.nd;
     if (have) {
         p = prm[ch];
         s = st[ch];
-        rt = *reinterpret_cast<const int *>(rate + (size_t)ch * rate_stride);
-        nd = min(max(ndone[ch], 0), nper);
-        cnt0 = *reinterpret_cast<const unsigned long long *>(cnt + (size_t)ch * cnt_stride);
-        if (cnt_after) cnt0 -= (unsigned long long)nd;
         if (p.kbits <= 0) nd = 0;                                           // the channel's monitor is off
     }
     // every wavefront of the workgroup walks as many chunks as its longest channel has: every one reaches every barrier
@@ -97,8 +86,9 @@ __global__ __launch_bounds__(GC_LOCK_WAVES * 64) void rx_lock_kernel(
     if (nd > 0 && cnt0 == 0) s = {0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0, 0, 0, 0, 0, 0};    // row 0 is the period with cnt == 0
     bool live = nd > 0 && !s.lost;
     unsigned newly = 0;
-    const double *pI = I + (size_t)ch * ch_stride, *pQ = Q + (size_t)ch * ch_stride;
-    const gnsscorr_trklog_t *plog = log + (size_t)ch * (size_t)nper;
+    const double *pI = r.pI, *pQ = r.pQ;
+    const gnsscorr_trklog_t *plog = r.plog;
+    const size_t row_stride = v.row_stride;
 
     for (int c = 0; c < nchunk; c++) {
         const int base = c << 6, e = base + lane, b = c & 1;
@@ -208,7 +198,12 @@ int lock_check_prm(const char *who, const gnsscorr_lockprm_t &p, int rate, int c
     return GNSSCORR_OK;
 }
 
-size_t lock_align(size_t n) { return (n + 15) & ~(size_t)15; }
+void lock_launch(gnsscorr_ctx *ctx, const GcRowsView &rows, const gnsscorr_lockprm_t *prm, gnsscorr_lock_t *st, unsigned *lostw)
+{
+    GcTimed t(ctx, "rx_lock");
+    hipLaunchKernelGGL(rx_lock_kernel, dim3((rows.nlist + GC_LOCK_WAVES - 1) / GC_LOCK_WAVES), dim3(GC_LOCK_WAVES * 64), 0, ctx->stream,
+                       rows, prm, st, lostw);
+}
 
 }  // namespace
 
@@ -224,116 +219,44 @@ extern "C" int gnsscorr_lock_run(gnsscorr_ctx *ctx, const gnsscorr_lockprm_t *pr
         if (ndone[i] < 0 || ndone[i] > nper) return gc_fail(GNSSCORR_EINVAL, "lock_run: channel %d: ndone %d of %d rows", i, ndone[i], nper);
     }
     if (nch == 0) return GNSSCORR_OK;
-    std::lock_guard<std::mutex> lk(ctx->mtx);
-    GC_HIP(hipSetDevice(ctx->device));
-    // one staging buffer, one transfer: prm, rate, ndone, cnt0, st, I, Q, log
-    const size_t units = (size_t)nch * nper;
-    const size_t o_prm = 0, o_rate = lock_align(o_prm + sizeof(gnsscorr_lockprm_t) * nch), o_nd = lock_align(o_rate + sizeof(int) * nch),
-                 o_cnt = lock_align(o_nd + sizeof(int) * nch), o_st = lock_align(o_cnt + sizeof(uint64_t) * nch),
-                 o_I = lock_align(o_st + sizeof(gnsscorr_lock_t) * nch), o_Q = lock_align(o_I + sizeof(double) * units),
-                 o_log = lock_align(o_Q + sizeof(double) * units), total = lock_align(o_log + sizeof(gnsscorr_trklog_t) * units);
-    std::vector<unsigned char> blob(total, 0);
-    memcpy(&blob[o_prm], prm, sizeof(gnsscorr_lockprm_t) * nch);
-    memcpy(&blob[o_rate], rate, sizeof(int) * nch);
-    memcpy(&blob[o_nd], ndone, sizeof(int) * nch);
-    memcpy(&blob[o_cnt], cnt0, sizeof(uint64_t) * nch);
-    memcpy(&blob[o_st], st, sizeof(gnsscorr_lock_t) * nch);
-    memcpy(&blob[o_I], I, sizeof(double) * units);
-    memcpy(&blob[o_Q], Q, sizeof(double) * units);
-    memcpy(&blob[o_log], log, sizeof(gnsscorr_trklog_t) * units);
-    GC_RESERVE(ctx, ctx->dlock_stage, total);
-    unsigned char *d = ctx->dlock_stage;
-    GC_HIP(hipMemcpyAsync(d, blob.data(), total, hipMemcpyHostToDevice, ctx->stream));
-    {
-        GcTimed t(ctx, "rx_lock");
-        hipLaunchKernelGGL(rx_lock_kernel, dim3((nch + GC_LOCK_WAVES - 1) / GC_LOCK_WAVES), dim3(GC_LOCK_WAVES * 64), 0, ctx->stream,
-                           (const int *)nullptr, nch, (const gnsscorr_lockprm_t *)(d + o_prm), (const char *)(d + o_rate), sizeof(int),
-                           (gnsscorr_lock_t *)(d + o_st), (const double *)(d + o_I), (const double *)(d + o_Q), (size_t)nper, (size_t)1,
-                           (const gnsscorr_trklog_t *)(d + o_log), nper, (const int *)(d + o_nd), (const char *)(d + o_cnt),
-                           sizeof(uint64_t), 0, (unsigned *)nullptr);
-    }
-    GC_HIP(hipGetLastError());
-    std::vector<gnsscorr_lock_t> out(nch);
-    GC_HIP(hipMemcpyAsync(out.data(), d + o_st, sizeof(gnsscorr_lock_t) * nch, hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    memcpy(st, out.data(), sizeof(gnsscorr_lock_t) * nch);
-    return GNSSCORR_OK;
+    return gc_stage_run(ctx, prm, rate, st, I, Q, log, ndone, cnt0, nch, nper, 1,
+                        [&](const GcRowsView &rows, const gnsscorr_lockprm_t *dprm, gnsscorr_lock_t *dst) { lock_launch(ctx, rows, dprm, dst, nullptr); });
 }
 
 extern "C" int gnsscorr_rx_lock_set(gnsscorr_ctx *ctx, int ch0, int nch, const gnsscorr_lockprm_t *prm)
 {
     if (!ctx || !ctx->rx.on) return gc_fail(GNSSCORR_ESTATE, "rx_lock_set: no gnsscorr_rx_start yet");
-    if (ch0 < 0 || nch < 0 || ch0 + nch > ctx->nch) return gc_fail(GNSSCORR_EINVAL, "rx_lock_set: channels %d..%d of %d", ch0, ch0 + nch - 1, ctx->nch);
-    if (nch == 0) return GNSSCORR_OK;
     GC_HIP(hipSetDevice(ctx->device));
     GcRx &rx = ctx->rx;
+    // the monitor's own, before it can be on: the verdict words and the end of a launch
+    GC_TRY(rx.lock_lost.reserve(ctx->nch, hipHostMallocMapped));
+    GC_TRY(ctx->ev_lock.make());
     gnsscorr_lockprm_t p = {0, 0, 0, 0, 0.0};
     if (prm && prm->kbits != 0) {
         p = *prm;
         p.pad = 0;
-        // the channels' nav bit lengths: one column of the device's loop states
-        std::vector<int> rate(nch);
-        GC_HIP(hipMemcpy2DAsync(rate.data(), sizeof(int), (const char *)(ctx->loop.dloop.p + ch0) + offsetof(gnsscorr_loop_t, rate),
-                                sizeof(gnsscorr_loop_t), sizeof(int), nch, hipMemcpyDeviceToHost, ctx->stream));
-        GC_HIP(hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < nch; i++) {
-            int rc = lock_check_prm("rx_lock_set", p, rate[i], ch0 + i);
-            if (rc) return rc;
-        }
     }
-    GC_RESERVE(ctx, rx.dlockprm, ctx->nch);
-    GC_RESERVE(ctx, rx.dlock, ctx->nch);
-    { int rc = rx.lock_list.reserve(ctx->nch, hipHostMallocMapped); if (rc) return rc; }
-    { int rc = rx.lock_lost.reserve(ctx->nch, hipHostMallocMapped); if (rc) return rc; }
-    GC_TRY(ctx->ev_lock.make());
-    for (int i = 0; i < nch; i++) rx.lockprm[ch0 + i] = p;
-    rx.lock_on = 0;
-    for (int i = 0; i < ctx->nch; i++) rx.lock_on += rx.lockprm[i].kbits != 0;
-    // behind whatever the stream still runs (a monitor launch of the last step included: its verdicts stay to be read)
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    GC_HIP(hipMemcpy(rx.dlockprm.p, rx.lockprm.data(), sizeof(gnsscorr_lockprm_t) * ctx->nch, hipMemcpyHostToDevice));
-    GC_HIP(hipMemset(rx.dlock.p + ch0, 0, sizeof(gnsscorr_lock_t) * nch));
-    return GNSSCORR_OK;
+    return rx.lock.set(ctx, "rx_lock_set", ch0, nch, p, lock_check_prm);
 }
 
 extern "C" int gnsscorr_rx_lock_status(gnsscorr_ctx *ctx, gnsscorr_lock_t *st, int *losses)
 {
     if (!ctx || !ctx->rx.on) return gc_fail(GNSSCORR_ESTATE, "rx_lock_status: no gnsscorr_rx_start yet");
     GC_HIP(hipSetDevice(ctx->device));
-    const int nch = ctx->nch;
-    if (st) {
-        if (ctx->rx.dlock) GC_HIP(hipMemcpyAsync(st, ctx->rx.dlock, sizeof(gnsscorr_lock_t) * nch, hipMemcpyDeviceToHost, ctx->stream));
-        else memset(st, 0, sizeof(gnsscorr_lock_t) * nch);                  // the monitor has never been on
-    }
+    if (st) GC_TRY(ctx->rx.lock.status(ctx, st));
     GC_HIP(hipStreamSynchronize(ctx->stream));
-    if (losses) for (int i = 0; i < nch; i++) losses[i] = ctx->rx.losses[i];
+    if (losses) for (int i = 0; i < ctx->nch; i++) losses[i] = ctx->rx.losses[i];
     return GNSSCORR_OK;
 }
 
 int gc_rx_lock_launch(gnsscorr_ctx *ctx, int nperiod)
 {
     GcRx &rx = ctx->rx;
-    rx.lock_listed.clear();
-    for (int i = 0; i < ctx->nch; i++)
-        if (rx.lockprm[i].kbits != 0 && rx.st[i].state == GNSSCORR_CH_TRACK) rx.lock_listed.push_back(i);
-    const int n = (int)rx.lock_listed.size();
+    const int n = rx.lock.fill(rx.st);
+    rx.lock_listed.assign(rx.lock.list.p, rx.lock.list.p + n);
     if (!n) return GNSSCORR_OK;
-    // the previous launch's event has been waited for (step 0): the kernel that read the list is over
-    for (int i = 0; i < n; i++) {
-        rx.lock_list[i] = rx.lock_listed[i];
-        rx.lock_lost[rx.lock_listed[i]] = 0;
-    }
-    {
-        GcTimed t(ctx, "rx_lock");
-        // trk.II is the correlator's QQ (ref src/sdrtrk.c:42): gnsscorr_trk_fetch's II rows are dcorrQ
-        hipLaunchKernelGGL(rx_lock_kernel, dim3((n + GC_LOCK_WAVES - 1) / GC_LOCK_WAVES), dim3(GC_LOCK_WAVES * 64), 0, ctx->stream,
-                           (const int *)rx.lock_list.dev, n, (const gnsscorr_lockprm_t *)rx.dlockprm.p,
-                           (const char *)ctx->loop.dloop.p + offsetof(gnsscorr_loop_t, rate), sizeof(gnsscorr_loop_t), rx.dlock.p,
-                           (const double *)ctx->out.dcorrQ.p, (const double *)ctx->out.dcorrI.p, (size_t)nperiod * ctx->ntap, (size_t)ctx->ntap,
-                           (const gnsscorr_trklog_t *)ctx->loop.dlog.p, nperiod, (const int *)ctx->loop.ddone.p,
-                           (const char *)ctx->loop.dloop.p + offsetof(gnsscorr_loop_t, cnt), sizeof(gnsscorr_loop_t), 1,
-                           rx.lock_lost.dev);
-    }
+    for (int i : rx.lock_listed) rx.lock_lost[i] = 0;
+    lock_launch(ctx, gc_rows_of_run(ctx, rx.lock.list.dev, n, nperiod), rx.lock.dprm, rx.lock.dst, rx.lock_lost.dev);
     GC_HIP(hipGetLastError());
     GC_HIP(hipEventRecord(ctx->ev_lock, ctx->stream));
     ctx->lock_pending = true;

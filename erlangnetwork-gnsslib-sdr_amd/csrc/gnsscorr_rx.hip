@@ -15,7 +15,7 @@
 // the failed search -- so that the schedule depends on the input alone.
 #include <vector>
 
-#include "gnsscorr_ctx.h"
+#include "gnsscorr_stage.h"
 
 #define GC_ACQSLEEP 2000        // ms, ref src/sdr.h (ACQSLEEP)
 
@@ -46,28 +46,14 @@ extern "C" int gnsscorr_rx_start(gnsscorr_ctx *ctx, int retry_ms)
     // the lock monitor is off for all; a launch of an earlier schedule is waited for and its verdicts dropped
     if (ctx->lock_pending) GC_HIP(hipEventSynchronize(ctx->ev_lock));
     ctx->lock_pending = false;
-    const gnsscorr_lockprm_t off = {0, 0, 0, 0, 0.0};
-    rx.lockprm.assign(ctx->nch, off);
     rx.losses.assign(ctx->nch, 0);
-    rx.lock_on = 0;
     rx.lock_listed.clear();
-    // so is the bit-synchronisation detector; the applied counts start over (behind a launch of an earlier schedule)
-    const gnsscorr_bsyncprm_t boff = {0, 0, 0, 0, 0.0};
-    rx.bsyncprm.assign(ctx->nch, boff);
-    rx.bsync_on = 0;
-    if (rx.dbsync_applied) {
-        GC_HIP(hipSetDevice(ctx->device));
-        GC_HIP(hipMemsetAsync(rx.dbsync_applied, 0, sizeof(int) * ctx->nch, ctx->stream));
-    }
-    // and the correlation monitor; its states start over (behind a launch of an earlier schedule)
-    gnsscorr_cfmprm_t coff;
-    memset(&coff, 0, sizeof(coff));
-    rx.cfmprm.assign(ctx->nch, coff);
-    rx.cfm_on = 0;
-    if (rx.dcfm) {
-        GC_HIP(hipSetDevice(ctx->device));
-        GC_HIP(hipMemsetAsync(rx.dcfm, 0, sizeof(gnsscorr_cfm_t) * ctx->nch, ctx->stream));
-    }
+    GC_HIP(hipSetDevice(ctx->device));
+    GC_TRY(rx.lock.start(ctx));
+    // so are bit synchronisation, whose applied counts start over with its states, and the correlation monitor
+    GC_TRY(rx.bsync.start(ctx));
+    if (rx.dbsync_applied) GC_HIP(hipMemsetAsync(rx.dbsync_applied, 0, sizeof(int) * ctx->nch, ctx->stream));
+    GC_TRY(rx.cfm.start(ctx));
     for (int i = 0; i < ctx->nch; i++) {
         rx.st[i].state = GNSSCORR_CH_SEARCH;
         rx.st[i].next_try = rx_first_try(ctx, i);
@@ -152,11 +138,11 @@ extern "C" int gnsscorr_rx_step(gnsscorr_ctx *ctx, int max_periods)
     int rc = gc_trk_run_loop(ctx, max_periods, wp.data());
     // 3b. bit synchronisation by symbol energy over the periods just tracked: a decision presets flagsync / synci in the
     //     device's loop state, which the next step's first period sees; nothing waits for it here
-    if (!rc && rx.bsync_on) rc = gc_rx_bsync_launch(ctx, max_periods);
+    if (!rc && rx.bsync.on) rc = gc_rx_bsync_launch(ctx, max_periods);
     // 4. the lock monitor over the periods just tracked, behind the loop's last tail; nothing waits for it here
-    if (!rc && rx.lock_on) rc = gc_rx_lock_launch(ctx, max_periods);
+    if (!rc && rx.lock.on) rc = gc_rx_lock_launch(ctx, max_periods);
     // 5. the correlation monitor over the same periods: it reports only (gnsscorr_rx_cfm_status), so no step reads it
-    if (!rc && rx.cfm_on) rc = gc_rx_cfm_launch(ctx, max_periods);
+    if (!rc && rx.cfm.on) rc = gc_rx_cfm_launch(ctx, max_periods);
     return rc;
 }
 
@@ -168,9 +154,7 @@ extern "C" int gnsscorr_rx_status(gnsscorr_ctx *ctx, gnsscorr_rxstat_t *st)
     const int nch = ctx->nch;
     // sdrthread's cnt of every channel: one column of the device's loop states, behind whatever the stream still runs
     std::vector<uint64_t> cnt(nch);
-    GC_HIP(hipMemcpy2DAsync(cnt.data(), sizeof(uint64_t), (const char *)ctx->loop.dloop.p + offsetof(gnsscorr_loop_t, cnt),
-                            sizeof(gnsscorr_loop_t), sizeof(uint64_t), nch, hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
+    GC_TRY(gc_loop_column(ctx, offsetof(gnsscorr_loop_t, cnt), sizeof(uint64_t), 0, nch, cnt.data()));
     for (int i = 0; i < nch; i++) {
         st[i] = ctx->rx.st[i];
         st[i].cnt = cnt[i];
@@ -256,9 +240,7 @@ extern "C" int gnsscorr_rx_nav_step(gnsscorr_ctx *ctx, int max_periods)
             nav.tracking[i] = nav.st[i].state == GNSSCORR_CH_TRACK;
         }
     } else {
-        GC_HIP(hipMemcpy2DAsync(nav.cnt.data(), sizeof(uint64_t), (const char *)ctx->loop.dloop.p + offsetof(gnsscorr_loop_t, cnt),
-                                sizeof(gnsscorr_loop_t), sizeof(uint64_t), nch, hipMemcpyDeviceToHost, ctx->stream));
-        GC_HIP(hipStreamSynchronize(ctx->stream));
+        GC_TRY(gc_loop_column(ctx, offsetof(gnsscorr_loop_t, cnt), sizeof(uint64_t), 0, nch, nav.cnt.data()));
         for (int i = 0; i < nch; i++) nav.tracking[i] = 1;
     }
     const int rc = gnsscorr_rxnav_feed(nav.nv, ctx, nav.log.data(), nav.ii0.data(), max_periods, nav.ndone.data(), nav.cnt.data(),

@@ -662,8 +662,9 @@ typedef struct {
  * fits (ref src/sdracq.c:24-26).  retry_ms <= 0: ACQSLEEP (2000).  Needs the channels set and gnsscorr_loop_set done
  * for every one of them (the constants the hand-over keeps); otherwise GNSSCORR_ESTATE.
  * May be called again on the same channels (after gnsscorr_ring_create it must be): the schedule starts over -- states,
- * attempts, losses, the monitor off, the verdicts of a pending monitor launch dropped -- while the device's tracking and
- * loop states are not touched.  A channel that is acquired again is handed over like any other and from then on is bit for
+ * attempts, losses, the verdicts of a pending monitor launch dropped; the lock monitor, bit synchronisation and the
+ * correlation monitor off for all, their device states and the bit-sync applied counts zero, so that every
+ * gnsscorr_rx_*_status reads zeros -- while the device's tracking and loop states are not touched.  A channel that is acquired again is handed over like any other and from then on is bit for
  * bit a channel of a fresh context; until then its gnsscorr_rxstat_t.cnt keeps the count of its last run (the next
  * hand-over restarts it at 0), and gnsscorr_loop_get shows the loop state that run left. */
 int  gnsscorr_rx_start(gnsscorr_ctx *ctx, int retry_ms);
@@ -707,8 +708,10 @@ int  gnsscorr_lock_run(gnsscorr_ctx *ctx, const gnsscorr_lockprm_t *prm, const i
                        const double *I, const double *Q, const gnsscorr_trklog_t *log, const int *ndone,
                        const uint64_t *cnt0, int nch, int nper);
 /* The monitor's parameters for channels ch0 .. ch0+nch-1 of the schedule (one prm for all of them); prm == NULL or
- * kbits == 0 switches it off for them.  Their detector state is zeroed.  gnsscorr_rx_start leaves the monitor off for
- * all.  Values as above, against each channel's gnsscorr_loop_t.rate; without gnsscorr_rx_start GNSSCORR_ESTATE.
+ * kbits == 0 switches it off for them.  Their detector state is zeroed; the state of a channel no call has named reads
+ * as zeros.  A range outside the channel set is GNSSCORR_EINVAL ("channels"), one whose ch0 + nch overflows an int
+ * included.  gnsscorr_rx_start leaves the monitor off for all and zeroes every state.
+ * Values as above, against each channel's gnsscorr_loop_t.rate; without gnsscorr_rx_start GNSSCORR_ESTATE.
  * With the monitor on, gnsscorr_rx_step
  *   0. reads the verdicts of the previous step's launch (it waits for that launch): a TRACK channel declared lost goes
  *      to SEARCH, due at this step's write position, and is searched in this very step if its look-back fits;
